@@ -11,6 +11,12 @@ used only for the barrier, the max-over-ranks time and the gather of the per-ran
 RANK / WORLD_SIZE in the environment LAUNCHES the N ranks itself (fresh child processes, started before this process
 touches the GPU); under `torch.distributed.run` (RANK / WORLD_SIZE set) it is one of the ranks.  Prints ONE JSON line
 on rank 0.
+
+A plain run does what the headline needs: set-up (the in-process pre-training included), --warmup untimed and --steps timed
+epochs, the line.  `--full` adds everything else the line has carried: the launch probe and the roofline objects, the fp32 and
+other 16-bit legs, the oracle-refereed `dice_delta`, the sliding-window inference leg, the CPU baseline and `parity_at_size`.
+`--dump-outputs DIR` writes what the last timed epoch returned (see step_outputs) as .npy files; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -149,7 +155,18 @@ def parse_args(argv=None):
                     help="rehearsal on a one-GPU box: every rank uses cuda:0 (implies --dist-backend gloo)")
     ap.add_argument("--stub-runner", type=float, default=None, metavar="SECONDS",
                     help="test hook: an epoch is a sleep of this length, no GPU is touched (implies gloo)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the launch probe and its one-stream roofline epoch, "
+                         "epoch_roofline, the fp32 / 16-bit legs and dice_delta, the sliding-window inference leg, the CPU "
+                         "baseline and parity_at_size (the options above that shape these legs act only with --full).  "
+                         "Without it a run sets up, warms up, times --steps epochs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed epoch handed its caller to DIR/<name>.npy: "
+                         "tta_epoch's loss and pseudo-Dice (float64) and a fixed sample of the adapted weights (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N-rank launcher
@@ -195,6 +212,14 @@ PRETRAIN = dict(batch=2, lr=3e-3, cases=6, storage="fp16", w_seed=7, seed=5, k_e
 _PRETRAINED = {}
 
 
+def atlas_cases(specs):
+    """synthetic.atlas_case(*spec) for every spec, generated by concurrent host threads."""
+    from concurrent.futures import ThreadPoolExecutor
+    from dg_tta_amd.synthetic import atlas_case
+    with ThreadPoolExecutor(max_workers=min(len(specs), 8)) as ex:
+        return list(ex.map(lambda s: atlas_case(*s), specs))
+
+
 def pretrained_weights(args, device):
     """He-initialised nnUNet 3d_fullres (seed 7) PRE-TRAINED on the source domain of the synthetic atlas task, once per process
     (every rank of an N > 1 run trains the same weights from the same seeds: no exchange).  What nnUNetTrainer_GIN_MIND does,
@@ -206,7 +231,7 @@ def pretrained_weights(args, device):
     from dg_tta_amd.mind import MIND3D
     from dg_tta_amd.pretraining.hooks import register_dg_hooks
     from dg_tta_amd.pretraining.supervised import pretrain_supervised
-    from dg_tta_amd.synthetic import atlas_case, he_init_, synthetic_label_mapping
+    from dg_tta_amd.synthetic import he_init_, synthetic_label_mapping
     from dg_tta_amd.tta.torch_utils import dice_coeff, get_batch, release_resident
     from dg_tta_amd.unet import HipPlainConvUNet
     key = (args.size, args.copt, args.pretrain_steps, args.pretrain_hooks)
@@ -214,7 +239,10 @@ def pretrained_weights(args, device):
         return _PRETRAINED[key]
     k, vol, patch = args.copt - 1, volume_edge(args.size), [args.size] * 3
     t0 = time.perf_counter()
-    cases = [atlas_case(vol, k, s, "source") for s in range(PRETRAIN["cases"])]
+    # the training cases and the unseen evaluation case side by side: each draws from a generator of its own, so they are
+    # the cases one after the other would give
+    *cases, test = atlas_cases([(vol, k, s, "source") for s in range(PRETRAIN["cases"])] +
+                               [(vol, k, PRETRAIN["k_eval_seed"], "source")])
     mapping, names = synthetic_label_mapping(k)
     sel = torch.tensor([mapping[n][0] for n in names])
     adt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[PRETRAIN["storage"]]
@@ -238,7 +266,6 @@ def pretrained_weights(args, device):
     for h in handles:
         h.remove()
     # hard Dice of an UNSEEN source case (centre patch; dice_coeff, torch_utils.py:107-117)
-    test = atlas_case(vol, k, PRETRAIN["k_eval_seed"], "source")
     with torch.no_grad():
         net.eval()
         net.set_selected_classes(sel)               # map_label(logits): the optimised classes, as the TTA loop evaluates them
@@ -358,6 +385,34 @@ class StubRunner:
         time.sleep(self.seconds)
         self.losses.append(0.0)
         self.dices.append(0.0)
+
+
+DUMP_WEIGHTS = 1 << 22          # --dump-outputs: at most this many adapted weights (16 MB of float32)
+
+
+def step_outputs(runner):
+    """What the last epoch handed its caller: tta_epoch's mean step loss and pseudo-Dice, and the adapted weights it left in
+    the model - every parameter in fp32, flattened in parameters() order, or a fixed seeded sample of DUMP_WEIGHTS of them
+    (sorted positions) when there are more."""
+    import numpy as np
+    import torch
+    out = {"loss": np.array(runner.losses[-1], dtype=np.float64), "pseudo_dice": np.array(runner.dices[-1], dtype=np.float64)}
+    if runner.model is not None:
+        with torch.no_grad():
+            flat = torch.cat([p.detach().float().reshape(-1) for p in runner.model.parameters()])
+            if flat.numel() > DUMP_WEIGHTS:
+                pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_WEIGHTS].sort().values
+                flat = flat[pick.to(flat.device)]
+            out["weights_sample"] = flat.cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, where):
+    import numpy as np
+    where = Path(where)
+    where.mkdir(parents=True, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(where / f"{name}.npy", arr)
 
 
 def oracle_step(n, copt, accum, seed_a=101, seed_b=102, w_seed=7, threads=None, state=None, imgs=None):
@@ -892,19 +947,21 @@ def run_rank(args):
 
     def timed_run(dtype, steps, warmup, seed):
         """W untimed + K timed epochs of the product path in `dtype`; returns (seconds max over ranks, per-rank seconds,
-        runner, roofline)."""
+        runner, roofline, outputs of the last timed epoch for --dump-outputs or None)."""
         torch.manual_seed(seed + rank)
         np.random.seed(seed + rank)
         runner = Runner(args, device, rank, dtype)
         for _ in range(warmup):
             runner.epoch()
-        probe = set_probe_(runner, ("dec", 3, 1))     # the 128^3 32->32 conv block (largest single-shape FLOP share)
+        # --full: the 128^3 32->32 conv block (largest single-shape FLOP share) timed with events inside the timed region
+        probe = set_probe_(runner, ("dec", 3, 1)) if args.full else None
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
             runner.epoch()
         barrier()
         dt, per_rank = over_ranks(time.perf_counter() - t0)
+        outputs = step_outputs(runner) if (args.dump_outputs and rank == 0) else None
         set_probe_(runner, None)
         roof = roofline_of(probe, args, dtype)
         if roof is not None and not stub and rank == 0:
@@ -931,7 +988,7 @@ def run_rank(args):
                     else:
                         os.environ[k] = v
             roof = merge_schedules(roof, one)
-        return dt, per_rank, runner, roof
+        return dt, per_rank, runner, roof, outputs
 
     main_dtype = args.dtype
     traj_file = ROOT / "profiles" / "fp32_trajectory.json"
@@ -946,16 +1003,18 @@ def run_rank(args):
                                          "loss": list(r.losses), "pseudo_dice": list(r.dices)}, indent=1))
         print(f"wrote {traj_file}")
         return
-    dt, per_rank, runner, roof = timed_run(main_dtype, args.steps, args.warmup, 1234)
+    dt, per_rank, runner, roof, outputs = timed_run(main_dtype, args.steps, args.warmup, 1234)
     losses, dice, all_dices = list(runner.losses), runner.dice, list(runner.dices)
     del runner
     if not stub:
         torch.cuda.empty_cache()
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
 
     # ---- reference precision (fp32) leg + the storage types side by side at the headline size: same seeds, same draws, same
     # number of epochs from the same (pre-trained) weights; hard Dice vs ground truth before and after the adaptation
     fp32_leg, at_size, other16 = None, None, None
-    if world == 1 and not stub and not args.no_fp32 and args.ab_epochs > 0:
+    if args.full and world == 1 and not stub and not args.no_fp32 and args.ab_epochs > 0:
         legs = {}
         for dtp in ("fp32", "fp16", "bf16"):
             torch.manual_seed(4321)
@@ -1057,9 +1116,10 @@ def run_rank(args):
                           "product_switches": None if stub else product_switches()},
                "per_rank_epochs_per_s": [round(args.steps / t, 5) for t in per_rank],
                "loss_last_epoch": losses[-1], "pseudo_dice": dice,
-               "epoch_tflop": round(EPOCH_TFLOP(args), 2),
-               "roofline": roof}
-        if not stub:
+               "epoch_tflop": round(EPOCH_TFLOP(args), 2), "full": args.full}
+        if args.full:
+            out["roofline"] = roof
+        if args.full and not stub:
             # the WHOLE epoch against the same peak: every kernel of the epoch, MFMA-class or not, over the
             # algorithmic FLOPs of the network passes; HBM traffic of a whole epoch from the committed PMC passes
             per_gpu_s = dt / args.steps
@@ -1082,7 +1142,7 @@ def run_rank(args):
         if args.weights == "pretrained" and not stub:
             out["pretraining"] = pretrained_weights(args, device)[1]
         dice_delta = None
-        if world == 1 and not stub and not args.no_fp32 and args.referee_epochs > 0 and args.weights == "pretrained":
+        if args.full and world == 1 and not stub and not args.no_fp32 and args.referee_epochs > 0 and args.weights == "pretrained":
             dice_delta = referee_tta_run(args, device)
             main = dice_delta.get(main_dtype)
             if main is not None:            # the headline dtype's numbers at the top level of the object
@@ -1090,7 +1150,7 @@ def run_rank(args):
                                   label_agreement=main["label_agreement"], dtype=main_dtype,
                                   dice_within_tolerance=main["dice_within_tolerance"],
                                   loss_within_tolerance=main["loss_within_tolerance"], within_tolerance=main["within_tolerance"])
-        if dice_delta is None and not stub and traj_file.exists():
+        if args.full and dice_delta is None and not stub and traj_file.exists():
             # N > 1 (or --no-fp32): rank 0's trajectory against the stored fp32 run of the same seed and sample
             tj = json.loads(traj_file.read_text())
             n = min(len(losses), len(tj["loss"]))
@@ -1111,9 +1171,9 @@ def run_rank(args):
             out["fp32"] = fp32_leg
         if other16 is not None:
             out[other16[0]] = other16[1]
-        if args.inference_size > 0 and not stub:      # (rank 0; at N > 1 the peers wait in the final barrier, as for the CPU baseline)
+        if args.full and args.inference_size > 0 and not stub:      # (rank 0; at N > 1 the peers wait in the final barrier)
             out["inference"] = inference_leg(args, device, main_dtype)
-        if not args.no_cpu_baseline and not stub:
+        if args.full and not args.no_cpu_baseline and not stub:
             # rank 0 only; at N > 1 the peers wait in the final barrier (the timed region is over) so that a SCALE line carries
             # its CPU baseline too; one measured step without warm-up there
             if world > 1:

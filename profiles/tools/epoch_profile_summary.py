@@ -82,7 +82,7 @@ for dt in dts:
         measured_on["traffic"] = (old.get("measured_on") or {}).get("traffic", "unrecorded (before round 6)")
         measured_on["traffic_carried_over_from"] = "the previous summary of this tag"
     ent = {"size": 128, "accum": 16, "storage": dt,
-           "how": "(3-epoch run - 1-epoch run) / 2 of `bench.py --dtype %s --warmup 0 --weights he --no-fp32 --no-cpu-baseline "
+           "how": "(3-epoch run - 1-epoch run) / 2 of `bench.py --full --dtype %s --warmup 0 --weights he --no-fp32 --no-cpu-baseline "
                   "--inference-size 0` under rocprofv3: --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes with --kernel-trace "
                   "only (FETCH x 2 on gfx950), --kernel-trace --stats with DGTTA_WGRAD_STREAM=0 DGTTA_PIPELINE_PREP=0 (one stream, so that durations add up) for the per-name time" % dt,
            "dispatches_per_epoch": (n3 - n1) / 2,

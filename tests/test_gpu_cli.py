@@ -93,7 +93,7 @@ def test_bench_two_real_ranks_on_one_gpu():
     import sys
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1",
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1",
                           "--size", "64", "--accum", "4", "--pretrain-steps", "30", "--cpu-size", "64", "--inference-size", "128"], env=env,
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -122,7 +122,7 @@ def test_bench_four_real_ranks_rehearsal_and_rank0_matches_the_single_run():
     import sys
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--steps", "2", "--warmup", "1", "--size", "64", "--accum", "4", "--pretrain-steps", "30", "--no-fp32",
+    common = ["--full", "--steps", "2", "--warmup", "1", "--size", "64", "--accum", "4", "--pretrain-steps", "30", "--no-fp32",
               "--inference-size", "0", "--cpu-size", "64", "--cpu-warmup", "0", "--no-parity"]
 
     def line(extra):
@@ -139,3 +139,28 @@ def test_bench_four_real_ranks_rehearsal_and_rank0_matches_the_single_run():
     assert four["roofline"] is not None and "epoch_frac" in four["roofline"] and "largest_consumer" in four["roofline"]
     assert four["dtype"] == one["dtype"] == "fp16"
     assert four["loss_last_epoch"] == one["loss_last_epoch"] and four["pseudo_dice"] == one["pseudo_dice"]
+
+
+def test_bench_plain_run_dumps_what_the_last_timed_epoch_returned(tmp_path):
+    """A plain `bench.py` run (no --full) with the REAL runner at 64^3: the line carries the headline and none of the --full
+    legs, and --dump-outputs holds the last timed epoch's loss and pseudo-Dice as the line reports them plus a finite sample
+    of the adapted weights."""
+    import os
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "64",
+                          "--accum", "4", "--pretrain-steps", "30", "--dump-outputs", str(tmp_path / "out")], env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 2 and out["dtype"] == "fp16" and out["ms_per_step"] > 0
+    assert not {"roofline", "epoch_roofline", "dice_delta", "fp32", "bf16", "inference", "cpu_baseline", "parity_at_size"} & set(out)
+    loss, dice = np.load(tmp_path / "out" / "loss.npy"), np.load(tmp_path / "out" / "pseudo_dice.npy")
+    assert loss.dtype == dice.dtype == np.float64
+    assert float(loss) == out["loss_last_epoch"] and float(dice) == out["pseudo_dice"]
+    w = np.load(tmp_path / "out" / "weights_sample.npy")
+    assert w.dtype == np.float32 and w.ndim == 1 and 0 < w.size <= 1 << 22 and np.isfinite(w).all()

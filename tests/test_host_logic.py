@@ -212,6 +212,9 @@ def test_model_folder_parsing_and_data_iterator(tmp_path, monkeypatch):
         torch.nn.init.normal_(p)
     torch.save({"network_weights": ref.state_dict(), "trainer_name": "nnUNetTrainer_GIN_MIND"},
                folder / "fold_0" / "checkpoint_final.pth")
+    # load_network turns the trainer's internal augmentation on (a process-wide variable): restored after the test, so that
+    # later tests in the same process see the default
+    monkeypatch.setenv("DG_TTA_INTERNAL_AUGMENTATION", os.environ.get("DG_TTA_INTERNAL_AUGMENTATION", "false"))
     pred, patch, net, params = nu.load_network(folder / "fold_0" / "checkpoint_final.pth", "cpu")
     assert patch == [16, 16, 16] and len(net._forward_pre_hooks) == 2
     for k, v in ref.state_dict().items():

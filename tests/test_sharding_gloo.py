@@ -123,6 +123,7 @@ def test_fanout_parent_reports_failed_children(tmp_path):
     from dg_tta_amd.run import _wait_children
     from dg_tta_amd.sharding import child_devices
     ok = subprocess.Popen([sys.executable, "-c", "pass"])
+    ok.wait()           # done before the failure, or the parent rightly stops it as a survivor (-SIGTERM)
     killed = subprocess.Popen([sys.executable, "-c", "import os, signal; os.kill(os.getpid(), signal.SIGABRT)"])
     waiting = subprocess.Popen([sys.executable, "-c", "import time; time.sleep(600)"])
     t0 = time.monotonic()
@@ -167,6 +168,40 @@ def test_bench_launches_its_own_ranks(tmp_path):
     res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--stub-runner", "0.01", "--steps", "1",
                           "--warmup", "0"], env=env1, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0 and json.loads(res.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain bench run prints the headline only (the roofline, the other legs and the baselines need --full) and
+    --dump-outputs writes the last timed epoch's loss and pseudo-Dice as float64 .npy files.  Stub runner: no GPU."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+
+    def line(*extra):
+        res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--stub-runner", "0.01", "--steps", "3",
+                              "--warmup", "1", *extra], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    import numpy as np
+    plain = line("--dump-outputs", str(tmp_path / "out"))
+    assert plain["full"] is False and plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert key in plain
+    assert not {"roofline", "epoch_roofline", "dice_delta", "fp32", "inference", "cpu_baseline", "parity_at_size"} & set(plain)
+    for name in ("loss", "pseudo_dice"):
+        arr = np.load(tmp_path / "out" / f"{name}.npy")
+        assert arr.dtype == np.float64 and arr.shape == ()
+    assert float(np.load(tmp_path / "out" / "loss.npy")) == plain["loss_last_epoch"]
+    full = line("--full")
+    assert full["full"] is True and "roofline" in full
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--stub-runner", "0.01", "--steps", "0"], env=env,
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode != 0 and "--steps" in res.stderr
 
 
 def test_bench_launcher_reports_a_failed_rank():
