@@ -56,6 +56,16 @@ SIGNATURES = {
     "dgtta_convT3d_bwd_ws_bytes": (SZ, [I, I, I, I, I, I]),
     "dgtta_convT3d_bwd_split_ws_bytes": (SZ, [I, I, I, I, I, I]),
     "dgtta_convT3d_k2s2_bwd": (I, [P, I, P, I, P, P, I, P, P, P, SZ, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_conv3d_kpacked_bytes": (SZ, [I, I, I, I]),
+    "dgtta_conv3d_kpack_weights": (I, [P, P, I, I, I, I, I, I, I, I, P]),
+    "dgtta_conv3d_fwd": (I, [P, I, P, P, P, I, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_conv3d_dgrad": (I, [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_conv3d_kwgrad_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I, I]),
+    "dgtta_conv3d_wgrad": (I, [P, I, P, I, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_convT3d_s_fwd_ws_bytes": (SZ, [I, I, I, I, I, I]),
+    "dgtta_convT3d_s_fwd": (I, [P, I, P, P, P, I, P, SZ, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_convT3d_s_bwd_ws_bytes": (SZ, [I, I, I, I, I, I, I, I, I]),
+    "dgtta_convT3d_s_bwd": (I, [P, I, P, I, P, P, I, P, P, P, SZ, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_seghead_fwd": (I, [P, I, P, P, P, I, P, I, I, I, I, I64, I, P]),
     "dgtta_seghead_bwd_ws_bytes": (SZ, [I, I, I, I64]),
     "dgtta_seghead_bwd": (I, [P, I, P, I, P, P, I, P, I, P, P, P, SZ, I, I, I64, I, I, P]),

@@ -1,0 +1,546 @@
+// Anisotropic convolutions of nnU-Net plans: [kd, 3, 3] kernels (kd = 1 or 3, padding kd / 2, 1, 1) with per-axis strides
+// (sd, sh, sw) in {1, 2}^3, and transposed convolutions with kernel = stride in {1, 2}^3.
+//
+//   GEMM view:  M = output voxels (32 per MFMA block, consecutive along W), N = output channels, K = KD x 9 taps x Cin.
+//   MFMA:       16-bit storage -> v_mfma_f32_32x32x16_{bf16,f16}; fp32 storage -> v_mfma_f32_32x32x2_f32 x4 (exact fp32 fma
+//               chain); fp32 accumulation in all cases (mfma_step of conv_common.h).
+//   Workgroup:  8 waves, output tile TD x TH x TW voxels (8 or 16 M-blocks of 32 voxels) x 32 output channels.
+//   LDS:        A = input halo tile of one K-chunk (16 channels; 8 for fp32), [16-byte channel group][halo voxel]; its extent
+//               is (T - 1) * S + K per axis, so a KD = 1, SD = 1 layer stages one plane per output plane instead of three.  Where
+//               SW = 2 the halo rows are staged de-interleaved by W parity so that the 32 lanes of an M-block read
+//               consecutive slots.  B = the chunk's weights [tap][group][cout] (KD x 9 taps only).
+//   Data gradient: stride 1 = this kernel on dy with the transposed weight image and mirrored taps; a strided layer runs
+//               one class per parity of its strided axes (2 to 8 classes, blockIdx.z), each a stride-1 conv over the taps
+//               that reach that parity (a class without taps - kd = 1 with sd = 2, odd planes - writes zeros).
+//   Weight gradient: the class-masked weight-gradient kernels of conv_wgrad.hip (only the present taps are multiplied)
+//               with the fixed-order slab reduction into torch layout [Cout][Cin][kd][3][3] (conva_wgrad_mfma).
+//   Transposed conv: the pointwise class GEMM of conv_mfma.hip with kd*kh*kw output classes (convTa_run).
+#include "conv_common.h"
+#include <stdlib.h>
+
+int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo);      // conv_mfma.hip
+size_t convT_packed_bytes(int CinP, int CoutP, int dtype);
+int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B,
+               int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st);
+size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);      // conv_wgrad.hip
+int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
+int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                      int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
+size_t conv_bias_grad_ws_bytes(int B, int C, int64_t V);      // unet_ref.hip
+int conv_bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C, int64_t V, int accumulate, int dtype,
+                   hipStream_t st);
+
+namespace {
+
+template <int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
+struct GeoA {
+  static constexpr int HD = KD / 2;                   // zero padding along D (1 for kd = 3, 0 for kd = 1)
+  static constexpr int NTAP = KD * 9;
+  static constexpr int RPM = 32 / MBW;
+  static constexpr int TW = MBW, TH = RPM * MBH, TD = MBD;
+  static constexpr int MB = MBH * MBD;
+  static constexpr int ID = (TD - 1) * SD + 1 + 2 * HD, IH = (TH - 1) * SH + 3, IW = (TW - 1) * SW + 3;
+  static constexpr int IWH = (SW == 2) ? (IW + 1) / 2 : IW;
+  static constexpr int ROW = (SW == 2) ? 2 * IWH : IW;
+  static constexpr int NV = ID * IH * ROW;
+  __host__ __device__ static constexpr int lds_col(int wx) { return (SW == 2) ? (wx & 1) * IWH + (wx >> 1) : wx; }
+};
+
+template <typename T, int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
+struct CfgA {
+  typedef GeoA<MBW, MBH, MBD, KD, SD, SH, SW> G;
+  static constexpr int EPV = Elem<T>::EPV;
+  static constexpr int NG = 2;                 // 16-byte channel groups per K-chunk (one MFMA k-step)
+  static constexpr int CK = NG * EPV;
+  static constexpr int NC = 32;
+  static constexpr int NW = 8;
+  static constexpr size_t A_BYTES = (size_t)NG * G::NV * 16;
+  static constexpr size_t B_BYTES = (size_t)G::NTAP * NG * NC * 16;
+  static constexpr size_t LDS_BYTES = A_BYTES + B_BYTES;
+};
+
+// x: view xv; y: view yv (+ the class's offsets); virtual tap t = kd * 9 + kh * 3 + kw uses weight tap cs.taps[cls].wt[t]
+// (-1: absent).  w: LDS-image order [N/32][K/(2*EPV)][ntaps_src][2][32][EPV] (conv_weight_image_index).
+template <typename T, int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
+__global__ __launch_bounds__(512) void conva_mfma_kernel(const T *__restrict__ x, View xv, const T *__restrict__ w, ConvClasses cs,
+                                                         const float *__restrict__ bias, T *__restrict__ y, View yv, int Cin,
+                                                         int Cout, int CinP, int tilesW, int tilesH, int tilesD,
+                                                         double *__restrict__ stats, int ntaps_src) {
+  typedef CfgA<T, MBW, MBH, MBD, KD, SD, SH, SW> Cfg;
+  typedef typename Cfg::G G;
+  constexpr int EPV = Cfg::EPV, NG = Cfg::NG, CK = Cfg::CK, NC = Cfg::NC, NW = Cfg::NW, NV = G::NV, NTAP = G::NTAP;
+  constexpr int MPW = G::MB / NW, NT = NW * 64;
+  const int cls = blockIdx.z;
+  x += cs.xoff[cls];
+  y += cs.yoff[cls];
+  const int accumulate = cs.acc[cls];
+  const int Di = xv.D, Hi = xv.H, Wi = xv.W, Do = yv.D, Ho = yv.H, Wo = yv.W;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4 *sA = reinterpret_cast<uint4 *>(smem);                    // [NG][NV]
+  uint4 *sB = reinterpret_cast<uint4 *>(smem + Cfg::A_BYTES);     // [NTAP][NG][NC]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+
+  // a contiguous run of tiles per XCD (neighbouring tiles share their halo)
+  int tlin = blockIdx.x;
+  if ((gridDim.x & 7) == 0) tlin = (tlin & 7) * (int)(gridDim.x >> 3) + (tlin >> 3);
+  int t = tlin;
+  const int tw = t % tilesW;
+  t /= tilesW;
+  const int th = t % tilesH;
+  t /= tilesH;
+  const int td = t % tilesD;
+  const int b = t / tilesD;
+  const int n0 = blockIdx.y * NC;
+  const int od0 = td * G::TD, oh0 = th * G::TH, ow0 = tw * G::TW;
+  const int id0 = od0 * SD - G::HD, ih0 = oh0 * SH - 1, iw0 = ow0 * SW - 1;
+
+  int a_off[MPW];
+#pragma unroll
+  for (int i = 0; i < MPW; ++i) {
+    const int mb = wave * MPW + i;
+    const int mbd = mb / MBH, mbh = mb % MBH;
+    const int row = mbh * G::RPM + r / MBW, col = r % MBW;
+    a_off[i] = ((mbd * SD) * G::IH + row * SH) * G::ROW + col;   // SW = 2: column index in the half row
+  }
+  f32x16_t acc[MPW];
+#pragma unroll
+  for (int i = 0; i < MPW; ++i)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[i][q] = 0.f;
+
+  const T *xbp = x + (int64_t)b * xv.sb;
+  const int cin_lim = (Cin + EPV - 1) / EPV * EPV;
+
+  __shared__ signed char s_wt[32];
+  if (tid < 32) s_wt[tid] = tid < NTAP ? cs.taps[cls].wt[tid] : (signed char)-1;
+  __syncthreads();
+
+  constexpr int NA = (NV * NG + NT - 1) / NT, NBL = (NTAP * NC * NG + NT - 1) / NT;
+  uint4 ra[NA], rb[NBL];
+  int wslot[NBL];
+#pragma unroll
+  for (int i = 0; i < NBL; ++i) {
+    const int idx = tid + i * NT;       // == LDS index (tap * NG + g) * NC + n
+    const int n = idx % NC, g = (idx / NC) % NG, tap = idx / (NG * NC);
+    const int wt = idx < NTAP * NC * NG ? s_wt[tap] : -1;
+    const int off = ((((n0 + n) / 32) * (CinP / (2 * EPV)) + g / 2) * ntaps_src + wt) * 64 + (g & 1) * 32 + (n0 + n) % 32;
+    wslot[i] = wt >= 0 ? off : -1;
+  }
+  auto load_chunk = [&](int kc) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int idx = tid + i * NT;
+      const int g = idx % NG, v = idx / NG;
+      const int wx_l = v % G::ROW, hy = (v / G::ROW) % G::IH, dz = v / (G::ROW * G::IH);
+      const int wx = (SW == 2) ? ((wx_l >= G::IWH) ? 2 * (wx_l - G::IWH) + 1 : 2 * wx_l) : wx_l;   // inverse of lds_col
+      const int gd = id0 + dz, gh = ih0 + hy, gw = iw0 + wx;
+      const int c = kc + g * EPV;
+      const bool ok = idx < NV * NG && wx < G::IW && (unsigned)gd < (unsigned)Di && (unsigned)gh < (unsigned)Hi &&
+                      (unsigned)gw < (unsigned)Wi && c < cin_lim;
+      const T *p = ok ? xbp + gd * xv.sd + gh * xv.sh + gw * xv.sw + c : x;
+      const uint4 val = *reinterpret_cast<const uint4 *>(p);
+      ra[i] = ok ? val : make_uint4(0, 0, 0, 0);
+    }
+    const int kterm = (kc / (2 * EPV)) * ntaps_src * 64;
+#pragma unroll
+    for (int i = 0; i < NBL; ++i) {
+      const bool ok = wslot[i] >= 0;
+      const T *p = w + (int64_t)(ok ? wslot[i] + kterm : 0) * EPV;
+      const uint4 val = *reinterpret_cast<const uint4 *>(p);
+      rb[i] = ok ? val : make_uint4(0, 0, 0, 0);
+    }
+  };
+  auto store_chunk = [&]() {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int idx = tid + i * NT;
+      if (idx < NV * NG) sA[(idx % NG) * NV + idx / NG] = ra[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NBL; ++i) {
+      const int idx = tid + i * NT;
+      if (idx < NTAP * NC * NG) sB[idx] = rb[i];
+    }
+  };
+
+  // register staging, software pipelined: the loads of chunk k + 1 are in flight while chunk k is multiplied
+  load_chunk(0);
+  for (int kc = 0; kc < CinP; kc += CK) {
+    __syncthreads();
+    store_chunk();
+    __syncthreads();
+    if (kc + CK < CinP) load_chunk(kc + CK);
+#pragma unroll
+    for (int tap = 0; tap < NTAP; ++tap) {
+      if (s_wt[tap] < 0) continue;     // wave-uniform
+      const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
+      const int tap_off = (kd * G::IH + kh) * G::ROW + G::lds_col(kw);
+      const uint4 bf = sB[(tap * NG + h) * NC + r];
+#pragma unroll
+      for (int i = 0; i < MPW; ++i) mfma_step<T>(sA[h * NV + a_off[i] + tap_off], bf, acc[i]);
+    }
+  }
+
+  // ---- epilogue: bias, convert, store (acc row m = (q&3) + 8*(q>>2) + 4*h, column = r); optional InstanceNorm partial sums
+  float st1 = 0.f, st2 = 0.f;
+  const int co = n0 + r;
+  const float bv = (bias && co < Cout) ? bias[co] : 0.f;
+#pragma unroll
+  for (int i = 0; i < MPW; ++i) {
+    const int mb = wave * MPW + i;
+    const int mbd = mb / MBH, mbh = mb % MBH;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int m = (q & 3) + 8 * (q >> 2) + 4 * h;
+      const int od = od0 + mbd, oh = oh0 + mbh * G::RPM + m / MBW, ow = ow0 + m % MBW;
+      if (co < Cout && od < Do && oh < Ho && ow < Wo) {
+        T *o = y + b * yv.sb + od * yv.sd + oh * yv.sh + ow * yv.sw + co;
+        float v = acc[i][q] + bv;
+        if (accumulate) v += ld_f<T>(o);
+        st_f<T>(o, v);
+        st1 += v;
+        st2 += v * v;
+      }
+    }
+  }
+  if (stats) {
+    __syncthreads();                       // all waves are done with the A/B tiles: reuse LDS for the reduction
+    float *red = reinterpret_cast<float *>(smem);      // [NW][NC][2]
+    const float a = st1 + __shfl_xor(st1, 32, 64), c2 = st2 + __shfl_xor(st2, 32, 64);
+    if (h == 0) {
+      red[(wave * NC + r) * 2 + 0] = a;
+      red[(wave * NC + r) * 2 + 1] = c2;
+    }
+    __syncthreads();
+    const int tiles_per_b = tilesW * tilesH * tilesD;
+    if (tid < NC && n0 + tid < Cout) {
+      double s = 0.0, ss = 0.0;
+#pragma unroll
+      for (int wv = 0; wv < NW; ++wv) {
+        s += (double)red[(wv * NC + tid) * 2 + 0];
+        ss += (double)red[(wv * NC + tid) * 2 + 1];
+      }
+      double *p = stats + 32 + (((int64_t)b * tiles_per_b + (tlin % tiles_per_b)) * Cout + n0 + tid) * 2;
+      p[0] = s;
+      p[1] = ss;
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid == 0) reinterpret_cast<long long *>(stats)[0] = tiles_per_b;
+  }
+}
+
+template <typename T, int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
+int launch_conva(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y, const View &yv,
+                 int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
+  typedef CfgA<T, MBW, MBH, MBD, KD, SD, SH, SW> Cfg;
+  typedef typename Cfg::G G;
+  static_assert(Cfg::LDS_BYTES <= 160 * 1024, "conva tile does not fit the LDS");
+  auto kern = conva_mfma_kernel<T, MBW, MBH, MBD, KD, SD, SH, SW>;
+  static DynLdsOnce lds_once;
+  DG_REQUIRE(ensure_dyn_lds(lds_once, reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess, DGTTA_ERR_LAUNCH,
+             "conv3d_fwd: cannot raise the dynamic LDS limit to %zu", (size_t)Cfg::LDS_BYTES);
+  const int tW = cdiv(yv.W, G::TW), tH = cdiv(yv.H, G::TH), tD = cdiv(yv.D, G::TD);
+  const int64_t tiles = (int64_t)tW * tH * tD * B;
+  DG_REQUIRE(tiles < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "conv3d_fwd: too many tiles");
+  DG_REQUIRE(!stats || (int64_t)tW * tH * tD <= conv3_mfma_max_tiles(yv.D, yv.H, yv.W), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_fwd: tile count exceeds the statistics buffer");
+  dim3 grid((unsigned)tiles, (unsigned)cdiv(CoutP, Cfg::NC), (unsigned)cs.n);
+  hipLaunchKernelGGL(kern, grid, dim3(Cfg::NW * 64), Cfg::LDS_BYTES, st, (const T *)x, xv, (const T *)w, cs, bias, (T *)y, yv, Cin,
+                     Cout, CinP, tW, tH, tD, stats, ntaps_src);
+  DG_CHECK_LAUNCH("conva_mfma_kernel");
+  return DGTTA_OK;
+}
+
+// tile shape from the output extent: (TD, TH, TW) = (4, 4, 32) where the halo fits the LDS (SD = 1), else (4, 4, 16) or
+// (4, 8, 8); each is a shape of conv3_mfma_max_tiles, so the InstanceNorm partial sums fit dgtta_conv3d_stats_bytes
+template <typename T, int KD, int SD, int SH, int SW>
+int dispatch_conva(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y, const View &yv,
+                   int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
+#define ARGS x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
+  if constexpr (SD == 1)
+    if (yv.W >= 32) return launch_conva<T, 32, 4, 4, KD, SD, SH, SW>(ARGS);
+  if (yv.W >= 16) return launch_conva<T, 16, 2, 4, KD, SD, SH, SW>(ARGS);
+  return launch_conva<T, 8, 2, 4, KD, SD, SH, SW>(ARGS);
+#undef ARGS
+}
+
+template <typename T, int KD>
+int dispatch_conva_strides(int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs,
+                           const float *bias, void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats,
+                           int ntaps_src, hipStream_t st) {
+#define ARGS x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
+  switch ((sd - 1) * 4 + (sh - 1) * 2 + (sw - 1)) {
+    case 0: return dispatch_conva<T, KD, 1, 1, 1>(ARGS);
+    case 1: return dispatch_conva<T, KD, 1, 1, 2>(ARGS);
+    case 2: return dispatch_conva<T, KD, 1, 2, 1>(ARGS);
+    case 3: return dispatch_conva<T, KD, 1, 2, 2>(ARGS);
+    case 4: return dispatch_conva<T, KD, 2, 1, 1>(ARGS);
+    case 5: return dispatch_conva<T, KD, 2, 1, 2>(ARGS);
+    case 6: return dispatch_conva<T, KD, 2, 2, 1>(ARGS);
+    case 7: return dispatch_conva<T, KD, 2, 2, 2>(ARGS);
+  }
+#undef ARGS
+  return DGTTA_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int run_conva(int kd, int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias,
+              void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
+  if (kd == 1)
+    return dispatch_conva_strides<T, 1>(sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st);
+  return dispatch_conva_strides<T, 3>(sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st);
+}
+
+int run_conva_dt(int dtype, int kd, int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs,
+                 const float *bias, void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats,
+                 int ntaps_src, hipStream_t st) {
+#define ARGS kd, sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
+  if (dtype == DGTTA_F32) return run_conva<float>(ARGS);
+  if (dtype == DGTTA_BF16) return run_conva<bf16_t>(ARGS);
+  return run_conva<f16_t>(ARGS);
+#undef ARGS
+}
+
+// torch [Cout][Cin][kd][3][3] fp32 -> imgF (N = co, K = ci) and imgB (N = ci, K = co), both with the real tap kd*9 + kh*3 + kw
+template <typename T>
+__global__ void conva_pack_kernel(const float *__restrict__ w, T *__restrict__ imgF, T *__restrict__ imgB, int Cin, int Cout,
+                                  int CinP, int CoutP, int ntaps) {
+  constexpr int EPV = Elem<T>::EPV;
+  const int CoutN = (CoutP + 31) / 32 * 32, CinN = (CinP + 31) / 32 * 32;
+  const int64_t nf = (int64_t)ntaps * CinP * CoutN, nb = (int64_t)ntaps * CoutP * CinN;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb); i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < nf) {
+      const int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), tap = (int)(i / ((int64_t)CinP * CoutN));
+      st_f<T>(imgF + conv_weight_image_index(co, ci, tap, CinP, ntaps, EPV),
+              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
+    }
+    if (i < nb) {
+      const int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), tap = (int)(i / ((int64_t)CoutP * CinN));
+      st_f<T>(imgB + conv_weight_image_index(ci, co, tap, CoutP, ntaps, EPV),
+              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
+    }
+  }
+}
+
+size_t esz_of(int dtype) { return dtype == DGTTA_F32 ? 4 : 2; }
+int64_t n32(int c) { return (int64_t)(c + 31) / 32 * 32; }
+int granule(int dtype) { return dtype == DGTTA_F32 ? 8 : 16; }
+bool dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
+bool stride_ok(int s) { return s == 1 || s == 2; }
+bool kernel_ok(int kd, int sd, int sh, int sw) { return (kd == 1 || kd == 3) && stride_ok(sd) && stride_ok(sh) && stride_ok(sw); }
+int odim(int i, int k, int s) { return (i + 2 * (k / 2) - k) / s + 1; }
+bool dims_ok(int B, int Cin, int Cout, int D, int H, int W) {
+  return B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0 && Cin <= (1 << 16) && Cout <= (1 << 16);
+}
+
+bool operand_ok_dt(int dtype, const void *p, long long ld, int C, int CP) {
+  if (dtype == DGTTA_F32) return operand_ok<float>(p, ld, C, CP);
+  if (dtype == DGTTA_BF16) return operand_ok<bf16_t>(p, ld, C, CP);
+  return operand_ok<f16_t>(p, ld, C, CP);
+}
+
+bool convt_strides_ok(int sd, int sh, int sw) { return stride_ok(sd) && stride_ok(sh) && stride_ok(sw) && sd * sh * sw > 1; }
+
+}  // namespace
+
+extern "C" size_t dgtta_conv3d_kpacked_bytes(int kd, int CinP, int CoutP, int dtype) {
+  if ((kd != 1 && kd != 3) || CinP <= 0 || CoutP <= 0 || CinP > (1 << 16) || CoutP > (1 << 16) || !dtype_ok(dtype)) return 0;
+  return (size_t)kd * 9 * ((size_t)CinP * n32(CoutP) + (size_t)CoutP * n32(CinP)) * esz_of(dtype);
+}
+
+extern "C" int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd, int kh, int kw, int Cin, int Cout, int CinP,
+                                          int CoutP, int dtype, void *stream) {
+  DG_REQUIRE(w_t && wpack, DGTTA_ERR_BADARG, "conv3d_kpack_weights: null pointer");
+  DG_REQUIRE(Cin > 0 && Cout > 0 && CinP >= Cin && CoutP >= Cout && CinP <= (1 << 16) && CoutP <= (1 << 16), DGTTA_ERR_BADARG,
+             "conv3d_kpack_weights: bad channel counts");
+  DG_REQUIRE((kd == 1 || kd == 3) && kh == 3 && kw == 3, DGTTA_ERR_UNSUPPORTED,
+             "conv3d_kpack_weights: kernel %dx%dx%d (supported: [1|3] x 3 x 3)", kd, kh, kw);
+  DG_REQUIRE(dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED, "conv3d_kpack_weights: dtype %d", dtype);
+  DG_REQUIRE(CinP % granule(dtype) == 0 && CoutP % granule(dtype) == 0, DGTTA_ERR_BADARG,
+             "conv3d_kpack_weights: padded channel counts must be multiples of %d", granule(dtype));
+  const int ntaps = kd * 9;
+  void *imgB = (char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esz_of(dtype);
+  const int64_t n = (int64_t)ntaps * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
+  const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DGTTA_F32)
+    hipLaunchKernelGGL((conva_pack_kernel<float>), dim3(blocks), dim3(256), 0, st, w_t, (float *)wpack, (float *)imgB, Cin, Cout,
+                       CinP, CoutP, ntaps);
+  else if (dtype == DGTTA_BF16)
+    hipLaunchKernelGGL((conva_pack_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, w_t, (bf16_t *)wpack, (bf16_t *)imgB, Cin,
+                       Cout, CinP, CoutP, ntaps);
+  else
+    hipLaunchKernelGGL((conva_pack_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, w_t, (f16_t *)wpack, (f16_t *)imgB, Cin, Cout,
+                       CinP, CoutP, ntaps);
+  DG_CHECK_LAUNCH("conva_pack_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_conv3d_fwd(const void *x, int ldx, const void *wpack, const float *bias, void *y, int ldy, void *stats, int B,
+                                int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw,
+                                int dtype, void *stream) {
+  DG_REQUIRE(x && wpack && y, DGTTA_ERR_BADARG, "conv3d_fwd: null pointer");
+  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && CinP >= Cin && CoutP >= Cout, DGTTA_ERR_BADARG, "conv3d_fwd: bad dims");
+  DG_REQUIRE(ldx >= Cin && ldy >= Cout, DGTTA_ERR_BADARG, "conv3d_fwd: ld < C");
+  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_fwd: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
+  DG_REQUIRE(operand_ok_dt(dtype, x, ldx, Cin, CinP), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_fwd: x must be 16-byte aligned with rows of whole 16 bytes, CinP a multiple of %d", granule(dtype));
+  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  const View xv = dense_view(B, Di, Hi, Wi, ldx), yv = dense_view(B, Do, Ho, Wo, ldy);
+  ConvClasses cs;
+  cs.n = 1;
+  cs.kseg = 0;
+  cs.acc[0] = 0;
+  cs.xoff[0] = cs.yoff[0] = 0;
+  for (int t = 0; t < 27; ++t) cs.taps[0].wt[t] = (signed char)(t < kd * 9 ? t : -1);
+  return run_conva_dt(dtype, kd, sd, sh, sw, x, xv, wpack, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, (double *)stats, kd * 9,
+                      (hipStream_t)stream);
+}
+
+extern "C" int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, void *dx, int lddx, int B, int Cin, int Cout, int CinP,
+                                  int CoutP, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype,
+                                  void *stream) {
+  DG_REQUIRE(dy && wpack && dx, DGTTA_ERR_BADARG, "conv3d_dgrad: null pointer");
+  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && CinP >= Cin && CoutP >= Cout, DGTTA_ERR_BADARG, "conv3d_dgrad: bad dims");
+  DG_REQUIRE(lddx >= Cin && lddy >= Cout, DGTTA_ERR_BADARG, "conv3d_dgrad: ld < C");
+  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_dgrad: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
+  DG_REQUIRE((sd == 1 || Di % 2 == 0) && (sh == 1 || Hi % 2 == 0) && (sw == 1 || Wi % 2 == 0), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_dgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
+  DG_REQUIRE(operand_ok_dt(dtype, dy, lddy, Cout, CoutP), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_dgrad: dy must be 16-byte aligned with rows of whole 16 bytes, CoutP a multiple of %d", granule(dtype));
+  const int ntaps = kd * 9;
+  const void *imgB = (const char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esz_of(dtype);
+  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  const View xv = dense_view(B, Do, Ho, Wo, lddy);
+  // one class per parity p of the strided axes; per axis the virtual tap v (0..k-1) reads dy[j + v - k/2] and carries weight
+  // tap t = p + k/2 - s * (v - k/2) where 0 <= t < k
+  ConvClasses cs;
+  cs.n = sd * sh * sw;
+  cs.kseg = 0;
+  View yv{};
+  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+  for (int c = 0; c < cs.n; ++c) {
+    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
+    long long off;
+    yv = lattice_view(Di, Hi, Wi, lddx, sd, sh, sw, par[0], par[1], par[2], &off);      // even extents: one shape for all classes
+    cs.xoff[c] = 0;
+    cs.yoff[c] = off;
+    cs.acc[c] = accumulate;
+    for (int t = 0; t < 27; ++t) cs.taps[c].wt[t] = -1;
+    for (int v = 0; v < ntaps; ++v) {
+      const int vv[3] = {v / 9, (v / 3) % 3, v % 3};
+      int real[3];
+      bool ok = true;
+      for (int a = 0; a < 3; ++a) {
+        const int pad = ks[a] / 2;
+        real[a] = par[a] + pad - ss[a] * (vv[a] - pad);
+        ok = ok && real[a] >= 0 && real[a] < ks[a];
+      }
+      if (ok) cs.taps[c].wt[v] = (signed char)(real[0] * 9 + real[1] * 3 + real[2]);
+    }
+  }
+  return run_conva_dt(dtype, kd, 1, 1, 1, dy, xv, imgB, cs, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, ntaps,
+                      (hipStream_t)stream);
+}
+
+// workspace: [bias partials][weight-gradient slabs]
+extern "C" size_t dgtta_conv3d_kwgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw) {
+  if (!dims_ok(B, Cin, Cout, Di, Hi, Wi) || !kernel_ok(kd, sd, sh, sw)) return 0;
+  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  return align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256) +
+         align_up(conva_wgrad_ws_bytes(B, Cin, Cout, Do, Ho, Wo), 256);
+}
+
+extern "C" int dgtta_conv3d_wgrad(const void *x, int ldx, const void *dy, int lddy, float *dw_t, float *db, void *ws, size_t ws_bytes,
+                                  int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate,
+                                  int dtype, void *stream) {
+  DG_REQUIRE(x && dy && dw_t && ws, DGTTA_ERR_BADARG, "conv3d_wgrad: null pointer");
+  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && lddy >= Cout, DGTTA_ERR_BADARG, "conv3d_wgrad: bad dims");
+  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_wgrad: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
+  DG_REQUIRE((sd == 1 || Di % 2 == 0) && (sh == 1 || Hi % 2 == 0) && (sw == 1 || Wi % 2 == 0), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_wgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
+  DG_REQUIRE(ws_bytes >= dgtta_conv3d_kwgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi, kd, sd, sh, sw), DGTTA_ERR_WORKSPACE,
+             "conv3d_wgrad: workspace too small");
+  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  const size_t bias_bytes = align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256);
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = conva_wgrad_mfma(x, ldx, dy, lddy, dw_t, (char *)ws + bias_bytes, ws_bytes - bias_bytes, B, Cin, Cout, Di, Hi, Wi,
+                                  kd, sd, sh, sw, accumulate, dtype, st);
+  if (rc == DGTTA_ERR_UNSUPPORTED)
+    dgtta_set_error("conv3d_wgrad: operands not taken by the MFMA kernel (16-byte aligned rows, Cout a multiple of %d)",
+                    dtype == DGTTA_F32 ? 4 : 8);
+  if (rc != DGTTA_OK) return rc;
+  if (db) return conv_bias_grad(dy, lddy, db, ws, B, Cout, (int64_t)Do * Ho * Wo, accumulate, dtype, st);
+  return DGTTA_OK;
+}
+
+// ---- ConvTranspose3d with kernel = stride (sd, sh, sw) in {1, 2}^3, not all 1:
+//      out[b][s*v + o][co] = bias[co] + sum_ci x[b][v][ci] w[ci][co][o]
+extern "C" size_t dgtta_convT3d_s_fwd_ws_bytes(int Cin, int Cout, int sd, int sh, int sw, int dtype) {
+  if (Cin <= 0 || Cout <= 0 || Cin > (1 << 16) || Cout > (1 << 16) || !convt_strides_ok(sd, sh, sw) || !dtype_ok(dtype)) return 0;
+  const int g = granule(dtype);
+  return align_up(convT_packed_bytes((Cin + g - 1) / g * g, (Cout + g - 1) / g * g, dtype), 256);
+}
+
+extern "C" int dgtta_convT3d_s_fwd(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws,
+                                   size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype,
+                                   void *stream) {
+  DG_REQUIRE(x && w_t && out && ws, DGTTA_ERR_BADARG, "convT3d_s_fwd: null pointer");
+  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && ldo >= Cout, DGTTA_ERR_BADARG, "convT3d_s_fwd: bad dims");
+  DG_REQUIRE(convt_strides_ok(sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
+             "convT3d_s_fwd: kernel = stride (%d,%d,%d), dtype %d not supported", sd, sh, sw, dtype);
+  DG_REQUIRE(ws_bytes >= dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, dtype), DGTTA_ERR_WORKSPACE,
+             "convT3d_s_fwd: workspace too small");
+  const int rc = convTa_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, dtype, (hipStream_t)stream);
+  if (rc == DGTTA_ERR_UNSUPPORTED) dgtta_set_error("convT3d_s_fwd: x must be 16-byte aligned with rows of whole 16 bytes");
+  return rc;
+}
+
+// workspace: [bias partials][packed weights][weight-gradient slabs]
+static size_t convTa_bias_region(int B, int Cout, int Di, int Hi, int Wi, int no) {
+  return align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Di * Hi * Wi * no), 256);
+}
+
+extern "C" size_t dgtta_convT3d_s_bwd_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
+  if (!dims_ok(B, Cin, Cout, Di, Hi, Wi) || !convt_strides_ok(sd, sh, sw)) return 0;
+  return convTa_bias_region(B, Cout, Di, Hi, Wi, sd * sh * sw) + dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, DGTTA_F32) +
+         align_up(conva_wgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi), 256);
+}
+
+extern "C" int dgtta_convT3d_s_bwd(const void *x, int ldx, const void *dout, int lddo, const float *w_t, void *dx, int lddx, float *dw_t,
+                                   float *db, void *ws, size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh,
+                                   int sw, int accumulate, int dtype, void *stream) {
+  DG_REQUIRE(x && dout && w_t && ws, DGTTA_ERR_BADARG, "convT3d_s_bwd: null pointer");
+  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && lddo >= Cout, DGTTA_ERR_BADARG, "convT3d_s_bwd: bad dims");
+  DG_REQUIRE(convt_strides_ok(sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
+             "convT3d_s_bwd: kernel = stride (%d,%d,%d), dtype %d not supported", sd, sh, sw, dtype);
+  DG_REQUIRE(ws_bytes >= dgtta_convT3d_s_bwd_ws_bytes(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw), DGTTA_ERR_WORKSPACE,
+             "convT3d_s_bwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const int no = sd * sh * sw;
+  void *ws_bias = ws;
+  void *ws_pack = (char *)ws + convTa_bias_region(B, Cout, Di, Hi, Wi, no);
+  void *ws_main = (char *)ws_pack + dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, DGTTA_F32);
+  const size_t main_bytes = ws_bytes - ((char *)ws_main - (char *)ws);
+  if (dx) {
+    DG_REQUIRE(lddx >= Cin, DGTTA_ERR_BADARG, "convT3d_s_bwd: lddx < Cin");
+    const int rc = convTa_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws_pack, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, dtype, st);
+    if (rc == DGTTA_ERR_UNSUPPORTED) dgtta_set_error("convT3d_s_bwd: dout must be 16-byte aligned with rows of whole 16 bytes");
+    if (rc != DGTTA_OK) return rc;
+  }
+  if (dw_t) {
+    const int rc = convTa_wgrad_mfma(x, ldx, dout, lddo, dw_t, ws_main, main_bytes, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, accumulate,
+                                     dtype, st);
+    if (rc == DGTTA_ERR_UNSUPPORTED)
+      dgtta_set_error("convT3d_s_bwd: operands not taken by the MFMA kernel (16-byte aligned rows, Cout a multiple of %d)",
+                      dtype == DGTTA_F32 ? 4 : 8);
+    if (rc != DGTTA_OK) return rc;
+  }
+  if (db) return conv_bias_grad(dout, lddo, db, ws_bias, B, Cout, (int64_t)Di * Hi * Wi * no, accumulate, dtype, st);
+  return DGTTA_OK;
+}

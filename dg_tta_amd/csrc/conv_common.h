@@ -144,17 +144,21 @@ inline View dense_view(int B, int D, int H, int W, int ld) {
   v.W = W;
   return v;
 }
-// sub-lattice of parity (pd,ph,pw) of a dense volume: elements 2v+p
-View parity_view(int D, int H, int W, int ld, int pd, int ph, int pw, long long *offset) {
+// sub-lattice of a dense volume with per-axis steps (sd,sh,sw) at offsets (pd,ph,pw): elements s*v+p
+View lattice_view(int D, int H, int W, int ld, int sd, int sh, int sw, int pd, int ph, int pw, long long *offset) {
   View v = dense_view(1, D, H, W, ld);
   *offset = ((long long)pd * H * W + (long long)ph * W + pw) * ld;
-  v.sd *= 2;
-  v.sh *= 2;
-  v.sw *= 2;
-  v.D = (D - pd + 1) / 2;
-  v.H = (H - ph + 1) / 2;
-  v.W = (W - pw + 1) / 2;
+  v.sd *= sd;
+  v.sh *= sh;
+  v.sw *= sw;
+  v.D = (D - pd + sd - 1) / sd;
+  v.H = (H - ph + sh - 1) / sh;
+  v.W = (W - pw + sw - 1) / sw;
   return v;
+}
+// sub-lattice of parity (pd,ph,pw) of a dense volume: elements 2v+p
+View parity_view(int D, int H, int W, int ld, int pd, int ph, int pw, long long *offset) {
+  return lattice_view(D, H, W, ld, 2, 2, 2, pd, ph, pw, offset);
 }
 
 template <typename T>

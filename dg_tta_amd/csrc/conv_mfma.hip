@@ -515,29 +515,6 @@ int dispatch_conv(const void *x, const View &xv, const void *w, const Taps &taps
 }
 
 
-// ConvTranspose3d k2 s2 weight packing: w_t[ci][co][o] fp32 -> image-ordered wf (N=co, K=ci) and wb (N=ci, K=co),
-// 8 "taps" = the 8 output offsets, zero padded
-template <typename T>
-__global__ void convT_pack_kernel(const float *__restrict__ w, T *__restrict__ wf, T *__restrict__ wb, int Cin, int Cout,
-                                  int CinP, int CoutP) {
-  constexpr int EPV = Elem<T>::EPV;
-  const int CoutN = (CoutP + 31) / 32 * 32, CinN = (CinP + 31) / 32 * 32;
-  const int64_t nf = (int64_t)8 * CinP * CoutN, nb = (int64_t)8 * CoutP * CinN;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb);
-       i += (int64_t)gridDim.x * blockDim.x) {
-    if (i < nf) {
-      int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), o = (int)(i / ((int64_t)CinP * CoutN));
-      st_f<T>(wf + conv_weight_image_index(co, ci, o, CinP, 8, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)ci * Cout + co) * 8 + o] : 0.f);
-    }
-    if (i < nb) {   // data-gradient role: N = ci, K = o*CoutP + co (the 8 parity segments concatenated along K), one tap
-      int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), o = (int)(i / ((int64_t)CoutP * CinN));
-      st_f<T>(wb + conv_weight_image_index(ci, o * CoutP + co, 0, 8 * CoutP, 1, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)ci * Cout + co) * 8 + o] : 0.f);
-    }
-  }
-}
-
 // conv 3x3x3 weight images: imgF (N=co, K=ci) and imgB (N=ci, K=co) with REAL tap indices
 template <typename T>
 __global__ void conv_pack_image_kernel(const float *__restrict__ w, T *__restrict__ imgF, T *__restrict__ imgB, int Cin,
@@ -662,7 +639,6 @@ int conv3_dgrad_s2_mfma(const void *dy, int lddy, const void *w_kmajor, void *dx
   return DGTTA_ERR_UNSUPPORTED;
 }
 
-// ConvTranspose3d(k2,s2) forward / data gradient as 8 single-tap launches (one per output offset o).
 static size_t n32(int c) { return (size_t)(c + 31) / 32 * 32; }
 size_t convT_packed_bytes(int CinP, int CoutP, int dtype) {
   return (size_t)8 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * (dtype == DGTTA_F32 ? 4 : 2);
@@ -691,27 +667,54 @@ int conv_pack_images(const float *w_t, void *img, int Cin, int Cout, int CinP, i
   return DGTTA_OK;
 }
 
+// ConvTranspose3d with kernel = stride (sd, sh, sw) in {1, 2}^3: no = sd * sh * sw output offsets (8 for the k2s2 layers,
+// fewer for the anisotropic plans' (1, 2, 2)-style ones).  Offset o = (od * sh + oh) * sw + ow (torch's flattening of the kernel)
+// writes the output lattice s * v + (od, oh, ow); the forward is one pointwise launch with `no` classes, the data gradient ONE
+// pointwise GEMM with the `no` lattices of dout concatenated along K.
+// Weight packing: w_t[ci][co][o] fp32 -> image-ordered wf (N=co, K=ci) and wb (N=ci, K=o*CoutP+co), zero padded.
+namespace {
 template <typename T>
-static int convT_run(int mode /*0 fwd, 1 dgrad*/, const void *in, int ldin, const float *w_t, const float *bias, void *out,
-                     int ldout, void *ws, int B, int Cin, int Cout, int Di, int Hi, int Wi, hipStream_t st) {
+__global__ void convTa_pack_kernel(const float *__restrict__ w, T *__restrict__ wf, T *__restrict__ wb, int Cin, int Cout, int CinP,
+                                   int CoutP, int no) {
+  constexpr int EPV = Elem<T>::EPV;
+  const int CoutN = (CoutP + 31) / 32 * 32, CinN = (CinP + 31) / 32 * 32;
+  const int64_t nf = (int64_t)no * CinP * CoutN, nb = (int64_t)no * CoutP * CinN;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb); i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < nf) {
+      int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), o = (int)(i / ((int64_t)CinP * CoutN));
+      st_f<T>(wf + conv_weight_image_index(co, ci, o, CinP, no, EPV), (ci < Cin && co < Cout) ? w[((int64_t)ci * Cout + co) * no + o] : 0.f);
+    }
+    if (i < nb) {   // data-gradient role: N = ci, K = o*CoutP + co (the no output lattices concatenated along K), one tap
+      int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), o = (int)(i / ((int64_t)CoutP * CinN));
+      st_f<T>(wb + conv_weight_image_index(ci, o * CoutP + co, 0, no * CoutP, 1, EPV),
+              (ci < Cin && co < Cout) ? w[((int64_t)ci * Cout + co) * no + o] : 0.f);
+    }
+  }
+}
+
+template <typename T>
+int convTa_run_t(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
+                 int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, hipStream_t st) {
   constexpr int EPV = Elem<T>::EPV;
   const int CinP = (Cin + 2 * EPV - 1) / (2 * EPV) * (2 * EPV), CoutP = (Cout + 2 * EPV - 1) / (2 * EPV) * (2 * EPV);
-  T *wf = (T *)ws, *wb = wf + (size_t)8 * CinP * n32(CoutP);
-  const int64_t n = (int64_t)8 * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
-  hipLaunchKernelGGL((convT_pack_kernel<T>), dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256),
-                     0, st, w_t, wf, wb, Cin, Cout, CinP, CoutP);
-  DG_CHECK_LAUNCH("convT_pack_kernel");
-  const int Do = 2 * Di, Ho = 2 * Hi, Wo = 2 * Wi;
+  const int no = sd * sh * sw;
   if (mode == 0 ? !operand_ok<T>(in, ldin, Cin, CinP) : !operand_ok<T>(in, ldin, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
+  T *wf = (T *)ws, *wb = wf + (size_t)no * CinP * n32(CoutP);
+  const int64_t n = (int64_t)no * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
+  hipLaunchKernelGGL((convTa_pack_kernel<T>), dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, st,
+                     w_t, wf, wb, Cin, Cout, CinP, CoutP, no);
+  DG_CHECK_LAUNCH("convTa_pack_kernel");
+  const int Do = sd * Di, Ho = sh * Hi, Wo = sw * Wi;
+  ConvClasses cs;
+  cs.kseg = 0;
   if (mode == 0) {
-    // forward: the 8 output offsets write disjoint sub-lattices -> one pointwise launch with 8 classes
-    ConvClasses cs;
-    cs.n = 8;
-    cs.kseg = 0;
-    View yv;
-    for (int o = 0; o < 8; ++o) {
+    // forward: the output offsets write disjoint lattices -> one pointwise launch with `no` classes
+    cs.n = no;
+    View yv{};
+    for (int o = 0; o < no; ++o) {
       long long off;
-      yv = parity_view(Do, Ho, Wo, ldout, o >> 2, (o >> 1) & 1, o & 1, &off);
+      yv = lattice_view(Do, Ho, Wo, ldout, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
+                     sw == 2 ? o % 2 : 0, &off);
       yv.sb = (long long)Do * Ho * Wo * ldout;
       cs.xoff[o] = 0;
       cs.yoff[o] = off;
@@ -720,26 +723,33 @@ static int convT_run(int mode /*0 fwd, 1 dgrad*/, const void *in, int ldin, cons
       cs.taps[o].wt[13] = (signed char)o;
     }
     const View xv = dense_view(B, Di, Hi, Wi, ldin);
-    return dispatch_conv_classes<T>(in, xv, wf, cs, bias, out, yv, B, Cin, Cout, CinP, CoutP, 0, st, nullptr, 8);
+    return dispatch_conv_classes<T>(in, xv, wf, cs, bias, out, yv, B, Cin, Cout, CinP, CoutP, 0, st, nullptr, no);
   }
-  // data gradient: dx[v][ci] = sum_o sum_co dout[2v+o][co] w[ci][co][o] = ONE pointwise GEMM with K = 8 x Cout, the 8
-  // parity sub-lattices of dout concatenated along K (segment offsets), no read-modify-write passes
-  ConvClasses cs;
+  // data gradient: ONE pointwise GEMM with K = no x Cout, the output lattices of dout concatenated along K
   cs.n = 1;
   cs.acc[0] = 0;
   cs.xoff[0] = cs.yoff[0] = 0;
   for (int t = 0; t < 27; ++t) cs.taps[0].wt[t] = -1;
   cs.taps[0].wt[13] = 0;
   cs.kseg = CoutP;
-  View xv;
-  for (int o = 0; o < 8; ++o) {
+  View xv{};
+  for (int o = 0; o < no; ++o) {
     long long off;
-    xv = parity_view(Do, Ho, Wo, ldin, o >> 2, (o >> 1) & 1, o & 1, &off);
+    xv = lattice_view(Do, Ho, Wo, ldin, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0, sw == 2 ? o % 2 : 0,
+                   &off);
     cs.segoff[o] = off;
   }
   xv.sb = (long long)Do * Ho * Wo * ldin;
   const View yv = dense_view(B, Di, Hi, Wi, ldout);
-  return dispatch_conv_classes<T>(in, xv, wb, cs, nullptr, out, yv, B, Cout, Cin, 8 * CoutP, CinP, 0, st, nullptr, 1);
+  return dispatch_conv_classes<T>(in, xv, wb, cs, nullptr, out, yv, B, Cout, Cin, no * CoutP, CinP, 0, st, nullptr, 1);
+}
+}  // namespace
+
+// ConvTranspose3d(k2,s2) forward / data gradient (the 8-offset case of the above).
+template <typename T>
+static int convT_run(int mode /*0 fwd, 1 dgrad*/, const void *in, int ldin, const float *w_t, const float *bias, void *out,
+                     int ldout, void *ws, int B, int Cin, int Cout, int Di, int Hi, int Wi, hipStream_t st) {
+  return convTa_run_t<T>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, st);
 }
 
 // convt_gemm.hip: register-operand kernels of the two large decoder stages
@@ -763,6 +773,16 @@ int convT_dgrad_mfma(const void *dout, int lddo, const float *w_t, void *dx, int
   if (dtype == DGTTA_F32) return convT_run<float>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
   if (dtype == DGTTA_BF16) return convT_run<bf16_t>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
   if (dtype == DGTTA_F16) return convT_run<f16_t>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
+  return DGTTA_ERR_UNSUPPORTED;
+}
+
+int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
+               int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st) {
+#define ARGS mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, st
+  if (dtype == DGTTA_F32) return convTa_run_t<float>(ARGS);
+  if (dtype == DGTTA_BF16) return convTa_run_t<bf16_t>(ARGS);
+  if (dtype == DGTTA_F16) return convTa_run_t<f16_t>(ARGS);
+#undef ARGS
   return DGTTA_ERR_UNSUPPORTED;
 }
 

@@ -1895,6 +1895,30 @@ int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw
   return DGTTA_ERR_UNSUPPORTED;
 }
 
+// ConvTranspose3d with kernel = stride (sd, sh, sw): dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[s v + o][co], one single-tap class
+// per output offset o = (od * sh + oh) * sw + ow (the dout lattice at that offset)
+template <typename T>
+static int convT_wgrad_classes(const void *x, const View &xv, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
+                               int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, hipStream_t st) {
+  const int no = sd * sh * sw;
+  WgradClasses wc;
+  RealTaps reals;
+  wc.n = no;
+  View yv{};
+  for (int o = 0; o < no; ++o) {
+    long long off;
+    yv = lattice_view(sd * Di, sh * Hi, sw * Wi, lddo, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
+                      sw == 2 ? o % 2 : 0, &off);
+    wc.xoff[o] = 0;
+    wc.yoff[o] = off;
+    wc.mask[o] = 1u << 13;
+    for (int t = 0; t < 27; ++t) reals.t[o].wt[t] = -1;
+    reals.t[o].wt[13] = (signed char)o;
+  }
+  return wgrad_launch_classes<T>(x, xv, dout, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, no, (long long)Cout * no, 1, accumulate,
+                                 st);
+}
+
 // ConvTranspose3d k2 s2 weight gradient: dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[2v+o][co]  (8 single-tap launches)
 template <typename T>
 static int convT_wgrad(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
@@ -1943,22 +1967,7 @@ static int convT_wgrad(const void *x, int ldx, const void *dout, int lddo, float
       return DGTTA_OK;
     }
   }
-  WgradClasses wc;
-  RealTaps reals;
-  wc.n = 8;
-  View yv;
-  for (int o = 0; o < 8; ++o) {
-    long long off;
-    yv = parity_view(2 * Di, 2 * Hi, 2 * Wi, lddo, o >> 2, (o >> 1) & 1, o & 1, &off);
-    yv.sb = (long long)8 * Di * Hi * Wi * lddo;
-    wc.xoff[o] = 0;
-    wc.yoff[o] = off;
-    wc.mask[o] = 1u << 13;
-    for (int t = 0; t < 27; ++t) reals.t[o].wt[t] = -1;
-    reals.t[o].wt[13] = (signed char)o;
-  }
-  return wgrad_launch_classes<T>(x, xv, dout, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, 8, (long long)Cout * 8, 1,
-                                 accumulate, st);
+  return convT_wgrad_classes<T>(x, xv, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, accumulate, st);
 }
 
 // fp32 transposed-conv weight gradient as six launches of the 16-bit kernel on exact three-term bf16 splits (see
@@ -2205,4 +2214,88 @@ bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int d
   const int g = conv3_wgrad_ring_launch((const void *)16, xv, (const void *)16, yv, nullptr, ws_bytes, B, Cin, Cout, dtype == DGTTA_F16, nullptr,
                                         &rc, (long long)B * D * H * W * 32, true);
   return rc == DGTTA_OK && g > 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight gradients of the anisotropic layers (conv_aniso.hip) on the class-masked kernels above.
+//   conv [kd][3][3], strides (sd, sh, sw) in {1, 2}:  dW[co][ci][t] = sum_{b,vo} dy[vo][co] x[s vo + t - pad][ci] per axis.
+//   A strided axis splits x into its two parity lattices: parity p at virtual offset u (-1, 0, +1) carries the real tap
+//   t = s u + p + pad where 0 <= t < k (stride 1: t = u + pad).  One class per parity combination that carries a tap (1 to 8),
+//   each a stride-1 problem over dy's lattice whose mask holds exactly the virtual taps with a real tap: the kernels multiply
+//   those only, and the fixed-order slab reduction writes them into torch layout [Cout][Cin][kd * 9].
+//   Strided axes need even input extents (every parity lattice then has dy's extent).
+static size_t wgrad_classes_bytes(int B, int Cin, int Cout, int D, int H, int W, int ncls) {
+  const WgradPlan p = wgrad_plan(B, Cin, Cout, D, H, W, ncls);
+  return (size_t)ncls * p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
+}
+
+// slabs for any class count 1..8 on a dy lattice of D x H x W (the plan's D split depends on the class count)
+size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W) {
+  size_t best = conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, D, H, W);
+  for (int n = 1; n <= 8; ++n) {
+    const size_t b = wgrad_classes_bytes(B, Cin, Cout, D, H, W, n);
+    best = b > best ? b : best;
+  }
+  return best;
+}
+
+int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
+  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+  const int Do = (Di + 2 * (kd / 2) - kd) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
+  const View yv = dense_view(B, Do, Ho, Wo, lddy);
+  WgradClasses wc;
+  RealTaps reals;
+  wc.n = 0;
+  for (int c = 0; c < sd * sh * sw; ++c) {
+    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
+    unsigned mask = 0;
+    Taps rt;
+    for (int t = 0; t < 27; ++t) {
+      const int u[3] = {t / 9 - 1, (t / 3) % 3 - 1, t % 3 - 1};
+      int real[3];
+      bool ok = true;
+      for (int a = 0; a < 3; ++a) {
+        real[a] = ss[a] * u[a] + par[a] + ks[a] / 2;
+        ok = ok && real[a] >= 0 && real[a] < ks[a];
+      }
+      rt.wt[t] = ok ? (signed char)(real[0] * 9 + real[1] * 3 + real[2]) : (signed char)-1;
+      if (ok) mask |= 1u << t;
+    }
+    if (!mask) continue;            // kd = 1 along a strided D: the odd planes carry no tap
+    wc.xoff[wc.n] = ((long long)par[0] * Hi * Wi + (long long)par[1] * Wi + par[2]) * ldx;
+    wc.yoff[wc.n] = 0;
+    wc.mask[wc.n] = mask;
+    reals.t[wc.n] = rt;
+    ++wc.n;
+  }
+  View xv = dense_view(B, Di, Hi, Wi, ldx);      // the parity lattices: steps s, extent of dy
+  xv.sd *= sd;
+  xv.sh *= sh;
+  xv.sw *= sw;
+  xv.D = Di / sd;
+  xv.H = Hi / sh;
+  xv.W = Wi / sw;
+  if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Do, Ho, Wo, wc.n)) return DGTTA_ERR_WORKSPACE;
+  const long long s_co = (long long)Cin * kd * 9, s_ci = kd * 9;
+  if (dtype == DGTTA_F32)
+    return wgrad_launch_classes<float>(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, 1, accumulate, st);
+  if (dtype == DGTTA_BF16)
+    return wgrad_launch_classes<bf16_t>(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, 1, accumulate, st);
+  if (dtype == DGTTA_F16)
+    return wgrad_launch_classes<f16_t>(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, 1, accumulate, st);
+  return DGTTA_ERR_UNSUPPORTED;
+}
+
+// (the anisotropic plans' transposed convs: convT_wgrad_classes with any kernel = stride)
+int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                      int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
+  if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Di, Hi, Wi, sd * sh * sw)) return DGTTA_ERR_WORKSPACE;
+  const View xv = dense_view(B, Di, Hi, Wi, ldx);
+#define ARGS x, xv, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, accumulate, st
+  if (dtype == DGTTA_F32) return convT_wgrad_classes<float>(ARGS);
+  if (dtype == DGTTA_BF16) return convT_wgrad_classes<bf16_t>(ARGS);
+  if (dtype == DGTTA_F16) return convT_wgrad_classes<f16_t>(ARGS);
+#undef ARGS
+  return DGTTA_ERR_UNSUPPORTED;
 }

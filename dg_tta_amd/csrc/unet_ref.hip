@@ -1456,6 +1456,15 @@ static int bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C
   return DGTTA_OK;
 }
 
+// the same reduction for the anisotropic layers (conv_aniso.hip): db[c] (+)= sum over B x V rows of dy, fixed order
+size_t conv_bias_grad_ws_bytes(int B, int C, int64_t V) {
+  if (B <= 0 || C <= 0 || V <= 0) return 0;
+  return (size_t)B * reduce_blocks(V, B) * C * 2 * sizeof(double);
+}
+int conv_bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C, int64_t V, int accumulate, int dtype, hipStream_t st) {
+  return bias_grad(dy, lddy, db, ws, B, C, V, accumulate, dtype, st);
+}
+
 static int k3_wgrad(const void *x, int ldx, long long x_block_stride, const void *dy, int lddy, float *dw_t, float *db, void *ws,
                     size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, int impl,
                     void *stream);

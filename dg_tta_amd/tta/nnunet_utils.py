@@ -31,14 +31,36 @@ def unet_cfg_from_plans(plans, dataset_json, configuration, in_channels):
         conf = parent
     if conf.get("UNet_class_name", "PlainConvUNet") != "PlainConvUNet":
         raise NotImplementedError(f"only PlainConvUNet is built, plans ask for {conf['UNet_class_name']}")
-    pools = conf["pool_op_kernel_sizes"]
-    if any(len(set(p)) != 1 or p[0] not in (1, 2) for p in pools) or any(k != [3, 3, 3] for k in conf["conv_kernel_sizes"]):
-        raise NotImplementedError("only isotropic stride 1/2 and 3x3x3 kernels are built")
+    pools, kernels = conf["pool_op_kernel_sizes"], conf["conv_kernel_sizes"]
     base, cap = conf["UNet_base_num_features"], conf["unet_max_num_features"]
     feats = tuple(min(base * 2 ** i, cap) for i in range(len(pools)))
-    return dict(features=feats, strides=tuple(p[0] for p in pools), n_conv_enc=tuple(conf["n_conv_per_stage_encoder"]),
-                n_conv_dec=tuple(conf["n_conv_per_stage_decoder"]), in_channels=in_channels,
-                num_classes=len(dataset_json["labels"])), list(conf["patch_size"])
+    cfg = dict(features=feats, n_conv_enc=tuple(conf["n_conv_per_stage_encoder"]),
+               n_conv_dec=tuple(conf["n_conv_per_stage_decoder"]), in_channels=in_channels, num_classes=len(dataset_json["labels"]))
+    if (all(len(p) == 3 and len(set(p)) == 1 and p[0] in (1, 2) for p in pools) and len(kernels) == len(pools)
+            and all(list(k) == [3, 3, 3] for k in kernels)):
+        cfg["strides"] = tuple(p[0] for p in pools)      # isotropic plan (TS104): int strides, no kernel_sizes
+    else:
+        cfg["strides"], cfg["kernel_sizes"] = anisotropic_stages(pools, kernels)
+    return {k: cfg[k] for k in ("features", "strides", "kernel_sizes", "n_conv_enc", "n_conv_dec", "in_channels", "num_classes")
+            if k in cfg}, list(conf["patch_size"])
+
+
+def anisotropic_stages(pools, kernels):
+    """Per-stage (stride, kernel) 3-tuples of an anisotropic PlainConvUNet plan, checked against what the kernels build:
+    conv_kernel_sizes [kd, 3, 3] with kd 1 or 3, pool_op_kernel_sizes 1 or 2 on each axis, stage 0 unpooled."""
+    if len(kernels) != len(pools):
+        raise NotImplementedError(f"plans list {len(pools)} pool_op_kernel_sizes but {len(kernels)} conv_kernel_sizes")
+    for i, (p, k) in enumerate(zip(pools, kernels)):
+        if len(k) != 3 or k[0] not in (1, 3) or list(k[1:]) != [3, 3]:
+            raise NotImplementedError(f"stage {i}: conv_kernel_sizes {list(k)} is not built (supported: [1, 3, 3] and [3, 3, 3])")
+        if len(p) != 3 or any(a not in (1, 2) for a in p):
+            raise NotImplementedError(f"stage {i}: pool_op_kernel_sizes {list(p)} is not built (supported: 1 or 2 on each axis)")
+    if list(pools[0]) != [1, 1, 1]:
+        raise NotImplementedError(f"stage 0: pool_op_kernel_sizes {list(pools[0])} is not built (stage 0 is unpooled: [1, 1, 1])")
+    for i, p in enumerate(pools[1:], 1):
+        if list(p) == [1, 1, 1]:
+            raise NotImplementedError(f"stage {i}: pool_op_kernel_sizes [1, 1, 1] below stage 0 is not built")
+    return tuple(tuple(int(a) for a in p) for p in pools), tuple(tuple(int(a) for a in k) for k in kernels)
 
 
 def trainer_hooks(trainer_name):

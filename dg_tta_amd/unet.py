@@ -38,13 +38,20 @@ def _pad(c, m):
 
 
 # ------------------------------------------------------------------------------------------------ parameter holders
+def _k3(k):
+    return tuple(k) if isinstance(k, (tuple, list)) else (k, k, k)
+
+
 class HipConv3d(nn.Module):
-    """Parameter holder for a 3x3x3 / 1x1x1 conv (weights in PyTorch layout so checkpoints load unchanged)."""
+    """Parameter holder for a 3x3x3 / 1x1x1 conv (weights in PyTorch layout so checkpoints load unchanged).  An anisotropic
+    layer (kernel (kd, 3, 3) or a per-axis stride, from anisotropic plans) keeps tuples in kernel_size / stride and aniso=True;
+    an isotropic one keeps today's ints."""
 
     def __init__(self, cin, cout, k, stride):
         super().__init__()
         self.in_channels, self.out_channels, self.kernel_size, self.stride = cin, cout, k, stride
-        self.weight = nn.Parameter(torch.empty(cout, cin, k, k, k))
+        self.aniso = isinstance(k, tuple) or isinstance(stride, tuple)
+        self.weight = nn.Parameter(torch.empty(cout, cin, *_k3(k)))
         self.bias = nn.Parameter(torch.empty(cout))
 
 
@@ -52,8 +59,18 @@ class HipConvTranspose3d(nn.Module):
     def __init__(self, cin, cout, k):
         super().__init__()
         self.in_channels, self.out_channels, self.kernel_size = cin, cout, k
-        self.weight = nn.Parameter(torch.empty(cin, cout, k, k, k))
+        self.aniso = isinstance(k, tuple)       # kernel = stride (kd, kh, kw) other than (2, 2, 2)
+        self.weight = nn.Parameter(torch.empty(cin, cout, *_k3(k)))
         self.bias = nn.Parameter(torch.empty(cout))
+
+
+def layer_geometry(kernel, stride):
+    """(kernel, stride) as a conv layer holds them: ints for a 3x3x3 kernel with an isotropic stride (the k3 kernels), tuples
+    otherwise (the anisotropic kernels)."""
+    k, s = _k3(kernel), _k3(stride)
+    if k == (3, 3, 3) and len(set(s)) == 1:
+        return 3, s[0]
+    return k, s
 
 
 class HipInstanceNorm3d(nn.Module):
@@ -71,18 +88,18 @@ class HipLeakyReLU(nn.Module):
 
 
 class ConvNormAct(nn.Module):
-    def __init__(self, cin, cout, stride):
+    def __init__(self, cin, cout, stride, kernel=3):
         super().__init__()
-        self.conv = HipConv3d(cin, cout, 3, stride)
+        self.conv = HipConv3d(cin, cout, *layer_geometry(kernel, stride))
         self.norm = HipInstanceNorm3d(cout)
         self.nonlin = HipLeakyReLU()
         self.all_modules = nn.Sequential(self.conv, self.norm, self.nonlin)
 
 
 class StackedConvs(nn.Module):
-    def __init__(self, n, cin, cout, first_stride):
+    def __init__(self, n, cin, cout, first_stride, kernel=3):
         super().__init__()
-        self.convs = nn.Sequential(*[ConvNormAct(cin if i == 0 else cout, cout, first_stride if i == 0 else 1)
+        self.convs = nn.Sequential(*[ConvNormAct(cin if i == 0 else cout, cout, first_stride if i == 0 else 1, kernel)
                                      for i in range(n)])
 
 
@@ -90,8 +107,9 @@ class Encoder(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         stages, cin = [], cfg["in_channels"]
-        for f, s, n in zip(cfg["features"], cfg["strides"], cfg["n_conv_enc"]):
-            stages.append(nn.Sequential(StackedConvs(n, cin, f, s)))
+        kernels = cfg.get("kernel_sizes") or (3,) * len(cfg["features"])
+        for f, s, n, k in zip(cfg["features"], cfg["strides"], cfg["n_conv_enc"], kernels):
+            stages.append(nn.Sequential(StackedConvs(n, cin, f, s, k)))
             cin = f
         self.stages = nn.Sequential(*stages)
 
@@ -101,12 +119,15 @@ class Decoder(nn.Module):
         super().__init__()
         self.encoder = encoder
         f, st = cfg["features"], cfg["strides"]
+        kernels = cfg.get("kernel_sizes") or (3,) * len(f)
         stages, ups, segs = [], [], []
         for s in range(1, len(f)):
             below, skip = f[-s], f[-(s + 1)]
-            assert st[-s] == 2, "only stride-2 (kernel-2) transposed convolutions are built"
-            ups.append(HipConvTranspose3d(below, skip, 2))
-            stages.append(StackedConvs(cfg["n_conv_dec"][s - 1], 2 * skip, skip, 1))
+            up = _k3(st[-s])
+            assert all(a in (1, 2) for a in up) and up != (1, 1, 1), f"transposed conv of stride {st[-s]} is not built"
+            # kernel = stride (nnU-Net's rule); the decoder convs use the kernel of the skip's encoder stage
+            ups.append(HipConvTranspose3d(below, skip, 2 if up == (2, 2, 2) else up))
+            stages.append(StackedConvs(cfg["n_conv_dec"][s - 1], 2 * skip, skip, 1, kernels[-(s + 1)]))
             segs.append(HipConv3d(skip, cfg["num_classes"], 1, 1))
         self.stages = nn.ModuleList(stages)
         self.transpconvs = nn.ModuleList(ups)
@@ -124,7 +145,9 @@ class HipPlainConvUNet(nn.Module):
 
     act_dtype: torch.float32 (parity mode), torch.bfloat16 or torch.float16 (16-bit storage + MFMA, fp32 accumulation;
     fp16 carries 3 more mantissa bits than bf16 and needs `loss_scale` for its gradients: BASELINE config 5).
-    conv_impl: 0 auto (MFMA where covered, else general VALU kernel), 1 force VALU, 2 force MFMA.
+    conv_impl: 0 auto (MFMA where covered, else general VALU kernel), 1 force VALU, 2 force MFMA.  It applies to the 3x3x3
+    layers with isotropic strides; the anisotropic layers of anisotropic plans (cfg "kernel_sizes" (kd, 3, 3) / per-axis
+    "strides") always run their matrix-core kernels (dgtta_conv3d_fwd / _dgrad / _wgrad, dgtta_convT3d_s_*).
     """
 
     def __init__(self, cfg=None, act_dtype=torch.float32, conv_impl=0):
@@ -289,6 +312,25 @@ class HipPlainConvUNet(nn.Module):
         return wpack
 
 
+    def kpacked(self, conv, dt, cinp, coutp):
+        """Packed weight blob of an anisotropic conv (dgtta_conv3d_kpack_weights), re-packed only when the parameter changed."""
+        w = conv.weight
+        key = (id(w), dt, cinp, coutp, "k")
+        ent = self._packed.get(key)
+        if ent is not None and ent[0] == w._version and ent[1].device == w.device:
+            return ent[1]
+        lib = _lib.load()
+        tdt = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}[dt]
+        kd, kh, kw = conv.kernel_size
+        nbytes = lib.dgtta_conv3d_kpacked_bytes(kd, cinp, coutp, dt)
+        wpack = torch.empty(nbytes // tdt.itemsize, dtype=tdt, device=w.device)
+        wsrc = w.detach().contiguous()
+        check(lib.dgtta_conv3d_kpack_weights(ptr(wsrc), ptr(wpack), kd, kh, kw, conv.in_channels, conv.out_channels, cinp, coutp,
+                                             dt, stream_of(w.device)), "dgtta_conv3d_kpack_weights")
+        self._packed[key] = (w._version, wpack)
+        return wpack
+
+
 class Grad16Sink:
     """Side channel for the gradient of the network output in the 16-bit storage type (see HipPlainConvUNet.forward):
     `put` by the loss backward, taken by _UNetFn.backward of the same pass."""
@@ -341,11 +383,18 @@ class _UNetFn(torch.autograd.Function):
         B, cin0, D, H, W = x.shape
         assert cin0 == cfg["in_channels"], f"expected {cfg['in_channels']} input channels, got {cin0}"
         nst = len(cfg["features"])
-        tot_stride = 1
-        for s in cfg["strides"]:
-            tot_stride *= s
-        assert D % tot_stride == 0 and H % tot_stride == 0 and W % tot_stride == 0, \
-            f"patch {D}x{H}x{W} must be divisible by {tot_stride}"
+        if all(isinstance(s, int) for s in cfg["strides"]):
+            tot_stride = 1
+            for s in cfg["strides"]:
+                tot_stride *= s
+            assert D % tot_stride == 0 and H % tot_stride == 0 and W % tot_stride == 0, \
+                f"patch {D}x{H}x{W} must be divisible by {tot_stride}"
+        else:       # anisotropic plan: per axis
+            tot = [1, 1, 1]
+            for s in cfg["strides"]:
+                tot = [a * b for a, b in zip(tot, _k3(s))]
+            assert D % tot[0] == 0 and H % tot[1] == 0 and W % tot[2] == 0, \
+                f"patch {D}x{H}x{W} must be divisible by {tot[0]}x{tot[1]}x{tot[2]} (the product of the strides per axis)"
         enc, dec = net.conv_blocks()
         CP = 8 if dt == F32 else 16      # channel padding granule of packed weights / first-layer input
 
@@ -378,9 +427,10 @@ class _UNetFn(torch.autograd.Function):
             s = conv.stride
             cout = conv.out_channels
             di, hi, wi = dims_in
-            do, ho, wo = _odim(di, s), _odim(hi, s), _odim(wi, s)
+            s3 = _k3(s)
+            do, ho, wo = _odim(di, s3[0]), _odim(hi, s3[1]), _odim(wi, s3[2])
             cinp, coutp = _pad(cin, CP), _pad(cout, CP)
-            wpack = net.packed(conv, dt, cinp, coutp)
+            wpack = net.kpacked(conv, dt, cinp, coutp) if conv.aniso else net.packed(conv, dt, cinp, coutp)
             y = torch.empty((B, do, ho, wo, cout), dtype=adt, device=dev)
             # InstanceNorm statistics ride on the conv epilogue (one reusable buffer: conv -> finalize are stream ordered)
             sbytes = lib.dgtta_conv3d_stats_bytes(B, cout, do, ho, wo)
@@ -391,7 +441,10 @@ class _UNetFn(torch.autograd.Function):
             if pr is not None:       # bench.py: time this layer's conv launch with events on the launch stream
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
-            if xbs:      # the input is the level-0 concat buffer as two 32-channel planes (see the encoder loop)
+            if conv.aniso:      # (kd, 3, 3) kernel / per-axis stride: the anisotropic kernels (csrc/conv_aniso.hip)
+                check(lib.dgtta_conv3d_fwd(u, ldu, ptr(wpack), ptr(conv.bias), ptr(y), cout, ptr(stats), B, cin, cout, cinp, coutp,
+                                           di, hi, wi, conv.kernel_size[0], *s3, dt, st), "dgtta_conv3d_fwd")
+            elif xbs:      # the input is the level-0 concat buffer as two 32-channel planes (see the encoder loop)
                 check(lib.dgtta_conv3d_k3_fwd_blocked(u, xbs, ptr(wpack), ptr(conv.bias), ptr(y), cout, ptr(stats), B, cin, cout, cinp,
                                                       coutp, di, hi, wi, dt, st), "dgtta_conv3d_k3_fwd_blocked")
             else:
@@ -434,15 +487,19 @@ class _UNetFn(torch.autograd.Function):
                 last = bi == len(blocks) - 1
                 z_out, ldz = None, None
                 if last and si < nst - 1:
-                    s = blk.conv.stride
-                    do, ho, wo = _odim(dims[0], s), _odim(dims[1], s), _odim(dims[2], s)
+                    s = _k3(blk.conv.stride)
+                    do, ho, wo = _odim(dims[0], s[0]), _odim(dims[1], s[1]), _odim(dims[2], s[2])
                     # Round 6: where a HALF of the concat buffer is 64 bytes per voxel (32 channels of 16-bit values: level 0), the
                     # two halves are kept as dense PLANES [up | skip] instead of interleaved rows of 2 C channels: the kernels that
                     # read one half (the stride-2 conv of the skip below, its weight gradient, the transposed conv's backward) then
                     # use whole 128-byte lines (the memory side moves whole lines: 4.3x the input fetched before, r05_ab.txt).
                     # The decoder conv that reads BOTH halves takes them as 32-channel blocks (dgtta_conv3d_k3_fwd_blocked) - where
                     # the ring kernels run (asked up front); DGTTA_PLANAR_CAT=0: the interleaved layout everywhere.
+                    # (the layers that read this buffer - the next stage's first conv, the decoder's first conv of this level, the
+                    # transposed conv - all isotropic: the anisotropic kernels take the interleaved layout)
+                    dk = nst - 2 - si
                     planar = (cstage * esz == 64 and impl != 1 and os.environ.get("DGTTA_PLANAR_CAT", "1") != "0"
+                              and not (enc[si + 1][0].conv.aniso or dec[dk][0].conv.aniso or net.decoder.transpconvs[dk].aniso)
                               and os.environ.get("DGTTA_SPLIT_CAT_GRAD", "1") != "0"
                               and lib.dgtta_conv3d_k3_blocked_supported(B, 2 * cstage, cstage, do, ho, wo, dt) == 1)
                     if planar:
@@ -464,12 +521,19 @@ class _UNetFn(torch.autograd.Function):
         for k, blocks in enumerate(dec):
             cat, cskip, cdims, cat_xbs = cat_bufs[-(k + 1)]
             up = net.decoder.transpconvs[k]
-            nbt = lib.dgtta_convT3d_fwd_ws_bytes(x_low_c, cskip, dt)
-            wst = ws_for(nbt)
             cat_ld = cskip if cat_xbs else 2 * cskip           # (planes: the up half is the dense tensor at the buffer's start)
-            check(lib.dgtta_convT3d_k2s2_fwd(x_low_ptr, x_low_ld, ptr(up.weight), ptr(up.bias), ptr(cat), cat_ld,
-                                             ptr(wst), nbt, B, x_low_c, cskip, low_dims[0], low_dims[1], low_dims[2], dt,
-                                             impl, st), "dgtta_convT3d_k2s2_fwd")
+            if up.aniso:
+                nbt = lib.dgtta_convT3d_s_fwd_ws_bytes(x_low_c, cskip, *up.kernel_size, dt)
+                wst = ws_for(nbt)
+                check(lib.dgtta_convT3d_s_fwd(x_low_ptr, x_low_ld, ptr(up.weight), ptr(up.bias), ptr(cat), cat_ld, ptr(wst), nbt, B,
+                                              x_low_c, cskip, low_dims[0], low_dims[1], low_dims[2], *up.kernel_size, dt, st),
+                      "dgtta_convT3d_s_fwd")
+            else:
+                nbt = lib.dgtta_convT3d_fwd_ws_bytes(x_low_c, cskip, dt)
+                wst = ws_for(nbt)
+                check(lib.dgtta_convT3d_k2s2_fwd(x_low_ptr, x_low_ld, ptr(up.weight), ptr(up.bias), ptr(cat), cat_ld,
+                                                 ptr(wst), nbt, B, x_low_c, cskip, low_dims[0], low_dims[1], low_dims[2], dt,
+                                                 impl, st), "dgtta_convT3d_k2s2_fwd")
             ups.append(dict(mod=up, x=x_low_ptr, ldx=x_low_ld, cin=x_low_c, cout=cskip, din=low_dims, cat=cat))
             u_ptr, ldu, cin, dims = cat.data_ptr(), cat_ld, 2 * cskip, cdims
             for bi, blk in enumerate(blocks):
@@ -696,7 +760,9 @@ class _UNetFn(torch.autograd.Function):
             if want(conv.weight) or want(conv.bias):
                 # fp32 storage: offer the split workspace - the weight gradient then runs as six launches of the
                 # 16-bit matrix-core kernels on exact three-term bf16 splits of x and dy (csrc/conv_wgrad.hip, round 5)
-                if dt == F32 and impl != 1 and (s == 1 or not ((di | hi | wi) & 1)):
+                if conv.aniso:
+                    nb = lib.dgtta_conv3d_kwgrad_ws_bytes(B, cin, cout, di, hi, wi, conv.kernel_size[0], *s)
+                elif dt == F32 and impl != 1 and (s == 1 or not ((di | hi | wi) & 1)):
                     nb = lib.dgtta_conv3d_wgrad_split_ws_bytes(B, cin, cout, do, ho, wo, s)
                 else:
                     nb = lib.dgtta_conv3d_wgrad_ws_bytes(B, cin, cout, do, ho, wo)
@@ -720,7 +786,10 @@ class _UNetFn(torch.autograd.Function):
                     wstream = main_stream if side is None else side
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record(wstream)
-                if rec["xbs"]:      # x = the level-0 concat buffer as two 32-channel planes
+                if conv.aniso:
+                    check(lib.dgtta_conv3d_wgrad(rec["u"], rec["ldu"], ptr(dy), cout, ptr(dw), ptr(db), ptr(w_), nb, B, cin, cout, di,
+                                                 hi, wi, conv.kernel_size[0], *s, ACC, dt, st_w), "dgtta_conv3d_wgrad")
+                elif rec["xbs"]:      # x = the level-0 concat buffer as two 32-channel planes
                     check(lib.dgtta_conv3d_k3_wgrad_blocked(rec["u"], rec["xbs"], ptr(dy), cout, ptr(dw), ptr(db), ptr(w_), nb, B,
                                                             cin, cout, di, hi, wi, ACC, dt, st_w), "dgtta_conv3d_k3_wgrad_blocked")
                 else:
@@ -733,12 +802,16 @@ class _UNetFn(torch.autograd.Function):
             where = rec["where"]
             if idx == 0:
                 break
-            wb = net.packed(conv, dt, rec["cinp"], rec["coutp"])
+            wb = net.kpacked(conv, dt, rec["cinp"], rec["coutp"]) if conv.aniso else net.packed(conv, dt, rec["cinp"], rec["coutp"])
             kind, sidx, bidx = where
+
+            def dgrad_aniso(dst, ld_dst, accumulate):
+                check(lib.dgtta_conv3d_dgrad(ptr(dy), cout, ptr(wb), dst, ld_dst, B, cin, cout, rec["cinp"], rec["coutp"], di, hi,
+                                             wi, conv.kernel_size[0], *s, accumulate, dt, st), "dgtta_conv3d_dgrad")
             if kind == "dec" and bidx == 0:
                 # input was the concat buffer of decoder stage sidx: gradient for [up | skip]
                 cat, cskip, cdims, cat_xbs = cat_bufs[-(sidx + 1)]
-                if cskip * esz == 64 and (cat_xbs or os.environ.get("DGTTA_SPLIT_CAT_GRAD", "1") != "0"):
+                if cskip * esz == 64 and not conv.aniso and (cat_xbs or os.environ.get("DGTTA_SPLIT_CAT_GRAD", "1") != "0"):
                     # 32 channels of 16-bit values = HALF a 128-byte line: as one [voxel][2 C] tensor every consumer of ONE half of this
                     # gradient (the transposed conv's backward, the stride-2 data gradient's accumulate, the InstanceNorm backward
                     # of the skip block) would fetch whole lines and use 64 bytes of each (profiles/r05_ab.txt, fetch_calib.sh).
@@ -756,38 +829,48 @@ class _UNetFn(torch.autograd.Function):
                     gc = torch.empty_like(cat)
                     gcat[sidx] = (gc, gc.data_ptr() + cskip * esz, 2 * cskip)
                     gc_ld = 2 * cskip
-                    check(lib.dgtta_conv3d_k3_dgrad(ptr(dy), cout, ptr(wb), ptr(gc), 2 * cskip, B, cin, cout, rec["cinp"],
-                                                    rec["coutp"], di, hi, wi, s, 0, dt, impl, st), "dgtta_conv3d_k3_dgrad")
+                    if conv.aniso:
+                        dgrad_aniso(ptr(gc), 2 * cskip, 0)
+                    else:
+                        check(lib.dgtta_conv3d_k3_dgrad(ptr(dy), cout, ptr(wb), ptr(gc), 2 * cskip, B, cin, cout, rec["cinp"],
+                                                        rec["coutp"], di, hi, wi, s, 0, dt, impl, st), "dgtta_conv3d_k3_dgrad")
                 # transposed-conv backward: dout = first half of the concat gradient
                 up = ups[sidx]
                 upm = up["mod"]
                 ld0, lh0, lw0 = up["din"]
                 glow = torch.empty((B, ld0, lh0, lw0, up["cin"]), dtype=adt, device=dev)
                 # fp32 storage: room for the weight gradient as six 16-bit launches on exact bf16 splits (as for the 3x3x3 convs)
-                nb = (lib.dgtta_convT3d_bwd_split_ws_bytes if dt == F32 and impl != 1 else
-                      lib.dgtta_convT3d_bwd_ws_bytes)(B, up["cin"], up["cout"], ld0, lh0, lw0)
+                if upm.aniso:
+                    nb = lib.dgtta_convT3d_s_bwd_ws_bytes(B, up["cin"], up["cout"], ld0, lh0, lw0, *upm.kernel_size)
+                else:
+                    nb = (lib.dgtta_convT3d_bwd_split_ws_bytes if dt == F32 and impl != 1 else
+                          lib.dgtta_convT3d_bwd_ws_bytes)(B, up["cin"], up["cout"], ld0, lh0, lw0)
                 w_ = ws_for(nb)
                 need_w = want(upm.weight) or want(upm.bias)
                 dwu = (gbuf(upm.weight) if want(upm.weight) else scratch_like(upm.weight)) if need_w else None
                 dbu = gbuf(upm.bias) if want(upm.bias) else None
+                if upm.aniso:
+                    def convt_bwd(dx, dw, db, ws, stream):
+                        check(lib.dgtta_convT3d_s_bwd(up["x"], up["ldx"], ptr(gc), gc_ld, ptr(upm.weight), dx, up["cin"], dw, db, ws,
+                                                      nb, B, up["cin"], up["cout"], ld0, lh0, lw0, *upm.kernel_size, ACC, dt, stream),
+                              "dgtta_convT3d_s_bwd")
+                else:
+                    def convt_bwd(dx, dw, db, ws, stream):
+                        check(lib.dgtta_convT3d_k2s2_bwd(up["x"], up["ldx"], ptr(gc), gc_ld, ptr(upm.weight), dx, up["cin"], dw, db,
+                                                         ws, nb, B, up["cin"], up["cout"], ld0, lh0, lw0, ACC, dt, impl, stream),
+                              "dgtta_convT3d_k2s2_bwd")
                 if side is None or not need_w:
-                    check(lib.dgtta_convT3d_k2s2_bwd(up["x"], up["ldx"], ptr(gc), gc_ld, ptr(upm.weight), ptr(glow),
-                                                     up["cin"], ptr(dwu), ptr(dbu), ptr(w_), nb, B, up["cin"], up["cout"],
-                                                     ld0, lh0, lw0, ACC, dt, impl, st), "dgtta_convT3d_k2s2_bwd")
+                    convt_bwd(ptr(glow), ptr(dwu), ptr(dbu), ptr(w_), st)
                 else:
                     # data gradient on the main chain, weight / bias gradient (a leaf) on the side stream
                     ev = torch.cuda.Event()
                     ev.record(main_stream)          # gc is complete
-                    check(lib.dgtta_convT3d_k2s2_bwd(up["x"], up["ldx"], ptr(gc), gc_ld, ptr(upm.weight), ptr(glow),
-                                                     up["cin"], None, None, ptr(w_), nb, B, up["cin"], up["cout"],
-                                                     ld0, lh0, lw0, ACC, dt, impl, st), "dgtta_convT3d_k2s2_bwd")
+                    convt_bwd(ptr(glow), None, None, ptr(w_), st)
                     side.wait_event(ev)
                     gc.record_stream(side)
                     with torch.cuda.stream(side):
                         w2 = ws_for(nb, "ws_side")
-                    check(lib.dgtta_convT3d_k2s2_bwd(up["x"], up["ldx"], ptr(gc), gc_ld, ptr(upm.weight), None,
-                                                     up["cin"], ptr(dwu), ptr(dbu), ptr(w2), nb, B, up["cin"], up["cout"],
-                                                     ld0, lh0, lw0, ACC, dt, impl, side.cuda_stream), "dgtta_convT3d_k2s2_bwd")
+                    convt_bwd(None, ptr(dwu), ptr(dbu), ptr(w2), side.cuda_stream)
                 gz_ptr, gz_ld = glow.data_ptr(), up["cin"]
                 keep_alive = [glow, gc, gcat[sidx][0]]
             elif kind == "enc" and bidx == 0:
@@ -796,8 +879,11 @@ class _UNetFn(torch.autograd.Function):
                 prev_stage = sidx - 1
                 dec_k = n_dec_stages - 1 - prev_stage
                 gc, gptr, gld = gcat[dec_k]          # (tensor that owns the skip half, its address, its row pitch)
-                check(lib.dgtta_conv3d_k3_dgrad(ptr(dy), cout, ptr(wb), gptr, gld, B, cin, cout, rec["cinp"],
-                                                rec["coutp"], di, hi, wi, s, 1, dt, impl, st), "dgtta_conv3d_k3_dgrad")
+                if conv.aniso:
+                    dgrad_aniso(gptr, gld, 1)
+                else:
+                    check(lib.dgtta_conv3d_k3_dgrad(ptr(dy), cout, ptr(wb), gptr, gld, B, cin, cout, rec["cinp"],
+                                                    rec["coutp"], di, hi, wi, s, 1, dt, impl, st), "dgtta_conv3d_k3_dgrad")
                 gz_ptr, gz_ld = gptr, gld
                 keep_alive = [gc]
             else:
@@ -805,7 +891,9 @@ class _UNetFn(torch.autograd.Function):
                 # the data gradient can leave the sums of that block's InstanceNorm backward (csrc/conv_rows.hip, GST)
                 gin = torch.empty((B, di, hi, wi, cin), dtype=adt, device=dev)
                 prev = saved[idx - 1]
-                if s == 1 and dt != F32 and prev["cout"] == cin and prev["dout"] == (di, hi, wi):
+                if conv.aniso:      # (no fused InstanceNorm statistics for the anisotropic layers)
+                    dgrad_aniso(ptr(gin), cin, 0)
+                elif s == 1 and dt != F32 and prev["cout"] == cin and prev["dout"] == (di, hi, wi):
                     pn = prev["mod"].norm
                     gbytes = lib.dgtta_conv3d_stats_bytes(B, cin, di, hi, wi)
                     gbuf_ = ws_for(gbytes, "gstats")

@@ -263,6 +263,47 @@ int dgtta_convT3d_k2s2_bwd(const void *x, int ldx, const void *dout, int lddo, c
                            float *dw_t, float *db, void *ws, size_t ws_bytes, int B, int Cin, int Cout, int Di,
                            int Hi, int Wi, int accumulate, int dtype, int impl, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Anisotropic PlainConvUNet layers: what nnU-Net 2.2.1's planner writes for data whose slice spacing is much coarser than
+ * its in-plane spacing (conv_kernel_sizes [kd, 3, 3], pool_op_kernel_sizes with 1 or 2 per axis).  Same conventions as the
+ * k3 family above; a layer with a 3x3x3 kernel and an isotropic stride keeps using the k3 entry points.
+ * Conv3d(Cin, Cout, kernel (kd, 3, 3), stride (sd, sh, sw), padding (kd / 2, 1, 1), bias) with kd in {1, 3} and strides in
+ * {1, 2}; output extent (i + 2 * pad - k) / s + 1 per axis.  Anything else returns DGTTA_ERR_UNSUPPORTED.  x / dy operands:
+ * 16-byte aligned rows (ld a multiple of 16 bytes).  Data and weight gradients of a strided axis need an even input extent.
+ * ------------------------------------------------------------------------------------------- */
+/* packs torch [Cout][Cin][kd][kh][kw] fp32 (kh = kw = 3) into one blob of dgtta_conv3d_kpacked_bytes: the matrix-core images of
+ * the forward (N = Cout, K = Cin) and of the data-gradient (N = Cin, K = Cout) orientation, kd * 9 taps each; CinP / CoutP =
+ * the channel counts zero padded to multiples of 8 (fp32) or 16 (16-bit). */
+size_t dgtta_conv3d_kpacked_bytes(int kd, int CinP, int CoutP, int dtype);
+int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd, int kh, int kw, int Cin, int Cout, int CinP, int CoutP,
+                               int dtype, void *stream);
+/* y[b][vo][co] = bias[co] + sum_{tap,ci} x[b][s*vo + tap - pad][ci] * w[co][ci][tap]   (per axis, zero padding).
+ * stats != NULL: the InstanceNorm partial sums as dgtta_conv3d_k3_fwd leaves them (dgtta_conv3d_stats_bytes of the output);
+ * NULL: dgtta_instnorm_lrelu_fwd computes them from y. */
+int dgtta_conv3d_fwd(const void *x, int ldx, const void *wpack, const float *bias, void *y, int ldy, void *stats, int B, int Cin,
+                     int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int dtype, void *stream);
+/* dx[b][vi][ci] = sum_{tap,co} dy[b][vo][co] * w[co][ci][tap] over s*vo + tap - pad = vi;  accumulate != 0: dx += (the
+ * skip-connection gradient sum).  Di, Hi, Wi: input extent. */
+int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, void *dx, int lddx, int B, int Cin, int Cout, int CinP, int CoutP,
+                       int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, void *stream);
+/* dw_t[co][ci][tap] (+)= sum_{b,vo} x[b][s*vo + tap - pad][ci] * dy[b][vo][co];  db[co] (+)= sum dy (db may be NULL).
+ * fp32 torch layout, fixed summation order (deterministic); accumulate != 0 adds to the existing gradients.
+ * Di, Hi, Wi: INPUT extent (also for the workspace query). */
+size_t dgtta_conv3d_kwgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw);
+int dgtta_conv3d_wgrad(const void *x, int ldx, const void *dy, int lddy, float *dw_t, float *db, void *ws, size_t ws_bytes, int B,
+                       int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype,
+                       void *stream);
+/* ConvTranspose3d(Cin, Cout, kernel = stride = (sd, sh, sw) in {1, 2}^3, not all 1, bias): w_t torch layout
+ * [Cin][Cout][sd][sh][sw] fp32.  out[b][s*v + o][co] = bias[co] + sum_ci x[b][v][ci] * w[ci][co][o].
+ * bwd: dx (overwritten; NULL: skipped), dw_t / db (+)= as for the k2s2 form (NULL: skipped). */
+size_t dgtta_convT3d_s_fwd_ws_bytes(int Cin, int Cout, int sd, int sh, int sw, int dtype);
+int dgtta_convT3d_s_fwd(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws, size_t ws_bytes,
+                        int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, void *stream);
+size_t dgtta_convT3d_s_bwd_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw);
+int dgtta_convT3d_s_bwd(const void *x, int ldx, const void *dout, int lddo, const float *w_t, void *dx, int lddx, float *dw_t,
+                        float *db, void *ws, size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh,
+                        int sw, int accumulate, int dtype, void *stream);
+
 /* 1x1x1 head fused with map_label(input_format="logits") (torch_utils.py:214-221): only the rows
  * sel[0..nsel) of the [Ccls][Cin] weight are evaluated (sel == NULL: all Ccls rows).
  * out fp32: NDHWC [B][V][ldo] (out_ndhwc=1) or NCDHW [B][nsel][V]. */
