@@ -23,6 +23,12 @@ SIGNATURES = {
     "dgtta_gin_chain_fwd": (I, [P, P, C.POINTER(I), C.POINTER(P), C.POINTER(P), P, P, SZ, I, I, I, I, P]),
     "dgtta_affine_warp3d_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P]),
     "dgtta_affine_warp3d_bwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_rf_field_ws_bytes": (SZ, [I, I, I, I]),
+    "dgtta_rf_field_fwd": (I, [P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
+    "dgtta_diffeo_fields_ws_bytes": (SZ, [I, I, I, I]),
+    "dgtta_diffeo_fields": (I, [P, F, P, P, P, SZ, I, I, I, I, I, P]),
+    "dgtta_dense_warp3d_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_dense_warp3d_bwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_softdice_ws_bytes": (SZ, [I, I, I64]),
     "dgtta_softdice_fwd": (I, [P, P, P, P, P, SZ, I, I, I64, I, I, I, P]),
     "dgtta_softdice_bwd": (I, [P, P, P, P, P, F, P, I, I, I64, I, I, P]),

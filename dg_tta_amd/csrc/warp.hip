@@ -4,25 +4,14 @@
 // HBM-bound gather: per output voxel 8 neighbour rows of C channels (L2 absorbs the 8x reuse) + one write;
 // algorithmic bytes = 2 * C * 4 B per voxel.
 #include "common.h"
+#include "sampler.h"
 #include <limits.h>
 
 namespace {
 
-// normalised base coordinate j of n, as at::affine_grid builds it: linspace(-1,1,n) * (n-1) / n
-__device__ __forceinline__ float base_coord(int j, int n) {
-  if (n <= 1) return 0.f;
-  const float step = 2.0f / (float)(n - 1);
-  float v = (j < n / 2) ? (-1.0f + step * (float)j) : (1.0f - step * (float)(n - 1 - j));
-  return (v * (float)(n - 1)) / (float)n;
-}
-
 // (Round 3 measured an XCD-contiguous tile order for these kernels - no gain forward, 20 % slower backward: both wait on L1
 // misses that hit in L2, not on HBM - and a cooperative owner / loader backward, bit-identical and no faster; both prototypes
 // were removed in round 5, the numbers are in DESIGN.md.)
-
-struct Sample {
-  float ix, iy, iz;
-};
 
 __device__ __forceinline__ Sample sample_from_base(const float *th, float x, float y, float z, int Ds, int Hs, int Ws,
                                                    int algebra, int pad_mode);
@@ -52,30 +41,6 @@ __device__ __forceinline__ Sample sample_from_base(const float *th, float x, flo
     s.iz = fminf((float)(Ds - 1), fmaxf(s.iz, 0.f));
   }
   return s;
-}
-
-struct Corners {
-  int x0, y0, z0;
-  float w[8];  // order tnw,tne,tsw,tse,bnw,bne,bsw,bse (t: z0, n: y0, w: x0) as ATen's grid_sampler_3d
-};
-
-__device__ __forceinline__ Corners corners(const Sample &s) {
-  Corners c;
-  const float fx = floorf(s.ix), fy = floorf(s.iy), fz = floorf(s.iz);
-  c.x0 = (int)fx;
-  c.y0 = (int)fy;
-  c.z0 = (int)fz;
-  const float ex = (fx + 1.0f) - s.ix, ey = (fy + 1.0f) - s.iy, ez = (fz + 1.0f) - s.iz;  // weights of the low side
-  const float ux = s.ix - fx, uy = s.iy - fy, uz = s.iz - fz;                                // weights of the high side
-  c.w[0] = ex * ey * ez;
-  c.w[1] = ux * ey * ez;
-  c.w[2] = ex * uy * ez;
-  c.w[3] = ux * uy * ez;
-  c.w[4] = ex * ey * uz;
-  c.w[5] = ux * ey * uz;
-  c.w[6] = ex * uy * uz;
-  c.w[7] = ux * uy * uz;
-  return c;
 }
 
 // VEC channels per thread (NDHWC: contiguous; NCDHW: VEC must be 1 and the thread loops over channels)

@@ -173,6 +173,84 @@ def affine_sample(src, theta, out_size, padding_mode="zeros", mode="bilinear", s
     return _warp_fwd_raw(src.float(), _f32c(theta), tuple(out_size), pad, interp, False, sub_const)
 
 
+# ------------------------------------------------------------------------------------------------ deformable augmentation
+def rf_field(draw, size_3d, box=5):
+    """get_rf_field (augmentation_utils.py:8-43) from its torch.randn draw [B,F,D//k,H//k,W//k]: three `box`^3 mean filters,
+    trilinear upsampling to size_3d, per (sample, field) zero mean and unit (1e-3 + std).  Returns [B,F,D,H,W] fp32."""
+    require_cuda(draw)
+    lib = _lib.load()
+    b, f, dl, hl, wl = draw.shape
+    d, h, w = (int(v) for v in size_3d)
+    draw = _f32c(draw)
+    field = torch.empty((b, f, d, h, w), dtype=torch.float32, device=draw.device)
+    nbytes = lib.dgtta_rf_field_ws_bytes(b * f, dl, hl, wl)
+    ws = _ws(nbytes, draw.device)
+    check(lib.dgtta_rf_field_fwd(ptr(draw), ptr(field), ptr(ws), nbytes, b * f, int(box), dl, hl, wl, d, h, w,
+                                 stream_of(draw.device)), "dgtta_rf_field_fwd")
+    return field
+
+
+def diffeo_fields(field, factor=1.0, time_steps=5):
+    """calc_consistent_diffeomorphic_field(field * factor, zeros, time_steps, ensure_inverse_consistency=True)
+    (augmentation_utils.py:46-135) of field [B,3,D,H,W].  Returns (disp, inverse) as contiguous [B,D,H,W,3]."""
+    require_cuda(field)
+    lib = _lib.load()
+    b, c, d, h, w = field.shape
+    assert c == 3
+    field = _f32c(field)
+    disp = torch.empty((b, d, h, w, 3), dtype=torch.float32, device=field.device)
+    inverse = torch.empty_like(disp)
+    nbytes = lib.dgtta_diffeo_fields_ws_bytes(b, d, h, w)
+    ws = _ws(nbytes, field.device)
+    check(lib.dgtta_diffeo_fields(ptr(field), float(factor), ptr(disp), ptr(inverse), ptr(ws), nbytes, b, d, h, w,
+                                  int(time_steps), stream_of(field.device)), "dgtta_diffeo_fields")
+    return disp, inverse
+
+
+class _DenseWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, disp, pad_mode):
+        lib = _lib.load()
+        b, c, d, h, w = src.shape
+        src, ndhwc, ldc = _warp_layout(src)
+        dst = empty_cl3d(b, c, d, h, w, torch.float32, src.device) if ndhwc else torch.empty_like(src)
+        check(lib.dgtta_dense_warp3d_fwd(ptr(src), ptr(disp), ptr(dst), b, c, d, h, w, ndhwc, ldc, ldc, pad_mode,
+                                         stream_of(src.device)), "dgtta_dense_warp3d_fwd")
+        ctx.save_for_backward(disp)
+        ctx.meta = (tuple(src.shape), pad_mode, bool(ndhwc))
+        return dst
+
+    @staticmethod
+    def backward(ctx, grad):
+        (disp,) = ctx.saved_tensors
+        (b, c, d, h, w), pad_mode, ndhwc = ctx.meta
+        lib = _lib.load()
+        if ndhwc:
+            grad = grad.contiguous(memory_format=torch.channels_last_3d)
+            gsrc = empty_cl3d(b, c, d, h, w, torch.float32, grad.device)
+        else:
+            grad = grad.contiguous()
+            gsrc = torch.empty((b, c, d, h, w), dtype=torch.float32, device=grad.device)
+        check(lib.dgtta_dense_warp3d_bwd(ptr(grad), ptr(disp), ptr(gsrc), b, c, d, h, w, int(ndhwc), c, c, pad_mode,
+                                         stream_of(grad.device)), "dgtta_dense_warp3d_bwd")
+        return gsrc, None, None
+
+
+def dense_warp(src, disp, padding_mode="zeros"):
+    """F.grid_sample(src, (0 * identity + disp) + identity, align_corners=False) with identity = F.affine_grid(eye): the
+    deformable call sites of calc_branch (tta.py:534-551 image, border; :572-575 logits, zeros).
+
+    src [B,C,D,H,W] fp32 (contiguous or channels_last_3d; the layout is preserved), disp [B,D,H,W,3] in (x, y, z) order.
+    Differentiable w.r.t. src only (the fields are constants, as in the reference); that gradient is summed with fp32
+    atomics, so its last bits vary from run to run."""
+    require_cuda(src, disp)
+    if tuple(disp.shape) != (src.shape[0], *src.shape[2:], 3):
+        raise ValueError(f"dense_warp: disp {tuple(disp.shape)} does not belong to src {tuple(src.shape)}")
+    src = src if src.dtype == torch.float32 else src.float()
+    pad = PAD_BORDER if padding_mode == "border" else PAD_ZEROS
+    return _DenseWarp.apply(src, _f32c(disp.detach()), pad)
+
+
 # ------------------------------------------------------------------------------------------------ loss
 class _ConsistencyLoss(torch.autograd.Function):
     @staticmethod

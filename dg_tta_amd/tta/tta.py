@@ -1,7 +1,8 @@
 """TTA driver — the per-sample / per-ensemble / per-epoch / accumulation loops of the reference's
 dg_tta/tta/tta.py (tta_main :93-373, calc_branch :480-579), with every tensor op executed by the HIP kernels:
 
-    get_batch (csrc/warp.hip) -> 2x calc_branch {GIN (gin.hip) -> affine warp, border (warp.hip) -> MIND pre-hook
+    get_batch (csrc/warp.hip) -> 2x calc_branch {GIN (gin.hip) -> affine warp, border (warp.hip; spatial_aug_type
+    "deformable": random diffeomorphic field + dense-grid warp, deform.hip) -> MIND pre-hook
     (mind3d.hip) -> PlainConvUNet fwd (unet_ref.hip / conv_mfma.hip) with map_label fused into the head -> inverse
     warp, zeros (warp.hip)} -> masked softmax + soft-Dice (softdice.hip) -> backward through both branches ->
     AdamW once per epoch (adamw.hip).
@@ -25,7 +26,8 @@ from ..sharding import (done_marker, failed_marker, mark_rank_done, mark_rank_fa
                         wait_for_done_markers, wait_for_files)
 from .._state import state_of
 from ..utils import disable_internal_augmentation, numpy_rng, upload_async
-from .augmentation_utils import get_rand_affine
+from . import augmentation_utils
+from .augmentation_utils import get_disp_field, get_rand_affine, low_res_size
 from .config_log_utils import (get_global_idx, get_parameters_save_path, is_template_modifier, plot_run_results)
 from .model_utils import apply_running_stats, buffer_running_stats, get_model_from_network
 from .torch_utils import (dice_coeff, fix_all, get_batch, get_map_idxs, map_label, release_all, release_norms,
@@ -80,11 +82,12 @@ def calc_branch(branch_id, config, model, intensity_aug_func, identity_grid, pat
                 R, R_inverse = get_rand_affine(batch_size, flip=False)
                 R, R_inverse = upload_async([R.float().contiguous(), R_inverse.float().contiguous()], device)
             elif config["spatial_aug_type"] == "deformable":
-                from .augmentation_utils import get_disp_field
-                get_disp_field()
+                with torch.no_grad():       # a displacement pair [B,D,H,W,3] takes the place of the two matrices
+                    R, R_inverse = get_disp_field(batch_size, list(imgs_aug.shape[2:]), factor=0.5, interpolation_factor=5,
+                                                  device=device)
             else:   # no displacement: identity resampling, as the reference's zero grid does
                 R = R_inverse = torch.eye(4, device=device)[:3][None].repeat(batch_size, 1, 1)
-            imgs_aug = ops.affine_warp(imgs_aug, R, padding_mode="border", tta_grid_algebra=True)
+            imgs_aug = _spatial_warp(imgs_aug, R, "border")
         model.apply(buffer_running_stats if branch_id == "branch_a" else apply_running_stats)
         branch_target = model(imgs_aug)
         if isinstance(branch_target, tuple):
@@ -97,8 +100,15 @@ def calc_branch(branch_id, config, model, intensity_aug_func, identity_grid, pat
         if isinstance(branch_target, tuple):
             branch_target = branch_target[0]
         if spatial:
-            branch_target = ops.affine_warp(branch_target, R_inverse, padding_mode="zeros", tta_grid_algebra=True)
+            branch_target = _spatial_warp(branch_target, R_inverse, "zeros")
         return branch_target
+
+
+def _spatial_warp(t, transform, padding_mode):
+    """A branch carries its spatial augmentation either as theta [B,3,4] or as a dense displacement [B,D,H,W,3]."""
+    if transform.dim() == 5:
+        return ops.dense_warp(t, transform, padding_mode=padding_mode)
+    return ops.affine_warp(t, transform, padding_mode=padding_mode, tta_grid_algebra=True)
 
 
 def calc_both_branches(config, model, intensity_aug_func, patch_size, batch_size, label_mapping, optimized_labels,
@@ -129,6 +139,9 @@ def prepare_both_branches(config, model, intensity_aug_func, batch_size, imgs, d
         augs, inverses, inverses_cpu = [[], []], [[], []], [[], []]
         want_noise = uses_mind_hook(model)
         noise = None
+        # deformable: each branch only DRAWS its low-resolution field noise in the loop (the reference's place in the draw
+        # order); the fields of all 2 * steps branches and the image warps are then evaluated in one launch each
+        field_draw, field_slots = None, []
         for step in range(steps):
             step_imgs = imgs() if callable(imgs) else imgs
             for k, branch_id in enumerate(("branch_a", "branch_b")):
@@ -142,11 +155,18 @@ def prepare_both_branches(config, model, intensity_aug_func, batch_size, imgs, d
                         R_inverse_cpu = R_inverse.float().contiguous()
                         R, R_inverse = upload_async([R.float().contiguous(), R_inverse_cpu], device)
                     elif config["spatial_aug_type"] == "deformable":
-                        from .augmentation_utils import get_disp_field
-                        get_disp_field()
+                        nb_ = imgs_aug.shape[0]
+                        if field_draw is None:
+                            low = low_res_size(imgs_aug.shape[2:], 5)
+                            field_draw = torch.empty((2 * steps * nb_, 3) + low, dtype=torch.float32, device=imgs_aug.device)
+                        slot = k * steps + step
+                        augmentation_utils.draw_field_noise_(field_draw[slot * nb_:(slot + 1) * nb_])
+                        field_slots.append(slot)
+                        R = None
                     else:
                         R = R_inverse = torch.eye(4, device=device)[:3][None].repeat(batch_size, 1, 1)
-                    imgs_aug = ops.affine_warp(imgs_aug, R, padding_mode="border", tta_grid_algebra=True)
+                    if R is not None:
+                        imgs_aug = ops.affine_warp(imgs_aug, R, padding_mode="border", tta_grid_algebra=True)
                 augs[k].append(imgs_aug)
                 inverses[k].append(R_inverse)
                 inverses_cpu[k].append(R_inverse_cpu)
@@ -158,12 +178,28 @@ def prepare_both_branches(config, model, intensity_aug_func, batch_size, imgs, d
                     slot = k * steps + step
                     draw_noise_(noise[slot * nb_:(slot + 1) * nb_])
         x = torch.cat(augs[0] + augs[1], dim=0)     # all of branch a (step order), then all of branch b
+        inverse_disp = None
+        if field_draw is not None:
+            per_ = x.shape[0] // (2 * steps)
+            if len(field_slots) < 2 * steps:        # do_spatial_aug_in names one branch: only its slots hold a draw
+                rows = torch.cat([torch.arange(s_ * per_, (s_ + 1) * per_) for s_ in sorted(field_slots)]).to(x.device)
+                disp, inv = get_disp_field(rows.numel(), list(x.shape[2:]), factor=0.5, interpolation_factor=5, device=device,
+                                           draw=field_draw[rows])
+                x[rows] = ops.dense_warp(x[rows], disp, padding_mode="border")
+                for j, s_ in enumerate(sorted(field_slots)):
+                    inverses[s_ // steps][s_ % steps] = inv[j * per_:(j + 1) * per_]
+            else:
+                disp, inverse_disp = get_disp_field(x.shape[0], list(x.shape[2:]), factor=0.5, interpolation_factor=5,
+                                                    device=device, draw=field_draw)
+                x = ops.dense_warp(x, disp, padding_mode="border")
+                for s_ in range(2 * steps):
+                    inverses[s_ // steps][s_ % steps] = inverse_disp[s_ * per_:(s_ + 1) * per_]
         feat = None
         if want_noise and precompute_mind:
             feat = MIND3D().forward(x, noise=noise, out_dtype=getattr(model, "act_dtype", torch.float32), groups=2 * steps)
             noise = None
     return {"x": x, "inverses": inverses[0] + inverses[1], "inverses_cpu": inverses_cpu[0] + inverses_cpu[1], "noise": noise,
-            "feat": feat, "per": augs[0][0].shape[0], "want_noise": want_noise}
+            "feat": feat, "per": augs[0][0].shape[0], "want_noise": want_noise, "inverse_disp": inverse_disp}
 
 
 def run_both_branches(prepared, config, model, label_mapping, optimized_labels, modifier_fn_module, head_is_fused=False,
@@ -202,7 +238,9 @@ def run_both_branches(prepared, config, model, label_mapping, optimized_labels, 
             both = both[0]
         if fast:
             if not fused_warp:
-                both = ops.affine_warp(both, torch.cat(inverses, dim=0), padding_mode="zeros", tta_grid_algebra=True)
+                # (deformable: the slices of `inverses` are views of one tensor, in this order)
+                inv_all = prepared.get("inverse_disp")
+                both = _spatial_warp(both, torch.cat(inverses, dim=0) if inv_all is None else inv_all, "zeros")
             ta, tb = both[:nb], both[nb:]
             ta._dgtta_pair = tb._dgtta_pair = both
             ta._dgtta_guard_items = tb._dgtta_guard_items = per
@@ -217,7 +255,7 @@ def run_both_branches(prepared, config, model, label_mapping, optimized_labels, 
             if isinstance(t, tuple):
                 t = t[0]
             if inverses[j] is not None:
-                t = ops.affine_warp(t, inverses[j], padding_mode="zeros", tta_grid_algebra=True)
+                t = _spatial_warp(t, inverses[j], "zeros")
             pieces.append(t)
         targets = [torch.cat(pieces[:steps], dim=0) if steps > 1 else pieces[0],
                    torch.cat(pieces[steps:], dim=0) if steps > 1 else pieces[1]]

@@ -99,6 +99,40 @@ int dgtta_affine_warp3d_bwd(const float *grad_dst, const float *theta, float *gr
                             int pad_mode, int tta_grid_algebra, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Deformable spatial augmentation (spatial_aug_type = "deformable").  Replaces get_rf_field and the
+ * inverse-consistent branch of calc_consistent_diffeomorphic_field (dg_tta/tta/augmentation_utils.py:8-43,
+ * :46-135) as get_disp_field composes them (:138-153, without the keyword get_rf_field does not take), and
+ * the two F.grid_sample calls of calc_branch through the dense grids (dg_tta/tta/tta.py:534-575).  fp32 only.
+ *
+ * rf_field: draw [P][Dl][Hl][Wl] = the torch.randn draw of P = batch * fields planes (the caller supplies it,
+ * so RNG semantics stay the caller's) -> three k^3 box filters (avg_pool3d, stride 1, padding k/2 counted in
+ * the divisor; k odd, every low-resolution axis >= k) -> trilinear upsampling to [P][D][H][W]
+ * (align_corners=False) -> per plane (x - mean) / (1e-3 + unbiased std).  ws: dgtta_rf_field_ws_bytes.
+ *
+ * diffeo_fields: field [N][3][D][H][W] -> disp, inverse [N][D][H][W][3] (the permuted layout the reference
+ * returns): field * factor / [D,H,W] / 2^time_steps / time_steps, time_steps iterations of
+ * d' = d/2 - sample(i, id + d)/2, i' = i/2 - sample(d, id + i)/2 (grid_sample border, align_corners=True,
+ * inverse starting at 0), then * 2^time_steps * [D,H,W].  As the reference writes it, channel c is scaled by
+ * the c-th of (D, H, W) while it displaces the c-th of (x, y, z).  ws: dgtta_diffeo_fields_ws_bytes.
+ *
+ * dense_warp3d: dst = F.grid_sample(src, (0 * identity + disp) + identity, align_corners=False), identity =
+ * F.affine_grid(eye) evaluated in the kernel; src / dst [B,C,D,H,W] NCDHW or NDHWC as in dgtta_affine_warp3d_*,
+ * disp [B][D][H][W][3] (x, y, z).  bwd: grad_src = adjoint w.r.t. src (disp gets no gradient; the fields are
+ * built without autograd in the reference).  grad_src is overwritten; it is summed with fp32 atomics, so its
+ * last bits depend on the order in which the additions arrive.
+ * ------------------------------------------------------------------------------------------- */
+size_t dgtta_rf_field_ws_bytes(int P, int Dl, int Hl, int Wl);
+int dgtta_rf_field_fwd(const float *draw, float *field, void *ws, size_t ws_bytes, int P, int k, int Dl, int Hl, int Wl,
+                       int D, int H, int W, void *stream);
+size_t dgtta_diffeo_fields_ws_bytes(int N, int D, int H, int W);
+int dgtta_diffeo_fields(const float *field, float factor, float *disp, float *inverse, void *ws, size_t ws_bytes, int N,
+                        int D, int H, int W, int time_steps, void *stream);
+int dgtta_dense_warp3d_fwd(const float *src, const float *disp, float *dst, int B, int C, int D, int H, int W, int ndhwc,
+                           int src_ldc, int dst_ldc, int pad_mode, void *stream);
+int dgtta_dense_warp3d_bwd(const float *grad_dst, const float *disp, float *grad_src, int B, int C, int D, int H, int W,
+                           int ndhwc, int src_ldc, int dst_ldc, int pad_mode, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Consistency loss.  Replaces dg_tta/tta/tta.py:263-271 + soft_dice_loss (torch_utils.py:90-104):
  * mask=(sum_c a>0)(sum_c b>0); sm=softmax_c * mask; dice_c = mean(2ab)/mean((a+b)^2/2);
  * loss = 1 - mean_{b, c>=start_class} dice.  la, lb: logits NDHWC [B][V][ldc], C classes, fp32.
