@@ -416,3 +416,34 @@ def test_checkpoint_that_does_not_fit_says_what_differs(tmp_path):
     msg = str(e.value)
     assert k0 in msg and "encoder.stages.0.0.convs.0.conv.kernel" in msg and k1 in msg and "checkpoint_final.pth" in msg
     assert "missing in the file (1)" in msg and "not known to the network (1)" in msg and "shape differs (1)" in msg
+
+
+@pytest.mark.parametrize("origins,w", [
+    ([(0, 0, 0)], 20),                                                              # a single window
+    ([(0, 0, 0), (0, 0, 10), (0, 0, 20), (0, 0, 27)], 20),                          # a row with a ragged last step
+    ([(2, 1, 0), (2, 1, 3), (2, 1, 6), (2, 1, 9), (2, 1, 12), (2, 1, 15), (2, 1, 17)], 16),   # step < w / 4: > 4 windows on a voxel
+    ([(0, 0, 0), (0, 0, 8), (0, 5, 0), (0, 5, 8), (4, 0, 0), (4, 0, 8), (4, 5, 3)], 12),      # rows that change x / y
+    ([(0, 0, 10), (0, 0, 0), (0, 0, 5), (0, 0, 30), (0, 0, 30), (0, 0, 12)], 10),   # non-monotonic z, a repeated origin, a gap
+])
+def test_window_segments_emit_every_window_position_once(origins, w):
+    """unet_exec.window_segments against a brute-force count per (window, position of the last axis): every pair is emitted
+    exactly once, no launch covers more than four windows, the windows of one launch share x / y and cover its whole segment."""
+    from dg_tta_amd.unet_exec import window_segments
+    expected = {(k, z): 1 for k, o in enumerate(origins) for z in range(o[2], o[2] + w)}
+    seen = {}
+    for launch in window_segments(origins, w):
+        if isinstance(launch, int):
+            part, a, b = [launch], origins[launch][2], origins[launch][2] + w
+        else:
+            sx, sy, a, b, part = launch
+            assert 2 <= len(set(part)) == len(part) <= 4 or len(part) == 1
+            assert all(origins[k][:2] == (sx, sy) for k in part)
+        assert a < b and len(part) <= 4
+        for k in part:
+            assert origins[k][2] <= a and b <= origins[k][2] + w
+            for z in range(a, b):
+                seen[(k, z)] = seen.get((k, z), 0) + 1
+    assert seen == expected
+    # a smaller cover limit splits the launches, nothing else
+    for launch in window_segments(origins, w, max_cover=2):
+        assert isinstance(launch, int) or len(launch[4]) <= 2

@@ -373,6 +373,7 @@ def test_feature_window_accumulate_kernel(dts):
     # segments of windows that overlap along the last axis (three windows at z = 3, 9, 14 of a row: up to three on a voxel), with and
     # without the folded InstanceNorm apply, against the same windows one by one: the same bits
     import ctypes as C
+    from dg_tta_amd.unet_exec import window_segments
     zs = [3, 9, 14]
     y = torch.randn(len(zs), *P, 32, device=DEV).to(tdt)
     mr = torch.stack([torch.randn(len(zs), 32, device=DEV), torch.rand(len(zs), 32, device=DEV) + 0.5], -1).contiguous()
@@ -387,16 +388,16 @@ def test_feature_window_accumulate_kernel(dts):
                 check(lib.dgtta_feature_window_accumulate(ptr(y[k]), ptr(gauss), ptr(one_f), ptr(one_n), 32, *P, X, Y, Z, 2, 1, sz, dt,
                                                           stream_of()), "plain")
         seg_f, seg_n = facc.clone(), nsum.clone()
-        cuts = sorted(set(zs + [v + P[2] for v in zs]))
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            cover = [k for k, sz in enumerate(zs) if sz <= a and b <= sz + P[2]]
+        launches = window_segments([(2, 1, sz) for sz in zs], P[2])
+        for sx, sy, a, b, cover in launches:
+            assert (sx, sy) == (2, 1)
             srcs = (C.c_void_p * len(cover))(*[y[k].data_ptr() for k in cover])
             mrs = (C.c_void_p * len(cover))(*[mr[k].data_ptr() for k in cover]) if norm else None
             zoffs = (C.c_int * len(cover))(*[a - zs[k] for k in cover])
             check(lib.dgtta_feature_window_accumulate_multi(srcs, mrs, zoffs, len(cover), ptr(gamma), ptr(beta), 0.01, ptr(gauss), ptr(seg_f),
                                                             ptr(seg_n), 32, *P, b - a, X, Y, Z, 2, 1, a, dt, stream_of()), "multi")
         torch.cuda.synchronize()
-        assert max(len([k for k, sz in enumerate(zs) if sz <= a and b <= sz + P[2]]) for a, b in zip(cuts[:-1], cuts[1:])) == 3
+        assert max(len(cover) for _, _, _, _, cover in launches) == 3
         assert torch.equal(seg_f, one_f) and torch.equal(seg_n, one_n) and not torch.equal(seg_f, facc)
 
 
