@@ -7,8 +7,9 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = Path(__file__).resolve().parent / "libdgtta_hip.so"
-SOURCES = ["lib.hip", "mind3d.hip", "gin.hip", "warp.hip", "softdice.hip", "dice_ce.hip", "adamw.hip", "resample.hip", "window_features.hip", "unet_ref.hip", "conv_mfma.hip", "conv_rows.hip", "conv_ring.hip",
-           "conv_wgrad.hip", "conv_wgrad_ring.hip", "convt_gemm.hip", "conv_s2.hip", "conv_aniso.hip", "deform.hip"]
+SOURCES = ["lib.hip", "mind3d.hip", "gin.hip", "warp.hip", "softdice.hip", "dice_ce.hip", "adamw.hip", "resample.hip", "window_features.hip",
+           "conv_dispatch.hip", "conv_ref.hip", "instnorm.hip", "seghead.hip", "layout_argmax.hip", "conv_mfma.hip", "conv_rows.hip",
+           "conv_ring.hip", "conv_wgrad.hip", "conv_wgrad_ring.hip", "convt_gemm.hip", "conv_s2.hip", "conv_aniso.hip", "deform.hip"]
 # conv_ring.hip: the 64-input-channel step body (432 MFMAs, 192 fragment reads, fully unrolled) is above hipcc's default
 # pragma-unroll threshold; partially unrolled its register arrays are indexed dynamically and land in scratch
 EXTRA_FLAGS = {"conv_ring.hip": ["-mllvm", "-pragma-unroll-threshold=262144"]}
@@ -30,26 +31,32 @@ def _stale(out, deps):
     return (not out.exists()) or any(d.stat().st_mtime > out.stat().st_mtime for d in deps)
 
 
-def build(force=False, verbose=True):
+def _build(obj_dir, flags, lib, link_flags=(), force=False, verbose=True, capture=False):
+    """Compiles every stale source into obj_dir with `flags` (6 at a time) and links `lib` if anything changed."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    obj_dir.mkdir(parents=True, exist_ok=True)
     hdrs = list(CSRC.glob("*.h")) + [CSRC.parents[1] / "include" / "dgtta.h"]
     objs, jobs = [], []
     for s in SOURCES:
-        src, obj = CSRC / s, CSRC / (s + ".o")
+        src, obj = CSRC / s, obj_dir / (s + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            jobs.append([hipcc, *FLAGS, *EXTRA_FLAGS.get(s, []), "-c", str(src), "-o", str(obj)])
+            jobs.append([hipcc, *flags, *EXTRA_FLAGS.get(s, []), "-c", str(src), "-o", str(obj)])
 
     def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+        subprocess.run(cmd, check=True, capture_output=capture)
 
     with ThreadPoolExecutor(max_workers=6) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _stale(LIB, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *map(str, objs)])
-    return LIB
+    if force or jobs or _stale(lib, objs):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *link_flags, "-o", str(lib), *map(str, objs)])
+    return lib
+
+
+def build(force=False, verbose=True):
+    return _build(CSRC, FLAGS, LIB, force=force, verbose=verbose)
 
 
 ASAN_DIR = CSRC.parents[1] / "build" / "asan"
@@ -62,27 +69,8 @@ def build_asan(verbose=False):
     checks, size queries, launch plans, dispatch) instrumented with AddressSanitizer + UndefinedBehaviorSanitizer, the
     device code left as it is (GPU sanitizers are not available on the pool).  Goes to build/asan/ (git-ignored), never
     into the package: the product always loads dg_tta_amd/libdgtta_hip.so.  tests/test_host_logic.py drives it."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    ASAN_DIR.mkdir(parents=True, exist_ok=True)
-    hdrs = list(CSRC.glob("*.h")) + [CSRC.parents[1] / "include" / "dgtta.h"]
-    lib = ASAN_DIR / "libdgtta_hip_asan.so"
-    objs, jobs = [], []
-    for s in SOURCES:
-        src, obj = CSRC / s, ASAN_DIR / (s + ".o")
-        objs.append(obj)
-        if _stale(obj, [src] + hdrs):
-            jobs.append([hipcc, *ASAN_FLAGS, *EXTRA_FLAGS.get(s, []), "-c", str(src), "-o", str(obj)])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True, capture_output=not verbose)
-
-    with ThreadPoolExecutor(max_workers=6) as ex:
-        list(ex.map(run, jobs))
-    if jobs or _stale(lib, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address,undefined", "-o", str(lib), *map(str, objs)])
-    return lib
+    return _build(ASAN_DIR, ASAN_FLAGS, ASAN_DIR / "libdgtta_hip_asan.so", ["-fsanitize=address,undefined"], verbose=verbose,
+                  capture=not verbose)
 
 
 DIAG_DIR = CSRC.parents[1] / "build" / "diag"
@@ -94,26 +82,7 @@ def build_diag(verbose=False):
     DGTTA_*_ABL, DGTTA_ROWS_VAR, DGTTA_RING_NT, DGTTA_WGRAD_RING_CLK switches that select them (results wrong by
     construction, stamps written behind the caller's buffers).  It lands beside the scripts that use it
     (profiles/tools/, loaded through DGTTA_LIB) and never in the package: the product library has none of this."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    DIAG_DIR.mkdir(parents=True, exist_ok=True)
-    hdrs = list(CSRC.glob("*.h")) + [CSRC.parents[1] / "include" / "dgtta.h"]
-    objs, jobs = [], []
-    for s in SOURCES:
-        src, obj = CSRC / s, DIAG_DIR / (s + ".o")
-        objs.append(obj)
-        if _stale(obj, [src] + hdrs):
-            jobs.append([hipcc, *FLAGS, "-DDGTTA_DIAG", *EXTRA_FLAGS.get(s, []), "-c", str(src), "-o", str(obj)])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-
-    with ThreadPoolExecutor(max_workers=6) as ex:
-        list(ex.map(run, jobs))
-    if jobs or _stale(DIAG_LIB, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(DIAG_LIB), *map(str, objs)])
-    return DIAG_LIB
+    return _build(DIAG_DIR, [*FLAGS, "-DDGTTA_DIAG"], DIAG_LIB, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -147,6 +147,51 @@ __device__ __forceinline__ void st_f<bf16_t>(bf16_t *p, float v) { *p = f32_to_b
 template <>
 __device__ __forceinline__ void st_f<f16_t>(f16_t *p, float v) { p->v = f32_to_f16(v); }
 
+// 16 bytes of storage <-> EPV = 16 / sizeof(T) floats (the vectorised InstanceNorm and head kernels)
+template <typename T>
+__device__ __forceinline__ void unpack16(const uint4 &v, float *f);
+template <>
+__device__ __forceinline__ void unpack16<float>(const uint4 &v, float *f) {
+  f[0] = __uint_as_float(v.x);
+  f[1] = __uint_as_float(v.y);
+  f[2] = __uint_as_float(v.z);
+  f[3] = __uint_as_float(v.w);
+}
+template <>
+__device__ __forceinline__ void unpack16<bf16_t>(const uint4 &v, float *f) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = __uint_as_float(w[i] << 16);
+    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+template <>
+__device__ __forceinline__ void unpack16<f16_t>(const uint4 &v, float *f) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) unpack2_16<f16_t>(w[i], f[2 * i], f[2 * i + 1]);
+}
+
+template <typename T>
+__device__ __forceinline__ uint4 pack16(const float *f);
+template <>
+__device__ __forceinline__ uint4 pack16<float>(const float *f) {
+  return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
+}
+template <>
+__device__ __forceinline__ uint4 pack16<bf16_t>(const float *f) {
+  unsigned w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) w[i] = (unsigned)f32_to_bf16(f[2 * i]) | ((unsigned)f32_to_bf16(f[2 * i + 1]) << 16);
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+template <>
+__device__ __forceinline__ uint4 pack16<f16_t>(const float *f) {
+  return make_uint4(pack2_16<f16_t>(f[0], f[1]), pack2_16<f16_t>(f[2], f[3]), pack2_16<f16_t>(f[4], f[5]),
+                    pack2_16<f16_t>(f[6], f[7]));
+}
+
 // ---------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

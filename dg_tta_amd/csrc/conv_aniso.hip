@@ -18,19 +18,6 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo);      // conv_mfma.hip
-size_t convT_packed_bytes(int CinP, int CoutP, int dtype);
-int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B,
-               int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st);
-size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);      // conv_wgrad.hip
-int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
-int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                      int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
-size_t conv_bias_grad_ws_bytes(int B, int C, int64_t V);      // unet_ref.hip
-int conv_bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C, int64_t V, int accumulate, int dtype,
-                   hipStream_t st);
-
 namespace {
 
 template <int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
@@ -324,7 +311,6 @@ __global__ void conva_pack_kernel(const float *__restrict__ w, T *__restrict__ i
   }
 }
 
-size_t esz_of(int dtype) { return dtype == DGTTA_F32 ? 4 : 2; }
 int64_t n32(int c) { return (int64_t)(c + 31) / 32 * 32; }
 int granule(int dtype) { return dtype == DGTTA_F32 ? 8 : 16; }
 bool dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
@@ -347,7 +333,7 @@ bool convt_strides_ok(int sd, int sh, int sw) { return stride_ok(sd) && stride_o
 
 extern "C" size_t dgtta_conv3d_kpacked_bytes(int kd, int CinP, int CoutP, int dtype) {
   if ((kd != 1 && kd != 3) || CinP <= 0 || CoutP <= 0 || CinP > (1 << 16) || CoutP > (1 << 16) || !dtype_ok(dtype)) return 0;
-  return (size_t)kd * 9 * ((size_t)CinP * n32(CoutP) + (size_t)CoutP * n32(CinP)) * esz_of(dtype);
+  return (size_t)kd * 9 * ((size_t)CinP * n32(CoutP) + (size_t)CoutP * n32(CinP)) * esize(dtype);
 }
 
 extern "C" int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd, int kh, int kw, int Cin, int Cout, int CinP,
@@ -361,7 +347,7 @@ extern "C" int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd,
   DG_REQUIRE(CinP % granule(dtype) == 0 && CoutP % granule(dtype) == 0, DGTTA_ERR_BADARG,
              "conv3d_kpack_weights: padded channel counts must be multiples of %d", granule(dtype));
   const int ntaps = kd * 9;
-  void *imgB = (char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esz_of(dtype);
+  void *imgB = (char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
   const int64_t n = (int64_t)ntaps * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
   const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
   hipStream_t st = (hipStream_t)stream;
@@ -413,7 +399,7 @@ extern "C" int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, v
   DG_REQUIRE(operand_ok_dt(dtype, dy, lddy, Cout, CoutP), DGTTA_ERR_UNSUPPORTED,
              "conv3d_dgrad: dy must be 16-byte aligned with rows of whole 16 bytes, CoutP a multiple of %d", granule(dtype));
   const int ntaps = kd * 9;
-  const void *imgB = (const char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esz_of(dtype);
+  const void *imgB = (const char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
   const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
   const View xv = dense_view(B, Do, Ho, Wo, lddy);
   // one class per parity p of the strided axes; per axis the virtual tap v (0..k-1) reads dy[j + v - k/2] and carries weight

@@ -1,6 +1,8 @@
-// Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_wgrad.hip).
+// Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
+// convt_gemm.hip, conv_aniso.hip, conv_wgrad.hip, conv_wgrad_ring.hip): operand descriptors, the launchers that take them,
+// tile geometry and the device helpers of the kernels.  Pointer-level functions are declared in conv_api.h.
 #pragma once
-#include "common.h"
+#include "conv_api.h"
 #include <stdlib.h>
 
 // operand descriptors shared by the launchers of all three translation units (external linkage)
@@ -32,6 +34,22 @@ struct ConvClasses {
 }  // namespace dgconv
 using namespace dgconv;
 
+// Launchers of the specialised kernels that the dispatchers of conv_mfma.hip / conv_wgrad.hip try first; the conv ones return
+// DGTTA_ERR_UNSUPPORTED for a launch they do not take, conv3_wgrad_ring_launch its slab count (0: nothing launched).
+// conv_rows.hip: row-reuse kernel
+int conv3_rows_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
+                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, int is_f16, hipStream_t st,
+                      RowsGstCtx *gst);
+// conv_ring.hip: D-ring kernel
+int conv3_ring_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
+                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int64_t stats_cap_slots, int ntaps_src,
+                      int is_f16, hipStream_t st, RowsGstCtx *gst, long long xkh = 0, bool dry = false);
+// conv_s2.hip: register-operand kernel of the two large stride-2 encoder transitions
+int conv3_s2_regs(const void *x, const View &xv, const void *wimg, const float *bias, void *y, const View &yv, int B, int Cin,
+                  int Cout, int CinP, int CoutP, double *stats, int64_t cap_slots, int dtype, hipStream_t st);
+// conv_wgrad_ring.hip: ring sweep of the weight gradient
+int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B,
+                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh = 0, bool dry = false);
 
 namespace {
 

@@ -17,15 +17,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-int conv3_rows_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, int is_f16, hipStream_t st,
-                      RowsGstCtx *gst);
-
-int conv3_ring_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int64_t stats_cap_slots, int ntaps_src,
-                      int is_f16, hipStream_t st, RowsGstCtx *gst, long long xkh = 0, bool dry = false);      // conv_ring.hip
-int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo);
-
 namespace {
 
 // x: view xv;  y: view yv;  virtual tap t uses weight tap taps.wt[t].
@@ -551,9 +542,6 @@ int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo) {
   return best;
 }
 
-int conv3_s2_regs(const void *x, const View &xv, const void *wimg, const float *bias, void *y, const View &yv, int B, int Cin,
-                  int Cout, int CinP, int CoutP, double *stats, int64_t cap_slots, int dtype, hipStream_t st);      // conv_s2.hip
-
 int conv3_fwd_mfma(const void *x, int ldx, const void *w_kmajor, int mirror, const float *bias, void *y, int ldy, int B,
                    int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int stride, int dtype,
                    hipStream_t st, double *stats, RowsGstCtx *gst, long long xkh, bool dry) {
@@ -641,14 +629,14 @@ int conv3_dgrad_s2_mfma(const void *dy, int lddy, const void *w_kmajor, void *dx
 
 static size_t n32(int c) { return (size_t)(c + 31) / 32 * 32; }
 size_t convT_packed_bytes(int CinP, int CoutP, int dtype) {
-  return (size_t)8 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * (dtype == DGTTA_F32 ? 4 : 2);
+  return (size_t)8 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * esize(dtype);
 }
 // image-ordered conv weights (imgF | imgB) appended to the [wf | wb] blob
 size_t conv_image_bytes(int CinP, int CoutP, int dtype) {
-  return (size_t)27 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * (dtype == DGTTA_F32 ? 4 : 2);
+  return (size_t)27 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * esize(dtype);
 }
 size_t conv_imgB_offset_bytes(int CinP, int CoutP, int dtype) {
-  return (size_t)27 * CinP * n32(CoutP) * (dtype == DGTTA_F32 ? 4 : 2);
+  return (size_t)27 * CinP * n32(CoutP) * esize(dtype);
 }
 int conv_pack_images(const float *w_t, void *img, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st) {
   const int64_t n = (int64_t)27 * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
@@ -751,11 +739,6 @@ static int convT_run(int mode /*0 fwd, 1 dgrad*/, const void *in, int ldin, cons
                      int ldout, void *ws, int B, int Cin, int Cout, int Di, int Hi, int Wi, hipStream_t st) {
   return convTa_run_t<T>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, st);
 }
-
-// convt_gemm.hip: register-operand kernels of the two large decoder stages
-bool convT_gemm_eligible(int mode, const void *in, int ldin, const void *out, int ldout, int Cin, int Cout, int Wi, int dtype);
-int convT_gemm_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B,
-                   int Cin, int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st);
 
 int convT_fwd_mfma(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws, int B, int Cin,
                    int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st) {

@@ -2,9 +2,6 @@
 #include "conv_common.h"
 #include <stdlib.h>
 
-int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B,
-                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh = 0, bool dry = false);      // conv_wgrad_ring.hip
-
 namespace {
 
 // =====================================================================================================================

@@ -1,0 +1,586 @@
+// InstanceNorm3d + LeakyReLU forward / backward (product kernels, HBM bound, VALU) and the per-channel reductions
+// they share with the conv layers: InstanceNorm statistics, InstanceNorm backward sums, bias gradients.
+// Semantics follow torch.nn.{InstanceNorm3d, LeakyReLU} as used by nnUNet's PlainConvUNet.
+#include "conv_api.h"
+
+namespace {
+
+// ============================================================================ per-channel reductions over rows
+// rows = voxels of one batch sample; MODE 0: (sum y, sum y^2)          [InstanceNorm statistics]
+//                                     MODE 1: (sum da, sum da*xhat)     [InstanceNorm backward]; da = gz*lrelu'(a)
+//                                     MODE 2: (sum y, 0)                [bias gradient]
+// grid (nblk, B); partial[b][blk][c][2] double; the finalize kernels sum blocks in fixed order.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void chan_reduce_kernel(const T *__restrict__ y, int ldy, const T *__restrict__ gz,
+                                                          int ldgz, const float *__restrict__ mean_rstd,
+                                                          const float *__restrict__ gamma,
+                                                          const float *__restrict__ beta, float slope,
+                                                          double *__restrict__ partial, int C, int64_t V) {
+  __shared__ float red[2][256];
+  const int b = blockIdx.y;
+  int CL = 1;
+  while (CL < C && CL < 64) CL <<= 1;  // channel lanes (power of two <= 64)
+  const int RG = 256 / CL;             // row groups
+  const int cl = threadIdx.x % CL, rg = threadIdx.x / CL;
+  const int64_t rows_per_blk = cdiv64(V, gridDim.x);
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk, r1 = (r0 + rows_per_blk < V) ? r0 + rows_per_blk : V;
+  for (int c0 = 0; c0 < C; c0 += CL) {
+    const int c = c0 + cl;
+    float s0 = 0.f, s1 = 0.f;
+    if (c < C) {
+      float mu = 0.f, rs = 0.f, ga = 0.f, be = 0.f;
+      if (MODE == 1) {
+        mu = mean_rstd[((int64_t)b * C + c) * 2];
+        rs = mean_rstd[((int64_t)b * C + c) * 2 + 1];
+        ga = gamma[c];
+        be = beta[c];
+      }
+      for (int64_t r = r0 + rg; r < r1; r += RG) {
+        const float v = ld_f<T>(y + ((int64_t)b * V + r) * ldy + c);
+        if (MODE == 0) {
+          s0 += v;
+          s1 += v * v;
+        } else if (MODE == 2) {
+          s0 += v;
+        } else {
+          const float xh = (v - mu) * rs;
+          const float a = xh * ga + be;
+          float g = ld_f<T>(gz + ((int64_t)b * V + r) * ldgz + c);
+          g = a > 0.f ? g : g * slope;
+          s0 += g;
+          s1 += g * xh;
+        }
+      }
+    }
+    __syncthreads();
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    __syncthreads();
+    if (rg == 0 && c < C) {
+      double t0 = 0.0, t1 = 0.0;
+      for (int k = 0; k < RG; ++k) {
+        t0 += (double)red[0][k * CL + cl];
+        t1 += (double)red[1][k * CL + cl];
+      }
+      double *p = partial + ((((int64_t)b * gridDim.x + blockIdx.x) * C) + c) * 2;
+      p[0] = t0;
+      p[1] = t1;
+    }
+  }
+}
+
+// 16-byte vectorised variant of chan_reduce_kernel (needs C, ld multiples of EPV = 16/sizeof(T) and aligned rows):
+// a thread owns EPV consecutive channels, 256/G rows are in flight per iteration (G = C/EPV), two rows per thread and
+// iteration for memory-level parallelism.  Same partial layout [b][blk][c][2] (double).
+template <typename T>
+struct VecOf {
+  static constexpr int EPV = 16 / sizeof(T);
+};
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void chan_reduce_vec_kernel(const T *__restrict__ y, int ldy, const T *__restrict__ gz,
+                                                              int ldgz, const float *__restrict__ mean_rstd,
+                                                              const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, float slope,
+                                                              double *__restrict__ partial, int C, int64_t V) {
+  constexpr int EPV = VecOf<T>::EPV;
+  extern __shared__ float sred[];          // [rpi][C][2]
+  const int b = blockIdx.y;
+  const int G = C / EPV, rpi = 256 / G;
+  const int cg = threadIdx.x % G, rg = threadIdx.x / G;
+  const bool active = rg < rpi;
+  // rows are dealt to the workgroups in turn, 2 rpi at a time (round 4): with one contiguous chunk of V / gridDim.x rows
+  // per workgroup the workgroups in flight read addresses a fixed 256 KiB (128^3 x 32 channels) apart - a few HBM channels
+  // at a time, 3.1-3.8 TB/s where the apply passes, which walk the tensor in this interleaved order, stream at 5
+  const int64_t r1 = V;
+  float s0[EPV], s1[EPV], mu[EPV], rs[EPV], ga[EPV], be[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) {
+    s0[e] = s1[e] = 0.f;
+    mu[e] = rs[e] = ga[e] = be[e] = 0.f;
+    if (MODE == 1 && active) {
+      const int c = cg * EPV + e;
+      mu[e] = mean_rstd[((int64_t)b * C + c) * 2];
+      rs[e] = mean_rstd[((int64_t)b * C + c) * 2 + 1];
+      ga[e] = gamma[c];
+      be[e] = beta[c];
+    }
+  }
+  if (active) {
+    const T *yb = y + (int64_t)b * V * ldy + cg * EPV;
+    const T *gb = (MODE == 1) ? gz + (int64_t)b * V * ldgz + cg * EPV : nullptr;
+    for (int64_t r = (int64_t)blockIdx.x * (2 * rpi) + rg; r < r1; r += (int64_t)gridDim.x * (2 * rpi)) {
+      const bool two = r + rpi < r1;
+      // streaming loads, as in the apply passes (the tensors are far larger than the caches and are read once per pass)
+      typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+      auto ldnt = [](const T *p) {
+        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
+        return make_uint4(v[0], v[1], v[2], v[3]);
+      };
+      uint4 v0 = ldnt(yb + r * ldy), v1 = make_uint4(0, 0, 0, 0);
+      uint4 g0 = make_uint4(0, 0, 0, 0), g1 = g0;
+      if (two) v1 = ldnt(yb + (r + rpi) * ldy);
+      if (MODE == 1) {
+        g0 = ldnt(gb + r * ldgz);
+        if (two) g1 = ldnt(gb + (r + rpi) * ldgz);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (k == 1 && !two) break;
+        float f[EPV], g[EPV];
+        unpack16<T>(k ? v1 : v0, f);
+        if (MODE == 1) unpack16<T>(k ? g1 : g0, g);
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) {
+          if (MODE == 0) {
+            s0[e] += f[e];
+            s1[e] += f[e] * f[e];
+          } else if (MODE == 2) {
+            s0[e] += f[e];
+          } else {
+            const float xh = (f[e] - mu[e]) * rs[e];
+            const float a = xh * ga[e] + be[e];
+            const float gg = a > 0.f ? g[e] : g[e] * slope;
+            s0[e] += gg;
+            s1[e] += gg * xh;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) {
+      sred[((rg * C) + cg * EPV + e) * 2 + 0] = s0[e];
+      sred[((rg * C) + cg * EPV + e) * 2 + 1] = s1[e];
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double t0 = 0.0, t1 = 0.0;
+    for (int k = 0; k < rpi; ++k) {
+      t0 += (double)sred[(k * C + c) * 2];
+      t1 += (double)sred[(k * C + c) * 2 + 1];
+    }
+    double *p = partial + ((((int64_t)b * gridDim.x + blockIdx.x) * C) + c) * 2;
+    p[0] = t0;
+    p[1] = t1;
+  }
+}
+
+template <typename T>
+static bool vec_ok(const void *p, int ld, int C) {
+  constexpr int EPV = 16 / sizeof(T);
+  return p && ((uintptr_t)p & 15) == 0 && ld % EPV == 0 && C % EPV == 0 && C / EPV <= 256;
+}
+
+// launches the vectorised reduction when the operands allow it, else the scalar kernel
+template <typename T, int MODE>
+static void launch_chan_reduce(const void *y, int ldy, const void *gz, int ldgz, const float *mean_rstd,
+                               const float *gamma, const float *beta, float slope, double *partial, int nblk, int B, int C,
+                               int64_t V, hipStream_t st) {
+  if (vec_ok<T>(y, ldy, C) && (MODE != 1 || vec_ok<T>(gz, ldgz, C))) {
+    constexpr int EPV = 16 / sizeof(T);
+    const int rpi = 256 / (C / EPV);
+    hipLaunchKernelGGL((chan_reduce_vec_kernel<T, MODE>), dim3(nblk, B), dim3(256), (size_t)rpi * C * 2 * sizeof(float), st,
+                       (const T *)y, ldy, (const T *)gz, ldgz, mean_rstd, gamma, beta, slope, partial, C, V);
+  } else {
+    hipLaunchKernelGGL((chan_reduce_kernel<T, MODE>), dim3(nblk, B), dim3(256), 0, st, (const T *)y, ldy, (const T *)gz,
+                       ldgz, mean_rstd, gamma, beta, slope, partial, C, V);
+  }
+}
+
+// 16-byte vectorised InstanceNorm+LeakyReLU apply kernels (forward MODE 0, backward MODE 1): grid (blocks, B); the
+// per-channel constants of sample b are staged in LDS once per workgroup; each thread streams 16-byte channel groups.
+// Same arithmetic as in_lrelu_apply_kernel / in_lrelu_bwd_apply_kernel.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__ y, int ldy, const T *__restrict__ gz,
+                                                           int ldgz, const float *__restrict__ mean_rstd,
+                                                           const float *__restrict__ gamma,
+                                                           const float *__restrict__ beta, const float *__restrict__ c12,
+                                                           T *__restrict__ out, int ldo, int C, int64_t V, float slope,
+                                                           int nt) {
+  constexpr int EPV = 16 / sizeof(T);
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  extern __shared__ float sc[];     // fwd: [C][2] (alpha, beta'); bwd: [C][6] (mu, rs, ga, be, c1, c2)
+  const int b = blockIdx.y;
+  constexpr int NK = MODE == 0 ? 2 : 6;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float mu = mean_rstd[((int64_t)b * C + c) * 2], rs = mean_rstd[((int64_t)b * C + c) * 2 + 1];
+    if (MODE == 0) {
+      const float al = rs * gamma[c];
+      sc[c * NK] = al;
+      sc[c * NK + 1] = beta[c] - mu * al;
+    } else {
+      sc[c * NK] = mu;
+      sc[c * NK + 1] = rs;
+      sc[c * NK + 2] = gamma[c];
+      sc[c * NK + 3] = beta[c];
+      sc[c * NK + 4] = c12[((int64_t)b * C + c) * 2];
+      sc[c * NK + 5] = c12[((int64_t)b * C + c) * 2 + 1];
+    }
+  }
+  __syncthreads();
+  const int G = C / EPV;
+  const int64_t items = V * G;
+  const T *yb = y + (int64_t)b * V * ldy;
+  const T *gb = MODE == 1 ? gz + (int64_t)b * V * ldgz : nullptr;
+  T *ob = out + (int64_t)b * V * ldo;
+  if (256 % G == 0) {
+    // fast path (G = 4, 8, 16, 32: every layer except the 320-channel bottleneck): a thread keeps ONE channel group for the
+    // whole launch, so its per-channel constants sit in registers (no LDS read per element, no 64-bit division per item),
+    // and two rows are in flight per iteration
+    const int c0 = (threadIdx.x % G) * EPV;
+    float kc[EPV][NK];
+#pragma unroll
+    for (int e = 0; e < EPV; ++e)
+#pragma unroll
+      for (int q = 0; q < NK; ++q) kc[e][q] = sc[(c0 + e) * NK + q];
+    const int rpb = 256 / G;                                             // rows per workgroup per step
+    const int64_t rstep = (int64_t)gridDim.x * rpb;
+    auto one = [&](const uint4 &yv, const uint4 &gv, int64_t row) {
+      float f[EPV], g[EPV], o[EPV];
+      unpack16<T>(yv, f);
+      if (MODE == 1) unpack16<T>(gv, g);
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        if constexpr (MODE == 0) {
+          o[e] = lrelu(f[e] * kc[e][0] + kc[e][1], slope);
+        } else {
+          const float xh = (f[e] - kc[e][0]) * kc[e][1];
+          const float a = xh * kc[e][2] + kc[e][3];
+          const float gg = a > 0.f ? g[e] : g[e] * slope;
+          o[e] = (kc[e][2] * kc[e][1]) * ((gg - kc[e][4]) - xh * kc[e][5]);
+        }
+      }
+      const uint4 pk = pack16<T>(o);
+      if (nt) {
+        const u32x4_t nv = {pk.x, pk.y, pk.z, pk.w};
+        __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t *>(ob + row * ldo + c0));
+      } else {
+        *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pk;
+      }
+    };
+    auto ld = [&](const T *p) {
+      if (nt) {
+        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
+        return make_uint4(v[0], v[1], v[2], v[3]);
+      }
+      return *reinterpret_cast<const uint4 *>(p);
+    };
+    for (int64_t row = (int64_t)blockIdx.x * rpb + threadIdx.x / G; row < V; row += 2 * rstep) {
+      const int64_t row2 = row + rstep;
+      const bool two = row2 < V;
+      const uint4 y0 = ld(yb + row * ldy + c0);
+      uint4 y1 = y0, g0 = y0, g1 = y0;
+      if (two) y1 = ld(yb + row2 * ldy + c0);
+      if (MODE == 1) {
+        g0 = ld(gb + row * ldgz + c0);
+        if (two) g1 = ld(gb + row2 * ldgz + c0);
+      }
+      one(y0, g0, row);
+      if (two) one(y1, g1, row2);
+    }
+    return;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / G;
+    const int c0 = (int)(i % G) * EPV;
+    float f[EPV], g[EPV], o[EPV];
+    unpack16<T>(*reinterpret_cast<const uint4 *>(yb + row * ldy + c0), f);
+    if (MODE == 1) unpack16<T>(*reinterpret_cast<const uint4 *>(gb + row * ldgz + c0), g);
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) {
+      const float *k = sc + (c0 + e) * NK;
+      if (MODE == 0) {
+        o[e] = lrelu(f[e] * k[0] + k[1], slope);
+      } else {
+        const float xh = (f[e] - k[0]) * k[1];
+        const float a = xh * k[2] + k[3];
+        const float gg = a > 0.f ? g[e] : g[e] * slope;
+        o[e] = (k[2] * k[1]) * ((gg - k[4]) - xh * k[5]);
+      }
+    }
+    *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pack16<T>(o);
+  }
+}
+
+// sum of two doubles over a 256-thread workgroup (fixed order: lanes by butterfly, then waves 0..3); result in all threads
+__device__ __forceinline__ void block_sum2_d(double &a, double &b, double *red /* >= 8 doubles of LDS */) {
+  a = wave_sum_d(a);
+  b = wave_sum_d(b);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    red[2 * w] = a;
+    red[2 * w + 1] = b;
+  }
+  __syncthreads();
+  a = (red[0] + red[2]) + (red[4] + red[6]);
+  b = (red[1] + red[3]) + (red[5] + red[7]);
+}
+
+
+// InstanceNorm statistics finalize: mean, rstd = 1/sqrt(biased var + eps).  One 256-thread workgroup per (b,c); the number of
+// partial blocks is read from the device-side header when hdr != NULL (statistics produced by the conv epilogue).
+__global__ void in_stats_finalize_kernel(const double *__restrict__ partial, const long long *__restrict__ hdr, int nblk_h,
+                                         int B, int C, int64_t V, float eps, float *__restrict__ mean_rstd) {
+  const int i = blockIdx.x;
+  const int b = i / C, c = i % C;
+  const int nblk = hdr ? (int)hdr[0] : nblk_h;
+  __shared__ double red[8];
+  double s = 0.0, ss = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 256) {
+    const double2 v = *reinterpret_cast<const double2 *>(partial + ((((int64_t)b * nblk + k) * C) + c) * 2);
+    s += v.x;
+    ss += v.y;
+  }
+  block_sum2_d(s, ss, red);
+  if (threadIdx.x == 0) {
+    const double mean = s / (double)V;
+    double var = ss / (double)V - mean * mean;
+    if (var < 0.0) var = 0.0;
+    mean_rstd[2 * i] = (float)mean;
+    mean_rstd[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+}
+
+// z = lrelu(y*alpha + beta'), alpha = rstd*gamma, beta' = beta - mean*alpha  (ATen's batch_norm transform form)
+template <typename T>
+__global__ void in_lrelu_apply_kernel(const T *__restrict__ y, int ldy, const float *__restrict__ mean_rstd,
+                                      const float *__restrict__ gamma, const float *__restrict__ beta,
+                                      T *__restrict__ z, int ldz, int C, int64_t V, float slope, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const int64_t row = i / C;  // b*V + v
+    const int b = (int)(row / V);
+    const float mu = mean_rstd[((int64_t)b * C + c) * 2], rs = mean_rstd[((int64_t)b * C + c) * 2 + 1];
+    const float al = rs * gamma[c];
+    const float bt = beta[c] - mu * al;
+    const float a = ld_f<T>(y + row * ldy + c) * al + bt;
+    st_f<T>(z + row * ldz + c, lrelu(a, slope));
+  }
+}
+
+// backward finalize: c1 = mean(da), c2 = mean(da*xhat); dgamma (+)= sum_b sum(da*xhat); dbeta (+)= sum_b sum(da).
+// one 256-thread workgroup per channel
+__global__ void in_bwd_finalize_kernel(const double *__restrict__ partial, int nblk, int B, int C, int64_t V,
+                                       float *__restrict__ c12, float *__restrict__ dgamma, float *__restrict__ dbeta,
+                                       int accumulate) {
+  const int c = blockIdx.x;
+  __shared__ double red[8];
+  double g_acc = 0.0, b_acc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 256) {
+      const double2 v = *reinterpret_cast<const double2 *>(partial + ((((int64_t)b * nblk + k) * C) + c) * 2);
+      s0 += v.x;
+      s1 += v.y;
+    }
+    block_sum2_d(s0, s1, red);
+    if (threadIdx.x == 0) {
+      c12[((int64_t)b * C + c) * 2] = (float)(s0 / (double)V);
+      c12[((int64_t)b * C + c) * 2 + 1] = (float)(s1 / (double)V);
+    }
+    b_acc += s0;
+    g_acc += s1;
+  }
+  if (threadIdx.x == 0) {
+    dgamma[c] = accumulate ? dgamma[c] + (float)g_acc : (float)g_acc;
+    dbeta[c] = accumulate ? dbeta[c] + (float)b_acc : (float)b_acc;
+  }
+}
+
+// The same from the partial sums the data-gradient kernel left (conv_rows.hip, GST): per (sample, tile) sums of g' and
+// g' * y in the layout of the forward statistics (header = tiles per sample); sum g' xhat = rstd (sum g' y - mean sum g').
+__global__ void in_bwd_finalize_gstats_kernel(const double *__restrict__ stats, int B, int C, int64_t V,
+                                              const float *__restrict__ mean_rstd, float *__restrict__ c12,
+                                              float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate) {
+  const int c = blockIdx.x;
+  __shared__ double red[8];
+  const int nblk = (int)reinterpret_cast<const long long *>(stats)[0];
+  const double *partial = stats + 32;
+  double g_acc = 0.0, b_acc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 256) {
+      const double2 v = *reinterpret_cast<const double2 *>(partial + ((((int64_t)b * nblk + k) * C) + c) * 2);
+      s0 += v.x;
+      s1 += v.y;
+    }
+    block_sum2_d(s0, s1, red);
+    const double mu = (double)mean_rstd[((int64_t)b * C + c) * 2], rs = (double)mean_rstd[((int64_t)b * C + c) * 2 + 1];
+    const double s1x = rs * (s1 - mu * s0);
+    if (threadIdx.x == 0) {
+      c12[((int64_t)b * C + c) * 2] = (float)(s0 / (double)V);
+      c12[((int64_t)b * C + c) * 2 + 1] = (float)(s1x / (double)V);
+    }
+    b_acc += s0;
+    g_acc += s1x;
+  }
+  if (threadIdx.x == 0) {
+    dgamma[c] = accumulate ? dgamma[c] + (float)g_acc : (float)g_acc;
+    dbeta[c] = accumulate ? dbeta[c] + (float)b_acc : (float)b_acc;
+  }
+}
+
+// dy = gamma*rstd*(da - c1 - xhat*c2)
+template <typename T>
+__global__ void in_lrelu_bwd_apply_kernel(const T *__restrict__ gz, int ldgz, const T *__restrict__ y, int ldy,
+                                          const float *__restrict__ mean_rstd, const float *__restrict__ gamma,
+                                          const float *__restrict__ beta, const float *__restrict__ c12,
+                                          T *__restrict__ dy, int lddy, int C, int64_t V, float slope, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const int64_t row = i / C;
+    const int b = (int)(row / V);
+    const int64_t bc = (int64_t)b * C + c;
+    const float mu = mean_rstd[bc * 2], rs = mean_rstd[bc * 2 + 1], ga = gamma[c];
+    const float xh = (ld_f<T>(y + row * ldy + c) - mu) * rs;
+    const float a = xh * ga + beta[c];
+    float g = ld_f<T>(gz + row * ldgz + c);
+    g = a > 0.f ? g : g * slope;
+    st_f<T>(dy + row * lddy + c, (ga * rs) * ((g - c12[bc * 2]) - xh * c12[bc * 2 + 1]));
+  }
+}
+
+__global__ void bias_finalize_kernel(const double *__restrict__ partial, int nblk, int B, int C, float *__restrict__ db,
+                                     int accumulate) {
+  const int c = blockIdx.x;   // one wave per channel
+  double s = 0.0;
+  for (int k = threadIdx.x; k < B * nblk; k += 64) s += partial[(((int64_t)k * C) + c) * 2];
+  s = wave_sum_d(s);
+  if (threadIdx.x == 0) db[c] = accumulate ? db[c] + (float)s : (float)s;
+}
+
+}  // namespace
+
+__global__ void set_header_kernel(long long *hdr, long long v) { hdr[0] = v; }
+
+// InstanceNorm statistics of y by a separate reduction pass, in the buffer layout of the conv epilogues
+// (dgtta_conv3d_stats_bytes): what the general forward kernel (conv_ref.hip), which has no such epilogue, is followed by
+int conv_stats_ref(const void *y, int ldy, void *stats, int B, int C, int64_t V, int dtype, hipStream_t st) {
+  const int nblk = reduce_blocks(V, B);
+  hipLaunchKernelGGL(set_header_kernel, dim3(1), dim3(1), 0, st, (long long *)stats, (long long)nblk);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((chan_reduce_kernel<T, 0>), dim3(nblk, B), dim3(256), 0, st, (const T *)y, ldy,
+                                       (const T *)nullptr, 0, nullptr, nullptr, nullptr, 0.f, (double *)stats + 32,
+                                       C, V));
+  DG_CHECK_LAUNCH("chan_reduce_kernel<0>");
+  return DGTTA_OK;
+}
+
+// bias gradient: db[c] (+)= sum over B x V rows of dy, fixed order; ws = conv_bias_grad_ws_bytes
+size_t conv_bias_grad_ws_bytes(int B, int C, int64_t V) {
+  if (B <= 0 || C <= 0 || V <= 0) return 0;
+  return (size_t)B * reduce_blocks(V, B) * C * 2 * sizeof(double);
+}
+int conv_bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C, int64_t V, int accumulate, int dtype, hipStream_t st) {
+  const int nblk = reduce_blocks(V, B);
+  double *partial = (double *)ws;
+  DISPATCH_T(dtype, (launch_chan_reduce<T, 2>(dy, lddy, nullptr, 0, nullptr, nullptr, nullptr, 0.f, partial, nblk, B, C, V, st)));
+  DG_CHECK_LAUNCH("chan_reduce_kernel<2>");
+  hipLaunchKernelGGL(bias_finalize_kernel, dim3(C), dim3(64), 0, st, partial, nblk, B, C, db, accumulate);
+  DG_CHECK_LAUNCH("bias_finalize_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" size_t dgtta_instnorm_ws_bytes(int B, int C, int64_t V) {
+  if (B <= 0 || C <= 0 || V <= 0) return 0;      // a size query of an empty problem (the launchers reject it with DGTTA_ERR_BADARG)
+  return align_up((size_t)B * reduce_blocks(V, B) * C * 2 * sizeof(double), 256) +
+         align_up((size_t)B * C * 2 * sizeof(float), 256);
+}
+
+extern "C" int dgtta_instnorm_lrelu_fwd(const void *y, int ldy, const void *stats, const float *gamma, const float *beta,
+                                        float *mean_rstd, void *z, int ldz, void *ws, size_t ws_bytes, int B, int C,
+                                        int64_t V, float eps, float slope, int dtype, void *stream) {
+  // z == NULL (round 5): the statistics only - the caller applies them itself (dgtta_feature_window_accumulate_norm)
+  DG_REQUIRE(y && gamma && beta && mean_rstd && ws, DGTTA_ERR_BADARG, "instnorm_lrelu_fwd: null pointer");
+  DG_REQUIRE(B > 0 && C > 0 && V > 0 && ldy >= C && (!z || ldz >= C), DGTTA_ERR_BADARG, "instnorm_lrelu_fwd: bad dims");
+  DG_REQUIRE(ws_bytes >= dgtta_instnorm_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "instnorm_lrelu_fwd: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = reduce_blocks(V, B);
+  if (stats) {   // partial sums came with the conv epilogue (header + partials)
+    hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(B * C), dim3(256), 0, st, (const double *)stats + 32,
+                       (const long long *)stats, 0, B, C, V, eps, mean_rstd);
+  } else {
+    double *partial = (double *)ws;
+    DISPATCH_T(dtype, (launch_chan_reduce<T, 0>(y, ldy, nullptr, 0, nullptr, nullptr, nullptr, 0.f, partial, nblk, B, C, V, st)));
+    DG_CHECK_LAUNCH("chan_reduce_kernel<0>");
+    hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(B * C), dim3(256), 0, st, (const double *)partial,
+                       (const long long *)nullptr, nblk, B, C, V, eps, mean_rstd);
+  }
+  DG_CHECK_LAUNCH("in_stats_finalize_kernel");
+  if (!z) return DGTTA_OK;
+  const int64_t total = (int64_t)B * V * C;
+  const int esz = (int)esize(dtype), epv = 16 / esz;
+  if (C % epv == 0 && ldy % epv == 0 && ldz % epv == 0 && !((uintptr_t)y & 15) && !((uintptr_t)z & 15) && C <= 2048) {
+    const int64_t items = V * (C / epv);
+    const int blocks = (int)(cdiv64(items, 256 * 4) < 4096 ? (cdiv64(items, 256 * 4) > 0 ? cdiv64(items, 256 * 4) : 1) : 4096);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_vec_kernel<T, 0>), dim3(blocks, B), dim3(256), (size_t)C * 2 * 4, st,
+                                         (const T *)y, ldy, (const T *)nullptr, 0, mean_rstd, gamma, beta, nullptr, (T *)z,
+                                         ldz, C, V, slope, dgtta_switches().in_nt - '0'));
+    DG_CHECK_LAUNCH("in_apply_vec_kernel<0>");
+    return DGTTA_OK;
+  }
+  DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st,
+                                       (const T *)y, ldy, mean_rstd, gamma, beta, (T *)z, ldz, C, V, slope, total));
+  DG_CHECK_LAUNCH("in_lrelu_apply_kernel");
+  return DGTTA_OK;
+}
+
+static int instnorm_bwd_impl(const void *gz, int ldgz, const void *y, int ldy, const float *gamma, const float *beta,
+                             const float *mean_rstd, void *dy, int lddy, float *dgamma, float *dbeta, const void *gstats,
+                             void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope, int accumulate, int dtype,
+                             void *stream, const char *name) {
+  DG_REQUIRE(gz && y && gamma && beta && mean_rstd && dy && dgamma && dbeta && ws, DGTTA_ERR_BADARG, "%s: null pointer", name);
+  DG_REQUIRE(B > 0 && C > 0 && V > 0 && ldy >= C && ldgz >= C && lddy >= C, DGTTA_ERR_BADARG, "%s: bad dims", name);
+  DG_REQUIRE(ws_bytes >= dgtta_instnorm_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "%s: workspace too small", name);
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = reduce_blocks(V, B);
+  double *partial = (double *)ws;
+  float *c12 = (float *)((char *)ws + align_up((size_t)B * nblk * C * 2 * sizeof(double), 256));
+  if (gstats) {     // the sums came out of the data-gradient kernel that produced gz: no pass over y and gz
+    hipLaunchKernelGGL(in_bwd_finalize_gstats_kernel, dim3(C), dim3(256), 0, st, (const double *)gstats, B, C, V, mean_rstd, c12,
+                       dgamma, dbeta, accumulate);
+    DG_CHECK_LAUNCH("in_bwd_finalize_gstats_kernel");
+  } else {
+    DISPATCH_T(dtype, (launch_chan_reduce<T, 1>(y, ldy, gz, ldgz, mean_rstd, gamma, beta, slope, partial, nblk, B, C, V, st)));
+    DG_CHECK_LAUNCH("chan_reduce_kernel<1>");
+    hipLaunchKernelGGL(in_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, B, C, V, c12, dgamma, dbeta,
+                       accumulate);
+    DG_CHECK_LAUNCH("in_bwd_finalize_kernel");
+  }
+  const int64_t total = (int64_t)B * V * C;
+  const int esz = (int)esize(dtype), epv = 16 / esz;
+  if (C % epv == 0 && ldy % epv == 0 && ldgz % epv == 0 && lddy % epv == 0 && !((uintptr_t)y & 15) && !((uintptr_t)gz & 15) &&
+      !((uintptr_t)dy & 15) && C <= 2048) {
+    const int64_t items = V * (C / epv);
+    const int blocks = (int)(cdiv64(items, 256 * 4) < 4096 ? (cdiv64(items, 256 * 4) > 0 ? cdiv64(items, 256 * 4) : 1) : 4096);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_vec_kernel<T, 1>), dim3(blocks, B), dim3(256), (size_t)C * 6 * 4, st,
+                                         (const T *)y, ldy, (const T *)gz, ldgz, mean_rstd, gamma, beta, c12, (T *)dy, lddy,
+                                         C, V, slope, dgtta_switches().in_nt - '0'));
+    DG_CHECK_LAUNCH("in_apply_vec_kernel<1>");
+    return DGTTA_OK;
+  }
+  DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_bwd_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st,
+                                       (const T *)gz, ldgz, (const T *)y, ldy, mean_rstd, gamma, beta, c12, (T *)dy, lddy,
+                                       C, V, slope, total));
+  DG_CHECK_LAUNCH("in_lrelu_bwd_apply_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_instnorm_lrelu_bwd(const void *gz, int ldgz, const void *y, int ldy, const float *gamma,
+                                        const float *beta, const float *mean_rstd, void *dy, int lddy, float *dgamma,
+                                        float *dbeta, void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope,
+                                        int accumulate, int dtype, void *stream) {
+  return instnorm_bwd_impl(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, nullptr, ws, ws_bytes, B, C, V,
+                           slope, accumulate, dtype, stream, "instnorm_lrelu_bwd");
+}
+
+extern "C" int dgtta_instnorm_lrelu_bwd_gstats(const void *gz, int ldgz, const void *y, int ldy, const float *gamma,
+                                               const float *beta, const float *mean_rstd, void *dy, int lddy,
+                                               float *dgamma, float *dbeta, const void *gstats, void *ws, size_t ws_bytes,
+                                               int B, int C, int64_t V, float slope, int accumulate, int dtype,
+                                               void *stream) {
+  DG_REQUIRE(gstats, DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_gstats: null statistics");
+  return instnorm_bwd_impl(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, gstats, ws, ws_bytes, B, C, V,
+                           slope, accumulate, dtype, stream, "instnorm_lrelu_bwd_gstats");
+}

@@ -3,7 +3,7 @@
 // with backward) and dg_tta/tta/torch_utils.py:55-73 (get_batch patch sampling, linear + nearest).
 // HBM-bound gather: per output voxel 8 neighbour rows of C channels (L2 absorbs the 8x reuse) + one write;
 // algorithmic bytes = 2 * C * 4 B per voxel.
-#include "common.h"
+#include "conv_api.h"
 #include "sampler.h"
 #include <limits.h>
 
@@ -1218,10 +1218,6 @@ extern "C" int dgtta_affine_warp3d_bwd(const float *grad_dst, const float *theta
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fused head + inverse warp (see head_warp_fwd_kernel)
-size_t head_wgrad_mfma_ws_bytes(int Cin, int nsel, int64_t rows);
-int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *dw_sel, void *ws, size_t ws_bytes, int Cin,
-                    int nsel, int64_t rows, int accumulate, int dtype, hipStream_t st, bool have_d16);
-
 static bool head_warp_shape_ok(int Cin, int nsel, int dtype) {
   return Cin == HW_CIN && nsel >= 4 && nsel <= HW_NS && nsel % 4 == 0 && (dtype == DGTTA_BF16 || dtype == DGTTA_F16);
 }

@@ -1,6 +1,6 @@
 """Patch sampler, losses, label mapping, grad freezing, hook helpers — same names and semantics as the reference's
 dg_tta/tta/torch_utils.py; numeric work runs in the HIP kernels (sampler: csrc/warp.hip, loss: csrc/softdice.hip,
-Dice counting: csrc/unet_ref.hip argmax_dice_kernel)."""
+Dice counting: csrc/layout_argmax.hip argmax_dice_kernel)."""
 from collections import OrderedDict
 
 import torch

@@ -3,9 +3,9 @@ dg_tta/tta/tta.py (tta_main :93-373, calc_branch :480-579), with every tensor op
 
     get_batch (csrc/warp.hip) -> 2x calc_branch {GIN (gin.hip) -> affine warp, border (warp.hip; spatial_aug_type
     "deformable": random diffeomorphic field + dense-grid warp, deform.hip) -> MIND pre-hook
-    (mind3d.hip) -> PlainConvUNet fwd (unet_ref.hip / conv_mfma.hip) with map_label fused into the head -> inverse
-    warp, zeros (warp.hip)} -> masked softmax + soft-Dice (softdice.hip) -> backward through both branches ->
-    AdamW once per epoch (adamw.hip).
+    (mind3d.hip) -> PlainConvUNet fwd (conv_dispatch.hip -> conv_mfma.hip, instnorm.hip, seghead.hip) with map_label
+    fused into the head -> inverse warp, zeros (warp.hip)} -> masked softmax + soft-Dice (softdice.hip) -> backward
+    through both branches -> AdamW once per epoch (adamw.hip).
 
 Behaviour kept bug-compatible with the reference: `have_grad_in` enables/disables autograd for BOTH
 branches (tta.py:496-498); epochs before `start_tta_at_epoch` only evaluate the loss; background is excluded from the
