@@ -10,7 +10,7 @@ from pathlib import Path
 LIB_PATH = Path(__file__).resolve().parent / "libdgtta_hip.so"
 
 _c_float_p = C.POINTER(C.c_float)
-P, I, I64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+P, I, I64, U64, F, SZ = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/dgtta.h one to one
 SIGNATURES = {
@@ -19,6 +19,8 @@ SIGNATURES = {
     "dgtta_reload_env": (I, []),
     "dgtta_mind3d_ws_bytes": (SZ, [I, I, I, I]),
     "dgtta_mind3d_fwd": (I, [P, P, F, I, C.POINTER(F), I, P, I, I, I, P, SZ, I, I, I, I, P]),
+    "dgtta_mind3d_noise_fill": (I, [P, U64, U64, I, I, I, I, I, P]),
+    "dgtta_mind3d_fwd_seeded": (I, [P, U64, U64, I, F, I, C.POINTER(F), I, P, I, I, I, P, SZ, I, I, I, I, P]),
     "dgtta_gin_ws_bytes": (SZ, [I, I, I, I]),
     "dgtta_gin_chain_fwd": (I, [P, P, C.POINTER(I), C.POINTER(P), C.POINTER(P), P, P, SZ, I, I, I, I, P]),
     "dgtta_affine_warp3d_fwd": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P]),

@@ -12,8 +12,12 @@
 // Pass C (mind_finish_kernel): var clamp to [1e-3, 1e3] x global mean, out = exp(-m/var), written
 //   NCDHW fp32 or NDHWC fp32/bf16.
 // Algorithmic HBM bytes per voxel: img 4 + noise 48 + ws 48 w + 48 r + out 48 (fp32) = 196 B.
+// Seeded form (dgtta_mind3d_fwd_seeded): pass A generates the noise of philox.h where the tensor form loads it (no noise tensor:
+// 148 B per voxel); dgtta_mind3d_noise_fill writes the same field out for callers and tests that want it.
 #include "common.h"
+#include "philox.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -69,6 +73,56 @@ struct MG {
   static constexpr size_t LDS_BYTES = (size_t)(ID * IH * IW + CG * TD * QH * QWP + CG * TD * TH * QWP + 8 + 16) * 4;
 };
 
+// Stage 1 of pass A for one column (qh, qw) of the q tile and channel group g in the SEEDED form: the noise of the group's
+// channels is generated (mind_noise, at the clamped voxel index the tensor form loads from) instead of loaded.  Same
+// arithmetic and tap order as the tensor form below, but the walk over the depths is a rolled loop with the window shifted
+// in registers: the generator is ~10x the per-depth work of the tensor form, and unrolled QD x NG times it is past the
+// compiler's unroll budget (the g loop then stays rolled and ssd[][] lands in scratch) and many times the instruction cache.
+template <int DELTA, int R, int CG>
+__device__ __forceinline__ void mind_column_seeded(const float *simg, float *sr1, const PhiloxKey &key, int bglob, int g,
+                                                   float rw, const Taps &taps, int d0, int h0, int w0, int D, int H, int W,
+                                                   int qh, int qw) {
+  typedef MG<DELTA, R, CG> G;
+  constexpr int IH = G::IH, IW = G::IW, QD = G::QD, QH = G::QH, QWP = G::QWP, NTAP = G::NTAP, HL = G::HL;
+  const int gh = clampi(h0 - R + qh, 0, H - 1), gw = clampi(w0 - R + qw, 0, W - 1);
+  const int ih_c = gh - (h0 - HL), iw_c = gw - (w0 - HL);
+  const int ih_p = clampi(gh + DELTA, 0, H - 1) - (h0 - HL), ih_m = clampi(gh - DELTA, 0, H - 1) - (h0 - HL);
+  const int iw_p = clampi(gw + DELTA, 0, W - 1) - (w0 - HL), iw_m = clampi(gw - DELTA, 0, W - 1) - (w0 - HL);
+  float win[CG][NTAP];      // win[c][t] = q_c[d + t] of the output depth d = qd - 2R
+#pragma unroll
+  for (int c = 0; c < CG; ++c)
+#pragma unroll
+    for (int t = 0; t < NTAP; ++t) win[c][t] = 0.f;
+#pragma unroll 1
+  for (int qd = 0; qd < QD; ++qd) {
+    const int gd = clampi(d0 - R + qd, 0, D - 1);
+    float nv[CG];
+    mind_noise<CG>(key, bglob, g * CG, (uint32_t)((gd * H + gh) * W + gw), nv);
+    const int id_c = gd - (d0 - HL), id_p = clampi(gd + DELTA, 0, D - 1) - (d0 - HL),
+              id_m = clampi(gd - DELTA, 0, D - 1) - (d0 - HL);
+    const float dp = simg[(id_p * IH + ih_c) * IW + iw_c], dm = simg[(id_m * IH + ih_c) * IW + iw_c];
+    const float hp = simg[(id_c * IH + ih_p) * IW + iw_c], hm = simg[(id_c * IH + ih_m) * IW + iw_c];
+    const float wp = simg[(id_c * IH + ih_c) * IW + iw_p], wm = simg[(id_c * IH + ih_c) * IW + iw_m];
+#pragma unroll
+    for (int c = 0; c < CG; ++c) {
+      const float ev = edge_sel(g * CG + c, dp, dm, hp, hm, wp, wm) + rw * nv[c];      // (g: constant after unrolling)
+#pragma unroll
+      for (int t = 0; t + 1 < NTAP; ++t) win[c][t] = win[c][t + 1];
+      win[c][NTAP - 1] = ev * ev;
+    }
+    if (qd >= NTAP - 1) {
+      const int d = qd - (NTAP - 1);
+#pragma unroll
+      for (int c = 0; c < CG; ++c) {
+        float acc = taps.g[0] * win[c][0];
+#pragma unroll
+        for (int t = 1; t < NTAP; ++t) acc += taps.g[t] * win[c][t];
+        sr1[((c * TD + d) * QH + qh) * QWP + qw] = acc;
+      }
+    }
+  }
+}
+
 // Pass A.  One workgroup per 8 x 8 x 32 output tile, channels in NG groups of CG:
 //   stage 1  thread = one (h', w') column of the q tile (halo R): walks the depths, forms q_c = (e_c + rw n_c)^2 for the
 //            group's channels from the six neighbours and runs the D filter on a (2R+1)-deep register window per channel
@@ -76,8 +130,12 @@ struct MG {
 //   stage 2  H filter, 4 adjacent w' columns per thread (16-byte LDS accesses): r1 -> r2[c][d][h][w'];
 //   stage 3  W filter: thread = 4 consecutive output voxels of a row, 16-byte reads per channel -> registers.
 // 2 barriers per group instead of 5 per channel, ~1/3 of the LDS instructions of the first version.
-template <int DELTA, int R, int CG>
-__global__ __launch_bounds__(NT) void mind_ssd_kernel(const float *__restrict__ img, const float *__restrict__ noise,
+// SEEDED: `noise` is a PhiloxKey instead of the tensor; stage 1 generates the group's values of its column and depth
+// (mind_column_seeded) and the prefetch registers do not exist.
+typedef const float *__restrict__ NoisePtr;
+template <int DELTA, int R, int CG, bool SEEDED>
+__global__ __launch_bounds__(NT) void mind_ssd_kernel(const float *__restrict__ img,
+                                                      std::conditional_t<SEEDED, PhiloxKey, NoisePtr> noise,
                                                       float rw, float *__restrict__ mws, double *__restrict__ partial,
                                                       int D, int H, int W, int tilesD, Taps taps) {
   typedef MG<DELTA, R, CG> G;
@@ -130,23 +188,28 @@ __global__ __launch_bounds__(NT) void mind_ssd_kernel(const float *__restrict__ 
   float ssd[VPT][12];
   // noise of the whole column for one channel group, fetched a full group ahead: the loads of group g+1 are issued while
   // group g runs
-  float nbuf[QD][CG];
-  const float *nzb = noise + (int64_t)b * 12 * V;
-  int gidx[QD];
+  float nbuf[SEEDED ? 1 : QD][CG];
+  const float *nzb = nullptr;
+  int gidx[SEEDED ? 1 : QD];
+  if constexpr (!SEEDED) {
+    nzb = noise + (int64_t)b * 12 * V;
 #pragma unroll
-  for (int qd = 0; qd < QD; ++qd) gidx[qd] = (clampi(d0 - R + qd, 0, D - 1) * H + gh) * W + gw;
-  if (col_on) {
+    for (int qd = 0; qd < QD; ++qd) gidx[qd] = (clampi(d0 - R + qd, 0, D - 1) * H + gh) * W + gw;
+    if (col_on) {
 #pragma unroll
-    for (int qd = 0; qd < QD; ++qd)
+      for (int qd = 0; qd < QD; ++qd)
 #pragma unroll
-      for (int c = 0; c < CG; ++c) nbuf[qd][c] = nzb[(int64_t)c * V + gidx[qd]];
+        for (int c = 0; c < CG; ++c) nbuf[qd][c] = nzb[(int64_t)c * V + gidx[qd]];
+    }
   }
   __syncthreads();      // simg ready
 
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     // ---- stage 1
-    if (col_on) {
+    if constexpr (SEEDED) {
+      if (col_on) mind_column_seeded<DELTA, R, CG>(simg, sr1, noise, noise.b0 + b, g, rw, taps, d0, h0, w0, D, H, W, qh, qw);
+    } else if (col_on) {
       float win[CG][NTAP];
       float nv[CG];
 #pragma unroll
@@ -187,7 +250,10 @@ __global__ __launch_bounds__(NT) void mind_ssd_kernel(const float *__restrict__ 
       // R = 3: the q tile has 14 x 38 = 532 columns for 512 threads; the last ones are walked by the first threads in
       // a second, unpipelined pass (noise loaded where it is used)
       const int col = tid + NT;
-      if (col < QH * QW) {
+      if constexpr (SEEDED) {
+        if (col < QH * QW)
+          mind_column_seeded<DELTA, R, CG>(simg, sr1, noise, noise.b0 + b, g, rw, taps, d0, h0, w0, D, H, W, col / QW, col % QW);
+      } else if (col < QH * QW) {
         const int qw2 = col % QW, qh2 = col / QW;
         const int gh2 = clampi(h0 - R + qh2, 0, H - 1), gw2 = clampi(w0 - R + qw2, 0, W - 1);
         const int jh_c = gh2 - (h0 - HL), jw_c = gw2 - (w0 - HL);
@@ -289,16 +355,16 @@ __global__ __launch_bounds__(NT) void mind_ssd_kernel(const float *__restrict__ 
   if (tid == 0) partial[tlin] = (double)tot;
 }
 
-template <int DELTA, int R, int CG>
-int launch_mind_ssd(const float *img, const float *noise, float rw, float *mws, double *partial, int D, int H, int W, int td,
-                    dim3 grid, const Taps &taps, hipStream_t st) {
+template <int DELTA, int R, int CG, bool SEEDED>
+int launch_mind_ssd(const float *img, std::conditional_t<SEEDED, PhiloxKey, const float *> noise, float rw, float *mws,
+                    double *partial, int D, int H, int W, int td, dim3 grid, const Taps &taps, hipStream_t st) {
   typedef MG<DELTA, R, CG> G;
   static_assert(G::LDS_BYTES <= 163840, "MIND tile does not fit the LDS");
   static DynLdsOnce once;
-  DG_REQUIRE(ensure_dyn_lds(once, (const void *)mind_ssd_kernel<DELTA, R, CG>, (int)G::LDS_BYTES) == hipSuccess,
+  DG_REQUIRE(ensure_dyn_lds(once, (const void *)mind_ssd_kernel<DELTA, R, CG, SEEDED>, (int)G::LDS_BYTES) == hipSuccess,
              DGTTA_ERR_LAUNCH, "mind3d: cannot raise the dynamic LDS limit to %zu", (size_t)G::LDS_BYTES);
-  hipLaunchKernelGGL((mind_ssd_kernel<DELTA, R, CG>), grid, dim3(NT), G::LDS_BYTES, st, img, noise, rw, mws, partial, D, H, W,
-                     td, taps);
+  hipLaunchKernelGGL((mind_ssd_kernel<DELTA, R, CG, SEEDED>), grid, dim3(NT), G::LDS_BYTES, st, img, noise, rw, mws, partial, D,
+                     H, W, td, taps);
   DG_CHECK_LAUNCH("mind_ssd_kernel");
   return DGTTA_OK;
 }
@@ -344,6 +410,21 @@ __global__ void mind_finish_kernel(const float *__restrict__ mws, const float *_
   }
 }
 
+// The noise field of philox.h as a tensor [B][12][V]: thread = one voxel of one 4-channel group (one Philox call), four
+// coalesced plane stores.
+__global__ void mind_noise_fill_kernel(float *__restrict__ noise, PhiloxKey key, int B, int64_t V) {
+  const int64_t total = (int64_t)B * 3 * V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t v = i % V, bg = i / V;
+    const int g = (int)(bg % 3), b = (int)(bg / 3);
+    float n[4];
+    mind_noise<4>(key, key.b0 + b, 4 * g, (uint32_t)v, n);
+    float *o = noise + ((int64_t)b * 12 + 4 * g) * V + v;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[(int64_t)c * V] = n[c];
+  }
+}
+
 void tile_counts(int D, int H, int W, int &td, int &th, int &tw) {
   td = cdiv(D, TD);
   th = cdiv(H, TH);
@@ -361,25 +442,34 @@ extern "C" size_t dgtta_mind3d_ws_bytes(int B, int D, int H, int W) {
   return m + p + 256;
 }
 
-extern "C" int dgtta_mind3d_fwd(const float *img, const float *noise, float rw, int delta, const float *h_taps, int ntaps,
-                                void *out, int out_ndhwc, int out_ldc, int out_dtype, void *ws, size_t ws_bytes, int B,
-                                int D, int H, int W, void *stream) {
-  DG_REQUIRE(img && noise && out && ws, DGTTA_ERR_BADARG, "mind3d_fwd: null pointer");
-  DG_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "mind3d_fwd: bad dims %d %d %d %d", B, D, H, W);
+// Argument checks shared by the tensor and the seeded entry point (`who` names the caller in the message).
+static int mind_check_args(const char *who, const void *img, const void *out, const void *ws, size_t ws_bytes, int delta,
+                           const float *h_taps, int ntaps, int out_ndhwc, int out_ldc, int out_dtype, int B, int D, int H,
+                           int W) {
+  DG_REQUIRE(img && out && ws, DGTTA_ERR_BADARG, "%s: null pointer", who);
+  DG_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "%s: bad dims %d %d %d %d", who, B, D, H, W);
   DG_REQUIRE(h_taps && (ntaps == 3 || ntaps == 5 || ntaps == 7), DGTTA_ERR_UNSUPPORTED,
-             "mind3d_fwd: %d filter taps (sigma up to 2, i.e. 3 / 5 / 7 taps, are built)", ntaps);
-  DG_REQUIRE(delta == 1 || delta == 2, DGTTA_ERR_UNSUPPORTED, "mind3d_fwd: delta %d (1 and 2 are built)", delta);
+             "%s: %d filter taps (sigma up to 2, i.e. 3 / 5 / 7 taps, are built)", who, ntaps);
+  DG_REQUIRE(delta == 1 || delta == 2, DGTTA_ERR_UNSUPPORTED, "%s: delta %d (1 and 2 are built)", who, delta);
   DG_REQUIRE(D <= 1024 && H <= 1024 && W <= 1024 && (int64_t)D * H * W < (1ll << 31), DGTTA_ERR_UNSUPPORTED,
-             "mind3d_fwd: each dim must be <= 1024 (got %d %d %d)", D, H, W);
-  DG_REQUIRE(ws_bytes >= dgtta_mind3d_ws_bytes(B, D, H, W), DGTTA_ERR_WORKSPACE, "mind3d_fwd: workspace too small");
+             "%s: each dim must be <= 1024 (got %d %d %d)", who, D, H, W);
+  DG_REQUIRE(ws_bytes >= dgtta_mind3d_ws_bytes(B, D, H, W), DGTTA_ERR_WORKSPACE, "%s: workspace too small", who);
   DG_REQUIRE(out_ndhwc ? (out_ldc >= 12) : (out_dtype == DGTTA_F32), DGTTA_ERR_BADARG,
-             "mind3d_fwd: NCDHW output must be fp32; NDHWC needs ldc >= 12");
-  DG_REQUIRE(out_dtype == DGTTA_F32 || out_dtype == DGTTA_BF16 || out_dtype == DGTTA_F16, DGTTA_ERR_BADARG,
-             "mind3d_fwd: bad dtype");
+             "%s: NCDHW output must be fp32; NDHWC needs ldc >= 12", who);
+  DG_REQUIRE(out_dtype == DGTTA_F32 || out_dtype == DGTTA_BF16 || out_dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: bad dtype",
+             who);
+  return DGTTA_OK;
+}
+
+// The three passes; `noise` is the tensor (SEEDED = false) or the PhiloxKey of the call.
+template <bool SEEDED>
+static int mind_run(const char *who, const float *img, std::conditional_t<SEEDED, PhiloxKey, const float *> noise, float rw,
+                    int delta, const float *h_taps, int ntaps, void *out, int out_ndhwc, int out_ldc, int out_dtype, void *ws,
+                    int B, int D, int H, int W, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   int td, th, tw;
   tile_counts(D, H, W, td, th, tw);
-  DG_REQUIRE((int64_t)td * B <= 65535 && th <= 65535, DGTTA_ERR_UNSUPPORTED, "mind3d_fwd: volume too large for grid");
+  DG_REQUIRE((int64_t)td * B <= 65535 && th <= 65535, DGTTA_ERR_UNSUPPORTED, "%s: volume too large for grid", who);
   const int64_t V = (int64_t)D * H * W;
   float *mws = (float *)ws;
   double *partial = (double *)((char *)ws + align_up((size_t)B * V * 12 * sizeof(float), 256));
@@ -393,7 +483,7 @@ extern "C" int dgtta_mind3d_fwd(const float *img, const float *noise, float rw, 
   const int R = ntaps / 2;
   int rc = DGTTA_ERR_UNSUPPORTED;
 #define MIND_CASE(DL, RR, CGG) \
-  if (delta == DL && R == RR) rc = launch_mind_ssd<DL, RR, CGG>(img, noise, rw, mws, partial, D, H, W, td, grid, taps, st);
+  if (delta == DL && R == RR) rc = launch_mind_ssd<DL, RR, CGG, SEEDED>(img, noise, rw, mws, partial, D, H, W, td, grid, taps, st);
   MIND_CASE(1, 1, 4) MIND_CASE(1, 2, 4) MIND_CASE(1, 3, 4) MIND_CASE(2, 1, 4) MIND_CASE(2, 2, 4) MIND_CASE(2, 3, 2)
 #undef MIND_CASE
   if (rc != DGTTA_OK) return rc;
@@ -415,5 +505,49 @@ extern "C" int dgtta_mind3d_fwd(const float *img, const float *noise, float rw, 
                        out_ldc, V, total);
   }
   DG_CHECK_LAUNCH("mind_finish_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_mind3d_fwd(const float *img, const float *noise, float rw, int delta, const float *h_taps, int ntaps,
+                                void *out, int out_ndhwc, int out_ldc, int out_dtype, void *ws, size_t ws_bytes, int B,
+                                int D, int H, int W, void *stream) {
+  DG_REQUIRE(noise, DGTTA_ERR_BADARG, "mind3d_fwd: null pointer");
+  const int rc = mind_check_args("mind3d_fwd", img, out, ws, ws_bytes, delta, h_taps, ntaps, out_ndhwc, out_ldc, out_dtype, B, D,
+                                 H, W);
+  if (rc != DGTTA_OK) return rc;
+  return mind_run<false>("mind3d_fwd", img, noise, rw, delta, h_taps, ntaps, out, out_ndhwc, out_ldc, out_dtype, ws, B, D, H, W,
+                         stream);
+}
+
+// Global sample indices enter counter word 1 as 4 b + c/4.
+static int mind_check_b0(const char *who, int b0, int B) {
+  DG_REQUIRE(b0 >= 0 && (int64_t)b0 + B <= (1ll << 29), DGTTA_ERR_BADARG, "%s: b0 %d + B %d outside [0, 2^29]", who, b0, B);
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_mind3d_fwd_seeded(const float *img, uint64_t seed, uint64_t offset, int b0, float rw, int delta,
+                                       const float *h_taps, int ntaps, void *out, int out_ndhwc, int out_ldc, int out_dtype,
+                                       void *ws, size_t ws_bytes, int B, int D, int H, int W, void *stream) {
+  int rc = mind_check_args("mind3d_fwd_seeded", img, out, ws, ws_bytes, delta, h_taps, ntaps, out_ndhwc, out_ldc, out_dtype, B,
+                           D, H, W);
+  if (rc == DGTTA_OK) rc = mind_check_b0("mind3d_fwd_seeded", b0, B);
+  if (rc != DGTTA_OK) return rc;
+  return mind_run<true>("mind3d_fwd_seeded", img, make_philox_key(seed, offset, b0), rw, delta, h_taps, ntaps, out, out_ndhwc,
+                        out_ldc, out_dtype, ws, B, D, H, W, stream);
+}
+
+extern "C" int dgtta_mind3d_noise_fill(float *noise, uint64_t seed, uint64_t offset, int b0, int B, int D, int H, int W,
+                                       void *stream) {
+  DG_REQUIRE(noise, DGTTA_ERR_BADARG, "mind3d_noise_fill: null pointer");
+  DG_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "mind3d_noise_fill: bad dims %d %d %d %d", B, D, H, W);
+  DG_REQUIRE((int64_t)D * H * W < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "mind3d_noise_fill: D H W must be < 2^31 (got %d %d %d)",
+             D, H, W);
+  const int rc = mind_check_b0("mind3d_noise_fill", b0, B);
+  if (rc != DGTTA_OK) return rc;
+  const int64_t V = (int64_t)D * H * W, total = (int64_t)B * 3 * V;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(mind_noise_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, noise, make_philox_key(seed, offset, b0),
+                     B, V);
+  DG_CHECK_LAUNCH("mind_noise_fill_kernel");
   return DGTTA_OK;
 }

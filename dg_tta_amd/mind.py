@@ -1,6 +1,9 @@
 """MIND3D descriptor — drop-in for dg_tta/mind.py (MIND3D :97-164, mind_hook :167-168), computed by the fused HIP
 kernels of csrc/mind3d.hip.  The Gaussian noise of mind.py:150 is drawn with torch.randn on the input's device
-(same generator the reference uses) and handed to the kernel, so seeding behaves exactly as in the reference."""
+(same generator the reference uses) and handed to the kernel, so seeding behaves exactly as in the reference.
+
+Opt-in: inside `kernel_noise(seed)` a call that was handed no noise tensor generates counter-based noise inside the kernel
+instead (ops.mind3d(seed=...): not torch.randn's stream, but no noise tensor and no generator state)."""
 import torch
 
 from . import ops
@@ -21,11 +24,39 @@ class MIND3D(torch.nn.Module):
         """Returns a logical [B,12,D,H,W] tensor.  Its memory is voxel-major with rows padded to 16 channels
         ([B,D,H,W,16], channels 12..15 zero), i.e. exactly what HipPlainConvUNet's first conv reads."""
         b, _, d, h, w = img.shape
+        if noise is None and _KERNEL_NOISE:
+            ctx = _KERNEL_NOISE[-1]
+            offset, ctx.calls = ctx.calls, ctx.calls + 1       # taken when the call is issued: the k-th call of the context
+            buf = ops.mind3d(img, None, self.randn_weighting, out_format="ndhwc", out_ldc=16, out_dtype=out_dtype, groups=groups,
+                             delta=self.delta, sigma=self.sigma, seed=ctx.seed, offset=offset, b0=0)
+            return buf[..., :12].permute(0, 4, 1, 2, 3)
         if noise is None:
             noise = torch.randn((b, 12, d, h, w), dtype=torch.float32, device=img.device, generator=device_generator())
         buf = ops.mind3d(img, noise, self.randn_weighting, out_format="ndhwc", out_ldc=16, out_dtype=out_dtype, groups=groups,
                          delta=self.delta, sigma=self.sigma)
         return buf[..., :12].permute(0, 4, 1, 2, 3)
+
+
+_KERNEL_NOISE = []      # the active kernel_noise contexts of this process, innermost last
+
+
+class kernel_noise:
+    """Context (per process, nests): a MIND3D.forward / mind_hook call that is handed no noise tensor computes the descriptor
+    with the seeded in-kernel noise of ops.mind3d(seed=...) instead of a torch.randn tensor.  The k-th such call since the
+    context was entered uses offset = k (counted from 0, in the order the calls are issued, whatever stream they run on) and
+    sample i of a call b = i: the result is a function of (seed, call order, input) alone.  No torch generator is read or
+    advanced and nothing waits for the device.  Outside any context MIND3D draws exactly as before."""
+
+    def __init__(self, seed):
+        self.seed, self.calls = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
+
+    def __enter__(self):
+        self.calls = 0
+        _KERNEL_NOISE.append(self)
+        return self
+
+    def __exit__(self, *exc):
+        _KERNEL_NOISE.remove(self)
 
 
 # Noise tensors drawn ahead of time by the batched two-branch path (tta.calc_both_branches): the reference draws a

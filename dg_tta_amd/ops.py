@@ -50,19 +50,44 @@ def gauss_taps(sigma):
     return (w / w.sum()).tolist()
 
 
-def mind3d(img, noise, randn_weighting=0.05, out_format="ncdhw", out_ldc=12, out_dtype=torch.float32, groups=1, delta=1,
-           sigma=1.0):
-    """MIND3D descriptor of img [B,1,D,H,W] with the randn draw `noise` [B,12,D,H,W] (reference: dg_tta/mind.py:142-164).
+def _u64(x):
+    return int(x) & 0xFFFFFFFFFFFFFFFF
+
+
+def mind3d_noise(b, d, h, w, seed, offset=0, b0=0, device="cuda"):
+    """The seeded MIND noise field [b,12,d,h,w] (fp32) of include/dgtta.h: Philox4x32-10 on (voxel, sample b0 + i, channel
+    group, offset) under the key `seed`, Box-Muller.  What mind3d(img, seed=...) generates inside its kernel."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DgttaError("dg_tta_amd ops run on the MI355X only: mind3d_noise got a CPU device (there is no CPU fallback)")
+    lib = _lib.load()
+    out = torch.empty((b, 12, d, h, w), dtype=torch.float32, device=device)
+    check(lib.dgtta_mind3d_noise_fill(ptr(out), _u64(seed), _u64(offset), int(b0), b, d, h, w, stream_of(out.device)),
+          "dgtta_mind3d_noise_fill")
+    return out
+
+
+def mind3d(img, noise=None, randn_weighting=0.05, out_format="ncdhw", out_ldc=12, out_dtype=torch.float32, groups=1, delta=1,
+           sigma=1.0, seed=None, offset=0, b0=0):
+    """MIND3D descriptor of img [B,1,D,H,W] (reference: dg_tta/mind.py:142-164) with exactly one of
+    `noise` [B,12,D,H,W], the randn draw of mind.py:150 as a tensor, or
+    `seed` (with `offset`, `b0`): the counter-based noise of mind3d_noise(B, D, H, W, seed, offset, b0), generated inside the
+    kernel - no noise tensor, no generator state.
 
     out_format 'ncdhw' -> contiguous [B,12,D,H,W] fp32; 'ndhwc' -> raw [B,D,H,W,out_ldc] buffer (fp32 or bf16).
     groups > 1: the batch is `groups` independent calls of B/groups samples (the variance clamp of mind.py:159-161
-    uses the mean over the whole call's batch), written into one output buffer.
+    uses the mean over the whole call's batch), written into one output buffer; group g of a seeded call starts at sample
+    b0 + g B/groups, so the grouping does not change a sample's noise.
     """
+    if (noise is None) == (seed is None):
+        raise ValueError("mind3d takes exactly one of `noise` (a tensor) and `seed` (in-kernel noise)")
     require_cuda(img, noise)
     lib = _lib.load()
     b, c, d, h, w = img.shape
-    assert c == 1 and tuple(noise.shape) == (b, 12, d, h, w)
-    img, noise = _f32c(img), _f32c(noise)
+    assert c == 1 and (noise is None or tuple(noise.shape) == (b, 12, d, h, w))
+    img = _f32c(img)
+    if noise is not None:
+        noise = _f32c(noise)
     ndhwc = out_format == "ndhwc"
     if ndhwc:
         out = torch.empty((b, d, h, w, out_ldc), dtype=out_dtype, device=img.device)
@@ -76,10 +101,13 @@ def mind3d(img, noise, randn_weighting=0.05, out_format="ncdhw", out_ldc=12, out
     h_taps = (C.c_float * len(taps))(*taps)
     for g in range(groups):
         sl = slice(g * bg, (g + 1) * bg)
-        check(lib.dgtta_mind3d_fwd(ptr(img[sl]), ptr(noise[sl]), float(randn_weighting), int(delta), h_taps, len(taps),
-                                   ptr(out[sl]), int(ndhwc),
-                                   int(out_ldc), dtype_code(out_dtype), ptr(ws), nbytes, bg, d, h, w,
-                                   stream_of(img.device)), "dgtta_mind3d_fwd")
+        tail = (float(randn_weighting), int(delta), h_taps, len(taps), ptr(out[sl]), int(ndhwc), int(out_ldc),
+                dtype_code(out_dtype), ptr(ws), nbytes, bg, d, h, w, stream_of(img.device))
+        if noise is not None:
+            check(lib.dgtta_mind3d_fwd(ptr(img[sl]), ptr(noise[sl]), *tail), "dgtta_mind3d_fwd")
+        else:
+            check(lib.dgtta_mind3d_fwd_seeded(ptr(img[sl]), _u64(seed), _u64(offset), int(b0) + g * bg, *tail),
+                  "dgtta_mind3d_fwd_seeded")
     return out
 
 

@@ -552,7 +552,7 @@ def tta_main(run_name, config, tta_data_dir, save_base_path, label_mapping, modi
                     break
             release_resident(tta_tens_list)      # this sample's volume leaves HBM
             if predict_here:
-                case = (sample, sample_id, sub_dir_tta)
+                case = (sample, sample_id, sub_dir_tta, smp_idx)
                 if len(mine) == ensemble_count:
                     np_state = np.random.get_state()
                     with torch.random.fork_rng(devices=[device]):      # CPU + device generator states restored on exit
@@ -583,6 +583,23 @@ def tta_main(run_name, config, tta_data_dir, save_base_path, label_mapping, modi
     return results
 
 
+def _inference_noise(config, smp_idx):
+    """Optional plan key `inference_mind_noise` (not a reference key): "tensor" (default) - the ensemble prediction draws its MIND
+    noise with torch.randn on the device generator, as the reference; "kernel" - it runs inside mind.kernel_noise(s): the noise
+    is generated inside the descriptor kernel, s from the plan's `seed` (else torch.initial_seed()) and the sample index, so a
+    case's prediction does not depend on generator state, on what ran before it or on the GPU count.  The TTA loop is not
+    inside the context: it always draws as the reference."""
+    import contextlib
+    mode = config.get("inference_mind_noise", "tensor")
+    if mode not in ("tensor", "kernel"):
+        raise ValueError(f"inference_mind_noise={mode!r}: 'tensor' or 'kernel'")
+    if mode == "tensor":
+        return contextlib.nullcontext()
+    from ..mind import kernel_noise
+    base = int(config["seed"]) if config.get("seed") is not None else torch.initial_seed()
+    return kernel_noise((base + 0x9E3779B97F4A7C15 * (int(smp_idx) + 1)) & 0xFFFFFFFFFFFFFFFF)
+
+
 def _predict_case(case, config, network, predictor, patch_size, label_mapping, modifier_fn_module, device, save_path,
                   tta_data_dir, results, world, timeout):
     """Ensemble prediction of one case + its evaluation target (reference: tta.py:379-446).
@@ -595,7 +612,7 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
     from .inference import export_segmentation, predict_ensemble
     from .image_io import read_image as read_nifti
     from .torch_utils import get_imgs
-    sample, sample_id, sub_dir_tta = case
+    sample, sample_id, sub_dir_tta, smp_idx = case
     ensemble_count = config["ensemble_count"]
     optimized_labels = config["optimized_labels"]
     paths = [get_parameters_save_path(sub_dir_tta, sample_id, e) for e in range(ensemble_count)]
@@ -610,7 +627,8 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
     image = get_imgs(sample["data"].unsqueeze(0)).squeeze(0)
     props = sample.get("data_properties") or {}
     nii = props.get("nifti_header")
-    acc, nsum, crop = predict_ensemble(image, model, params, patch_size)
+    with _inference_noise(config, smp_idx):
+        acc, nsum, crop = predict_ensemble(image, model, params, patch_size)
     plans = getattr(predictor, "plans", None)
     original = nii is not None and plans is not None and "shape_before_cropping" in props
     seg = export_segmentation(acc, nsum, crop, props if original else None, plans, getattr(predictor, "configuration", None))

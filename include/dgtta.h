@@ -68,6 +68,32 @@ int dgtta_mind3d_fwd(const float *img, const float *noise, float randn_weighting
                      int D, int H, int W, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Seeded MIND noise: a counter-based stand-in for the randn draw of mind.py:150 that needs no noise
+ * tensor and no generator state.  It is NOT torch.randn's stream.  n[b,c,d,h,w], c in 0..11, is
+ *   (x0,x1,x2,x3) = Philox4x32-10(counter = (v, 4*b + c/4, offset_lo, offset_hi), key = (seed_lo, seed_hi))
+ *         v = (d*H + h)*W + w  (< 2^31),  b = b0 + the sample's index inside the call (b0 + B <= 2^29)
+ *   u_i = ((x_i >> 9) + 0.5) * 2^-23                    exact in fp32, in (0,1)
+ *   c%4 == 0: sqrt(-2 ln u0) cos(2 pi u1)   1: sqrt(-2 ln u0) sin(2 pi u1)
+ *         2: sqrt(-2 ln u2) cos(2 pi u3)   3: sqrt(-2 ln u2) sin(2 pi u3)
+ * Philox4x32-10 as published (Random123): multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on
+ * word 2), key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds with the key bumped between rounds, round
+ * output (hi1^c1^k0, lo1, hi0^c3^k1, lo0); counter 0 / key 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ * A value depends on (seed, offset, b, c, v) only: not on tiling, grouping or launch geometry.
+ *
+ * noise_fill: writes that field as [B,12,D,H,W] fp32 (the testable face of the definition; also for
+ * callers who want the tensor).
+ * fwd_seeded: dgtta_mind3d_fwd with the field generated inside the descriptor kernel where the tensor
+ * form loads it (voxels of the replicate-padded halo take the noise of the clamped voxel, as there);
+ * same checks, workspace and outputs.  fwd_seeded(img, seed, ...) equals fwd(img, noise_fill(seed, ...))
+ * up to the last bits of the library's log / sincos between two kernels.
+ * ------------------------------------------------------------------------------------------- */
+int dgtta_mind3d_noise_fill(float *noise, uint64_t seed, uint64_t offset, int b0, int B, int D, int H, int W,
+                            void *stream);
+int dgtta_mind3d_fwd_seeded(const float *img, uint64_t seed, uint64_t offset, int b0, float randn_weighting, int delta,
+                            const float *h_taps, int ntaps, void *out, int out_ndhwc, int out_ldc, int out_dtype,
+                            void *ws, size_t ws_bytes, int B, int D, int H, int W, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GIN random-convolution chain.  Replaces GINGroupConv.forward / GradlessGCReplayNonlinBlock.forward
  * (dg_tta/gin.py:168-230, :59-122) for gin_aug's fixed config (1->2->2->2->1 channels, 4 layers).
  * x,out [B,1,D,H,W] fp32.  alpha [B].  ksz[4] HOST ints in {1,3}.  ker[l] = device pointer to

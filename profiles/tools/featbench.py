@@ -8,8 +8,10 @@ DEV = "cuda:0"
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 what = sys.argv[3].split(",") if len(sys.argv) > 3 else ["gin", "mind", "mind_bf16"]
+ITERS = int(sys.argv[4]) if len(sys.argv) > 4 else 20      # 1: one timed step (under rocprofv3 --kernel-trace --stats)
 
-def timeit(fn, iters=20):
+def timeit(fn, iters=None):
+    iters = iters or ITERS
     for _ in range(3): fn()
     torch.cuda.synchronize()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
@@ -41,3 +43,13 @@ if "mind_bf16" in what:
     print(f"mind3d bf16 out (noise input) {n}^3 x{B}: {t:8.1f} us per sample")
     t = timeit(lambda: torch.randn(B, 12, n, n, n, device=DEV))
     print(f"torch.randn noise draw       {n}^3 x{B}: {t:8.1f} us per sample")
+if "mind_seeded" in what:
+    # tensor noise (the randn draw + mind_ssd reading it back) against the seeded kernel (mind_ssd generating it), bf16 output,
+    # one variance-clamp mean per sample as the inference windows use it; and the fill kernel on its own
+    m = MIND3D()
+    t = timeit(lambda: m(x, out_dtype=torch.bfloat16, groups=B))
+    print(f"mind3d bf16 out, randn draw included {n}^3 x{B}: {t:8.1f} us per sample")
+    t = timeit(lambda: ops.mind3d(x, seed=1, out_format="ndhwc", out_ldc=16, out_dtype=torch.bfloat16, groups=B))
+    print(f"mind3d bf16 out, seeded in-kernel    {n}^3 x{B}: {t:8.1f} us per sample")
+    t = timeit(lambda: ops.mind3d_noise(B, n, n, n, seed=1, device=DEV))
+    print(f"mind3d_noise fill                    {n}^3 x{B}: {t:8.1f} us per sample")
