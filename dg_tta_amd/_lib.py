@@ -40,6 +40,9 @@ SIGNATURES = {
     "dgtta_dice_ce_ws_bytes": (SZ, [I, I, I64]),
     "dgtta_dice_ce_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I64, F, I, P]),
     "dgtta_dice_ce_bwd": (I, [P, I, P, P, F, P, P, I, I, I, I64, P]),
+    "dgtta_dice_ce_ds_ws_bytes": (SZ, [I, I, I, I, I]),
+    "dgtta_dice_ce_ds_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, F, I, P]),
+    "dgtta_dice_ce_ds_bwd": (I, [P, I, P, P, F, P, P, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_adamw_step": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I64), I, F, F, F, F, F,
                              I, F, P, P]),
     "dgtta_grads_nonfinite": (I, [C.POINTER(P), C.POINTER(I64), I, P, P]),
@@ -77,6 +80,7 @@ SIGNATURES = {
     "dgtta_seghead_fwd": (I, [P, I, P, P, P, I, P, I, I, I, I, I64, I, P]),
     "dgtta_seghead_bwd_ws_bytes": (SZ, [I, I, I, I64]),
     "dgtta_seghead_bwd": (I, [P, I, P, I, P, P, I, P, I, P, P, P, SZ, I, I, I64, I, I, P]),
+    "dgtta_seghead_bwd_acc": (I, [P, I, P, I, P, P, I, P, I, P, P, P, SZ, I, I, I64, I, I, I, P]),
     "dgtta_seghead_warp_supported": (I, [P, I, I, I, I, I, I, I]),
     "dgtta_seghead_warp_bwd_ws_bytes": (SZ, [I, I, I, I, I, I]),
     "dgtta_seghead_warp_fwd": (I, [P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),

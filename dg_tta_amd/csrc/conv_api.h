@@ -90,6 +90,15 @@ size_t head_wgrad_mfma_ws_bytes(int Cin, int nsel, int64_t rows);
 int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *dw_sel, void *ws, size_t ws_bytes, int Cin,
                     int nsel, int64_t rows, int accumulate, int dtype, hipStream_t st, bool have_d16);
 
+// ---------------------------------------------------------------------------------------------------- seghead_mfma.hip
+// 1x1x1 heads with Cin a multiple of 32 (32..320), nsel <= 128, 16-bit storage; DGTTA_ERR_UNSUPPORTED for anything else
+int head_fwd_mfma(const void *x, int ldx, const float *w, const float *bias, const int *sel, int nsel, float *out, int ldo, int Cin,
+                  int64_t rows, int dtype, hipStream_t st);
+int head_dgrad_mfma(const float *dout, int lddo, const float *w, const int *sel, int nsel, void *dx, int lddx, int Cin, int64_t rows,
+                    int accumulate_dx, int dtype, hipStream_t st);
+int head_wgrad_rows_mfma(const void *x, int ldx, const float *dout, int lddo, float *part, int nsplit, int nsel, int Cin, int64_t rows,
+                         int dtype, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------------------- conv_ref.hip
 // launchers of the general-shape VALU kernels: every Cin / Cout / ld; the weight gradients leave nsplit partial sums in
 // `part` and add them up in order into dw_t

@@ -10,6 +10,14 @@
 // Logits are voxel-major [B][V][ldc] fp32 (what the head writes); a workgroup stages 128 rows through LDS as one contiguous run,
 // one lane = one voxel inside the tile; HBM-bound and NOT on the timed path.
 // Deterministic: per-workgroup partial sums (double) in fixed slots, one finalize workgroup adds them in slot order.
+//
+// Deep supervision (dgtta_dice_ce_ds_*): the same loss at a LOWER resolution [B][d][h][w] against the FULL-resolution label map
+// [B][D][H][W], D = d sd etc. with integer strides: the label of low-resolution voxel (i, j, k) is
+//   labels[i sd + sd / 2][j sh + sh / 2][k sw + sw / 2]                  (integer division)
+// - what an order-0 resize with half-pixel centres and round-half-up picks for an integer factor.  nnU-Net trains its auxiliary
+// outputs against label maps downsampled by DownsampleSegForDSTransform2 [3P nnunetv2==2.2.1, not available here]: this rule
+// is a restatement FROM MEMORY of that transform's nearest-neighbour choice and is UNPINNED.  The kernels read the label
+// through the index map below: no downsampled label tensor exists.  Strides (1, 1, 1) are the plain loss, bit for bit.
 #include "common.h"
 
 namespace {
@@ -18,6 +26,18 @@ constexpr int DC_MAXC = 128;
 constexpr int DC_TILE = 128;               // voxels per tile: rows are staged through LDS as ONE contiguous run (a lane that walks
                                            // its own 420-byte row straight from memory runs at 0.3 TB/s, DESIGN.md "20x trap")
 constexpr int DC_THREADS = 256;
+
+// where the label of voxel v of sample b lives: dense [B][V], or a strided view of a full-resolution map (h == 0: dense)
+struct DcLabels {
+  int h, w, sd, sh, sw;
+  int64_t H, W, Vfull;
+  __device__ __forceinline__ int64_t at(int b, int64_t v, int64_t V) const {
+    if (h == 0) return (int64_t)b * V + v;
+    const int64_t i = v / ((int64_t)h * w), rem = v - i * ((int64_t)h * w);
+    const int64_t j = rem / w, k = rem - j * w;
+    return (int64_t)b * Vfull + ((i * sd + sd / 2) * H + (j * sh + sh / 2)) * W + (k * sw + sw / 2);
+  }
+};
 
 __host__ __device__ inline int dc_pitch(int C) { return C | 1; }
 inline int dc_blocks(int64_t V) {
@@ -64,14 +84,13 @@ __device__ __forceinline__ void dc_tile_store(const float *tile, float *dst, int
 // partial[(b * nblk + blk) * (3C + 2) + {c, C + c, 2C + c, 3C, 3C + 1}] = {sum p y, sum p, sum y, sum -log p_y, valid voxels}
 __global__ __launch_bounds__(DC_THREADS) void dice_ce_fwd_kernel(const float *__restrict__ logits, int ldc,
                                                                const int64_t *__restrict__ labels, double *__restrict__ partial,
-                                                               int C, int64_t V) {
+                                                               int C, int64_t V, DcLabels lm) {
   extern __shared__ float dc_tile[];               // [DC_TILE][C | 1]
   __shared__ int s_lab[DC_TILE];
   __shared__ float s_red[16];
   const int LDP = dc_pitch(C);
   const int b = blockIdx.y, t = threadIdx.x;
   const float *lb = logits + (int64_t)b * V * ldc;
-  const int64_t *yb = labels + (int64_t)b * V;
   double aI = 0.0, aP = 0.0, aY = 0.0, ce = 0.0, nv_tot = 0.0;
   const int64_t ntile = (V + DC_TILE - 1) / DC_TILE;
   for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
@@ -84,7 +103,7 @@ __global__ __launch_bounds__(DC_THREADS) void dice_ce_fwd_kernel(const float *__
       float *row = dc_tile + t * LDP;
       int y = -1;
       if (t < nv) {
-        const int64_t yl = yb[v0 + t];
+        const int64_t yl = labels[lm.at(b, v0 + t, V)];
         y = (yl >= 0 && yl < C) ? (int)yl : -1;
       }
       if (y >= 0) {
@@ -204,7 +223,8 @@ __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const double *__
 __global__ __launch_bounds__(DC_THREADS) void dice_ce_bwd_kernel(const float *__restrict__ logits, int ldc,
                                                                const int64_t *__restrict__ labels, const float *__restrict__ coef,
                                                                float scale, const float *__restrict__ scale_dev,
-                                                               float *__restrict__ grad, int ldg, int B, int C, int64_t V) {
+                                                               float *__restrict__ grad, int ldg, int B, int C, int64_t V,
+                                                               DcLabels lm) {
   extern __shared__ float dc_tile[];               // [DC_TILE][C | 1]: logits in, gradient out
   __shared__ float s_coef[2 * DC_MAXC];
   const int LDP = dc_pitch(C);
@@ -221,7 +241,7 @@ __global__ __launch_bounds__(DC_THREADS) void dice_ce_bwd_kernel(const float *__
     __syncthreads();
     if (t < nv) {
       float *row = dc_tile + t * LDP;
-      const int64_t yl = labels[(int64_t)b * V + v0 + t];
+      const int64_t yl = labels[lm.at(b, v0 + t, V)];
       if (yl < 0 || yl >= C) {
         for (int c = 0; c < C; ++c) row[c] = 0.f;
       } else {
@@ -258,8 +278,8 @@ extern "C" size_t dgtta_dice_ce_ws_bytes(int B, int C, int64_t V) {
   return align_up(dc_partial_doubles(B, C, V) * sizeof(double), 256) + align_up(((size_t)2 * B * C + 1) * sizeof(float), 256);
 }
 
-extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
-                                 size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, void *stream) {
+static int dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws, size_t ws_bytes,
+                       int B, int C, int64_t V, float smooth, int do_bg, void *stream, const DcLabels &lm) {
   DG_REQUIRE(logits && labels && loss3 && dice && ws, DGTTA_ERR_BADARG, "dice_ce_fwd: null pointer");
   DG_REQUIRE(B > 0 && B <= 8 && C >= 2 && C <= DC_MAXC && V > 0 && ldc >= C, DGTTA_ERR_BADARG,
              "dice_ce_fwd: need 1<=B<=8, 2<=C<=%d, ldc>=C (B=%d C=%d ldc=%d)", DC_MAXC, B, C, ldc);
@@ -272,7 +292,7 @@ extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *la
   static DynLdsOnce once;
   DG_REQUIRE(ensure_dyn_lds(once, (const void *)dice_ce_fwd_kernel, DC_TILE * dc_pitch(DC_MAXC) * (int)sizeof(float)) == hipSuccess,
              DGTTA_ERR_LAUNCH, "dice_ce_fwd: cannot raise the dynamic LDS limit");
-  hipLaunchKernelGGL(dice_ce_fwd_kernel, dim3(nblk, B), dim3(DC_THREADS), lds, st, logits, ldc, labels, partial, C, V);
+  hipLaunchKernelGGL(dice_ce_fwd_kernel, dim3(nblk, B), dim3(DC_THREADS), lds, st, logits, ldc, labels, partial, C, V, lm);
   DG_CHECK_LAUNCH("dice_ce_fwd_kernel");
   hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, nblk, B, C, smooth, do_bg ? 0 : 1, loss3, dice,
                      coef);
@@ -280,9 +300,9 @@ extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *la
   return DGTTA_OK;
 }
 
-extern "C" int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, const void *ws, float grad_scale,
-                                 const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int64_t V,
-                                 void *stream) {
+static int dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, const void *ws, float grad_scale,
+                       const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int64_t V, void *stream,
+                       const DcLabels &lm) {
   DG_REQUIRE(logits && labels && ws && grad_logits, DGTTA_ERR_BADARG, "dice_ce_bwd: null pointer");
   DG_REQUIRE(B > 0 && B <= 8 && C >= 2 && C <= DC_MAXC && V > 0 && ldc >= C && ldg >= C, DGTTA_ERR_BADARG, "dice_ce_bwd: bad dims");
   const float *coef = (const float *)((const char *)ws + align_up(dc_partial_doubles(B, C, V) * sizeof(double), 256));
@@ -293,7 +313,53 @@ extern "C" int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *la
   DG_REQUIRE(ensure_dyn_lds(once, (const void *)dice_ce_bwd_kernel, DC_TILE * dc_pitch(DC_MAXC) * (int)sizeof(float)) == hipSuccess,
              DGTTA_ERR_LAUNCH, "dice_ce_bwd: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(dice_ce_bwd_kernel, dim3((unsigned)gx, B), dim3(DC_THREADS), lds, (hipStream_t)stream, logits, ldc, labels, coef,
-                     grad_scale, grad_scale_dev, grad_logits, ldg, B, C, V);
+                     grad_scale, grad_scale_dev, grad_logits, ldg, B, C, V, lm);
   DG_CHECK_LAUNCH("dice_ce_bwd_kernel");
   return DGTTA_OK;
+}
+
+static const DcLabels DC_DENSE = {0, 0, 1, 1, 1, 0, 0, 0};
+
+extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
+                                 size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, void *stream) {
+  return dice_ce_fwd(logits, ldc, labels, loss3, dice, ws, ws_bytes, B, C, V, smooth, do_bg, stream, DC_DENSE);
+}
+
+extern "C" int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, const void *ws, float grad_scale,
+                                 const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int64_t V,
+                                 void *stream) {
+  return dice_ce_bwd(logits, ldc, labels, ws, grad_scale, grad_scale_dev, grad_logits, ldg, B, C, V, stream, DC_DENSE);
+}
+
+// ---- the same loss on logits [B][d][h][w][ld] against the full-resolution label map [B][d sd][h sh][w sw]
+static bool dc_ds_dims_ok(int d, int h, int w, int sd, int sh, int sw) {
+  return d > 0 && h > 0 && w > 0 && sd > 0 && sh > 0 && sw > 0 && (int64_t)d * sd < (1ll << 31) && (int64_t)h * sh < (1ll << 31) &&
+         (int64_t)w * sw < (1ll << 31);
+}
+static DcLabels dc_ds_labels(int d, int h, int w, int sd, int sh, int sw) {
+  DcLabels lm = {h, w, sd, sh, sw, (int64_t)h * sh, (int64_t)w * sw, (int64_t)d * sd * h * sh * w * sw};
+  return lm;
+}
+
+extern "C" size_t dgtta_dice_ce_ds_ws_bytes(int B, int C, int d, int h, int w) {
+  if (d <= 0 || h <= 0 || w <= 0) return 0;
+  return dgtta_dice_ce_ws_bytes(B, C, (int64_t)d * h * w);
+}
+
+extern "C" int dgtta_dice_ce_ds_fwd(const float *logits, int ldc, const int64_t *labels_full, float *loss3, float *dice, void *ws,
+                                    size_t ws_bytes, int B, int C, int d, int h, int w, int sd, int sh, int sw, float smooth,
+                                    int do_bg, void *stream) {
+  DG_REQUIRE(dc_ds_dims_ok(d, h, w, sd, sh, sw), DGTTA_ERR_BADARG, "dice_ce_ds_fwd: bad dims %dx%dx%d strides %d,%d,%d", d, h, w, sd,
+             sh, sw);
+  return dice_ce_fwd(logits, ldc, labels_full, loss3, dice, ws, ws_bytes, B, C, (int64_t)d * h * w, smooth, do_bg, stream,
+                     dc_ds_labels(d, h, w, sd, sh, sw));
+}
+
+extern "C" int dgtta_dice_ce_ds_bwd(const float *logits, int ldc, const int64_t *labels_full, const void *ws, float grad_scale,
+                                    const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int d, int h, int w,
+                                    int sd, int sh, int sw, void *stream) {
+  DG_REQUIRE(dc_ds_dims_ok(d, h, w, sd, sh, sw), DGTTA_ERR_BADARG, "dice_ce_ds_bwd: bad dims %dx%dx%d strides %d,%d,%d", d, h, w, sd,
+             sh, sw);
+  return dice_ce_bwd(logits, ldc, labels_full, ws, grad_scale, grad_scale_dev, grad_logits, ldg, B, C, (int64_t)d * h * w, stream,
+                     dc_ds_labels(d, h, w, sd, sh, sw));
 }

@@ -1,6 +1,7 @@
 // 1x1x1 segmentation head on selected rows of the weight (map_label folded in): forward, data gradient, weight gradient.
 // VALU kernels by shape (general, 32-channel register rows, LDS-staged coalesced, wide 33..128 classes); the MFMA weight
-// gradient of the production shape is head_wgrad_mfma (conv_wgrad.hip).
+// gradient of the production shape is head_wgrad_mfma (conv_wgrad.hip); heads with more than 32 input channels in 16-bit
+// storage (the auxiliary heads of deep supervision) run the matrix-core kernels of seghead_mfma.hip.
 #include "conv_api.h"
 
 namespace {
@@ -32,7 +33,7 @@ __global__ void head_fwd_kernel(const T *__restrict__ x, int ldx, const float *_
   }
 }
 
-template <typename T>
+template <typename T, bool ACC>
 __global__ void head_dgrad_kernel(const float *__restrict__ dout, int lddo, const float *__restrict__ w,
                                   const int *__restrict__ sel, int nsel, T *__restrict__ dx, int lddx, int Cin,
                                   int64_t total) {
@@ -41,6 +42,7 @@ __global__ void head_dgrad_kernel(const float *__restrict__ dout, int lddo, cons
     const int64_t row = i / Cin;
     float acc = 0.f;
     for (int k = 0; k < nsel; ++k) acc = __builtin_fmaf(dout[row * lddo + k], w[(int64_t)(sel ? sel[k] : k) * Cin + ci], acc);
+    if (ACC) acc += ld_f<T>(dx + row * lddx + ci);      // the rows already hold another consumer's gradient
     st_f<T>(dx + row * lddx + ci, acc);
   }
 }
@@ -362,6 +364,10 @@ extern "C" int dgtta_seghead_fwd(const void *x, int ldx, const float *w, const f
     DG_CHECK_LAUNCH("head_fwd_fast_kernel");
     return DGTTA_OK;
   }
+  if (Cin != 32 && out_ndhwc) {      // more than 32 channels in 16-bit storage (the auxiliary heads): matrix cores
+    const int rc = head_fwd_mfma(x, ldx, w, bias, sel, nsel, out, ldo, Cin, (int64_t)B * V, dtype, (hipStream_t)stream);
+    if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
+  }
   const int64_t total = (int64_t)B * V * nsel;
   if (out_ndhwc)
     DISPATCH_T(dtype, hipLaunchKernelGGL((head_fwd_kernel<T, true>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0,
@@ -392,9 +398,78 @@ extern "C" size_t dgtta_seghead_bwd_ws_bytes(int B, int Cin, int nsel, int64_t V
   return head_bias_region(B, nsel, V) + (a > c ? a : c);
 }
 
-extern "C" int dgtta_seghead_bwd(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel,
-                                 int nsel, void *dx, int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
-                                 int B, int Cin, int64_t V, int accumulate, int dtype, void *stream) {
+// data gradient on the vector ALUs: the general kernel where dx is added to or the shape has no kernel of its own, else the
+// 32-channel kernels (they overwrite).  *d16: set where the kernel leaves a 16-bit copy of dout at ws_main for head_wgrad_mfma
+static int head_dgrad_valu(const float *dout, int lddo, const float *w, const int *sel, int nsel, void *dx, int lddx, bool want_d16,
+                           void *ws_main, size_t main_bytes, int Cin, int64_t rows, int accumulate_dx, int dtype, hipStream_t st,
+                           unsigned short **d16) {
+  if (accumulate_dx || Cin != 32 || nsel > HWD_MAXK) {
+    const int64_t total = rows * Cin;
+    if (accumulate_dx)
+      DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_kernel<T, true>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st, dout,
+                                           lddo, w, sel, nsel, (T *)dx, lddx, Cin, total));
+    else
+      DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_kernel<T, false>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st, dout,
+                                           lddo, w, sel, nsel, (T *)dx, lddx, Cin, total));
+    DG_CHECK_LAUNCH("head_dgrad_kernel");
+    return DGTTA_OK;
+  }
+  if (nsel <= 32) {
+    const int blocks = (int)(cdiv64(rows, 256) < 8192 ? cdiv64(rows, 256) : 8192);
+    if (lddx == 32 && lddo == nsel && nsel <= 16 && ((uintptr_t)dx & 15) == 0) {
+      if (want_d16 && dtype != DGTTA_F32 && head_wgrad_mfma_ws_bytes(Cin, nsel, rows) > 0 &&
+          main_bytes >= head_wgrad_mfma_ws_bytes(Cin, nsel, rows)) {
+        *d16 = (unsigned short *)ws_main;       // the first region of head_wgrad_mfma's workspace
+      }
+      DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_lds_kernel<T>), dim3(blocks), dim3(256), 0, st, dout, w, sel, nsel,
+                                           (T *)dx, rows, *d16));
+      DG_CHECK_LAUNCH("head_dgrad_lds_kernel");
+    } else {
+      DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_fast_kernel<T, 32>), dim3(blocks), dim3(256), 0, st, dout, lddo, w,
+                                           sel, nsel, (T *)dx, lddx, rows));
+      DG_CHECK_LAUNCH("head_dgrad_fast_kernel");
+    }
+    return DGTTA_OK;
+  }
+  // the wide head: 64-row tiles through LDS
+  const size_t lds = ((size_t)HWD_MAXK * 32 + (size_t)HWD_ROWS * (nsel | 1)) * sizeof(float);
+  const int64_t nt = cdiv64(rows, HWD_ROWS);
+  DISPATCH_T(dtype, {
+    static DynLdsOnce once;
+    DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(head_dgrad_wide_kernel<T>),
+                              (HWD_MAXK * 32 + HWD_ROWS * (HWD_MAXK | 1)) * (int)sizeof(float)) == hipSuccess,
+               DGTTA_ERR_LAUNCH, "seghead_bwd: cannot raise the dynamic LDS limit");
+    hipLaunchKernelGGL((head_dgrad_wide_kernel<T>), dim3((unsigned)(nt < 4096 ? nt : 4096)), dim3(256), lds, st, dout, lddo, w, sel,
+                       nsel, (T *)dx, lddx, rows);
+  });
+  DG_CHECK_LAUNCH("head_dgrad_wide_kernel");
+  return DGTTA_OK;
+}
+
+// per-split partials of the weight gradient, part[ns][nsel][Cin], on the vector ALUs
+static int head_wgrad_parts_valu(const void *x, int ldx, const float *dout, int lddo, float *part, int ns, int nsel, int Cin,
+                                 int64_t rows, int dtype, hipStream_t st) {
+  if (Cin == 32 && nsel > 32 && nsel <= HWD_MAXK) {
+    const size_t lds = ((size_t)HWD_ROWS * 33 + (size_t)HWD_ROWS * (nsel | 1) + HWD_MAXK) * sizeof(float);
+    DISPATCH_T(dtype, {
+      static DynLdsOnce once;
+      DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(head_wgrad_wide_kernel<T>),
+                                (HWD_ROWS * 33 + HWD_ROWS * (HWD_MAXK | 1) + HWD_MAXK) * (int)sizeof(float)) == hipSuccess,
+                 DGTTA_ERR_LAUNCH, "seghead_bwd: cannot raise the dynamic LDS limit");
+      hipLaunchKernelGGL((head_wgrad_wide_kernel<T>), dim3(ns), dim3(256), lds, st, (const T *)x, ldx, dout, lddo, part, nsel, rows);
+    });
+    DG_CHECK_LAUNCH("head_wgrad_wide_kernel");
+    return DGTTA_OK;
+  }
+  DISPATCH_T(dtype, hipLaunchKernelGGL((head_wgrad_kernel<T>), dim3(cdiv(Cin * nsel, 256), ns), dim3(256), 0, st, (const T *)x, ldx,
+                                       dout, lddo, part, Cin, nsel, rows));
+  DG_CHECK_LAUNCH("head_wgrad_kernel");
+  return DGTTA_OK;
+}
+
+static int seghead_bwd(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel, int nsel, void *dx,
+                       int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes, int B, int Cin, int64_t V, int accumulate,
+                       int accumulate_dx, int dtype, void *stream) {
   DG_REQUIRE(x && dout && w && ws, DGTTA_ERR_BADARG, "seghead_bwd: null pointer");
   DG_REQUIRE(B > 0 && Cin > 0 && nsel > 0 && V > 0 && ldx >= Cin && lddo >= nsel, DGTTA_ERR_BADARG, "seghead_bwd: bad dims");
   DG_REQUIRE(ws_bytes >= dgtta_seghead_bwd_ws_bytes(B, Cin, nsel, V), DGTTA_ERR_WORKSPACE, "seghead_bwd: workspace too small");
@@ -406,69 +481,44 @@ extern "C" int dgtta_seghead_bwd(const void *x, int ldx, const float *dout, int 
   unsigned short *d16 = nullptr;      // 16-bit copy of dout written by the data-gradient kernel for the weight gradient
   if (dx) {
     DG_REQUIRE(lddx >= Cin, DGTTA_ERR_BADARG, "seghead_bwd: lddx < Cin");
-    if (Cin == 32 && nsel <= 32) {
-      const int blocks = (int)(cdiv64(rows, 256) < 8192 ? cdiv64(rows, 256) : 8192);
-      if (lddx == 32 && lddo == nsel && nsel <= 16 && ((uintptr_t)dx & 15) == 0) {
-        if (dw_sel && dtype != DGTTA_F32 && head_wgrad_mfma_ws_bytes(Cin, nsel, rows) > 0 &&
-            main_bytes >= head_wgrad_mfma_ws_bytes(Cin, nsel, rows)) {
-          d16 = (unsigned short *)ws_main;       // the first region of head_wgrad_mfma's workspace
-        }
-        DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_lds_kernel<T>), dim3(blocks), dim3(256), 0, st, dout, w, sel, nsel,
-                                             (T *)dx, rows, d16));
-        DG_CHECK_LAUNCH("head_dgrad_lds_kernel");
-      } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_fast_kernel<T, 32>), dim3(blocks), dim3(256), 0, st, dout, lddo, w,
-                                             sel, nsel, (T *)dx, lddx, rows));
-        DG_CHECK_LAUNCH("head_dgrad_fast_kernel");
-      }
-    } else if (Cin == 32 && nsel <= HWD_MAXK) {      // the wide head: 64-row tiles through LDS
-      const size_t lds = ((size_t)HWD_MAXK * 32 + (size_t)HWD_ROWS * (nsel | 1)) * sizeof(float);
-      const int64_t nt = cdiv64(rows, HWD_ROWS);
-      DISPATCH_T(dtype, {
-        static DynLdsOnce once;
-        DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(head_dgrad_wide_kernel<T>),
-                                  (HWD_MAXK * 32 + HWD_ROWS * (HWD_MAXK | 1)) * (int)sizeof(float)) == hipSuccess,
-                   DGTTA_ERR_LAUNCH, "seghead_bwd: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((head_dgrad_wide_kernel<T>), dim3((unsigned)(nt < 4096 ? nt : 4096)), dim3(256), lds, st, dout, lddo, w, sel,
-                           nsel, (T *)dx, lddx, rows);
-      });
-      DG_CHECK_LAUNCH("head_dgrad_wide_kernel");
-    } else {
-      const int64_t total = rows * Cin;
-      DISPATCH_T(dtype, hipLaunchKernelGGL((head_dgrad_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st, dout,
-                                           lddo, w, sel, nsel, (T *)dx, lddx, Cin, total));
-      DG_CHECK_LAUNCH("head_dgrad_kernel");
-    }
+    // adding to dx (an auxiliary head: the rows hold the transposed conv's gradient) or more than 32 channels: the matrix-core
+    // kernel where it applies; everything else on the vector ALUs.  (accumulate_dx with Cin == 32 in 16-bit storage also lands on
+    // the matrix-core kernel: no head of a real plan asks for it - the 32-channel head is the full-resolution one, whose rows
+    // nobody wrote before - but the entry point accepts it.  That kernel leaves no 16-bit copy of dout, so d16 stays null and
+    // head_wgrad_mfma converts dout itself.)
+    int rc = DGTTA_ERR_UNSUPPORTED;
+    if (accumulate_dx || Cin != 32) rc = head_dgrad_mfma(dout, lddo, w, sel, nsel, dx, lddx, Cin, rows, accumulate_dx, dtype, st);
+    if (rc == DGTTA_ERR_UNSUPPORTED)
+      rc = head_dgrad_valu(dout, lddo, w, sel, nsel, dx, lddx, dw_sel != nullptr, ws_main, main_bytes, Cin, rows, accumulate_dx, dtype,
+                           st, &d16);
+    if (rc != DGTTA_OK) return rc;
   }
   if (dw_sel) {
     int rc = head_wgrad_mfma(x, ldx, dout, lddo, dw_sel, ws_main, main_bytes, Cin, nsel, rows, accumulate, dtype, st,
                              d16 != nullptr);
-    if (rc == DGTTA_ERR_UNSUPPORTED) {
+    if (rc == DGTTA_ERR_UNSUPPORTED) {      // per-split partials (the 32-channel kernels keep their shapes), added in order
       const int ns = head_splits(rows);
       float *part = (float *)ws_main;
-      if (Cin == 32 && nsel > 32 && nsel <= HWD_MAXK) {
-        const size_t lds = ((size_t)HWD_ROWS * 33 + (size_t)HWD_ROWS * (nsel | 1) + HWD_MAXK) * sizeof(float);
-        DISPATCH_T(dtype, {
-          static DynLdsOnce once;
-          DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(head_wgrad_wide_kernel<T>),
-                                    (HWD_ROWS * 33 + HWD_ROWS * (HWD_MAXK | 1) + HWD_MAXK) * (int)sizeof(float)) == hipSuccess,
-                     DGTTA_ERR_LAUNCH, "seghead_bwd: cannot raise the dynamic LDS limit");
-          hipLaunchKernelGGL((head_wgrad_wide_kernel<T>), dim3(ns), dim3(256), lds, st, (const T *)x, ldx, dout, lddo, part, nsel,
-                             rows);
-        });
-        DG_CHECK_LAUNCH("head_wgrad_wide_kernel");
-      } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((head_wgrad_kernel<T>), dim3(cdiv(Cin * nsel, 256), ns), dim3(256), 0, st,
-                                             (const T *)x, ldx, dout, lddo, part, Cin, nsel, rows));
-        DG_CHECK_LAUNCH("head_wgrad_kernel");
-      }
-      const int64_t n = (int64_t)nsel * Cin;
-      rc = reduce_splits(part, dw_sel, n, ns, accumulate, st);
-      if (rc != DGTTA_OK) return rc;
-    } else if (rc != DGTTA_OK) {
-      return rc;
+      rc = DGTTA_ERR_UNSUPPORTED;
+      if (Cin != 32) rc = head_wgrad_rows_mfma(x, ldx, dout, lddo, part, ns, nsel, Cin, rows, dtype, st);
+      if (rc == DGTTA_ERR_UNSUPPORTED) rc = head_wgrad_parts_valu(x, ldx, dout, lddo, part, ns, nsel, Cin, rows, dtype, st);
+      if (rc == DGTTA_OK) rc = reduce_splits(part, dw_sel, (int64_t)nsel * Cin, ns, accumulate, st);
     }
+    if (rc != DGTTA_OK) return rc;
   }
   if (db_sel) return conv_bias_grad(dout, lddo, db_sel, ws_bias, B, nsel, V, accumulate, DGTTA_F32, st);
   return DGTTA_OK;
+}
+
+extern "C" int dgtta_seghead_bwd(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel,
+                                 int nsel, void *dx, int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
+                                 int B, int Cin, int64_t V, int accumulate, int dtype, void *stream) {
+  return seghead_bwd(x, ldx, dout, lddo, w, sel, nsel, dx, lddx, dw_sel, db_sel, ws, ws_bytes, B, Cin, V, accumulate, 0, dtype, stream);
+}
+
+extern "C" int dgtta_seghead_bwd_acc(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel,
+                                     int nsel, void *dx, int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
+                                     int B, int Cin, int64_t V, int accumulate, int accumulate_dx, int dtype, void *stream) {
+  return seghead_bwd(x, ldx, dout, lddo, w, sel, nsel, dx, lddx, dw_sel, db_sel, ws, ws_bytes, B, Cin, V, accumulate, accumulate_dx,
+                     dtype, stream);
 }

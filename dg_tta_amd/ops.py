@@ -411,6 +411,92 @@ def dice_ce_loss(logits, labels, smooth=1e-5, do_bg=False):
     return _DiceCE.apply(logits.float(), labels, smooth, do_bg)
 
 
+class _DiceCEStrided(torch.autograd.Function):
+    """DC+CE of low-resolution logits against a strided view of the full-resolution label map (csrc/dice_ce.hip, _ds)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, strides, smooth, do_bg):
+        lib = _lib.load()
+        b, c, d, h, w = logits.shape
+        logits = logits.contiguous(memory_format=torch.channels_last_3d)
+        labels = labels.contiguous()
+        loss3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+        dice = torch.empty((b, c), dtype=torch.float32, device=logits.device)
+        nbytes = lib.dgtta_dice_ce_ds_ws_bytes(b, c, d, h, w)
+        ws = _ws(nbytes, logits.device)
+        check(lib.dgtta_dice_ce_ds_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, d, h, w, *strides,
+                                       float(smooth), int(do_bg), stream_of(logits.device)), "dgtta_dice_ce_ds_fwd")
+        ctx.save_for_backward(logits, labels, ws)
+        ctx.meta = (b, c, d, h, w, strides)
+        ctx.mark_non_differentiable(dice)
+        return loss3[0], dice, loss3[1:].detach()
+
+    @staticmethod
+    def backward(ctx, gloss, _gdice, _gparts):
+        logits, labels, ws = ctx.saved_tensors
+        b, c, d, h, w, strides = ctx.meta
+        lib = _lib.load()
+        g = torch.empty_like(logits, memory_format=torch.preserve_format)
+        gs = gloss.reshape(1).float().contiguous()      # (carries the scale's weight of the multi-scale sum)
+        check(lib.dgtta_dice_ce_ds_bwd(ptr(logits), c, ptr(labels), ptr(ws), 1.0, ptr(gs), ptr(g), c, b, c, d, h, w, *strides,
+                                       stream_of(logits.device)), "dgtta_dice_ce_ds_bwd")
+        return g, None, None, None, None
+
+
+def deep_supervision_weights(n):
+    """nnU-Net's weights of the multi-scale loss for n outputs (highest resolution first): 2^-i, the lowest resolution set to 0,
+    normalised to sum 1 (5 outputs: [8/15, 4/15, 2/15, 1/15, 0]; one output: [1])."""
+    w = [2.0 ** -i for i in range(n)]
+    if n > 1:
+        w[-1] = 0.0
+    tot = sum(w)
+    return [x / tot for x in w]
+
+
+def _label_strides(out_shape, label_shape):
+    strides = []
+    for o, full in zip(out_shape, label_shape):
+        if o <= 0 or full % o:
+            raise ValueError(f"deep_supervision_loss: output {tuple(out_shape)} does not divide the label map {tuple(label_shape)}")
+        strides.append(full // o)
+    return tuple(strides)
+
+
+def deep_supervision_loss(outputs, labels, smooth=1e-5, do_bg=False, weights=None):
+    """nnU-Net's multi-scale loss (DeepSupervisionWrapper [3P] around DC_and_CE_loss): sum_i w_i * dice_ce(outputs[i], labels at
+    the resolution of outputs[i]).  outputs: logits [B,C,d_i,h_i,w_i], highest resolution first (what HipPlainConvUNet returns
+    with deep_supervision on); labels: the FULL-resolution integer map [B,1,D,H,W] / [B,D,H,W] - every output is compared
+    with the strided view labels[i sd + sd/2, j sh + sh/2, k sw + sw/2] of it (csrc/dice_ce.hip; a restatement from memory of
+    nnU-Net's DownsampleSegForDSTransform2, unpinned), no downsampled label map is built.  The strides follow from the shapes
+    and must divide exactly (ValueError).  weights: default deep_supervision_weights(len(outputs)); a zero-weight scale is
+    skipped in both directions.  Returns (loss, [per-scale loss or None where skipped]); differentiable w.r.t. every output."""
+    outputs = list(outputs)
+    if labels.dim() == 5:
+        labels = labels[:, 0]
+    if weights is None:
+        weights = deep_supervision_weights(len(outputs))
+    if len(weights) != len(outputs):
+        raise ValueError(f"deep_supervision_loss: {len(weights)} weights for {len(outputs)} outputs")
+    strides = [_label_strides(o.shape[2:], labels.shape[1:]) for o in outputs]
+    for o in outputs:
+        if o.shape[0] != labels.shape[0]:
+            raise ValueError("deep_supervision_loss: batch sizes of outputs and labels differ")
+    require_cuda(labels, *outputs)
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    total, per_scale = None, []
+    for o, st, wgt in zip(outputs, strides, weights):
+        if wgt == 0:
+            per_scale.append(None)
+            continue
+        li, _, _ = _DiceCEStrided.apply(o.float(), labels, st, smooth, do_bg)
+        per_scale.append(li.detach())
+        total = li * wgt if total is None else total + li * wgt
+    if total is None:
+        raise ValueError("deep_supervision_loss: every weight is zero")
+    return total, per_scale
+
+
 class _SoftDice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

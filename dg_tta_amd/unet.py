@@ -128,9 +128,13 @@ class HipPlainConvUNet(nn.Module):
     conv_impl: 0 auto (MFMA where covered, else general VALU kernel), 1 force VALU, 2 force MFMA.  It applies to the 3x3x3
     layers with isotropic strides; the anisotropic layers of anisotropic plans (cfg "kernel_sizes" (kd, 3, 3) / per-axis
     "strides") always run their matrix-core kernels (dgtta_conv3d_fwd / _dgrad / _wgrad, dgtta_convT3d_s_*).
+    deep_supervision (a plain attribute, as nnU-Net's decoder.deep_supervision: toggle it at will): forward returns a tuple of
+    logits, highest resolution first - element 0 is the usual output, element i is seg_layers[-1-i] on the output of decoder
+    stage n-1-i - and the backward takes a gradient for each (ops.deep_supervision_loss).  It does not combine with
+    fuse_output_warp / fuse_window_accumulate / fuse_window_feature_accumulate (ValueError).
     """
 
-    def __init__(self, cfg=None, act_dtype=torch.float32, conv_impl=0):
+    def __init__(self, cfg=None, act_dtype=torch.float32, conv_impl=0, deep_supervision=False):
         super().__init__()
         cfg = dict(PLANS_3D_FULLRES if cfg is None else cfg)
         self.cfg = cfg
@@ -153,6 +157,7 @@ class HipPlainConvUNet(nn.Module):
         self.selected_classes = None   # optional LongTensor: evaluate only these head rows (== map_label 'logits')
         self._fused_warp = None        # (theta on the device, theta on the host) while fuse_output_warp() is active
         self._window_acc = None        # sliding-window target while fuse_window_accumulate() is active
+        self.deep_supervision = bool(deep_supervision)
 
     def __deepcopy__(self, memo):
         # get_model_from_network deep-copies the network per ensemble member: do not drag the packed-weight cache along
@@ -171,6 +176,11 @@ class HipPlainConvUNet(nn.Module):
     def set_selected_classes(self, idx):
         """Fuses map_label(..., 'logits') (torch_utils.py:214-221) into the head: forward returns only these rows."""
         self.selected_classes = None if idx is None else torch.as_tensor(idx, dtype=torch.int32)
+
+    def _no_deep_supervision(self, what):
+        if self.deep_supervision:
+            raise ValueError(f"{what} does not combine with deep_supervision=True (the fused kernels know one head): "
+                             "switch net.deep_supervision off first")
 
     @contextlib.contextmanager
     def _during(self, attr, make):
@@ -200,6 +210,7 @@ class HipPlainConvUNet(nn.Module):
     def fuse_output_warp(self, theta_dev, theta_host):
         """Context: the next forward returns affine_warp(logits, theta, zeros, tta_grid_algebra) computed by the fused
         head + warp kernels (and its backward runs the fused gather).  Check can_fuse_output_warp first."""
+        self._no_deep_supervision("fuse_output_warp")
         return self._during("_fused_warp", lambda: (theta_dev.float().contiguous(), theta_host.detach().float().contiguous()))
 
     # -- head fused with the Gaussian window accumulation of the sliding-window inference (csrc/warp.hip)
@@ -215,6 +226,7 @@ class HipPlainConvUNet(nn.Module):
             raise ValueError(f"fuse_window_accumulate: the accumulator is fp32 or fp16, not {acc.dtype}")
         if not (acc.is_contiguous() and nsum.dtype == torch.float32 and gauss.dtype == torch.float32):
             raise ValueError("fuse_window_accumulate: contiguous accumulator, fp32 weight sum and fp32 Gaussian expected")
+        self._no_deep_supervision("fuse_window_accumulate")
         return self._during("_window_acc", lambda: (acc, nsum, gauss, list(origins)))
 
     # -- the same in FEATURE space (csrc/window_features.hip): the head is linear and last, so the window accumulator
@@ -230,12 +242,16 @@ class HipPlainConvUNet(nn.Module):
         if not (facc.dtype == torch.float32 and facc.is_contiguous() and facc.shape[-1] == 32 and nsum.dtype == torch.float32 and
                 gauss.dtype == torch.float32):
             raise ValueError("fuse_window_feature_accumulate: contiguous fp32 accumulator [X,Y,Z,32], fp32 weight sum and Gaussian expected")
+        self._no_deep_supervision("fuse_window_feature_accumulate")
         return self._during("_window_acc", lambda: (facc, nsum, gauss, list(origins), "features"))
 
     def forward(self, x):
         sel = self.selected_classes
         if sel is not None and sel.device != x.device:
             sel = self.selected_classes = sel.to(x.device)
+        ds = bool(self.deep_supervision)
+        if ds and (self._fused_warp is not None or self._window_acc is not None):      # switched on inside a fuse_* context
+            self._no_deep_supervision("fuse_output_warp" if self._fused_warp is not None else "a fuse_window_* context")
         params = [p for p in self.parameters()]
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         # With the head fused into the inverse warp and 16-bit storage, the network's backward can take the gradient of
@@ -246,7 +262,7 @@ class HipPlainConvUNet(nn.Module):
         if (need_grad and self._fused_warp is not None and self.act_dtype in (torch.bfloat16, torch.float16)
                 and os.environ.get("DGTTA_GRAD16", "1") != "0"):
             sink = Grad16Sink(self.act_dtype)
-        y = _UNetFn.apply(self, x, sel, need_grad, sink, *params)
+        y = _UNetFn.apply(self, x, sel, need_grad, sink, ds, *params)
         if sink is not None:
             y._dgtta_grad16 = sink
         return y

@@ -436,7 +436,9 @@ def _encoder_forward(p, enc, ups, dec, x):
 
 
 def _decoder_forward(p, ups, dec, cats, x, feat_fold):
-    """Runs the decoder from the deepest activation x; returns the rows the segmentation head reads."""
+    """Runs the decoder from the deepest activation x; returns every stage's output rows (the last: what the segmentation
+    head reads, the others: what the auxiliary heads of deep supervision read)."""
+    stage_rows = []
     for up, stage, cat in zip(ups, dec, reversed(cats)):
         up.fwd(p, x, cat.rows())
         x = cat.rows()
@@ -445,7 +447,8 @@ def _decoder_forward(p, ups, dec, cats, x, feat_fold):
             # its InstanceNorm + LeakyReLU apply runs inside the accumulation kernel, z is never written
             fold = feat_fold and blk is dec[-1][-1]
             x = _block_forward(p, blk, x, xbs=cat.xbs if blk is stage[0] else 0, stats_only=fold)
-    return x
+        stage_rows.append(x)
+    return stage_rows
 
 
 def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
@@ -508,7 +511,44 @@ def _head_forward(p, head, z, sel, nsel, fw, dims):
     return out
 
 
+def _aux_heads_forward(p, net, dec, stage_rows, sel, nsel):
+    """Deep supervision: seg_layers[k] (the selected rows) on the output rows of decoder stage k, for every stage but the last;
+    returned highest resolution first (the order of nnU-Net's decoder, after the full-resolution output)."""
+    return [_head_forward(p, net.decoder.seg_layers[k], stage_rows[k], sel, nsel, None, dec[k][-1].dout)
+            for k in range(len(dec) - 2, -1, -1)]
+
+
 # ------------------------------------------------------------------------------------------------ backward steps
+def _scatter_head_grads(p, head, sel, dws, dbs):
+    """Adds the compact weight / bias gradient rows of a head (its selected rows) into the parameters' gradient buffers."""
+    cin = head.in_channels
+    gw, gb = p.gbuf(head.weight), p.gbuf(head.bias)
+    if sel is None:
+        gw.view(-1, cin).add_(dws)       # buffers start at zero (or hold earlier accumulation steps)
+        gb.add_(dbs)
+    else:
+        gw.view(-1, cin).index_add_(0, sel.long(), dws)
+        gb.index_add_(0, sel.long(), dbs)
+
+
+def _aux_head_backward(p, head, z, sel, nsel, gout, gz, dims):
+    """Backward of an auxiliary head from gout, the gradient of its logits: ADDS its data gradient to the rows gz (which the
+    transposed conv's backward has just written) and its weight / bias gradient to the parameters' buffers."""
+    D, H, W = dims
+    cin = head.in_channels
+    assert gz.ld >= cin and z.ld >= cin
+    g = gout.contiguous(memory_format=torch.channels_last_3d).float()      # [B,nsel,D,H,W] stored NDHWC
+    need_hw = head.weight.requires_grad or head.bias.requires_grad
+    dws = p.empty(nsel, cin, dtype=torch.float32) if need_hw else None
+    dbs = p.empty(nsel, dtype=torch.float32) if need_hw else None
+    nb = p.lib.dgtta_seghead_bwd_ws_bytes(p.B, cin, nsel, D * H * W)
+    ws = p.ws.get(nb)
+    check(p.lib.dgtta_seghead_bwd_acc(z.ptr, z.ld, ptr(g), nsel, ptr(head.weight), ptr(sel), nsel, gz.ptr, gz.ld, ptr(dws), ptr(dbs),
+                                      ptr(ws), nb, p.B, cin, D * H * W, 0, 1, p.dt, p.st), "dgtta_seghead_bwd_acc")
+    if need_hw:
+        _scatter_head_grads(p, head, sel, dws, dbs)
+
+
 def _head_backward(p, head, z, sel, nsel, fw, g16, gout, dims):
     """Backward of `_head_forward` from gout (or g16, what the loss left in the Grad16Sink): the gradient rows of z."""
     lib, B, dt, st = p.lib, p.B, p.dt, p.st
@@ -536,13 +576,7 @@ def _head_backward(p, head, z, sel, nsel, fw, g16, gout, dims):
         check(lib.dgtta_seghead_bwd(z.ptr, z.ld, ptr(g), nsel, ptr(head.weight), ptr(sel), nsel, ptr(gz), cin, ptr(dws), ptr(dbs),
                                     ptr(ws), nb, B, cin, D * H * W, 0, dt, st), "dgtta_seghead_bwd")
     if need_hw:
-        gw, gb = p.gbuf(head.weight), p.gbuf(head.bias)
-        if sel is None:
-            gw.view(-1, cin).add_(dws)       # buffers start at zero (or hold earlier accumulation steps)
-            gb.add_(dbs)
-        else:
-            gw.view(-1, cin).index_add_(0, sel.long(), dws)
-            gb.index_add_(0, sel.long(), dbs)
+        _scatter_head_grads(p, head, sel, dws, dbs)
     return _Rows(gz, gz.data_ptr(), cin)
 
 
@@ -630,7 +664,7 @@ class _UNetFn(torch.autograd.Function):
     """Whole-network autograd node: forward saves raw conv outputs, normalised activations and IN statistics."""
 
     @staticmethod
-    def forward(ctx, net, x, sel, need_grad, sink, *params):
+    def forward(ctx, net, x, sel, need_grad, sink, deep_supervision, *params):
         _lib.require_cuda(x)
         B, cin0, D, H, W = x.shape
         dims = (D, H, W)
@@ -644,7 +678,8 @@ class _UNetFn(torch.autograd.Function):
                      head.in_channels == cfg["features"][0] == 32)
         enc, ups, dec = _plan(p, cin0, dims)
         z, cats = _encoder_forward(p, enc, ups, dec, _input_rows(p, x))
-        z = _decoder_forward(p, ups, dec, cats, z, feat_fold)
+        stage_rows = _decoder_forward(p, ups, dec, cats, z, feat_fold)
+        z = stage_rows[-1]
         if wa is not None:
             assert not need_grad and sel is None and z.ld == head.in_channels and len(wa[3]) == B, "fuse_window_accumulate: misuse"
             if len(wa) > 4:      # feature space: no head here
@@ -655,19 +690,27 @@ class _UNetFn(torch.autograd.Function):
         nsel = head.out_channels if sel is None else int(sel.numel())
         fw = net._fused_warp
         out = _head_forward(p, head, z, sel, nsel, fw, dims)
+        aux = _aux_heads_forward(p, net, dec, stage_rows, sel, nsel) if deep_supervision else []
         if need_grad:
+            ctx.set_materialize_grads(False)      # an output the loss does not use contributes nothing and launches nothing
+            ctx.aux = [(stage_rows[k], dec[k][-1].dout) for k in range(len(dec) - 1)] if deep_supervision else None
             ctx.net, ctx.sel, ctx.params = net, sel, params
             ctx.blocks = [blk for stage in enc + dec for blk in stage]
             ctx.ups, ctx.cats = ups, cats
             ctx.meta = (B, dims, nsel, z)
             ctx.fused_warp = fw
             ctx.sink = sink if fw is not None else None
+        if deep_supervision:
+            return (out.permute(0, 4, 1, 2, 3),) + tuple(a.permute(0, 4, 1, 2, 3) for a in aux)
         return out.permute(0, 4, 1, 2, 3)
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, *gaux):
         net, blocks, ups, cats = ctx.net, ctx.blocks, ctx.ups, ctx.cats
         B, dims, nsel, z = ctx.meta
+        if gout is None:      # the loss used auxiliary outputs only
+            dev = next(g for g in gaux if g is not None).device
+            gout = torch.zeros((B, nsel) + tuple(dims), dtype=torch.float32, device=dev)
         p = _BackwardPass(net, gout.device, B)
         g16 = ctx.sink.take() if ctx.sink is not None else None      # the loss left its gradient in the storage type
         gz = _head_backward(p, net.decoder.seg_layers[-1], z, ctx.sel, nsel, ctx.fused_warp, g16, gout, dims)
@@ -684,6 +727,10 @@ class _UNetFn(torch.autograd.Function):
             if kind == "dec" and bidx == 0:
                 gup, gskip[sidx] = _concat_grad(p, blk, dy, cats[-(sidx + 1)])
                 gz = _up_backward(p, ups[sidx], gup)
+                # gz = the gradient rows of decoder stage sidx - 1's output: its auxiliary head (output n - sidx of n) adds to them
+                if sidx > 0 and gaux and gaux[len(ups) - 1 - sidx] is not None:
+                    za, adims = ctx.aux[sidx - 1]
+                    _aux_head_backward(p, net.decoder.seg_layers[sidx - 1], za, ctx.sel, nsel, gaux[len(ups) - 1 - sidx], gz, adims)
             elif kind == "enc" and bidx == 0:
                 # input was the previous encoder stage's output, which lives in the skip half of a concat buffer
                 # and already holds the decoder's skip gradient: accumulate into it.
@@ -693,4 +740,4 @@ class _UNetFn(torch.autograd.Function):
                 gz, gstats = _plain_grad(p, blk, dy, blocks[idx - 1])
         if p.side is not None:
             p.main_stream.wait_stream(p.side)         # gradients complete before anything downstream (optimizer, next pass)
-        return (None,) * 5 + tuple(p.grads.get(id(q)) if q.requires_grad else None for q in ctx.params)
+        return (None,) * 6 + tuple(p.grads.get(id(q)) if q.requires_grad else None for q in ctx.params)

@@ -205,6 +205,20 @@ int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float
                       size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, void *stream);
 int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, const void *ws, float grad_scale,
                       const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int64_t V, void *stream);
+/* The same loss at a lower resolution (deep supervision): logits / grad_logits fp32 [B][d][h][w][ld], labels_full the
+ * FULL-resolution int64 map [B][d sd][h sh][w sw] with integer strides; the label of low-resolution voxel (i, j, k) is
+ * labels_full[i sd + sd / 2][j sh + sh / 2][k sw + sw / 2] (integer division) - the voxel an order-0 resize with half-pixel
+ * centres and round-half-up picks.  Restated from memory of nnU-Net's DownsampleSegForDSTransform2 [3P nnunetv2==2.2.1, not
+ * available here]: UNPINNED.  No downsampled label tensor is materialised.  Same smooth / do_bg / ignore rule / loss3 / dice
+ * / ws contract as above with V = d h w; the per-scale weight of the multi-scale loss goes in through grad_scale(_dev).
+ * Strides (1, 1, 1) give dgtta_dice_ce_fwd / _bwd bit for bit. */
+size_t dgtta_dice_ce_ds_ws_bytes(int B, int C, int d, int h, int w);
+int dgtta_dice_ce_ds_fwd(const float *logits, int ldc, const int64_t *labels_full, float *loss3, float *dice, void *ws,
+                         size_t ws_bytes, int B, int C, int d, int h, int w, int sd, int sh, int sw, float smooth, int do_bg,
+                         void *stream);
+int dgtta_dice_ce_ds_bwd(const float *logits, int ldc, const int64_t *labels_full, const void *ws, float grad_scale,
+                         const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int d, int h, int w, int sd,
+                         int sh, int sw, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * AdamW (decoupled weight decay, bias-corrected, no amsgrad) over a list of tensors.  Replaces
@@ -374,6 +388,13 @@ size_t dgtta_seghead_bwd_ws_bytes(int B, int Cin, int nsel, int64_t V);
 int dgtta_seghead_bwd(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel,
                       int nsel, void *dx, int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
                       int B, int Cin, int64_t V, int accumulate, int dtype, void *stream);
+/* + accumulate_dx: dx += dout . W_sel instead of dx = (an auxiliary head of deep supervision adds to the gradient rows that the
+ * next transposed conv's backward wrote; no temporary, no add pass).  Same workspace.  Heads with Cin a multiple of 32
+ * (32..320; 64.. without accumulate_dx), nsel <= 128 and 16-bit storage run on the matrix cores (csrc/seghead_mfma.hip), as
+ * does dgtta_seghead_fwd for them; every other shape runs the general kernels. */
+int dgtta_seghead_bwd_acc(const void *x, int ldx, const float *dout, int lddo, const float *w, const int *sel,
+                          int nsel, void *dx, int lddx, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
+                          int B, int Cin, int64_t V, int accumulate, int accumulate_dx, int dtype, void *stream);
 
 /* Segmentation head fused with the inverse warp of its logits: the two steps at the end of calc_branch
  * (dg_tta/tta/tta.py:560-575: model() -> map_label(logits) -> grid_sample(..., R_inverse grid, zeros padding)) in one launch
