@@ -347,14 +347,30 @@ __global__ __launch_bounds__(256) void warp_bwd_gather_kernel(const float *__res
 }
 
 // Fallback for maps the gather kernel declines (singular / extreme minification): zero, then scatter with atomics.
-__global__ void warp_bwd_zero_if_declined_kernel(const float *__restrict__ theta, float *__restrict__ gsrc, int B, int Ds,
-                                                 int Hs, int Ws, int Dd, int Hd, int Wd, int algebra, int64_t per_batch) {
+// (only the C operand columns of a row: with src_ldc > C the rest of the row belongs to somebody else)
+__global__ void warp_bwd_zero_if_declined_kernel(const float *__restrict__ theta, float *__restrict__ gsrc, int B, int C,
+                                                 int src_ldc, int Ds, int Hs, int Ws, int Dd, int Hd, int Wd, int algebra,
+                                                 int64_t per_batch) {
   for (int b = 0; b < B; ++b) {
     if (inverse_map(theta + b * 12, Ds, Hs, Ws, Dd, Hd, Wd, algebra).ok) continue;
     float *g = gsrc + (int64_t)b * per_batch;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_batch; i += (int64_t)gridDim.x * blockDim.x)
-      g[i] = 0.f;
+    if (src_ldc == C) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_batch; i += (int64_t)gridDim.x * blockDim.x)
+        g[i] = 0.f;
+    } else {      // rows of a wider buffer: the operand columns only, as warp_zero_columns_kernel
+      const int64_t total = per_batch / src_ldc * C;
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        g[(i / C) * src_ldc + i % C] = 0.f;
+    }
   }
+}
+
+// zeroes the C operand columns of `rows` rows of leading dimension ldc > C (a channel slice of a wider buffer: a memset over
+// rows * ldc elements would clear the neighbouring columns and run past the last row's operand)
+__global__ void warp_zero_columns_kernel(float *__restrict__ g, int C, int ldc, int64_t rows) {
+  const int64_t total = rows * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+    g[(i / C) * ldc + i % C] = 0.f;
 }
 
 // NDHWC, trilinear, 4 channels per thread: the general kernel above spends most of its time on the five 64-bit
@@ -1187,8 +1203,8 @@ extern "C" int dgtta_affine_warp3d_bwd(const float *grad_dst, const float *theta
       hipLaunchKernelGGL((warp_bwd_gather_kernel<16, false>), grid, dim3(256), 0, st, grad_dst, theta, grad_src, C, Ds,
                          Hs, Ws, Dd, Hd, Wd, src_ldc, dst_ldc, tta_grid_algebra, gx, gy);
     DG_CHECK_LAUNCH("warp_bwd_gather_kernel");
-    hipLaunchKernelGGL(warp_bwd_zero_if_declined_kernel, dim3(256), dim3(256), 0, st, theta, grad_src, B, Ds, Hs, Ws, Dd,
-                       Hd, Wd, tta_grid_algebra, Vs * src_ldc);
+    hipLaunchKernelGGL(warp_bwd_zero_if_declined_kernel, dim3(256), dim3(256), 0, st, theta, grad_src, B, C, src_ldc, Ds, Hs,
+                       Ws, Dd, Hd, Wd, tta_grid_algebra, Vs * src_ldc);
     DG_CHECK_LAUNCH("warp_bwd_zero_if_declined_kernel");
     const int64_t tot2 = (int64_t)B * Vd * C;
     hipLaunchKernelGGL((warp_bwd_kernel<1, true>), dim3(grid_for(tot2)), dim3(256), 0, st, grad_dst, theta, grad_src, C,
@@ -1197,8 +1213,12 @@ extern "C" int dgtta_affine_warp3d_bwd(const float *grad_dst, const float *theta
     return DGTTA_OK;
   }
   // general path: zero grad_src, then scatter with fp32 atomics
-  {
-    const size_t nb = ndhwc ? (size_t)B * Vs * src_ldc * sizeof(float) : (size_t)B * C * Vs * sizeof(float);
+  if (ndhwc && src_ldc != C) {
+    hipLaunchKernelGGL(warp_zero_columns_kernel, dim3(grid_for((int64_t)B * Vs * C)), dim3(256), 0, st, grad_src, C, src_ldc,
+                       (int64_t)B * Vs);
+    DG_CHECK_LAUNCH("warp_zero_columns_kernel");
+  } else {
+    const size_t nb = (size_t)B * C * Vs * sizeof(float);
     hipError_t e = hipMemsetAsync(grad_src, 0, nb, st);
     DG_REQUIRE(e == hipSuccess, DGTTA_ERR_LAUNCH, "warp_bwd: memset failed: %s", hipGetErrorString(e));
   }
@@ -1227,8 +1247,14 @@ static size_t head_warp_bias_region(int B, int D, int H, int W) {
   return align_up((size_t)nblk * HW_NS * sizeof(double), 256);
 }
 
+// The weight gradient of the fused backward is head_wgrad_mfma on the 16-bit copy of the gathered gradient, whose rows (nsel
+// 16-bit values) are read in 16-byte pieces: 8 or 16 selected classes.  There is no fp32 copy to fall back on (the two-step
+// path's dgtta_seghead_bwd has one), so 4 and 12 classes get the fused forward and the fused data / bias gradient only.
+static bool head_warp_wgrad_ok(int nsel) { return nsel % 8 == 0; }
+
 extern "C" int dgtta_seghead_warp_supported(const float *h_theta, int B, int Cin, int nsel, int D, int H, int W, int dtype) {
   if (!h_theta || B <= 0 || B > 16 || D <= 0 || H <= 0 || W <= 0 || !head_warp_shape_ok(Cin, nsel, dtype)) return 0;
+  if (!head_warp_wgrad_ok(nsel)) return 0;     // (the caller may want the head's weight gradient)
   if (head_wgrad_mfma_ws_bytes(Cin, nsel, (int64_t)B * D * H * W) == 0) return 0;
   for (int b = 0; b < B; ++b)
     if (!host_map_ok(h_theta + 12 * b, D, H, W)) return 0;
@@ -1291,6 +1317,8 @@ static int seghead_warp_bwd_impl(const void *z, const void *gout, int gout16, co
   DG_REQUIRE(z && gout && theta && h_theta && w && gz && ws, DGTTA_ERR_BADARG, "seghead_warp_bwd: null pointer");
   DG_REQUIRE(B > 0 && B <= 16 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "seghead_warp_bwd: bad dims");
   DG_REQUIRE(head_warp_shape_ok(Cin, nsel, dtype), DGTTA_ERR_UNSUPPORTED, "seghead_warp_bwd: unsupported shape / dtype");
+  DG_REQUIRE(!dw_sel || head_warp_wgrad_ok(nsel), DGTTA_ERR_UNSUPPORTED,
+             "seghead_warp_bwd: the weight gradient needs 8 or 16 selected classes (nsel %d; use the unfused path)", nsel);
   DG_REQUIRE(((uintptr_t)gout & 15) == 0 && ((uintptr_t)gz & 15) == 0, DGTTA_ERR_BADARG, "seghead_warp_bwd: unaligned operand");
   const size_t need = dgtta_seghead_warp_bwd_ws_bytes(B, Cin, nsel, D, H, W);
   DG_REQUIRE(need > 0, DGTTA_ERR_UNSUPPORTED, "seghead_warp_bwd: voxel count must be a multiple of 128");

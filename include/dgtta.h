@@ -407,7 +407,10 @@ int dgtta_seghead_bwd_acc(const void *x, int ldx, const float *dout, int lddo, c
  * fallback here, so maps it would decline (singular / strongly minifying) are rejected with DGTTA_ERR_UNSUPPORTED before
  * anything is launched and the caller uses dgtta_seghead_* + dgtta_affine_warp3d_*.  ws: dgtta_seghead_warp_bwd_ws_bytes
  * (0 = shape not offered: B*D*H*W must be a multiple of 128). */
-/* 1 when the fused pair applies to this shape / dtype and to every map of the HOST array h_theta [B][3][4], else 0. */
+/* 1 when the fused pair applies to this shape / dtype and to every map of the HOST array h_theta [B][3][4], else 0.  The
+ * weight gradient of the fused backward needs nsel = 8 or 16: with 4 or 12 selected classes this returns 0 and
+ * dgtta_seghead_warp_bwd refuses dw_sel != NULL with DGTTA_ERR_UNSUPPORTED before anything is launched (gz and db_sel alone
+ * are computed). */
 int dgtta_seghead_warp_supported(const float *h_theta, int B, int Cin, int nsel, int D, int H, int W, int dtype);
 size_t dgtta_seghead_warp_bwd_ws_bytes(int B, int Cin, int nsel, int D, int H, int W);
 int dgtta_seghead_warp_fwd(const void *z, const float *w, const float *bias, const int *sel, int nsel, const float *theta,
