@@ -104,6 +104,10 @@ SIGNATURES = {
     "dgtta_feature_logits_chunk_f64": (I, [P, I64, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_logits_chunk_f64_t": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_argmax_merge_f64": (I, [P, I64, I, I, P, P, I, P]),
+    "dgtta_label_bboxes": (I, [P, P, I, I, I, I, P, P]),
+    "dgtta_label_surface": (I, [P, I, I, I, I64, I, I, I, I, I, I, P, P]),
+    "dgtta_edt_ws_bytes": (SZ, [I, I, I]),
+    "dgtta_edt_sq": (I, [P, P, P, SZ, I, I, I, F, F, F, P]),
 }
 
 _lib = None

@@ -633,6 +633,77 @@ def argmax_dice_from_labels(pred, labels, num_classes):
     return pr, counts
 
 
+# ------------------------------------------------------------------------------------------------ surface distances
+def _label_map3(t, name):
+    require_cuda(t)
+    if t.dim() != 3 or t.dtype != torch.int64 or not t.is_contiguous():
+        raise ValueError(f"{name}: contiguous int64 label map [D,H,W] expected")
+    return t
+
+
+def label_bboxes(a, b, nlab):
+    """Inclusive bounding boxes of every label < nlab in the union of two int64 label maps [D,H,W] of equal shape: int32
+    [nlab,6] = (lo d, lo h, lo w, hi d, hi h, hi w); a label in neither map has lo > hi."""
+    _label_map3(a, "label_bboxes"), _label_map3(b, "label_bboxes")
+    if a.shape != b.shape:
+        raise ValueError(f"label_bboxes: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+    lib = _lib.load()
+    boxes = torch.empty((int(nlab), 6), dtype=torch.int32, device=a.device)
+    d, h, w = a.shape
+    check(lib.dgtta_label_bboxes(ptr(a), ptr(b), d, h, w, int(nlab), ptr(boxes), stream_of(a.device)), "dgtta_label_bboxes")
+    return boxes
+
+
+def label_surface(label_map, label, box=None, out=None):
+    """Surface voxels of (label_map == label) inside the crop box (d0, h0, w0, cd, ch, cw) (default: the whole volume): uint8
+    [cd,ch,cw], 1 where the voxel carries the label and one of its six face neighbours (read from the full map; outside the volume
+    counts) does not.  `out`: a uint8 buffer of at least cd*ch*cw elements to write into."""
+    _label_map3(label_map, "label_surface")
+    lib = _lib.load()
+    d, h, w = label_map.shape
+    d0, h0, w0, cd, ch, cw = (0, 0, 0, d, h, w) if box is None else (int(v) for v in box)
+    n = cd * ch * cw
+    if out is None:
+        surf = torch.empty((cd, ch, cw), dtype=torch.uint8, device=label_map.device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < n or out.device != label_map.device:
+            raise ValueError("label_surface: out must be a contiguous uint8 buffer of at least cd*ch*cw elements on the map's device")
+        surf = out.reshape(-1)[:n].view(cd, ch, cw)
+    check(lib.dgtta_label_surface(ptr(label_map), d, h, w, int(label), d0, h0, w0, cd, ch, cw, ptr(surf), stream_of(label_map.device)),
+          "dgtta_label_surface")
+    return surf
+
+
+def edt_ws_bytes(d, h, w):
+    return int(_lib.load().dgtta_edt_ws_bytes(int(d), int(h), int(w)))
+
+
+def edt_sq(site, spacing=(1.0, 1.0, 1.0), out=None, ws=None):
+    """Exact squared Euclidean distance transform (csrc/surface.hip): site uint8 [D,H,W] -> fp32 [D,H,W], the squared physical
+    distance to the nearest nonzero voxel of `site` at the per-axis `spacing` (d, h, w); +inf everywhere without a site.  `out`
+    (fp32, at least D*H*W elements) and `ws` (uint8, at least edt_ws_bytes(D,H,W)) let a caller reuse its buffers."""
+    require_cuda(site)
+    if site.dim() != 3 or site.dtype != torch.uint8 or not site.is_contiguous():
+        raise ValueError("edt_sq: contiguous uint8 site mask [D,H,W] expected")
+    lib = _lib.load()
+    d, h, w = site.shape
+    n = d * h * w
+    if out is None:
+        dist2 = torch.empty((d, h, w), dtype=torch.float32, device=site.device)
+    else:
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n or out.device != site.device:
+            raise ValueError("edt_sq: out must be a contiguous fp32 buffer of at least D*H*W elements on the mask's device")
+        dist2 = out.reshape(-1)[:n].view(d, h, w)
+    nbytes = lib.dgtta_edt_ws_bytes(d, h, w)
+    if ws is None:
+        ws = _ws(nbytes, site.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < nbytes or ws.device != site.device:
+        raise ValueError("edt_sq: ws must be a uint8 buffer of at least edt_ws_bytes(D,H,W) bytes on the mask's device")
+    sd, sh, sw = (float(s) for s in spacing)
+    check(lib.dgtta_edt_sq(ptr(site), ptr(dist2), ptr(ws), ws.numel(), d, h, w, sd, sh, sw, stream_of(site.device)), "dgtta_edt_sq")
+    return dist2
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

@@ -664,15 +664,19 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
 def evaluate_run(save_path, config, modifier_fn_module, device="cuda"):
     """postprocess_results_fn + summary_{Ts,Tr}.json over a finished run directory (reference: tta.py:447-470).  Runs in
     the single process, in rank 0 after the filesystem barrier, or in the fan-out parent of `dgtta run_tta --gpus N`
-    after every child has exited."""
+    after every child has exited.  The plan keys `evaluation_surface_metrics` (bool, default off) and
+    `evaluation_nsd_tolerance_mm` (default 1.0) add HD95 / HD / ASSD / NSD to the summaries (evaluation.py)."""
     from .evaluation import compute_metrics_on_folder_simple
     save_path, out = Path(save_path), {}
+    surface = bool(config.get("evaluation_surface_metrics", False))
+    nsd_tol = float(config.get("evaluation_nsd_tolerance_mm", 1.0))
     for bucket in ["Ts", "Tr"]:
         refs, preds = save_path / f"mapped_target_labels{bucket}", save_path / f"tta_output{bucket}"
         if refs.is_dir() and preds.is_dir():
             modifier_fn_module.ModifierFunctions.postprocess_results_fn(preds)
             summary = compute_metrics_on_folder_simple(refs, preds, list(range(len(config["optimized_labels"]))),
-                                                       output_file=save_path / f"summary_{bucket}.json", device=device)
+                                                       output_file=save_path / f"summary_{bucket}.json", device=device,
+                                                       surface_metrics=surface, nsd_tolerance_mm=nsd_tol)
             out[("summary", bucket)] = summary["foreground_mean"]["Dice"]
     return out
 

@@ -521,6 +521,39 @@ int dgtta_feature_logits_chunk_f64(const float *facc, int64_t member_stride, con
                                    double *dst, int M, int Cin, int C, int X, int Y, int Z, int x0, int y0, int z0, int xs, int ys,
                                    int zs, int c0, int cg, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surface-distance metrics of the folder evaluation (HD95, HD, ASSD, NSD; dg_tta_amd/tta/evaluation.py).  The reference
+ * delegates evaluation to nnU-Net (dg_tta/tta/tta.py:447-470) and computes none of them: the definitions are the published
+ * ones, UNPINNED.  Label maps are int64 [D][H][W].
+ *
+ * label_bboxes: boxes int32 [nlab][6] = (lo d, lo h, lo w, hi d, hi h, hi w), the inclusive bounding box of the voxels that
+ * carry label l in map a OR in map b; a label in neither gets the empty box (INT_MAX x 3, -1 x 3: lo > hi).  The table is
+ * initialised here; values outside [0, nlab) are passed over.  nlab <= 1024.
+ *
+ * label_surface: surf uint8 [cd][ch][cw] = S(map == label) inside the crop box that starts at (d0, h0, w0): 1 where the
+ * voxel carries the label and at least one of its six face neighbours does not.  Outside the VOLUME counts as "does not";
+ * the box edge is no edge: neighbours are read from the full map.
+ *
+ * edt_sq: dist2 float [D][H][W] = squared physical distance from every voxel to the nearest nonzero voxel of `site`
+ * (uint8 [D][H][W]); +inf everywhere when there is none.  Exact and separable, three passes of one operator along W, then H,
+ * then D, starting from 0 at a site and +inf elsewhere:
+ *     out[i] = min_j ( in[j] + (s * (float)(i - j))^2 )           s = the axis' spacing (sw, sh, sd)
+ * evaluated in fp32 in exactly this order - the product, its square, the add, the min - with no fused multiply-add.  At unit
+ * spacing every value is an integer below 2^24 and the result is exact.  Otherwise, with u = 2^-24 and the spacings taken as
+ * the floats they are: a pass rounds the product (which the square counts twice), the square and the sum; the W pass adds to 0
+ * or +inf, which is exact, and a term is rounded by the sums of the later passes only, so the W term collects 3 + 2 roundings,
+ * the H term 3 + 2, the D term 3 + 1: the relative error against real arithmetic is at most (1 + u)^5 - 1 = 5 u to first
+ * order.  Spacings in (0, 1e6].  Every axis at most DGTTA_EDT_MAX_AXIS voxels (above:
+ * DGTTA_ERR_UNSUPPORTED).  ws: dgtta_edt_ws_bytes(D, H, W) bytes, 4-byte aligned; site, dist2 and ws must not overlap.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_EDT_MAX_AXIS 1024
+int dgtta_label_bboxes(const int64_t *a, const int64_t *b, int D, int H, int W, int nlab, int *boxes, void *stream);
+int dgtta_label_surface(const int64_t *map, int D, int H, int W, int64_t label, int d0, int h0, int w0, int cd, int ch, int cw,
+                        uint8_t *surf, void *stream);
+size_t dgtta_edt_ws_bytes(int D, int H, int W);
+int dgtta_edt_sq(const uint8_t *site, float *dist2, void *ws, size_t ws_bytes, int D, int H, int W, float sd, float sh, float sw,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
