@@ -108,6 +108,10 @@ SIGNATURES = {
     "dgtta_label_surface": (I, [P, I, I, I, I64, I, I, I, I, I, I, P, P]),
     "dgtta_edt_ws_bytes": (SZ, [I, I, I]),
     "dgtta_edt_sq": (I, [P, P, P, SZ, I, I, I, F, F, F, P]),
+    "dgtta_cc_ws_bytes": (SZ, [I, I, I]),
+    "dgtta_cc_label": (I, [P, P, I, I, I, I, I, P, P, SZ, P]),
+    "dgtta_cc_sizes": (I, [P, I64, P, P]),
+    "dgtta_cc_filter": (I, [P, P, I, P, P, I64, I, I, I64, P, P, P, SZ, P]),
 }
 
 _lib = None

@@ -704,6 +704,91 @@ def edt_sq(site, spacing=(1.0, 1.0, 1.0), out=None, ws=None):
     return dist2
 
 
+# ------------------------------------------------------------------------------------------------ connected components
+CC_MAX_TABLE = 1024
+
+
+def _group_table(group, label_map, name):
+    if (group.dim() != 1 or group.dtype != torch.int32 or not group.is_contiguous() or group.device != label_map.device
+            or not 0 < group.numel() <= CC_MAX_TABLE):
+        raise ValueError(f"{name}: group must be a contiguous int32 table of 1 to {CC_MAX_TABLE} entries on the map's device")
+    return group
+
+
+def _cc_buffer(out, n, dtype, device, name, what):
+    if out.dtype != dtype or not out.is_contiguous() or out.numel() < n or out.device != device:
+        raise ValueError(f"{name}: {what} must be a contiguous {str(dtype).replace('torch.', '')} buffer of at least D*H*W elements "
+                         f"on the map's device")
+    return out.reshape(-1)[:n]
+
+
+def _cc_ws(ws, nbytes, device, name):
+    if ws is None:
+        return _ws(nbytes, device)
+    if ws.dtype != torch.uint8 or ws.numel() < nbytes or ws.device != device:
+        raise ValueError(f"{name}: ws must be a uint8 buffer of at least cc_ws_bytes(D,H,W) bytes on the map's device")
+    return ws
+
+
+def cc_ws_bytes(d, h, w):
+    return int(_lib.load().dgtta_cc_ws_bytes(int(d), int(h), int(w)))
+
+
+def cc_label(label_map, group, connectivity=26, out=None, ws=None):
+    """Canonical connected components (csrc/components.hip) of an int64 label map [D,H,W]: int32 [D,H,W], 0 where
+    g = group[label] is 0 (labels outside the int32 table `group` included), elsewhere 1 + the smallest linear index of the voxel's
+    component.  Voxels are connected iff they are neighbours under `connectivity` (6, 18, 26) and have equal, non-zero g.  `out`
+    (int32, at least D*H*W elements) and `ws` (uint8, at least cc_ws_bytes(D,H,W)) let a caller reuse its buffers."""
+    _label_map3(label_map, "cc_label")
+    _group_table(group, label_map, "cc_label")
+    lib = _lib.load()
+    d, h, w = label_map.shape
+    n = d * h * w
+    cc = (torch.empty(n, dtype=torch.int32, device=label_map.device) if out is None
+          else _cc_buffer(out, n, torch.int32, label_map.device, "cc_label", "out")).view(d, h, w)
+    ws = _cc_ws(ws, lib.dgtta_cc_ws_bytes(d, h, w), label_map.device, "cc_label")
+    check(lib.dgtta_cc_label(ptr(label_map), ptr(group), group.numel(), d, h, w, int(connectivity), ptr(cc), ptr(ws), ws.numel(),
+                             stream_of(label_map.device)), "dgtta_cc_label")
+    return cc
+
+
+def cc_sizes(cc, out=None):
+    """size int32 [D*H*W] of a cc_label result: size[r] = the number of voxels with cc == r + 1 (0 where r is not a component's
+    first voxel).  `out`: an int32 buffer of at least D*H*W elements."""
+    require_cuda(cc)
+    if cc.dtype != torch.int32 or not cc.is_contiguous() or cc.numel() == 0:
+        raise ValueError("cc_sizes: contiguous int32 component map expected")
+    n = cc.numel()
+    size = torch.empty(n, dtype=torch.int32, device=cc.device) if out is None else _cc_buffer(out, n, torch.int32, cc.device, "cc_sizes",
+                                                                                                "out")
+    check(_lib.load().dgtta_cc_sizes(ptr(cc), n, ptr(size), stream_of(cc.device)), "dgtta_cc_sizes")
+    return size
+
+
+def cc_filter(label_map, group, cc, size, keep_largest=True, min_voxels=0, background=0, out=None, ws=None):
+    """(filtered map int64 [D,H,W], removed int64 [len(group)]): a voxel with g != 0 keeps its label iff (not keep_largest or its
+    component is the largest of its group, ties to the smaller cc) and its component has at least min_voxels voxels, otherwise it
+    becomes `background`; g == 0 passes through.  removed[c] = voxels removed from group c.  `cc`, `size`: cc_label / cc_sizes of the
+    same map and table.  `out` (int64, at least D*H*W elements) and `ws` as in cc_label."""
+    _label_map3(label_map, "cc_filter")
+    _group_table(group, label_map, "cc_filter")
+    lib = _lib.load()
+    d, h, w = label_map.shape
+    n = d * h * w
+    cc = _cc_buffer(cc, n, torch.int32, label_map.device, "cc_filter", "cc")
+    size = _cc_buffer(size, n, torch.int32, label_map.device, "cc_filter", "size")
+    if not 0 <= int(min_voxels) < 2 ** 31:
+        raise ValueError("cc_filter: min_voxels must be in [0, 2^31)")
+    res = (torch.empty(n, dtype=torch.int64, device=label_map.device) if out is None
+           else _cc_buffer(out, n, torch.int64, label_map.device, "cc_filter", "out")).view(d, h, w)
+    ws = _cc_ws(ws, lib.dgtta_cc_ws_bytes(d, h, w), label_map.device, "cc_filter")
+    removed = torch.empty(group.numel(), dtype=torch.int64, device=label_map.device)
+    check(lib.dgtta_cc_filter(ptr(label_map), ptr(group), group.numel(), ptr(cc), ptr(size), n, int(bool(keep_largest)), int(min_voxels),
+                              int(background), ptr(res), ptr(removed), ptr(ws), ws.numel(), stream_of(label_map.device)),
+          "dgtta_cc_filter")
+    return res, removed
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

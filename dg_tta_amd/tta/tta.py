@@ -635,6 +635,7 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
     del acc, nsum
     seg = map_label(torch.as_tensor(seg.astype(np.int64))[None],
                     get_map_idxs(label_mapping, optimized_labels, "pretrain_labels"), input_format="argmaxed")[0]
+    seg = _postprocess_prediction(seg, config, device)
     # (the prediction is written in the format of the case's image, as SimpleITK's writer picks it from the file name)
     out = Path(str(save_path / sample_id) + ((nii.get("ext") or ".nii.gz") if nii is not None else ".npy"))
     out.parent.mkdir(exist_ok=True, parents=True)
@@ -659,6 +660,21 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
         target = map_label(target[None], tta_idxs, input_format="argmaxed")[0]
         ref_path.parent.mkdir(exist_ok=True, parents=True)
         _save_label_map(ref_path, target.numpy().astype(np.int16), nii)
+
+
+def _postprocess_prediction(seg, config, device):
+    """The connected-component filter that the plan keys `postprocessing_*` ask for (postprocessing.py), applied to a mapped
+    prediction [D,H,W]; `seg` itself, without a GPU call, when none of them asks for anything."""
+    from .postprocessing import keep_largest_components, postprocessing_settings
+    settings = postprocessing_settings(config)
+    if settings is None:
+        return seg
+    out, removed = keep_largest_components(seg, device=device, **settings)
+    names = config["optimized_labels"]
+    print("Post-processing removed voxels: " + ", ".join(
+        f"{'+'.join(names[l] for l in k) if isinstance(k, tuple) else names[k] if isinstance(k, int) else k}={v}"
+        for k, v in removed.items()))
+    return out
 
 
 def evaluate_run(save_path, config, modifier_fn_module, device="cuda"):

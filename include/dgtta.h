@@ -554,6 +554,40 @@ size_t dgtta_edt_ws_bytes(int D, int H, int W);
 int dgtta_edt_sq(const uint8_t *site, float *dist2, void *ws, size_t ws_bytes, int D, int H, int W, float sd, float sh, float sw,
                  void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected-component post-processing of a prediction (dg_tta_amd/tta/postprocessing.py): keep the largest component of an
+ * organ, drop small islands.  The reference leaves this to the user's postprocess_results_fn; the definitions below are this
+ * library's, UNPINNED.  Label maps are int64 [D][H][W]; n = D*H*W must be below 2^31 - 1 (DGTTA_ERR_UNSUPPORTED otherwise):
+ * components are named by int32.
+ *
+ * group: int32 [ntab] on the device, ntab <= DGTTA_CC_MAX_TABLE.  g(i) = group[map[i]], and 0 where map[i] lies outside
+ * [0, ntab) or the entry lies outside [0, ntab).  Group 0 is "not looked at".  Two voxels are connected iff they are neighbours
+ * under `connectivity` (6 faces, 18 + edges, 26 + corners) and have equal, non-zero g: each label its own group, several
+ * labels sharing a group (a region), or all foreground in one group.
+ *
+ * cc_label: cc int32 [D][H][W] = 0 where g == 0, elsewhere 1 + the smallest linear index (d*H + h)*W + w of the voxel's
+ * component: canonical, the same on every run.  ws: dgtta_cc_ws_bytes(D, H, W) bytes, 4-byte aligned; it holds the
+ * union-find forest, which is built tile by tile in LDS, united across tile borders with atomicMin (always the larger root
+ * under the smaller) and flattened by a launch of its own.
+ *
+ * cc_sizes: size int32 [n]; size[r] = the number of voxels with cc == r + 1, so 0 wherever r is not a component's first
+ * voxel.  Cleared here.
+ *
+ * cc_filter: out int64 [n].  winner[c] = the largest component of group c, ties to the smaller cc.  A voxel with g != 0
+ * keeps its label iff (keep_largest == 0 or its component is winner[g]) and its component has at least min_voxels voxels;
+ * otherwise it becomes `background`.  Voxels with g == 0 pass through.  removed int64 [ntab] (8-byte aligned) = the number
+ * of voxels removed per group id, cleared here.  cc and size must come from cc_label / cc_sizes with the same map and
+ * group table.  ws: at least 8 * ntab bytes, 8-byte aligned (dgtta_cc_ws_bytes is enough; the buffer of cc_label may be
+ * reused).  out must not overlap map.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_CC_MAX_TABLE 1024
+size_t dgtta_cc_ws_bytes(int D, int H, int W);
+int dgtta_cc_label(const int64_t *map, const int *group, int ntab, int D, int H, int W, int connectivity, int *cc, void *ws,
+                   size_t ws_bytes, void *stream);
+int dgtta_cc_sizes(const int *cc, int64_t n, int *size, void *stream);
+int dgtta_cc_filter(const int64_t *map, const int *group, int ntab, const int *cc, const int *size, int64_t n, int keep_largest,
+                    int min_voxels, int64_t background, int64_t *out, int64_t *removed, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
