@@ -12,7 +12,7 @@
 //   Data gradient: stride 1 = this kernel on dy with the transposed weight image and mirrored taps; a strided layer runs
 //               one class per parity of its strided axes (2 to 8 classes, blockIdx.z), each a stride-1 conv over the taps
 //               that reach that parity (a class without taps - kd = 1 with sd = 2, odd planes - writes zeros).
-//   Weight gradient: the class-masked weight-gradient kernels of conv_wgrad.hip (only the present taps are multiplied)
+//   Weight gradient: the class-masked weight-gradient kernels of conv_wgrad_rows.hip (through conv_wgrad.hip) (only the present taps are multiplied)
 //               with the fixed-order slab reduction into torch layout [Cout][Cin][kd][3][3] (conva_wgrad_mfma).
 //   Transposed conv: the pointwise class GEMM of conv_mfma.hip with kd*kh*kw output classes (convTa_run).
 #include "conv_common.h"

@@ -70,22 +70,26 @@ int convT_gemm_run(int mode, const void *in, int ldin, const float *w_t, const f
                    int Cin, int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad.hip
-int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, float *db, void *ws, size_t ws_bytes,
-                     int B, int Cin, int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype,
-                     hipStream_t st, long long xkh = 0);
+// weight gradients on the matrix cores (the View-level launchers of these units are in conv_wgrad_common.h)
+int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                     int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st, long long xkh = 0);
 size_t conv3_wgrad_mfma_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);
 size_t conv3_wgrad_split_extra_bytes(int B, int Cin, int Cout, int D, int H, int W, int stride);
 bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int dtype);
+size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);
+int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
+                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------- convt_wgrad.hip
 int convT_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
                      int Cin, int Cout, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st, float *bias_part,
                      size_t bias_part_bytes, int *bias_units);
 int convT_bias_finalize(const float *part, int units, int Cout, float *db, int accumulate, hipStream_t st);
 size_t convT_wgrad_split_extra_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi);
-size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);
-int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
 int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
                       int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------- head_wgrad.hip
 size_t head_wgrad_mfma_ws_bytes(int Cin, int nsel, int64_t rows);
 int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *dw_sel, void *ws, size_t ws_bytes, int Cin,
                     int nsel, int64_t rows, int accumulate, int dtype, hipStream_t st, bool have_d16);

@@ -1,6 +1,7 @@
 // Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
-// convt_gemm.hip, conv_aniso.hip, conv_wgrad.hip, conv_wgrad_ring.hip): operand descriptors, the launchers that take them,
-// tile geometry and the device helpers of the kernels.  Pointer-level functions are declared in conv_api.h.
+// convt_gemm.hip, conv_aniso.hip, conv_wgrad_ring.hip and, through conv_wgrad_common.h, the other weight-gradient units):
+// operand descriptors, the launchers that take them, tile geometry and the device helpers of the kernels.  Pointer-level
+// functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h.
 #pragma once
 #include "conv_api.h"
 #include <stdlib.h>

@@ -196,7 +196,7 @@ static int k3_wgrad(const void *x, int ldx, long long x_block_stride, const void
   float *part = (float *)((char *)ws + bias_bytes); // main region
   bool done = false;
   if (impl != 1) {
-    int rc = conv3_wgrad_mfma(x, ldx, dy, lddy, dw_t, nullptr, part, ws_bytes - bias_bytes, B, Cin, Cout, Di, Hi, Wi,
+    int rc = conv3_wgrad_mfma(x, ldx, dy, lddy, dw_t, part, ws_bytes - bias_bytes, B, Cin, Cout, Di, Hi, Wi,
                               stride, accumulate, dtype, st, x_block_stride);
     if (rc == DGTTA_OK) done = true;
     else if (rc != DGTTA_ERR_UNSUPPORTED) return rc;

@@ -1,0 +1,218 @@
+// Shared declarations of the weight-gradient translation units (conv_wgrad.hip: host dispatch; conv_wgrad_rows.hip,
+// conv_wgrad_flat.hip, conv_wgrad_s2.hip, convt_wgrad.hip, conv_wgrad_reduce.hip, head_wgrad.hip: kernels and their launchers):
+// the launch descriptors, the launchers that cross files (each declared here, once; the defining file includes this header)
+// and the device helpers that more than one kernel file uses.  All kernels leave fp32 partial slabs [27 taps][32 ci][32 co],
+// one per workgroup and channel-block pair; wgrad_reduce_launch sums them in a fixed order.
+#pragma once
+#include "conv_common.h"
+#include <type_traits>
+
+namespace dgconv {
+// Up to 8 independent classes per launch (blockIdx.z): operand offsets + tap mask per class, one slab set per class.
+struct WgradClasses {
+  int n;
+  unsigned mask[8];
+  long long xoff[8], yoff[8];
+};
+struct RealTaps {
+  Taps t[8];
+};
+// tiles of tW x tH voxels of the dy lattice, D split into nsd ranges of DR slices; units = columns of the volume
+struct WgradPlan {
+  int tW, tH, nsd, DR, cibs, cobs;
+  int64_t units;
+};
+}  // namespace dgconv
+
+// the storage types the weight-gradient entry points take; anything else is DGTTA_ERR_UNSUPPORTED (no error text)
+static inline bool wgrad_dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad.hip
+// plan of a launch with ncls classes over tiles of tileW x tileH voxels (32 x 4: the stride-1 kernels; WT2::TWO x WT2::TH: the
+// one-pass stride-2 and transposed-conv kernels)
+WgradPlan wgrad_plan(int B, int Cin, int Cout, int D, int H, int W, int ncls, int tileW, int tileH);
+size_t wgrad_classes_bytes(int B, int Cin, int Cout, int D, int H, int W, int ncls);
+// class launch of the stride-1 kernels + slab reduction into dw[co*s_co + ci*s_ci + real_tap*s_tap]; wgrad_launch: one class
+int wgrad_launch_classes(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B,
+                         int Cin, int Cout, const WgradClasses &wc, const RealTaps &reals, long long s_co, long long s_ci,
+                         long long s_tap, int accumulate, int dtype, hipStream_t st, long long xkh = 0, bool split_leg = false);
+int wgrad_launch(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B, int Cin,
+                 int Cout, unsigned tapmask, const Taps &real, long long s_co, long long s_ci, long long s_tap, int accumulate,
+                 int dtype, hipStream_t st, long long xkh = 0, bool split_leg = false);
+// fp32 operands as three bf16 planes each (exact three-term splits): plane size, the two split passes, the order of the six products
+size_t wgrad_split_plane_bytes(int B, int C, int D, int H, int W);
+int wgrad_split_planes(const float *x, int ldx, int Cin, int64_t rows_x, size_t plane_x_bytes, const float *dy, int lddy, int Cout,
+                       int64_t rows_y, size_t plane_y_bytes, void *planes, bf16_t *xs[3], bf16_t *gs[3], hipStream_t st);
+constexpr int WGRAD_SPLIT_PAIRS[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};      // (x plane, dy plane), in this order
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad_rows.hip
+// stride-1 kernels; one slab per workgroup at slabs[(class, pair, blockIdx.x)].  dtype: the storage type (tr / tr8: 16-bit only)
+int conv3_wgrad_mfma_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
+                            const WgradPlan &p, const WgradClasses &wc, int dtype, hipStream_t st);
+int conv3_wgrad_tr_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
+                          const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab, int dtype, hipStream_t st);
+int conv3_wgrad_tr8_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
+                           const WgradPlan &p, int upw, int64_t nslab, int dtype, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad_flat.hip
+// planes of W <= 16; returns the number of slabs per channel-block pair (0: shape not taken)
+int64_t wgrad_flat_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B, int Cin,
+                          int Cout, int dtype, hipStream_t st, int *rc);
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad_s2.hip
+// one-pass stride-2 kernels (x at full resolution); two_blocks: the 8-wave kernel that shares the x tile between two
+// output-channel blocks
+int conv3_wgrad_s2_launch(const void *x, const View &xfull, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
+                          const WgradPlan &p, bool two_blocks, int dtype, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad_reduce.hip
+// dw (+)= sum over the nslab slabs of every pair, fixed order; ncls slab sets with the tap tables reals.t[0 .. ncls).  `dense`
+// (optional): the one table of a single-class launch, offered to the dense-layout kernel
+int wgrad_reduce_launch(const float *slabs, float *dw, int Cin, int Cout, const WgradPlan &p, int ncls, int64_t nslab, int accumulate,
+                        const RealTaps &reals, const Taps *dense, long long s_co, long long s_ci, long long s_tap, hipStream_t st);
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+
+// Workgroups are dispatched round robin over the 8 XCDs (each with its own L2), units are columns of the volume whose x
+// tiles overlap their H neighbours' by the halo rows: give every XCD a CONTIGUOUS range of units, so that the halo is
+// fetched from HBM by one L2 instead of two (DGTTA_WGRAD_XCD=0: units in dispatch order)
+__device__ __forceinline__ int xcd_unit(int xcd_map) {
+  const int i = blockIdx.x, n = gridDim.x;
+  if (!xcd_map || (n & 7)) return i;
+  return (i & 7) * (n >> 3) + (i >> 3);
+}
+
+template <typename T>
+struct WG {
+  static constexpr int EPV = Elem<T>::EPV;
+  static constexpr int GC = 32 / EPV;            // channel groups (of EPV channels) per 32-channel tile
+  static constexpr int NCH_Y = 32 / EPV;         // voxel runs per dy row
+  static constexpr int NCH_X = 32 / EPV + 1;     // voxel runs per x row; run c covers wx = EPV*c - 1 .. EPV*c + EPV - 2
+  static constexpr int TH = 4, XR = TH + 2;
+  static constexpr int XSLOT = XR * NCH_X * 32;  // uint4 per x slice
+  static constexpr int YSLOT = TH * NCH_Y * 32;
+  static constexpr int NUX = XR * NCH_X * GC, NUY = TH * NCH_Y * GC, NU = NUX + NUY;
+  static constexpr int ROUNDS = (NU + 255) / 256;
+  static constexpr size_t LDS_BYTES = (size_t)(4 * XSLOT + 2 * YSLOT) * 16;
+  static constexpr int NSTEP = 32 / (4 * EPV);   // MFMA k-steps per voxel row (bf16 1, fp32 2)
+  // LDS slot (in uint4) of channel c (0..31) of voxel run `run` in row `row`.  Within a channel group the EPV slots are
+  // XOR-swizzled so that the 8 lanes of a ds_write_b128 group (which differ in channel group / run parity and all write
+  // the same in-group channel j) hit 8 different 16-byte bank slots; readers apply the same map (still one distinct
+  // slot per lane of a 16-lane read group).
+  __device__ static __forceinline__ int slot(int row, int run, int nruns, int c) {
+    const int cg = c / EPV, j = c % EPV;
+    const int sw = (EPV == 8) ? ((cg | ((run & 1) << 2)) & 7) : ((cg >> 1) & 3);
+    return (row * nruns + run) * 32 + cg * EPV + (j ^ sw);
+  }
+};
+
+template <typename T>
+__device__ __forceinline__ void transpose_unit(const uint4 *in, uint4 *out);
+template <>
+__device__ __forceinline__ void transpose_unit<float>(const uint4 *in, uint4 *out) {   // 4 voxels x 4 channels
+  out[0] = make_uint4(in[0].x, in[1].x, in[2].x, in[3].x);
+  out[1] = make_uint4(in[0].y, in[1].y, in[2].y, in[3].y);
+  out[2] = make_uint4(in[0].z, in[1].z, in[2].z, in[3].z);
+  out[3] = make_uint4(in[0].w, in[1].w, in[2].w, in[3].w);
+}
+__device__ __forceinline__ unsigned pack_lo(unsigned a, unsigned b) { return (a & 0xffffu) | (b << 16); }
+__device__ __forceinline__ unsigned pack_hi(unsigned a, unsigned b) { return (a >> 16) | (b & 0xffff0000u); }
+template <>
+__device__ __forceinline__ void transpose_unit<bf16_t>(const uint4 *in, uint4 *out) {  // 8 voxels x 8 channels
+#define TR_PAIR(c, fld)                                                                                      \
+  out[c] = make_uint4(pack_lo(in[0].fld, in[1].fld), pack_lo(in[2].fld, in[3].fld), pack_lo(in[4].fld, in[5].fld), \
+                      pack_lo(in[6].fld, in[7].fld));                                                        \
+  out[c + 1] = make_uint4(pack_hi(in[0].fld, in[1].fld), pack_hi(in[2].fld, in[3].fld),                       \
+                          pack_hi(in[4].fld, in[5].fld), pack_hi(in[6].fld, in[7].fld));
+  TR_PAIR(0, x) TR_PAIR(2, y) TR_PAIR(4, z) TR_PAIR(6, w)
+#undef TR_PAIR
+}
+
+template <>
+__device__ __forceinline__ void transpose_unit<f16_t>(const uint4 *in, uint4 *out) { transpose_unit<bf16_t>(in, out); }
+
+// A operand for tap column kw from the aligned run `c` and the next run's first dwords (e0, e1)
+template <typename T>
+__device__ __forceinline__ uint4 shift_run(const uint4 &c, unsigned e0, unsigned e1, int kw);
+template <>
+__device__ __forceinline__ uint4 shift_run<bf16_t>(const uint4 &c, unsigned e0, unsigned, int kw) {
+  if (kw == 0) return c;
+  if (kw == 2) return make_uint4(c.y, c.z, c.w, e0);
+  return make_uint4((c.x >> 16) | (c.y << 16), (c.y >> 16) | (c.z << 16), (c.z >> 16) | (c.w << 16),
+                    (c.w >> 16) | (e0 << 16));
+}
+template <>
+__device__ __forceinline__ uint4 shift_run<f16_t>(const uint4 &c, unsigned e0, unsigned e1, int kw) {
+  return shift_run<bf16_t>(c, e0, e1, kw);          // pure 16-bit lane moves
+}
+template <>
+__device__ __forceinline__ uint4 shift_run<float>(const uint4 &c, unsigned e0, unsigned e1, int kw) {
+  if (kw == 0) return c;
+  if (kw == 1) return make_uint4(c.y, c.z, c.w, e0);
+  return make_uint4(c.z, c.w, e0, e1);
+}
+
+template <typename T>
+__device__ __forceinline__ void mfma16(const uint4 &a, const uint4 &b, f32x4_t &acc);
+template <>
+__device__ __forceinline__ void mfma16<bf16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0,
+                                                0, 0);
+}
+template <>
+__device__ __forceinline__ void mfma16<f16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
+}
+// 32x32x16 step on transposed-read operands (kept as bf16x8 bit patterns; the storage type picks the instruction)
+template <typename T16>
+__device__ __forceinline__ f32x16_t mfma32_tr(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc);
+template <>
+__device__ __forceinline__ f32x16_t mfma32_tr<bf16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ f32x16_t mfma32_tr<f16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ void mfma16<float>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
+}
+
+// LDS geometry of the kernels with hardware-transposed operand reads (conv3_wgrad_tr_kernel and its 8-wave variant): tiles of
+// 4 rows x 32 voxels, slices voxel-major [row][voxel][32 channels = 64 B], a ring of 4 x slices (halo of 1) and 2 dy slices
+struct WT {
+  static constexpr int TH = 4, XR = TH + 2;
+  static constexpr int XW = 36;                         // voxels per x row in LDS (34 used)
+  static constexpr int X_ROW_B = XW * 64, X_SLICE_B = XR * X_ROW_B;
+  static constexpr int Y_ROW_B = 32 * 64, Y_SLICE_B = TH * Y_ROW_B;
+  static constexpr int LDS_BYTES = 4 * X_SLICE_B + 2 * Y_SLICE_B;
+  static constexpr int NPX = XR * 3, NPY = TH * 2, NP = NPX + NPY;      // DMA pieces per slice
+};
+
+__device__ __forceinline__ bf16x8_t tr_operand(const unsigned char *p) {
+  // two 4-voxel transposed reads = 8 consecutive voxels (k) of this lane's channel
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)p);
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(p + 4 * 64));
+  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+
+// tile geometry of the one-pass stride-2 kernels (conv_wgrad_s2.hip); the transposed-conv kernel tiles its input lattice alike
+struct WT2 {
+  static constexpr int TH = 2, TWO = 16;                // output rows / voxels per tile
+  static constexpr int XR = 2 * TH + 1, XW = 36;        // x rows per slice, voxels per x row in LDS (33 used)
+  static constexpr int X_ROW_B = XW * 64, X_SLICE_B = XR * X_ROW_B;
+  static constexpr int Y_ROW_B = TWO * 64, Y_SLICE_B = TH * Y_ROW_B;
+  static constexpr int NXS = 5;                         // x ring slots
+  static constexpr int LDS_BYTES = NXS * X_SLICE_B + 2 * Y_SLICE_B;
+  static constexpr int NPX1 = XR * 3;                   // DMA pieces per x slice (16 + 16 + 1 voxels per row)
+};
+
+}  // namespace

@@ -3,7 +3,7 @@
 //   dg_tta/tta/tta.py:275 `loss_accum.backward()`; topology dg_tta/__resources__/dummy_results/*/plans.json:279-401)
 // Same arithmetic, operand reads (ds_read_b64_tr_b16 out of voxel-major LDS slices filled by LDS-DMA), MFMA shape
 // (32x32x16: M = ci, N = co, K = 16 voxels along W), tap split (7 taps per wave) and slab output as conv3_wgrad_tr_kernel
-// (conv_wgrad.hip).  What differs is the schedule that kernel was bound by - its DMA of slice d + 2 was issued during slice
+// (conv_wgrad_rows.hip).  What differs is the schedule that kernel was bound by - its DMA of slice d + 2 was issued during slice
 // d and waited for at the END of slice d (under one slice = ~0.9 us to land, with a workgroup-wide drain and barrier):
 //   * ONE 8-wave workgroup per CU, persistent over (column, D-segment) jobs, column = 8 rows x 32 voxels (halo 1.33x instead
 //     of 1.59x); waves 2r and 2r + 1 ... wave w owns row half (w & 1) and taps (w >> 1) + 4 i: 56 MFMAs per wave and slice;

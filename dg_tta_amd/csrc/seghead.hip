@@ -1,6 +1,6 @@
 // 1x1x1 segmentation head on selected rows of the weight (map_label folded in): forward, data gradient, weight gradient.
 // VALU kernels by shape (general, 32-channel register rows, LDS-staged coalesced, wide 33..128 classes); the MFMA weight
-// gradient of the production shape is head_wgrad_mfma (conv_wgrad.hip); heads with more than 32 input channels in 16-bit
+// gradient of the production shape is head_wgrad_mfma (head_wgrad.hip); heads with more than 32 input channels in 16-bit
 // storage (the auxiliary heads of deep supervision) run the matrix-core kernels of seghead_mfma.hip.
 #include "conv_api.h"
 
