@@ -85,6 +85,11 @@ struct RowsGstCtx {
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// grid of a grid-stride launch with 256 threads per workgroup: one thread per item, at most 8192 workgroups
+static inline int grid_for(int64_t total) {
+  const int64_t b = (total + 255) / 256;
+  return (int)(b < 8192 ? b : 8192);
+}
 
 // ---------------------------------------------------------------- bf16 storage helpers
 typedef unsigned short bf16_t;  // raw bits
@@ -112,6 +117,12 @@ template <>
 __device__ __forceinline__ unsigned short f32_to_16<bf16_t>(float f) { return f32_to_bf16(f); }
 template <>
 __device__ __forceinline__ unsigned short f32_to_16<f16_t>(float f) { return f32_to_f16(f); }
+template <typename T>
+__device__ __forceinline__ float from16(unsigned short h);
+template <>
+__device__ __forceinline__ float from16<bf16_t>(unsigned short h) { return bf16_to_f32(h); }
+template <>
+__device__ __forceinline__ float from16<f16_t>(unsigned short h) { return f16_to_f32(h); }
 template <typename T>
 __device__ __forceinline__ unsigned pack2_16(float lo, float hi) {
   return (unsigned)f32_to_16<T>(lo) | ((unsigned)f32_to_16<T>(hi) << 16);

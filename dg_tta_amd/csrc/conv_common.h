@@ -1,9 +1,11 @@
 // Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
 // convt_gemm.hip, conv_aniso.hip, conv_wgrad_ring.hip and, through conv_wgrad_common.h, the other weight-gradient units):
-// operand descriptors, the launchers that take them, tile geometry and the device helpers of the kernels.  Pointer-level
-// functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h.
+// operand descriptors and views, the launchers that take them, tile geometry and the weight image index.  Pointer-level
+// functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h; the device
+// primitives that are not about convolutions (vector types, MFMA wrappers, LDS-DMA) live in gfx950.h.
 #pragma once
 #include "conv_api.h"
+#include "gfx950.h"
 #include <stdlib.h>
 
 // operand descriptors shared by the launchers of all three translation units (external linkage)
@@ -54,12 +56,6 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;                  // result of ds_read_b64_tr_b16
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-
 template <typename T>
 struct Elem;
 template <>
@@ -74,27 +70,6 @@ template <>
 struct Elem<f16_t> {
   static constexpr int EPV = 8;
 };
-
-template <typename T>
-__device__ __forceinline__ void mfma_step(const uint4 &a, const uint4 &b, f32x16_t &acc);
-template <>
-__device__ __forceinline__ void mfma_step<bf16_t>(const uint4 &a, const uint4 &b, f32x16_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0,
-                                                0, 0);
-}
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-template <>
-__device__ __forceinline__ void mfma_step<f16_t>(const uint4 &a, const uint4 &b, f32x16_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mfma_step<float>(const uint4 &a, const uint4 &b, f32x16_t &acc) {
-  // lane half h holds channels 4h..4h+3 of the 8-channel k-step; instruction j contracts the pair {j, 4+j}
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
 
 // Tile geometry.  MBW: voxels of an M-block along W (32/16/8); an M-block spans RPM = 32/MBW rows of H.
 // MBH x MBD M-blocks per workgroup (MPW = MBH*MBD/4 per wave).  S = stride; S == 0 selects the POINTWISE variant
@@ -130,26 +105,6 @@ struct ConvCfg {
 };
 
 __device__ const uint4 g_zero16 = {0u, 0u, 0u, 0u};
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-// LDS-DMA of 16 bytes per lane: lane i's bytes land at lds_addr + 16*i (lds_addr wave-uniform).  Issued from inline asm
-// on purpose: the compiler then keeps no s_waitcnt bookkeeping for it (with the builtin it drains vmcnt(0) before the
-// next ds_read, i.e. before the MFMA phase the copy is meant to overlap); the kernel waits with dma_wait_all() before
-// the barrier that publishes the buffer.  M0 is compiler-reserved, so it is saved and restored in the same statement.
-__device__ __forceinline__ void dma16_to_lds(const void *gsrc, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_addr)
-               : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// workgroup barrier that orders LDS traffic only: __syncthreads() would also drain vmcnt, i.e. wait for DMA in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ unsigned lds_addr_of(const void *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void_t *)p);
-}
 
 inline View dense_view(int B, int D, int H, int W, int ld) {
   (void)B;

@@ -36,9 +36,6 @@
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 // KH = number of 32-channel K halves: 1 = 32 input channels (8 waves: 4 row pairs x 2 output-channel halves, 8-row tiles),
 // 2 = 64 input channels (round 4b).  With 64 input channels a wave's weights are 27 taps x 2 K halves = 216 registers, which
 // only fits ONE wave per SIMD: 4 waves of up to 512 registers (2 row pairs x 2 output-channel halves, 4-row tiles); a plane of
@@ -73,102 +70,28 @@ __device__ __forceinline__ void ring_sched_interleave() {
   }
 }
 
-template <typename T16>
-__device__ __forceinline__ void mfma16(const uint4 &a, const uint4 &b, f32x4_t &acc);
-template <>
-__device__ __forceinline__ void mfma16<bf16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mfma16<f16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-
 // two fp32 -> one packed 16-bit pair by ONE instruction (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32: what a vector fptrunc selects on
 // gfx950, round to nearest even like the scalar conversions of common.h, which cost three instructions per pair)
 template <typename T16>
 __device__ __forceinline__ unsigned pack2_pk(float lo, float hi);
 template <>
 __device__ __forceinline__ unsigned pack2_pk<f16_t>(float lo, float hi) {
-  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, h2_t));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, f16x2_t));
 }
 template <>
 __device__ __forceinline__ unsigned pack2_pk<bf16_t>(float lo, float hi) {
-  typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, b2_t));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
 
-// LDS-DMA through a buffer descriptor: lane i's 16 bytes land at lds_addr + 16 i; a lane whose offset is outside the
-// descriptor's range delivers zeros.  Inline asm for the reason given at dma16_to_lds (no compiler-side vmcnt bookkeeping).
-__device__ __forceinline__ void dma16_buf_to_lds(u32x4_t rsrc, unsigned voff, unsigned soff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_addr)
-               : "memory");
-}
 template <bool NT_ST>
 __device__ __forceinline__ void store16_buf(u32x4_t rsrc, unsigned voff, unsigned soff, u32x4_t val) {
   if (NT_ST) asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt" ::"v"(val), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
   else asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(val), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
-__device__ __forceinline__ void vm_wait_all_but(int n) {      // the n youngest vector-memory operations may stay in flight
-  if (n > 40) n = 40;       // (fewer in flight than allowed: always safe)
-  switch (n) {
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-    case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-    case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-    case 23: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-    case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    case 25: asm volatile("s_waitcnt vmcnt(25)" ::: "memory"); break;
-    case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-    case 27: asm volatile("s_waitcnt vmcnt(27)" ::: "memory"); break;
-    case 28: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
-    case 29: asm volatile("s_waitcnt vmcnt(29)" ::: "memory"); break;
-    case 30: asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); break;
-    case 31: asm volatile("s_waitcnt vmcnt(31)" ::: "memory"); break;
-    case 32: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-    case 33: asm volatile("s_waitcnt vmcnt(33)" ::: "memory"); break;
-    case 34: asm volatile("s_waitcnt vmcnt(34)" ::: "memory"); break;
-    case 35: asm volatile("s_waitcnt vmcnt(35)" ::: "memory"); break;
-    case 36: asm volatile("s_waitcnt vmcnt(36)" ::: "memory"); break;
-    case 37: asm volatile("s_waitcnt vmcnt(37)" ::: "memory"); break;
-    case 38: asm volatile("s_waitcnt vmcnt(38)" ::: "memory"); break;
-    case 39: asm volatile("s_waitcnt vmcnt(39)" ::: "memory"); break;
-    case 40: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-__device__ __forceinline__ u32x4_t make_rsrc(const void *base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4_t r;
-  r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);      // stride 0
-  r[2] = __builtin_amdgcn_readfirstlane(bytes);
-  r[3] = 0x00020000u;                                                         // raw 32-bit data format (gfx9 family)
-  return r;
-}
-constexpr unsigned OOB = 0x80000000u;      // beyond every descriptor this kernel builds (the launcher checks < 2^31 bytes)
+
+// the n youngest vector-memory operations may stay in flight; n above the 40 cases is clamped, not dropped to vmcnt(0) as
+// vm_wait_all_but would (fewer in flight than allowed is always safe, and keeps the overlap)
+__device__ __forceinline__ void ring_wait_all_but(int n) { vm_wait_all_but<40>(min(n, 40)); }
 
 // GST: the launch is the DATA GRADIENT of a conv whose input was z = LeakyReLU(InstanceNorm(y_prev)); the epilogue also leaves the
 // sums the InstanceNorm backward of that previous block needs (conv_rows.hip, GST: same definition, same partial-sum layout,
@@ -305,7 +228,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
       const int g = (lane & 3) ^ (((u >> 2) & 1) << 1);
       const int gh = oh0 - 1 + row, gw = ow0 - 1 + u;
       const bool ok = idx < 2 * C::PIECES && e < C::NVOX && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
-      return ok ? (unsigned)((gh * xv.sh + gw * xv.sw + kh * khoff + g * 8) * 2) : OOB;
+      return ok ? (unsigned)((gh * xv.sh + gw * xv.sw + kh * khoff + g * 8) * 2) : RSRC_OOB;
     };
     unsigned poff[KH == 1 ? C::NPW : 1];
     if (KH == 1) {
@@ -314,8 +237,8 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
     }
     // output: lane (row rho = q, voxel v) stores 8 channels of voxel v + 16 (rho & 1) after the row swaps
     const int ovox = v + 16 * (q & 1);
-    const unsigned ooff = (ow0 + ovox < W) ? (unsigned)((ovox * yv.sw + chalf * 16 + (q >> 1) * 8) * 2) : OOB;
-    const unsigned goff = (GST && ow0 + ovox < W) ? (unsigned)((ovox * gst.v.sw + chalf * 16 + (q >> 1) * 8) * 2) : OOB;
+    const unsigned ooff = (ow0 + ovox < W) ? (unsigned)((ovox * yv.sw + chalf * 16 + (q >> 1) * 8) * 2) : RSRC_OOB;
+    const unsigned goff = (GST && ow0 + ovox < W) ? (unsigned)((ovox * gst.v.sw + chalf * 16 + (q >> 1) * 8) * 2) : RSRC_OOB;
     const bool wv0 = ow0 + v < W, wv1 = ow0 + 16 + v < W;      // this lane's voxel of tile half 0 / 1 inside the volume
     const bool full_w = ow0 + 32 <= W;
 
@@ -326,7 +249,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
         const int gd = d0 - 1 + ip + idx / C::PIECES;
         const bool dok = (unsigned)gd < (unsigned)D;
         const unsigned soff = dok ? (unsigned)(gd * xv.sd * 2) : 0u;
-        const unsigned voff = (KH == 1 ? poff[KH == 1 ? i : 0] : piece_off(i)) | (dok ? 0u : OOB);
+        const unsigned voff = (KH == 1 ? poff[KH == 1 ? i : 0] : piece_off(i)) | (dok ? 0u : RSRC_OOB);
         const bool half1 = KH == 2 && ((idx / C::SUB_PIECES) % KH) == 1;          // (wave-uniform)
         dma16_buf_to_lds(half1 ? rx1 : rx, voff, soff, lds0 + pr * (2 * C::PLANE) + idx * 1024);
         return 1;
@@ -392,7 +315,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
         } else {
           asm volatile("" ::"v"(val), "s"(soff));
         }
-        if (GST && goff != OOB) {       // (a voxel beyond W contributes nothing)
+        if (GST && goff != RSRC_OOB) {       // (a voxel beyond W contributes nothing)
           const u32x4_t yq = gy[oh];
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
@@ -466,7 +389,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
         const int dz = rs >> 2, hy = rs & 3;
         if (BAR7 && rs == 7) {
           stamp(1);
-          vm_wait_all_but(issued - mark_cur);
+          ring_wait_all_but(issued - mark_cur);
           lds_barrier();
           stamp(2);
         }
@@ -519,7 +442,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
     if (ABL == 6) tprev = __builtin_amdgcn_s_memtime();
     const int mark_p = issue_group(0, 0);
     mark_cur = issue_group(1, 2);      // planes 2, 3: needed behind M_0
-    vm_wait_all_but(issued - mark_p);
+    ring_wait_all_but(issued - mark_p);
     lds_barrier();      // planes 0, 1 are there
     stamp(0);
     int kk = 0;         // k mod 3: ring pair that holds the step's first two planes

@@ -455,11 +455,7 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
             // 16-channel half is fetched one phase later.  PMC, 128^3 32->32, one sample: FETCH 353 -> 197 MB (134 MB
             // of input; the rest is the D-halo of consecutive jobs), WRITE unchanged (DGTTA_ROWS_ABL=8: plain stores)
             if (ABL == 8) *reinterpret_cast<uint4 *>(orow + ow * yv.sw) = val;
-            else if (ABL != 2) {
-              typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-              const u32x4_t nv = {val.x, val.y, val.z, val.w};
-              __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t *>(orow + ow * yv.sw));
-            }
+            else if (ABL != 2) st16_nt(orow + ow * yv.sw, val);
           }
         };
         // (a wave reads back only its own slab: LDS operations of one wave complete in order); the read-back and stores

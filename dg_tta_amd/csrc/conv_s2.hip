@@ -153,11 +153,7 @@ __global__ __launch_bounds__(512) void conv_s2_regs_kernel(const T *__restrict__
         for (int t = 0; t < 2; ++t) {
           const int m = t * 16 + (lane >> 2), cq = (lane & 3) * 8, owm = wb * 32 + m;
           const uint4 val = *reinterpret_cast<const uint4 *>(slab + m * 32 + cq);
-          if (owm < Wo) {
-            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-            const u32x4_t nv = {val.x, val.y, val.z, val.w};
-            __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t *>(yrow + (long long)owm * yv.sw + nb * 32 + cq));
-          }
+          if (owm < Wo) st16_nt(yrow + (long long)owm * yv.sw + nb * 32 + cq, val);
         }
       }
     }

@@ -1,8 +1,9 @@
 // Shared declarations of the weight-gradient translation units (conv_wgrad.hip: host dispatch; conv_wgrad_rows.hip,
 // conv_wgrad_flat.hip, conv_wgrad_s2.hip, convt_wgrad.hip, conv_wgrad_reduce.hip, head_wgrad.hip: kernels and their launchers):
 // the launch descriptors, the launchers that cross files (each declared here, once; the defining file includes this header)
-// and the device helpers that more than one kernel file uses.  All kernels leave fp32 partial slabs [27 taps][32 ci][32 co],
-// one per workgroup and channel-block pair; wgrad_reduce_launch sums them in a fixed order.
+// and the weight-gradient device helpers that more than one kernel file uses (the MFMA wrappers and tr_operand: gfx950.h).
+// All kernels leave fp32 partial slabs [27 taps][32 ci][32 co], one per workgroup and channel-block pair; wgrad_reduce_launch
+// sums them in a fixed order.
 #pragma once
 #include "conv_common.h"
 #include <type_traits>
@@ -72,8 +73,6 @@ int wgrad_reduce_launch(const float *slabs, float *dw, int Cin, int Cout, const 
                         const RealTaps &reals, const Taps *dense, long long s_co, long long s_ci, long long s_tap, hipStream_t st);
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 // Workgroups are dispatched round robin over the 8 XCDs (each with its own L2), units are columns of the volume whose x
 // tiles overlap their H neighbours' by the halo rows: give every XCD a CONTIGUOUS range of units, so that the halo is
@@ -154,36 +153,6 @@ __device__ __forceinline__ uint4 shift_run<float>(const uint4 &c, unsigned e0, u
   return make_uint4(c.z, c.w, e0, e1);
 }
 
-template <typename T>
-__device__ __forceinline__ void mfma16(const uint4 &a, const uint4 &b, f32x4_t &acc);
-template <>
-__device__ __forceinline__ void mfma16<bf16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0,
-                                                0, 0);
-}
-template <>
-__device__ __forceinline__ void mfma16<f16_t>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-// 32x32x16 step on transposed-read operands (kept as bf16x8 bit patterns; the storage type picks the instruction)
-template <typename T16>
-__device__ __forceinline__ f32x16_t mfma32_tr(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc);
-template <>
-__device__ __forceinline__ f32x16_t mfma32_tr<bf16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x16_t mfma32_tr<f16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mfma16<float>(const uint4 &a, const uint4 &b, f32x4_t &acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-
 // LDS geometry of the kernels with hardware-transposed operand reads (conv3_wgrad_tr_kernel and its 8-wave variant): tiles of
 // 4 rows x 32 voxels, slices voxel-major [row][voxel][32 channels = 64 B], a ring of 4 x slices (halo of 1) and 2 dy slices
 struct WT {
@@ -194,15 +163,6 @@ struct WT {
   static constexpr int LDS_BYTES = 4 * X_SLICE_B + 2 * Y_SLICE_B;
   static constexpr int NPX = XR * 3, NPY = TH * 2, NP = NPX + NPY;      // DMA pieces per slice
 };
-
-__device__ __forceinline__ bf16x8_t tr_operand(const unsigned char *p) {
-  // two 4-voxel transposed reads = 8 consecutive voxels (k) of this lane's channel
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)p);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(p + 4 * 64));
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
 
 // tile geometry of the one-pass stride-2 kernels (conv_wgrad_s2.hip); the transposed-conv kernel tiles its input lattice alike
 struct WT2 {

@@ -30,8 +30,6 @@
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
 struct WR {
   static constexpr int TH = 8, XR = TH + 2, XW = 34;
   static constexpr int X_ROW_B = XW * 64, XP = (XR * X_ROW_B + 1023) / 1024, X_SLICE_B = XP * 1024;      // 22 pieces
@@ -48,75 +46,12 @@ constexpr int WR_LDS_TOTAL = WR::LDS_BYTES + 1024;
 static_assert(WR_LDS_TOTAL <= 160 * 1024, "wgrad ring does not fit the LDS");
 static_assert(4 * 7 * 16 * 64 * 4 <= WR::LDS_BYTES, "final combine buffer");
 
-__device__ __forceinline__ void wr_dma16(u32x4_t rsrc, unsigned voff, unsigned soff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_addr)
-               : "memory");
-}
-__device__ __forceinline__ void wr_wait_all_but(int n) {      // the n youngest vector-memory operations may stay in flight
-  switch (n) {
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;      // (n > 10 never happens; 0 is always safe)
-  }
-}
-__device__ __forceinline__ u32x4_t wr_rsrc(const void *base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  u32x4_t r;
-  r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-  r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  r[2] = __builtin_amdgcn_readfirstlane(bytes);
-  r[3] = 0x00020000u;
-  return r;
-}
-constexpr unsigned WR_OOB = 0x80000000u;
-
-typedef __attribute__((ext_vector_type(8))) short wr_s16x8_t;
-__device__ __forceinline__ bf16x8_t wr_operand(const unsigned char *p) {      // 8 consecutive voxels (k) of this lane's channel
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)p);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(p + 4 * 64));
-  const wr_s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
 __device__ __forceinline__ bf16x8_t wr_operand2(const unsigned char *p0, const unsigned char *p1) {      // the two reads at their own addresses
   const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)p0);
   const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)p1);
-  const wr_s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, v);
 }
-template <typename T16>
-__device__ __forceinline__ f32x16_t wr_mfma(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc);
-template <>
-__device__ __forceinline__ f32x16_t wr_mfma<bf16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x16_t wr_mfma<f16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x16_t &acc) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-template <typename T16>
-__device__ __forceinline__ f32x4_t wr_mfma16(const bf16x8_t &a, const bf16x8_t &b, const f32x4_t &acc);
-template <>
-__device__ __forceinline__ f32x4_t wr_mfma16<bf16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x4_t &acc) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4_t wr_mfma16<f16_t>(const bf16x8_t &a, const bf16x8_t &b, const f32x4_t &acc) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-
 // scheduling pattern of one (row, k-step) iteration: NM MFMAs with NR LDS reads dealt out behind them, the first MFMA first
 template <int NM, int NR>
 __device__ __forceinline__ void wr_sched_interleave() {
@@ -242,8 +177,8 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
     const int b = j / nseg;
     const int h0 = th * WR::TH, w0 = tw * 32;
     const int d_begin = seg * DR, d_end = (d_begin + DR < D) ? d_begin + DR : D;
-    const u32x4_t rx = wr_rsrc(x + (long long)b * xv.sb + (xkh ? cib * xkh : (long long)cib * 32), x_bytes),
-                  ry = wr_rsrc(dy + (long long)b * yv.sb + cob * 32, y_bytes);
+    const u32x4_t rx = make_rsrc(x + (long long)b * xv.sb + (xkh ? cib * xkh : (long long)cib * 32), x_bytes),
+                  ry = make_rsrc(dy + (long long)b * yv.sb + cob * 32, y_bytes);
 
     // per-lane source offsets of this wave's DMA pieces (piece idx = wave + 8 i of the 22 x + 16 dy pieces of a slice pair):
     // lane -> voxel 16 P + lane / 4, 16-byte channel chunk lane & 3
@@ -259,13 +194,13 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
         if (MF16) chunk ^= ((u >> 3) & 1) << 1;
         const int gh = h0 - 1 + row, gw = w0 - 1 + u;
         const bool ok = e < WR::NVOX && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W && cib * 32 + chunk * 8 < cin_lim;
-        poff[i] = ok ? (unsigned)((gh * xv.sh + gw * xv.sw + chunk * 8) * 2) : WR_OOB;
+        poff[i] = ok ? (unsigned)((gh * xv.sh + gw * xv.sw + chunk * 8) * 2) : RSRC_OOB;
       } else {
         const int p = idx - WR::XP, row = p >> 1, vox = 16 * (p & 1) + (lane >> 2);
         if (MF16) chunk ^= ((vox >> 3) & 1) << 1;
         const int gh = h0 + row, gw = w0 + vox;
         const bool ok = idx < WR::NP && gh < H && gw < W && cob * 32 + chunk * 8 < Cout;
-        poff[i] = ok ? (unsigned)((gh * yv.sh + gw * yv.sw + chunk * 8) * 2) : WR_OOB;
+        poff[i] = ok ? (unsigned)((gh * yv.sh + gw * yv.sw + chunk * 8) * 2) : RSRC_OOB;
       }
     }
     // piece i of x slice xd into ring slot xslot / dy slice yd into ring slot yslot (either may be switched off)
@@ -274,14 +209,14 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
       if (idx < WR::XP) {
         if (!do_x) return 0;
         const bool dok = (unsigned)xd < (unsigned)D;
-        wr_dma16(rx, poff[i] | (dok ? 0u : WR_OOB), dok ? (unsigned)(xd * xv.sd * 2) : 0u, lds0 + xslot * WR::X_SLICE_B + idx * 1024);
+        dma16_buf_to_lds(rx, poff[i] | (dok ? 0u : RSRC_OOB), dok ? (unsigned)(xd * xv.sd * 2) : 0u, lds0 + xslot * WR::X_SLICE_B + idx * 1024);
         return 1;
       }
       if (idx < WR::NP) {
         if (!do_y) return 0;
         const bool dok = (unsigned)yd < (unsigned)D;
-        wr_dma16(ry, poff[i] | (dok ? 0u : WR_OOB), dok ? (unsigned)(yd * yv.sd * 2) : 0u,
-                 lds0 + WR::NXS * WR::X_SLICE_B + yslot * WR::Y_SLICE_B + (idx - WR::XP) * 1024);
+        dma16_buf_to_lds(ry, poff[i] | (dok ? 0u : RSRC_OOB), dok ? (unsigned)(yd * yv.sd * 2) : 0u,
+                         lds0 + WR::NXS * WR::X_SLICE_B + yslot * WR::Y_SLICE_B + (idx - WR::XP) * 1024);
         return 1;
       }
       return 0;
@@ -297,8 +232,8 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
       for (int q = 0; q < 4; ++q) r[q] = isx ? rx[q] : ry[q];
       const unsigned lds_piece = isx ? (unsigned)(xslot * WR::X_SLICE_B + idx * 1024)
                                      : (unsigned)(WR::NXS * WR::X_SLICE_B + yslot * WR::Y_SLICE_B + (idx - WR::XP) * 1024);
-      wr_dma16(r, poff[i] | (dok ? 0u : WR_OOB), dok ? (unsigned)(sd * (isx ? xv.sd : yv.sd) * 2) : 0u,
-               lds0 + (valid ? lds_piece : (unsigned)WR::LDS_BYTES));
+      dma16_buf_to_lds(r, poff[i] | (dok ? 0u : RSRC_OOB), dok ? (unsigned)(sd * (isx ? xv.sd : yv.sd) * 2) : 0u,
+                       lds0 + (valid ? lds_piece : (unsigned)WR::LDS_BYTES));
     };
     // (x(xd) lives in slot (xd + 1) mod NXS, dy(yd) in slot yd mod NYS)
     auto issue_piece = [&](int i, int xd, bool do_x, int yd, bool do_y) -> int {
@@ -322,7 +257,7 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
     for (int d = d_begin; d < d_end; ++d) {
       unsigned long long tw0 = 0;
       if (CLK) tw0 = __builtin_amdgcn_s_memtime();
-      wr_wait_all_but(issued - mark_cur);      // this wave's pieces of x(d + 1), dy(d) have landed ...
+      vm_wait_all_but<10>(issued - mark_cur);      // this wave's pieces of x(d + 1), dy(d) have landed ...
       lds_barrier();                           // ... and everyone's; every wave is done with slice d - 1
       if (CLK) t_wait += __builtin_amdgcn_s_memtime() - tw0;
       const bool more = d + 2 < d_end;         // x(d + 3), dy(d + 2): first read in slice d + 2
@@ -352,11 +287,11 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
         // (REUSE: k-step outside, rows inside; a slot that is not new in a row takes the previous row's next slot)
         auto load_it = [&](int it, bf16x8_t(&a)[NA], const bf16x8_t(&prev)[NA], bf16x8_t &bb) {
           const int oh = REUSE ? (it & 3) : (it >> 1), ks = REUSE ? (it >> 2) : (it & 1);
-          bb = wr_operand(ys + oh * WR::Y_ROW_B + ks * 1024);
+          bb = tr_operand(ys + oh * WR::Y_ROW_B + ks * 1024);
 #pragma unroll
           for (int i = 0; i < NA; ++i) {
             const bool fresh = !REUSE || oh == 0 || i == NA - 1 || (PAIR ? i == 2 : (i == 2 || i == 5));
-            if (fresh) a[i] = wr_operand(sX + xa[i] + oh * WR::X_ROW_B + ks * 1024);
+            if (fresh) a[i] = tr_operand(sX + xa[i] + oh * WR::X_ROW_B + ks * 1024);
             else a[i] = prev[i + 1];
           }
         };
@@ -366,7 +301,7 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
             f32x16_t c;
 #pragma unroll
             for (int q = 0; q < 16; ++q) c[q] = accf[i][q];
-            c = wr_mfma<T16>(afr[it & 1][i], bfr[it & 1], c);
+            c = mfma32_tr<T16>(afr[it & 1][i], bfr[it & 1], c);
 #pragma unroll
             for (int q = 0; q < 16; ++q) accf[i][q] = c[q];
           }
@@ -374,10 +309,10 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
         if constexpr (REUSE) {
           // the slice's first operands in the order the MFMAs want them (left to itself the scheduler sorts the reads of
           // iterations 0 and 1 by address, and the first MFMA after the barrier waits for fourteen reads of all eight waves)
-          bfr[0] = wr_operand(ys);
+          bfr[0] = tr_operand(ys);
 #pragma unroll
           for (int i = 0; i < NA; ++i) {
-            afr[0][i] = wr_operand(sX + xa[i]);
+            afr[0][i] = tr_operand(sX + xa[i]);
             if (i % 2 == 0) __builtin_amdgcn_sched_barrier(0);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -457,7 +392,7 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
             for (int cb = 0; cb < 2; ++cb) {
               f32x4_t c = {accf[i][(ca * 2 + cb) * 4 + 0], accf[i][(ca * 2 + cb) * 4 + 1], accf[i][(ca * 2 + cb) * 4 + 2],
                            accf[i][(ca * 2 + cb) * 4 + 3]};
-              c = wr_mfma16<T16>(fb[u & 1][ca], bb[oh & 1][cb], c);
+              c = mfma16_tr<T16>(fb[u & 1][ca], bb[oh & 1][cb], c);
 #pragma unroll
               for (int r = 0; r < 4; ++r) accf[i][(ca * 2 + cb) * 4 + r] = c[r];
             }

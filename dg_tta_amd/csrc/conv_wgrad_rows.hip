@@ -431,7 +431,6 @@ __global__ __launch_bounds__(512, 1) void conv3_wgrad_tr8_kernel(const bf16_t *_
     for (int i = 0; i < (WT::NPX + 7) / 8; ++i) issue_piece(i, d_begin + sl, (d_begin + sl) & 3, 0, 0, true, false);
   dma_wait_all();
   lds_barrier();
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
   for (int d = d_begin; d < d_end; ++d) {
     const bool more = d + 1 < d_end;
     const unsigned char *ys = sY + (d & 1) * WT8::Y_SLICE_B + lane_off_y;

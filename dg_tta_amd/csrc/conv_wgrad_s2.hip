@@ -105,7 +105,6 @@ __global__ __launch_bounds__(256, 2) void conv3_wgrad_tr_s2_kernel(const bf16_t 
       // K-step = the 16 output voxels of the row
       const s16x4_t blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(ys + oh * WT2::Y_ROW_B));
       const s16x4_t bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(ys + oh * WT2::Y_ROW_B + 4 * 64));
-      typedef __attribute__((ext_vector_type(8))) short s16x8_t;
       const s16x8_t bv = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
       const bf16x8_t bfr = __builtin_bit_cast(bf16x8_t, bv);
       bf16x8_t afr[7];
@@ -248,7 +247,6 @@ __global__ __launch_bounds__(512, 2) void conv3_wgrad_tr_s2x_kernel(const bf16_t
     for (int oh = 0; oh < WT2::TH; ++oh) {
       const s16x4_t blo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(ys + oh * WT2::Y_ROW_B));
       const s16x4_t bhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t *)(ys + oh * WT2::Y_ROW_B + 4 * 64));
-      typedef __attribute__((ext_vector_type(8))) short s16x8_t;
       const s16x8_t bv = {blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
       const bf16x8_t bfr = __builtin_bit_cast(bf16x8_t, bv);
       bf16x8_t afr[7];

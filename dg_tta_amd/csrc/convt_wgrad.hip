@@ -91,7 +91,6 @@ __global__ __launch_bounds__(256, 2) void convT_wgrad_tr_kernel(const bf16_t *__
   // bias gradient sum_v dout[v][co] on the side (round 4; the first input-channel group's workgroups only): an x operand that is 1
   // in row 0 and 0 elsewhere leaves the column sums of the dout fragments in row 0 of a third accumulator pair - the pass
   // over dout that chan_reduce_vec_kernel<., 2> made for them (1.5 ms per epoch) is not needed
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
   const bool do_bias = bias_part != nullptr && cig == 0;
   const short one16 = sizeof(T16) == 2 && std::is_same<T16, f16_t>::value ? (short)0x3C00 : (short)0x3F80;
   const short o1 = (lane & 31) == 0 ? one16 : (short)0;

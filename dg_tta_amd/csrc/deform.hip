@@ -332,11 +332,6 @@ __global__ __launch_bounds__(256) void dense_warp_bwd_kernel(const float *__rest
   }
 }
 
-int grid_for(int64_t total) {
-  const int64_t b = (total + 255) / 256;
-  return (int)(b < 8192 ? b : 8192);
-}
-
 int check_rf(const char *name, int P, int k, int Dl, int Hl, int Wl, int D, int H, int W) {
   DG_REQUIRE(P > 0 && Dl > 0 && Hl > 0 && Wl > 0 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "%s: bad dims", name);
   DG_REQUIRE(k >= 1 && (k & 1), DGTTA_ERR_UNSUPPORTED, "%s: the box width must be odd (got %d)", name, k);

@@ -9,7 +9,7 @@
 // Pass B (gin_norm_kernel): fixed-order double sum -> ||x||_F, ||mixed||_F per sample.
 // Pass C (gin_scale_kernel): out = mixed * (1/(||mixed||+1e-5)) * ||x||   (gin.py:228, same operation order).
 // Algorithmic HBM bytes per voxel: 4 r + 4 w + 4 r + 4 w = 16 B.
-#include "common.h"
+#include "gfx950.h"
 
 namespace {
 
@@ -54,8 +54,6 @@ __global__ void gin_prep_kernel(GinArgs a, float *__restrict__ wtab) {
     if (tid < cout[l]) wt[324 + 2 * l + tid] = a.shift[l][b * cout[l] + tid];
   }
 }
-
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 // acc.{lo,hi} += w.{lo,hi} * v.lo   /   * v.hi   (v_pk_fma_f32 with the second operand's half broadcast by op_sel)
 __device__ __forceinline__ void pk_fma_blo(f32x2_t &acc, const f32x2_t &w, const f32x2_t &v) {

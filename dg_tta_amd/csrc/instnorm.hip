@@ -2,6 +2,7 @@
 // they share with the conv layers: InstanceNorm statistics, InstanceNorm backward sums, bias gradients.
 // Semantics follow torch.nn.{InstanceNorm3d, LeakyReLU} as used by nnUNet's PlainConvUNet.
 #include "conv_api.h"
+#include "gfx950.h"
 
 namespace {
 
@@ -112,17 +113,12 @@ __global__ __launch_bounds__(256) void chan_reduce_vec_kernel(const T *__restric
     for (int64_t r = (int64_t)blockIdx.x * (2 * rpi) + rg; r < r1; r += (int64_t)gridDim.x * (2 * rpi)) {
       const bool two = r + rpi < r1;
       // streaming loads, as in the apply passes (the tensors are far larger than the caches and are read once per pass)
-      typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-      auto ldnt = [](const T *p) {
-        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
-        return make_uint4(v[0], v[1], v[2], v[3]);
-      };
-      uint4 v0 = ldnt(yb + r * ldy), v1 = make_uint4(0, 0, 0, 0);
+      uint4 v0 = ld16_nt(yb + r * ldy), v1 = make_uint4(0, 0, 0, 0);
       uint4 g0 = make_uint4(0, 0, 0, 0), g1 = g0;
-      if (two) v1 = ldnt(yb + (r + rpi) * ldy);
+      if (two) v1 = ld16_nt(yb + (r + rpi) * ldy);
       if (MODE == 1) {
-        g0 = ldnt(gb + r * ldgz);
-        if (two) g1 = ldnt(gb + (r + rpi) * ldgz);
+        g0 = ld16_nt(gb + r * ldgz);
+        if (two) g1 = ld16_nt(gb + (r + rpi) * ldgz);
       }
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -199,7 +195,6 @@ __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__
                                                            T *__restrict__ out, int ldo, int C, int64_t V, float slope,
                                                            int nt) {
   constexpr int EPV = 16 / sizeof(T);
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
   extern __shared__ float sc[];     // fwd: [C][2] (alpha, beta'); bwd: [C][6] (mu, rs, ga, be, c1, c2)
   const int b = blockIdx.y;
   constexpr int NK = MODE == 0 ? 2 : 6;
@@ -252,18 +247,11 @@ __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__
         }
       }
       const uint4 pk = pack16<T>(o);
-      if (nt) {
-        const u32x4_t nv = {pk.x, pk.y, pk.z, pk.w};
-        __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t *>(ob + row * ldo + c0));
-      } else {
-        *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pk;
-      }
+      if (nt) st16_nt(ob + row * ldo + c0, pk);
+      else *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pk;
     };
     auto ld = [&](const T *p) {
-      if (nt) {
-        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
-        return make_uint4(v[0], v[1], v[2], v[3]);
-      }
+      if (nt) return ld16_nt(p);
       return *reinterpret_cast<const uint4 *>(p);
     };
     for (int64_t row = (int64_t)blockIdx.x * rpb + threadIdx.x / G; row < V; row += 2 * rstep) {

@@ -23,13 +23,6 @@ constexpr int HM_ROWS = 64;      // rows of a tile
 constexpr int HM_PAD = 8;        // pad elements of an LDS row (16 bytes)
 constexpr int HM_WP = HM_ROWS + HM_PAD;      // pitch of the transposed tiles of the weight gradient
 
-template <typename T16>
-__device__ __forceinline__ float from16(unsigned short h);
-template <>
-__device__ __forceinline__ float from16<bf16_t>(unsigned short h) { return bf16_to_f32(h); }
-template <>
-__device__ __forceinline__ float from16<f16_t>(unsigned short h) { return f16_to_f32(h); }
-
 __device__ __forceinline__ f32x16_t zero_acc() {
   f32x16_t a;
 #pragma unroll

@@ -1,4 +1,5 @@
-// Sliding-window inference in FEATURE space (round 5; BASELINE config 3).
+// Sliding-window inference in FEATURE space (round 5; BASELINE config 3); window_logits.hip is the
+// logit-space form it replaces.
 //
 // What the reference does (nnunetv2==2.2.1 predict_sliding_window_return_logits, reached from
 // dg_tta/tta/nnunet_utils.py:116-125, 208-230; ensemble loop dg_tta/tta/tta.py:396-413): every window's logits over ALL
@@ -19,7 +20,7 @@
 // fp32 features with the fp32 weights instead of on 16-bit features window by window), so labels can differ from the
 // logits-space accumulator where the top-2 margin is at rounding level - tests/test_inference.py compares both forms with the
 // CPU restatement outside such ties.  nnU-Net itself is absent from /root/reference: this stage is "parity unpinned" either way.
-#include "common.h"
+#include "gfx950.h"
 
 namespace {
 
@@ -234,7 +235,6 @@ __global__ __launch_bounds__(256) void feature_head_argmax_kernel(const float *_
 // Measured at 512^3 x 105 classes (profiles/tools/headargmax_bench.py): one member 14.3 ms (vector-ALU kernel 15.5: the per-tile
 // initialisation and argmax scan cost as much as one member's products), the plan's ensemble of three 29.0 ms against 179 ms - the
 // vector-ALU kernel keeps several members' partial sums in LDS and is bound by that traffic; here a further member is 7.3 ms of MFMAs.
-typedef float wf_f32x16_t __attribute__((ext_vector_type(16)));
 constexpr int WF_WPITCH = 36;
 
 template <int NCB>      // class blocks of 32 (C <= 32 NCB)
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void feature_head_argmax_mfma_kernel(const flo
   for (; t < ntile; t += tstep) {
     const int64_t v = voxel_of(t);
     const float n = nsum[v];
-    wf_f32x16_t acc[NCB];
+    f32x16_t acc[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll

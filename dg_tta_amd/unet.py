@@ -213,7 +213,7 @@ class HipPlainConvUNet(nn.Module):
         self._no_deep_supervision("fuse_output_warp")
         return self._during("_fused_warp", lambda: (theta_dev.float().contiguous(), theta_host.detach().float().contiguous()))
 
-    # -- head fused with the Gaussian window accumulation of the sliding-window inference (csrc/warp.hip)
+    # -- head fused with the Gaussian window accumulation of the sliding-window inference (csrc/window_logits.hip)
     def can_fuse_window_accumulate(self):
         return (os.environ.get("DGTTA_FUSE_HEAD_ACCUMULATE", "1") != "0" and self.selected_classes is None and
                 self.act_dtype in (torch.float16, torch.bfloat16) and self.decoder.seg_layers[-1].in_channels == 32 and
