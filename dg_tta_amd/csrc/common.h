@@ -54,7 +54,7 @@ static inline hipError_t ensure_dyn_lds(DynLdsOnce &o, const void *fn, int bytes
 }
 
 // context of a data-gradient launch that also produces the InstanceNorm backward statistics of the previous block: built by
-// dgtta_conv3d_k3_dgrad_gstats and handed DOWN the dispatch chain as an argument (conv3_fwd_mfma -> dispatch_conv ->
+// dgtta_conv3d_k3_dgrad_gstats and handed DOWN the dispatch chain in its launch descriptor (conv3_fwd_mfma -> ConvLaunch::gst ->
 // conv3_ring_launch / conv3_rows_launch); the launcher that takes it sets `produced`, the generic kernels ignore it
 struct RowsGstCtx {
   const void *y;

@@ -219,8 +219,7 @@ __global__ __launch_bounds__(512) void conva_mfma_kernel(const T *__restrict__ x
 }
 
 template <typename T, int MBW, int MBH, int MBD, int KD, int SD, int SH, int SW>
-int launch_conva(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y, const View &yv,
-                 int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
+int launch_conva(const ConvLaunch &L, const ConvClasses &cs) {
   typedef CfgA<T, MBW, MBH, MBD, KD, SD, SH, SW> Cfg;
   typedef typename Cfg::G G;
   static_assert(Cfg::LDS_BYTES <= 160 * 1024, "conva tile does not fit the LDS");
@@ -228,14 +227,15 @@ int launch_conva(const void *x, const View &xv, const void *w, const ConvClasses
   static DynLdsOnce lds_once;
   DG_REQUIRE(ensure_dyn_lds(lds_once, reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess, DGTTA_ERR_LAUNCH,
              "conv3d_fwd: cannot raise the dynamic LDS limit to %zu", (size_t)Cfg::LDS_BYTES);
+  const View &yv = L.yv;
   const int tW = cdiv(yv.W, G::TW), tH = cdiv(yv.H, G::TH), tD = cdiv(yv.D, G::TD);
-  const int64_t tiles = (int64_t)tW * tH * tD * B;
+  const int64_t tiles = (int64_t)tW * tH * tD * L.B;
   DG_REQUIRE(tiles < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "conv3d_fwd: too many tiles");
-  DG_REQUIRE(!stats || (int64_t)tW * tH * tD <= conv3_mfma_max_tiles(yv.D, yv.H, yv.W), DGTTA_ERR_UNSUPPORTED,
+  DG_REQUIRE(!L.stats || (int64_t)tW * tH * tD <= conv3_mfma_max_tiles(yv.D, yv.H, yv.W), DGTTA_ERR_UNSUPPORTED,
              "conv3d_fwd: tile count exceeds the statistics buffer");
-  dim3 grid((unsigned)tiles, (unsigned)cdiv(CoutP, Cfg::NC), (unsigned)cs.n);
-  hipLaunchKernelGGL(kern, grid, dim3(Cfg::NW * 64), Cfg::LDS_BYTES, st, (const T *)x, xv, (const T *)w, cs, bias, (T *)y, yv, Cin,
-                     Cout, CinP, tW, tH, tD, stats, ntaps_src);
+  dim3 grid((unsigned)tiles, (unsigned)cdiv(L.CoutP, Cfg::NC), (unsigned)cs.n);
+  hipLaunchKernelGGL(kern, grid, dim3(Cfg::NW * 64), Cfg::LDS_BYTES, L.st, (const T *)L.x, L.xv, (const T *)L.w, cs, L.bias, (T *)L.y,
+                     yv, L.Cin, L.Cout, L.CinP, tW, tH, tD, L.stats, L.ntaps_src);
   DG_CHECK_LAUNCH("conva_mfma_kernel");
   return DGTTA_OK;
 }
@@ -243,88 +243,43 @@ int launch_conva(const void *x, const View &xv, const void *w, const ConvClasses
 // tile shape from the output extent: (TD, TH, TW) = (4, 4, 32) where the halo fits the LDS (SD = 1), else (4, 4, 16) or
 // (4, 8, 8); each is a shape of conv3_mfma_max_tiles, so the InstanceNorm partial sums fit dgtta_conv3d_stats_bytes
 template <typename T, int KD, int SD, int SH, int SW>
-int dispatch_conva(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y, const View &yv,
-                   int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
-#define ARGS x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
+int dispatch_conva(const ConvLaunch &L, const ConvClasses &cs) {
   if constexpr (SD == 1)
-    if (yv.W >= 32) return launch_conva<T, 32, 4, 4, KD, SD, SH, SW>(ARGS);
-  if (yv.W >= 16) return launch_conva<T, 16, 2, 4, KD, SD, SH, SW>(ARGS);
-  return launch_conva<T, 8, 2, 4, KD, SD, SH, SW>(ARGS);
-#undef ARGS
+    if (L.yv.W >= 32) return launch_conva<T, 32, 4, 4, KD, SD, SH, SW>(L, cs);
+  if (L.yv.W >= 16) return launch_conva<T, 16, 2, 4, KD, SD, SH, SW>(L, cs);
+  return launch_conva<T, 8, 2, 4, KD, SD, SH, SW>(L, cs);
 }
 
 template <typename T, int KD>
-int dispatch_conva_strides(int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs,
-                           const float *bias, void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats,
-                           int ntaps_src, hipStream_t st) {
-#define ARGS x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
+int dispatch_conva_strides(const ConvLaunch &L, const ConvClasses &cs, int sd, int sh, int sw) {
   switch ((sd - 1) * 4 + (sh - 1) * 2 + (sw - 1)) {
-    case 0: return dispatch_conva<T, KD, 1, 1, 1>(ARGS);
-    case 1: return dispatch_conva<T, KD, 1, 1, 2>(ARGS);
-    case 2: return dispatch_conva<T, KD, 1, 2, 1>(ARGS);
-    case 3: return dispatch_conva<T, KD, 1, 2, 2>(ARGS);
-    case 4: return dispatch_conva<T, KD, 2, 1, 1>(ARGS);
-    case 5: return dispatch_conva<T, KD, 2, 1, 2>(ARGS);
-    case 6: return dispatch_conva<T, KD, 2, 2, 1>(ARGS);
-    case 7: return dispatch_conva<T, KD, 2, 2, 2>(ARGS);
+    case 0: return dispatch_conva<T, KD, 1, 1, 1>(L, cs);
+    case 1: return dispatch_conva<T, KD, 1, 1, 2>(L, cs);
+    case 2: return dispatch_conva<T, KD, 1, 2, 1>(L, cs);
+    case 3: return dispatch_conva<T, KD, 1, 2, 2>(L, cs);
+    case 4: return dispatch_conva<T, KD, 2, 1, 1>(L, cs);
+    case 5: return dispatch_conva<T, KD, 2, 1, 2>(L, cs);
+    case 6: return dispatch_conva<T, KD, 2, 2, 1>(L, cs);
+    case 7: return dispatch_conva<T, KD, 2, 2, 2>(L, cs);
   }
-#undef ARGS
   return DGTTA_ERR_UNSUPPORTED;
 }
 
 template <typename T>
-int run_conva(int kd, int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias,
-              void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, hipStream_t st) {
-  if (kd == 1)
-    return dispatch_conva_strides<T, 1>(sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st);
-  return dispatch_conva_strides<T, 3>(sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st);
+int run_conva(const ConvLaunch &L, const ConvClasses &cs, int kd, int sd, int sh, int sw) {
+  if (kd == 1) return dispatch_conva_strides<T, 1>(L, cs, sd, sh, sw);
+  return dispatch_conva_strides<T, 3>(L, cs, sd, sh, sw);
 }
 
-int run_conva_dt(int dtype, int kd, int sd, int sh, int sw, const void *x, const View &xv, const void *w, const ConvClasses &cs,
-                 const float *bias, void *y, const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats,
-                 int ntaps_src, hipStream_t st) {
-#define ARGS kd, sd, sh, sw, x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
-  if (dtype == DGTTA_F32) return run_conva<float>(ARGS);
-  if (dtype == DGTTA_BF16) return run_conva<bf16_t>(ARGS);
-  return run_conva<f16_t>(ARGS);
-#undef ARGS
+// dtype: one of the three storage types (the entry points check dtype_ok first)
+int run_conva_dt(int dtype, const ConvLaunch &L, const ConvClasses &cs, int kd, int sd, int sh, int sw) {
+  DISPATCH_T(dtype, return run_conva<T>(L, cs, kd, sd, sh, sw));
 }
 
-// torch [Cout][Cin][kd][3][3] fp32 -> imgF (N = co, K = ci) and imgB (N = ci, K = co), both with the real tap kd*9 + kh*3 + kw
-template <typename T>
-__global__ void conva_pack_kernel(const float *__restrict__ w, T *__restrict__ imgF, T *__restrict__ imgB, int Cin, int Cout,
-                                  int CinP, int CoutP, int ntaps) {
-  constexpr int EPV = Elem<T>::EPV;
-  const int CoutN = (CoutP + 31) / 32 * 32, CinN = (CinP + 31) / 32 * 32;
-  const int64_t nf = (int64_t)ntaps * CinP * CoutN, nb = (int64_t)ntaps * CoutP * CinN;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb); i += (int64_t)gridDim.x * blockDim.x) {
-    if (i < nf) {
-      const int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), tap = (int)(i / ((int64_t)CinP * CoutN));
-      st_f<T>(imgF + conv_weight_image_index(co, ci, tap, CinP, ntaps, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
-    }
-    if (i < nb) {
-      const int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), tap = (int)(i / ((int64_t)CoutP * CinN));
-      st_f<T>(imgB + conv_weight_image_index(ci, co, tap, CoutP, ntaps, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
-    }
-  }
-}
-
-int64_t n32(int c) { return (int64_t)(c + 31) / 32 * 32; }
-int granule(int dtype) { return dtype == DGTTA_F32 ? 8 : 16; }
-bool dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
 bool stride_ok(int s) { return s == 1 || s == 2; }
 bool kernel_ok(int kd, int sd, int sh, int sw) { return (kd == 1 || kd == 3) && stride_ok(sd) && stride_ok(sh) && stride_ok(sw); }
-int odim(int i, int k, int s) { return (i + 2 * (k / 2) - k) / s + 1; }
 bool dims_ok(int B, int Cin, int Cout, int D, int H, int W) {
   return B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0 && Cin <= (1 << 16) && Cout <= (1 << 16);
-}
-
-bool operand_ok_dt(int dtype, const void *p, long long ld, int C, int CP) {
-  if (dtype == DGTTA_F32) return operand_ok<float>(p, ld, C, CP);
-  if (dtype == DGTTA_BF16) return operand_ok<bf16_t>(p, ld, C, CP);
-  return operand_ok<f16_t>(p, ld, C, CP);
 }
 
 bool convt_strides_ok(int sd, int sh, int sw) { return stride_ok(sd) && stride_ok(sh) && stride_ok(sw) && sd * sh * sw > 1; }
@@ -344,24 +299,9 @@ extern "C" int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd,
   DG_REQUIRE((kd == 1 || kd == 3) && kh == 3 && kw == 3, DGTTA_ERR_UNSUPPORTED,
              "conv3d_kpack_weights: kernel %dx%dx%d (supported: [1|3] x 3 x 3)", kd, kh, kw);
   DG_REQUIRE(dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED, "conv3d_kpack_weights: dtype %d", dtype);
-  DG_REQUIRE(CinP % granule(dtype) == 0 && CoutP % granule(dtype) == 0, DGTTA_ERR_BADARG,
-             "conv3d_kpack_weights: padded channel counts must be multiples of %d", granule(dtype));
-  const int ntaps = kd * 9;
-  void *imgB = (char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
-  const int64_t n = (int64_t)ntaps * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
-  const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DGTTA_F32)
-    hipLaunchKernelGGL((conva_pack_kernel<float>), dim3(blocks), dim3(256), 0, st, w_t, (float *)wpack, (float *)imgB, Cin, Cout,
-                       CinP, CoutP, ntaps);
-  else if (dtype == DGTTA_BF16)
-    hipLaunchKernelGGL((conva_pack_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, w_t, (bf16_t *)wpack, (bf16_t *)imgB, Cin,
-                       Cout, CinP, CoutP, ntaps);
-  else
-    hipLaunchKernelGGL((conva_pack_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, w_t, (f16_t *)wpack, (f16_t *)imgB, Cin, Cout,
-                       CinP, CoutP, ntaps);
-  DG_CHECK_LAUNCH("conva_pack_kernel");
-  return DGTTA_OK;
+  DG_REQUIRE(CinP % conv_granule(dtype) == 0 && CoutP % conv_granule(dtype) == 0, DGTTA_ERR_BADARG,
+             "conv3d_kpack_weights: padded channel counts must be multiples of %d", conv_granule(dtype));
+  return conv_pack_images(w_t, wpack, kd * 9, Cin, Cout, CinP, CoutP, dtype, (hipStream_t)stream);
 }
 
 extern "C" int dgtta_conv3d_fwd(const void *x, int ldx, const void *wpack, const float *bias, void *y, int ldy, void *stats, int B,
@@ -372,18 +312,14 @@ extern "C" int dgtta_conv3d_fwd(const void *x, int ldx, const void *wpack, const
   DG_REQUIRE(ldx >= Cin && ldy >= Cout, DGTTA_ERR_BADARG, "conv3d_fwd: ld < C");
   DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
              "conv3d_fwd: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
-  DG_REQUIRE(operand_ok_dt(dtype, x, ldx, Cin, CinP), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_fwd: x must be 16-byte aligned with rows of whole 16 bytes, CinP a multiple of %d", granule(dtype));
-  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
-  const View xv = dense_view(B, Di, Hi, Wi, ldx), yv = dense_view(B, Do, Ho, Wo, ldy);
-  ConvClasses cs;
-  cs.n = 1;
-  cs.kseg = 0;
-  cs.acc[0] = 0;
-  cs.xoff[0] = cs.yoff[0] = 0;
-  for (int t = 0; t < 27; ++t) cs.taps[0].wt[t] = (signed char)(t < kd * 9 ? t : -1);
-  return run_conva_dt(dtype, kd, sd, sh, sw, x, xv, wpack, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, (double *)stats, kd * 9,
-                      (hipStream_t)stream);
+  DG_REQUIRE(operand_ok(epv_of(dtype), x, ldx, Cin, CinP), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_fwd: x must be 16-byte aligned with rows of whole 16 bytes, CinP a multiple of %d", conv_granule(dtype));
+  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
+  Taps taps;
+  for (int t = 0; t < 27; ++t) taps.wt[t] = (signed char)(t < kd * 9 ? t : -1);
+  const ConvLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), wpack, bias, y, dense_view(B, Do, Ho, Wo, ldy), B, Cin, Cout, CinP, CoutP,
+                     (double *)stats, kd * 9, (hipStream_t)stream};
+  return run_conva_dt(dtype, L, single_class(taps, 0), kd, sd, sh, sw);
 }
 
 extern "C" int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, void *dx, int lddx, int B, int Cin, int Cout, int CinP,
@@ -396,47 +332,23 @@ extern "C" int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, v
              "conv3d_dgrad: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
   DG_REQUIRE((sd == 1 || Di % 2 == 0) && (sh == 1 || Hi % 2 == 0) && (sw == 1 || Wi % 2 == 0), DGTTA_ERR_UNSUPPORTED,
              "conv3d_dgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
-  DG_REQUIRE(operand_ok_dt(dtype, dy, lddy, Cout, CoutP), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_dgrad: dy must be 16-byte aligned with rows of whole 16 bytes, CoutP a multiple of %d", granule(dtype));
+  DG_REQUIRE(operand_ok(epv_of(dtype), dy, lddy, Cout, CoutP), DGTTA_ERR_UNSUPPORTED,
+             "conv3d_dgrad: dy must be 16-byte aligned with rows of whole 16 bytes, CoutP a multiple of %d", conv_granule(dtype));
   const int ntaps = kd * 9;
   const void *imgB = (const char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
-  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
-  const View xv = dense_view(B, Do, Ho, Wo, lddy);
-  // one class per parity p of the strided axes; per axis the virtual tap v (0..k-1) reads dy[j + v - k/2] and carries weight
-  // tap t = p + k/2 - s * (v - k/2) where 0 <= t < k
-  ConvClasses cs;
-  cs.n = sd * sh * sw;
-  cs.kseg = 0;
-  View yv{};
-  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
-  for (int c = 0; c < cs.n; ++c) {
-    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
-    long long off;
-    yv = lattice_view(Di, Hi, Wi, lddx, sd, sh, sw, par[0], par[1], par[2], &off);      // even extents: one shape for all classes
-    cs.xoff[c] = 0;
-    cs.yoff[c] = off;
-    cs.acc[c] = accumulate;
-    for (int t = 0; t < 27; ++t) cs.taps[c].wt[t] = -1;
-    for (int v = 0; v < ntaps; ++v) {
-      const int vv[3] = {v / 9, (v / 3) % 3, v % 3};
-      int real[3];
-      bool ok = true;
-      for (int a = 0; a < 3; ++a) {
-        const int pad = ks[a] / 2;
-        real[a] = par[a] + pad - ss[a] * (vv[a] - pad);
-        ok = ok && real[a] >= 0 && real[a] < ks[a];
-      }
-      if (ok) cs.taps[c].wt[v] = (signed char)(real[0] * 9 + real[1] * 3 + real[2]);
-    }
-  }
-  return run_conva_dt(dtype, kd, 1, 1, 1, dy, xv, imgB, cs, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, ntaps,
-                      (hipStream_t)stream);
+  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
+  // one stride-1 class per parity of the strided axes
+  View yv;
+  const ConvClasses cs = dgrad_parity_classes(kd, sd, sh, sw, Di, Hi, Wi, lddx, accumulate, &yv);
+  const ConvLaunch L{dy, dense_view(B, Do, Ho, Wo, lddy), imgB, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, ntaps,
+                     (hipStream_t)stream};
+  return run_conva_dt(dtype, L, cs, kd, 1, 1, 1);
 }
 
 // workspace: [bias partials][weight-gradient slabs]
 extern "C" size_t dgtta_conv3d_kwgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw) {
   if (!dims_ok(B, Cin, Cout, Di, Hi, Wi) || !kernel_ok(kd, sd, sh, sw)) return 0;
-  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
   return align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256) +
          align_up(conva_wgrad_ws_bytes(B, Cin, Cout, Do, Ho, Wo), 256);
 }
@@ -452,7 +364,7 @@ extern "C" int dgtta_conv3d_wgrad(const void *x, int ldx, const void *dy, int ld
              "conv3d_wgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
   DG_REQUIRE(ws_bytes >= dgtta_conv3d_kwgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi, kd, sd, sh, sw), DGTTA_ERR_WORKSPACE,
              "conv3d_wgrad: workspace too small");
-  const int Do = odim(Di, kd, sd), Ho = odim(Hi, 3, sh), Wo = odim(Wi, 3, sw);
+  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
   const size_t bias_bytes = align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256);
   hipStream_t st = (hipStream_t)stream;
   const int rc = conva_wgrad_mfma(x, ldx, dy, lddy, dw_t, (char *)ws + bias_bytes, ws_bytes - bias_bytes, B, Cin, Cout, Di, Hi, Wi,
@@ -469,8 +381,7 @@ extern "C" int dgtta_conv3d_wgrad(const void *x, int ldx, const void *dy, int ld
 //      out[b][s*v + o][co] = bias[co] + sum_ci x[b][v][ci] w[ci][co][o]
 extern "C" size_t dgtta_convT3d_s_fwd_ws_bytes(int Cin, int Cout, int sd, int sh, int sw, int dtype) {
   if (Cin <= 0 || Cout <= 0 || Cin > (1 << 16) || Cout > (1 << 16) || !convt_strides_ok(sd, sh, sw) || !dtype_ok(dtype)) return 0;
-  const int g = granule(dtype);
-  return align_up(convT_packed_bytes((Cin + g - 1) / g * g, (Cout + g - 1) / g * g, dtype), 256);
+  return convT_pack_region(Cin, Cout, dtype);
 }
 
 extern "C" int dgtta_convT3d_s_fwd(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws,

@@ -1,7 +1,7 @@
 // Pointer-level functions of the network building blocks that are defined in one translation unit and called from another:
-// each is declared here, once, with its default arguments; the defining file includes this header too, so the compiler sees
-// declaration and definition together.  (The View / Taps-level launchers of the MFMA units are in conv_common.h.)
-// Also the small host helpers those units share.  Needs only common.h.
+// each is declared here, once; the defining file includes this header too, so the compiler sees declaration and definition
+// together.  (The View / Taps-level launchers of the MFMA units and their launch descriptor are in conv_common.h.)
+// Also the small host helpers those units share: the dtype fan-out, element / granule / output sizes.  Needs only common.h.
 #pragma once
 #include "common.h"
 
@@ -24,9 +24,13 @@
     }                                                                                  \
   } while (0)
 
+static inline bool dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
 static inline size_t esize(int dtype) { return dtype == DGTTA_F32 ? 4 : 2; }      // bytes per stored element
 
-static inline int out_dim(int i, int s) { return (i + 2 - 3) / s + 1; }           // 3x3x3 conv, padding 1, stride s
+static inline int conv_granule(int dtype) { return dtype == DGTTA_F32 ? 8 : 16; } // padded channel counts of the MFMA kernels: 32 bytes
+static inline size_t n32(int c) { return (size_t)(c + 31) / 32 * 32; }            // weight images: whole 32-channel N blocks
+
+static inline int out_dim(int i, int s, int k = 3) { return (i + 2 * (k / 2) - k) / s + 1; }   // extent-k conv, padding k / 2, stride s
 
 static inline int gs_blocks(int64_t total, int cap = 16384) {                     // grid of a grid-stride loop, 256 threads
   int64_t b = (total + 255) / 256;
@@ -48,14 +52,20 @@ static inline int reduce_blocks(int64_t V, int B) {
 // MFMA implementations; return DGTTA_ERR_UNSUPPORTED when the shape is not covered.
 int conv3_fwd_mfma(const void *x, int ldx, const void *w_kmajor, int mirror, const float *bias, void *y, int ldy, int B,
                    int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int stride, int dtype,
-                   hipStream_t st, double *stats, RowsGstCtx *gst = nullptr, long long xkh = 0, bool dry = false);
+                   hipStream_t st, double *stats, RowsGstCtx *gst, long long xkh, bool dry);
 int conv3_dgrad_s2_mfma(const void *dy, int lddy, const void *w_kmajor, void *dx, int lddx, int B, int Cin, int Cout,
                         int CinP, int CoutP, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st);
 int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo);
 size_t conv_image_bytes(int CinP, int CoutP, int dtype);
 size_t conv_imgB_offset_bytes(int CinP, int CoutP, int dtype);
-int conv_pack_images(const float *w_t, void *img, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st);
+// torch [Cout][Cin][ntaps] fp32 -> image-ordered [imgF | imgB] (ntaps = 27, or kd * 9 for the anisotropic kernels)
+int conv_pack_images(const float *w_t, void *img, int ntaps, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st);
 size_t convT_packed_bytes(int CinP, int CoutP, int dtype);
+// workspace region of a transposed conv's packed weights (channel counts padded to the granule)
+static inline size_t convT_pack_region(int Cin, int Cout, int dtype) {
+  const int g = conv_granule(dtype);
+  return align_up(convT_packed_bytes((Cin + g - 1) / g * g, (Cout + g - 1) / g * g, dtype), 256);
+}
 int convT_fwd_mfma(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws, int B, int Cin,
                    int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st);
 int convT_dgrad_mfma(const void *dout, int lddo, const float *w_t, void *dx, int lddx, void *ws, int B, int Cin, int Cout,
@@ -72,7 +82,7 @@ int convT_gemm_run(int mode, const void *in, int ldin, const float *w_t, const f
 // ---------------------------------------------------------------------------------------------------- conv_wgrad.hip
 // weight gradients on the matrix cores (the View-level launchers of these units are in conv_wgrad_common.h)
 int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                     int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st, long long xkh = 0);
+                     int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st, long long xkh);
 size_t conv3_wgrad_mfma_ws_bytes(int B, int Cin, int Cout, int D, int H, int W);
 size_t conv3_wgrad_split_extra_bytes(int B, int Cin, int Cout, int D, int H, int W, int stride);
 bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int dtype);

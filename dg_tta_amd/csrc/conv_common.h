@@ -1,7 +1,8 @@
 // Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
 // convt_gemm.hip, conv_aniso.hip, conv_wgrad_ring.hip and, through conv_wgrad_common.h, the other weight-gradient units):
-// operand descriptors and views, the launchers that take them, tile geometry and the weight image index.  Pointer-level
-// functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h; the device
+// operand descriptors and views, the launch descriptor of the forward / data-gradient dispatch chains (ConvLaunch) and the
+// launchers that take it, the class tables (single_class, dgrad_parity_classes), tile geometry and the weight image index.
+// Pointer-level functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h; the device
 // primitives that are not about convolutions (vector types, MFMA wrappers, LDS-DMA) live in gfx950.h.
 #pragma once
 #include "conv_api.h"
@@ -34,25 +35,42 @@ struct ConvClasses {
   long long segoff[8];
 };
 
+// One forward / data-gradient launch as the dispatch chain hands it down: operands and their views, channel counts (Cin / CinP
+// are the GEMM's K, Cout / CoutP its N), the InstanceNorm partial sums to leave (or null), the tap count of the weight image
+// and the stream.  The three riders concern the ring / row-reuse launchers only:
+//   gst: InstanceNorm-backward context of dgtta_conv3d_k3_dgrad_gstats;
+//   xkh != 0: x holds its two 32-channel K halves as dense planes xkh elements apart - only the ring kernel reads that layout;
+//   dry: no launch, DGTTA_OK iff the ring kernel would take this call (dgtta_conv3d_k3_blocked_supported).
+struct ConvLaunch {
+  const void *x;
+  View xv;
+  const void *w;
+  const float *bias;
+  void *y;
+  View yv;
+  int B, Cin, Cout, CinP, CoutP;
+  double *stats;
+  int ntaps_src;
+  hipStream_t st;
+  RowsGstCtx *gst = nullptr;
+  long long xkh = 0;
+  bool dry = false;
+};
+
 }  // namespace dgconv
 using namespace dgconv;
 
 // Launchers of the specialised kernels that the dispatchers of conv_mfma.hip / conv_wgrad.hip try first; the conv ones return
 // DGTTA_ERR_UNSUPPORTED for a launch they do not take, conv3_wgrad_ring_launch its slab count (0: nothing launched).
 // conv_rows.hip: row-reuse kernel
-int conv3_rows_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, int is_f16, hipStream_t st,
-                      RowsGstCtx *gst);
+int conv3_rows_launch(const ConvLaunch &L, const Taps &taps, int is_f16);
 // conv_ring.hip: D-ring kernel
-int conv3_ring_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int64_t stats_cap_slots, int ntaps_src,
-                      int is_f16, hipStream_t st, RowsGstCtx *gst, long long xkh = 0, bool dry = false);
-// conv_s2.hip: register-operand kernel of the two large stride-2 encoder transitions
-int conv3_s2_regs(const void *x, const View &xv, const void *wimg, const float *bias, void *y, const View &yv, int B, int Cin,
-                  int Cout, int CinP, int CoutP, double *stats, int64_t cap_slots, int dtype, hipStream_t st);
-// conv_wgrad_ring.hip: ring sweep of the weight gradient
+int conv3_ring_launch(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slots, int is_f16);
+// conv_s2.hip: register-operand kernel of the two large stride-2 encoder transitions (L.w: the forward weight image)
+int conv3_s2_regs(const ConvLaunch &L, int64_t cap_slots, int dtype);
+// conv_wgrad_ring.hip: ring sweep of the weight gradient (xkh, dry: as in ConvLaunch)
 int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B,
-                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh = 0, bool dry = false);
+                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh, bool dry);
 
 namespace {
 
@@ -135,9 +153,9 @@ View parity_view(int D, int H, int W, int ld, int pd, int ph, int pw, long long 
   return lattice_view(D, H, W, ld, 2, 2, 2, pd, ph, pw, offset);
 }
 
-template <typename T>
-bool operand_ok(const void *p, long long ld_elems, int Cin, int CinP) {
-  constexpr int EPV = Elem<T>::EPV;
+inline int epv_of(int dtype) { return dtype == DGTTA_F32 ? 4 : 8; }      // Elem<T>::EPV of a runtime dtype
+// an operand the MFMA kernels can read: 16-byte aligned rows of whole 16-byte groups (EPV elements), K padded to a k-step
+inline bool operand_ok(int EPV, const void *p, long long ld_elems, int Cin, int CinP) {
   return ld_elems % EPV == 0 && ((uintptr_t)p & 15) == 0 && CinP % (2 * EPV) == 0 &&
          ld_elems >= (Cin + EPV - 1) / EPV * EPV;
 }
@@ -146,6 +164,43 @@ inline Taps identity_taps(int mirror) {
   Taps t;
   for (int i = 0; i < 27; ++i) t.wt[i] = (signed char)(mirror ? 26 - i : i);
   return t;
+}
+
+// one class over the whole operands (offsets 0, plain channels)
+inline ConvClasses single_class(const Taps &taps, int accumulate) {
+  ConvClasses cs{};
+  cs.n = 1;
+  cs.acc[0] = accumulate;
+  cs.taps[0] = taps;
+  return cs;
+}
+
+// Data gradient of a [kd, 3, 3] conv with strides (sd, sh, sw) in {1, 2}^3 as stride-1 gathers of dy: one class per parity p
+// of the strided axes (class index = parities flattened in D, H, W order), writing the sub-lattice s * j + p of dx (*yv: its
+// view - with even strided extents one shape serves all classes).  Per axis the virtual tap v (0..k-1) reads dy[j + v - k/2]
+// and carries weight tap t = p + k/2 - s * (v - k/2) where 0 <= t < k.
+inline ConvClasses dgrad_parity_classes(int kd, int sd, int sh, int sw, int Di, int Hi, int Wi, int lddx, int accumulate, View *yv) {
+  ConvClasses cs{};
+  cs.n = sd * sh * sw;
+  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+  for (int c = 0; c < cs.n; ++c) {
+    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
+    *yv = lattice_view(Di, Hi, Wi, lddx, sd, sh, sw, par[0], par[1], par[2], &cs.yoff[c]);
+    cs.acc[c] = accumulate;
+    for (int t = 0; t < 27; ++t) cs.taps[c].wt[t] = -1;
+    for (int v = 0; v < kd * 9; ++v) {
+      const int vv[3] = {v / 9, (v / 3) % 3, v % 3};
+      int real[3];
+      bool ok = true;
+      for (int a = 0; a < 3; ++a) {
+        const int pad = ks[a] / 2;
+        real[a] = par[a] + pad - ss[a] * (vv[a] - pad);
+        ok = ok && real[a] >= 0 && real[a] < ks[a];
+      }
+      if (ok) cs.taps[c].wt[v] = (signed char)(real[0] * 9 + real[1] * 3 + real[2]);
+    }
+  }
+  return cs;
 }
 
 // index of element (n, k, tap) in the LDS-image-ordered weight array [N/32][K/(2*EPV)][ntaps][2][32][EPV]

@@ -35,8 +35,8 @@ extern "C" int dgtta_conv3d_pack_weights(const float *w_t, void *wpack, int Cin,
   DG_REQUIRE(Cin > 0 && Cout > 0 && CinP >= Cin && CoutP >= Cout, DGTTA_ERR_BADARG, "pack_weights: bad channel counts");
   const int rc = conv3_pack_weights_ref(w_t, wf, wb, Cin, Cout, CinP, CoutP, dtype, (hipStream_t)stream);
   if (rc != DGTTA_OK) return rc;
-  if (CinP % (dtype == DGTTA_F32 ? 8 : 16) == 0 && CoutP % (dtype == DGTTA_F32 ? 8 : 16) == 0)
-    return conv_pack_images(w_t, const_cast<void *>(img_of(wpack, CinP, CoutP, dtype)), Cin, Cout, CinP, CoutP, dtype,
+  if (CinP % conv_granule(dtype) == 0 && CoutP % conv_granule(dtype) == 0)
+    return conv_pack_images(w_t, const_cast<void *>(img_of(wpack, CinP, CoutP, dtype)), 27, Cin, Cout, CinP, CoutP, dtype,
                             (hipStream_t)stream);
   return DGTTA_OK;
 }
@@ -62,7 +62,7 @@ static int k3_fwd(const void *x, int ldx, long long x_block_stride, const void *
   hipStream_t st = (hipStream_t)stream;
   if (impl != 1) {
     int rc = conv3_fwd_mfma(x, ldx, img_of(wpack, CinP, CoutP, dtype), 0, bias, y, ldy, B, Cin, Cout, CinP, CoutP, Di, Hi,
-                            Wi, stride, dtype, st, (double *)stats, nullptr, x_block_stride);
+                            Wi, stride, dtype, st, (double *)stats, nullptr, x_block_stride, false);
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
     DG_REQUIRE(x_block_stride == 0, DGTTA_ERR_UNSUPPORTED,
                "conv3d_k3_fwd_blocked: only the D-ring kernel reads x as 32-channel planes (ask dgtta_conv3d_k3_blocked_supported)");
@@ -118,7 +118,7 @@ static int k3_dgrad(const void *dy, int lddy, const void *wpack, void *dx, int l
     // stride-1 data gradient == forward conv of dy with the mirrored, transposed weights (wb)
     // (imgB: N = ci, K = co; taps mirrored)
     int rc = conv3_fwd_mfma(dy, lddy, imgB_of(wpack, CinP, CoutP, dtype), 1, nullptr, dx, lddx, B, Cout, Cin, CoutP, CinP, Di,
-                            Hi, Wi, 1, dtype, st, nullptr, gst);
+                            Hi, Wi, 1, dtype, st, nullptr, gst, 0, false);
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
     DG_REQUIRE(impl == 0, DGTTA_ERR_UNSUPPORTED, "conv3d_k3_dgrad: shape not covered by the MFMA kernel");
   }
@@ -223,11 +223,6 @@ extern "C" int dgtta_conv3d_k3_wgrad_blocked(const void *x, long long x_block_st
                                              int accumulate, int dtype, void *stream) {
   DG_REQUIRE(x_block_stride > 0 && x_block_stride % 8 == 0, DGTTA_ERR_BADARG, "conv3d_k3_wgrad_blocked: block stride must be a positive multiple of 8 elements");
   return k3_wgrad(x, 32, x_block_stride, dy, lddy, dw_t, db, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, 1, accumulate, dtype, 0, stream);
-}
-
-static size_t convT_pack_region(int Cin, int Cout, int dtype) {
-  const int g = (dtype == DGTTA_F32) ? 8 : 16;
-  return align_up(convT_packed_bytes((Cin + g - 1) / g * g, (Cout + g - 1) / g * g, dtype), 256);
 }
 
 extern "C" size_t dgtta_convT3d_fwd_ws_bytes(int Cin, int Cout, int dtype) {

@@ -26,7 +26,7 @@ namespace {
 // need dy at 8 shifts (0/+1 per axis) only; a wave keeps 8 accumulators (one per class), reads each shifted A fragment
 // once and feeds the (class, tap) pairs that use it (27 in total = every real tap once).  Class c is written to
 // y + cs.yoff[c] with the strides of yv (the parity view).  Replaces 8 class launches that each re-staged the dy tile.
-template <typename T, int MBW, int MBH, int MBD, int S, int NB, int KSPC, int ABL = 0, int NW = 4, bool AC = false>   // ABL: diagnostic ablation; NW waves
+template <typename T, int MBW, int MBH, int MBD, int S, int NB, int KSPC, int NW = 4, bool AC = false>   // NW waves
 __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict__ x, View xv, const T *__restrict__ w,
                                                          ConvClasses cs, const float *__restrict__ bias,
                                                          T *__restrict__ y, View yv, int Cin, int Cout, int CinP,
@@ -129,10 +129,6 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
       const bool ok = idx < NV * NG && (S != 2 || wx < G::IW) && (unsigned)gd < (unsigned)Di &&
                       (unsigned)gh < (unsigned)Hi && (unsigned)gw < (unsigned)Wi && c < cin_lim;
       const T *p = ok ? xbp + soff + gd * xv.sd + gh * xv.sh + gw * xv.sw + c : x;
-      if (ABL == 1) {
-        ra[i] = make_uint4(idx, 0, 0, 0);
-        continue;
-      }
       const uint4 val = *reinterpret_cast<const uint4 *>(p);
       ra[i] = ok ? val : make_uint4(0, 0, 0, 0);
     }
@@ -141,10 +137,6 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
     for (int i = 0; i < NBL; ++i) {
       const bool ok = wslot[i] >= 0;
       const T *p = w + (int64_t)(ok ? wslot[i] + kterm : 0) * EPV;
-      if (ABL == 1 || ABL == 4) {
-        rb[i] = make_uint4(tid + i * NT, 0, 0, 0);
-        continue;
-      }
       const uint4 val = *reinterpret_cast<const uint4 *>(p);
       rb[i] = ok ? val : make_uint4(0, 0, 0, 0);
     }
@@ -153,10 +145,6 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int idx = tid + i * NT;
-      if (ABL == 2) {
-        asm volatile("" ::"v"(ra[i].x));
-        continue;
-      }
       if (idx < NV * NG) sA[(idx % NG) * NV + idx / NG] = ra[i];
     }
 #pragma unroll
@@ -214,15 +202,13 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
         const int g = 2 * ks + h;
         uint4 bf[NB];
 #pragma unroll
-        for (int j = 0; j < NB; ++j) bf[j] = (ABL == 7) ? make_uint4(tap, j, tid, 1) : sB[(tb * NG + g) * NC + j * 32 + r];
+        // (through a temporary: assigned directly, the fp32 (32,4,4) stride-1 build addresses one of these reads differently)
+        for (int j = 0; j < NB; ++j) bf[j] = uint4(sB[(tb * NG + g) * NC + j * 32 + r]);
 #pragma unroll
         for (int i = 0; i < MPW; ++i) {
-          const uint4 af = (ABL == 6 || ABL == 7) ? make_uint4(tap, i, tid, 0) : sA[g * NV + a_off[i] + tap_off];
+          const uint4 af = sA[g * NV + a_off[i] + tap_off];
 #pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            if (ABL == 3) acc[i][j][0] += __uint_as_float(af.x ^ bf[j].x);
-            else mfma_step<T>(af, bf[j], acc[i][j]);
-          }
+          for (int j = 0; j < NB; ++j) mfma_step<T>(af, bf[j], acc[i][j]);
         }
       }
     }
@@ -343,11 +329,7 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
           T *o = y + b * yv.sb + od * yv.sd + oh * yv.sh + ow * yv.sw + co;
           float v = acc[i][j][q] + bv;
           if (accumulate) v += ld_f<T>(o);
-          if (ABL == 5) {
-            if (v == 1234.5f) st_f<T>(o, v);
-          } else {
-            st_f<T>(o, v);
-          }
+          st_f<T>(o, v);
           st1[j] += v;
           st2[j] += v * v;
         }
@@ -382,155 +364,125 @@ __global__ __launch_bounds__(NW * 64) void conv3_mfma_kernel(const T *__restrict
   }
 }
 
-// all-classes stride-2 data gradient (AC = true): tiles over the dy lattice, grid.z = 1
-template <typename T, int MBW, int MBH, int MBD>
-int launch_conv_allcls(const void *x, const View &xv, const void *w, const ConvClasses &cs, void *y, const View &yv, int B,
-                       int Cin, int Cout, int CinP, int CoutP, hipStream_t st) {
-  typedef ConvCfg<T, MBW, MBH, MBD, 1, 1, 1> Cfg;
-  typedef typename Cfg::G G;
-  auto kern = conv3_mfma_kernel<T, MBW, MBH, MBD, 1, 1, 1, 0, 8, true>;
-  static DynLdsOnce lds_once;
-  DG_REQUIRE(ensure_dyn_lds(lds_once, reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess,
-             DGTTA_ERR_LAUNCH, "conv3_mfma: cannot raise the dynamic LDS limit to %zu", (size_t)Cfg::LDS_BYTES);
-  const int tW = cdiv(yv.W, G::TW), tH = cdiv(yv.H, G::TH), tD = cdiv(yv.D, G::TD);
-  const int64_t tiles = (int64_t)tW * tH * tD * B;
-  DG_REQUIRE(tiles < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "conv3_mfma: too many tiles");
-  dim3 grid((unsigned)tiles, (unsigned)cdiv(CoutP, Cfg::NC), 1u);
-  hipLaunchKernelGGL(kern, grid, dim3(8 * 64), Cfg::LDS_BYTES, st, (const T *)x, xv, (const T *)w, cs, (const float *)nullptr,
-                     (T *)y, yv, Cin, Cout, CinP, CoutP, tW, tH, tD, (double *)nullptr, 27);
-  DG_CHECK_LAUNCH("conv3_mfma_kernel<all classes>");
-  return DGTTA_OK;
-}
-
-template <typename T, int MBW, int MBH, int MBD, int S, int NB, int KSPC, int NW = 4>
-int launch_conv(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y,
-                const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src,
-                hipStream_t st) {
+// AC: the all-classes stride-2 data gradient - tiles over the dy lattice, grid.z = 1 (its launch has no bias or statistics)
+template <typename T, int MBW, int MBH, int MBD, int S, int NB, int KSPC, int NW = 4, bool AC = false>
+int launch_conv(const ConvLaunch &L, const ConvClasses &cs) {
   typedef ConvCfg<T, MBW, MBH, MBD, S, NB, KSPC> Cfg;
   typedef typename Cfg::G G;
-  auto kern = conv3_mfma_kernel<T, MBW, MBH, MBD, S, NB, KSPC, 0, NW>;
+  auto kern = conv3_mfma_kernel<T, MBW, MBH, MBD, S, NB, KSPC, NW, AC>;
   static DynLdsOnce lds_once;
   DG_REQUIRE(ensure_dyn_lds(lds_once, reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess,
              DGTTA_ERR_LAUNCH, "conv3_mfma: cannot raise the dynamic LDS limit to %zu", (size_t)Cfg::LDS_BYTES);
-  const int tW = cdiv(yv.W, G::TW), tH = cdiv(yv.H, G::TH), tD = cdiv(yv.D, G::TD);
-  const int64_t tiles = (int64_t)tW * tH * tD * B;
+  const int tW = cdiv(L.yv.W, G::TW), tH = cdiv(L.yv.H, G::TH), tD = cdiv(L.yv.D, G::TD);
+  const int64_t tiles = (int64_t)tW * tH * tD * L.B;
   DG_REQUIRE(tiles < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "conv3_mfma: too many tiles");
-  dim3 grid((unsigned)tiles, (unsigned)cdiv(CoutP, Cfg::NC), (unsigned)cs.n);
-  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, st, (const T *)x, xv, (const T *)w, cs, bias, (T *)y, yv,
-                     Cin, Cout, CinP, CoutP, tW, tH, tD, stats, ntaps_src);
-  DG_CHECK_LAUNCH("conv3_mfma_kernel");
+  dim3 grid((unsigned)tiles, (unsigned)cdiv(L.CoutP, Cfg::NC), AC ? 1u : (unsigned)cs.n);
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), Cfg::LDS_BYTES, L.st, (const T *)L.x, L.xv, (const T *)L.w, cs, L.bias, (T *)L.y,
+                     L.yv, L.Cin, L.Cout, L.CinP, L.CoutP, tW, tH, tD, L.stats, L.ntaps_src);
+  DG_CHECK_LAUNCH(AC ? "conv3_mfma_kernel<all classes>" : "conv3_mfma_kernel");
   return DGTTA_OK;
 }
 
-// picks the tile shape from the (virtual) output extent
+// picks the kernel and the tile shape from the (virtual) output extent; stride 0: pointwise (centre tap only, no halo)
 template <typename T>
-int dispatch_conv_classes(const void *x, const View &xv, const void *w, const ConvClasses &cs, const float *bias, void *y,
-                          const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, int stride, hipStream_t st,
-                          double *stats = nullptr, int ntaps_src = 27, RowsGstCtx *gst = nullptr, long long xkh = 0, bool dry = false) {
-  // xkh != 0: x holds its two 32-channel K halves as dense planes xkh elements apart - only the ring kernel reads that layout;
-  // dry: no launch, DGTTA_OK iff the ring kernel would take this call (dgtta_conv3d_k3_blocked_supported)
-#define ARGS x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st
-  const long long vox = (long long)yv.D * yv.H * yv.W * B;
-  if ((xkh || dry) && stride != 1) return DGTTA_ERR_UNSUPPORTED;
-  if (stride == 0) {      // pointwise (centre tap only, no halo)
-    if (yv.W >= 32) return launch_conv<T, 32, 4, 4, 0, 1, 1, 8>(ARGS);
-    if (yv.W >= 16) return launch_conv<T, 16, 4, 4, 0, 1, 1, 8>(ARGS);
-    if (vox <= 4096) return launch_conv<T, 8, 2, 2, 0, 1, 1>(ARGS);
-    return launch_conv<T, 8, 2, 8, 0, 1, 1, 8>(ARGS);
+int dispatch_conv_classes(const ConvLaunch &L, const ConvClasses &cs, int stride) {
+  const View &yv = L.yv;
+  const bool ring_only = L.xkh || L.dry;      // a layout / a question that only the ring kernel knows
+  const long long vox = (long long)yv.D * yv.H * yv.W * L.B;
+  if (ring_only && stride != 1) return DGTTA_ERR_UNSUPPORTED;
+  if (stride == 0) {
+    if (yv.W >= 32) return launch_conv<T, 32, 4, 4, 0, 1, 1, 8>(L, cs);
+    if (yv.W >= 16) return launch_conv<T, 16, 4, 4, 0, 1, 1, 8>(L, cs);
+    if (vox <= 4096) return launch_conv<T, 8, 2, 2, 0, 1, 1>(L, cs);
+    return launch_conv<T, 8, 2, 8, 0, 1, 1, 8>(L, cs);
   }
   if (stride == 1 && sizeof(T) == 2 && yv.W >= 32 && cs.n == 1 && cs.acc[0] == 0 && cs.kseg == 0 && cs.xoff[0] == 0 &&
       cs.yoff[0] == 0) {
     const int rows = dgtta_switches().conv_rows;   // DGTTA_CONV_ROWS (tests): '0' forces the generic kernel, '1' this one
+    const int is_f16 = (int)std::is_same<T, f16_t>::value;
     bool all_taps = true;
     for (int t = 0; t < 27; ++t) all_taps = all_taps && cs.taps[0].wt[t] >= 0;
-    const bool vec_out = Cout % 8 == 0 && ((uintptr_t)y & 15) == 0 && yv.sw % 8 == 0 && yv.sh % 8 == 0 &&
+    const bool vec_out = L.Cout % 8 == 0 && ((uintptr_t)L.y & 15) == 0 && yv.sw % 8 == 0 && yv.sh % 8 == 0 &&
                          yv.sd % 8 == 0 && yv.sb % 8 == 0;
     // enough (tile, channel block) jobs to fill the chip with one persistent workgroup per CU; below that the generic kernel wins
-    const long long njobs = (long long)cdiv(yv.W, 32) * cdiv(yv.H, 8) * cdiv(yv.D, 4) * cdiv(CoutP, 32) * B;
+    const long long njobs = (long long)cdiv(yv.W, 32) * cdiv(yv.H, 8) * cdiv(yv.D, 4) * cdiv(L.CoutP, 32) * L.B;
     // 32 or 64 input channels: the D-ring kernel (conv_ring.hip; DGTTA_CONV_RING=0: its predecessor below, =3: only 32 channels)
-    if (all_taps && vec_out && ((Cin == 32 && CinP == 32) || (Cin == 64 && CinP == 64)) && (njobs >= 512 || dgtta_switches().conv_ring == '1') &&
-        dgtta_switches().conv_ring != '0' && rows != '1') {
-      const int rc = conv3_ring_launch(x, xv, w, cs.taps[0], bias, y, yv, B, Cin, Cout, CinP, CoutP, stats,
-                                       conv3_mfma_max_tiles(yv.D, yv.H, yv.W), ntaps_src, (int)std::is_same<T, f16_t>::value, st, gst,
-                                       xkh, dry);
-      if (rc != DGTTA_ERR_UNSUPPORTED || xkh || dry) return rc;
+    if (all_taps && vec_out && ((L.Cin == 32 && L.CinP == 32) || (L.Cin == 64 && L.CinP == 64)) &&
+        (njobs >= 512 || dgtta_switches().conv_ring == '1') && dgtta_switches().conv_ring != '0' && rows != '1') {
+      const int rc = conv3_ring_launch(L, cs.taps[0], conv3_mfma_max_tiles(yv.D, yv.H, yv.W), is_f16);
+      if (rc != DGTTA_ERR_UNSUPPORTED || ring_only) return rc;
     }
-    if (xkh || dry) return DGTTA_ERR_UNSUPPORTED;
-    if (all_taps && vec_out && (njobs >= 256 || rows == '1') && rows != '0')
-      return conv3_rows_launch(x, xv, w, cs.taps[0], bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src,
-                               (int)std::is_same<T, f16_t>::value, st, gst);
+    if (ring_only) return DGTTA_ERR_UNSUPPORTED;
+    if (all_taps && vec_out && (njobs >= 256 || rows == '1') && rows != '0') return conv3_rows_launch(L, cs.taps[0], is_f16);
   }
-  if (xkh || dry) return DGTTA_ERR_UNSUPPORTED;
+  if (ring_only) return DGTTA_ERR_UNSUPPORTED;
   if (stride == 1) {
     // 8 waves per workgroup (2 M-blocks each): 16 waves per CU hide the LDS / barrier latency (+27 % over 4 waves; the
     // other tile shapes tried in round 1 - 2 k-steps per chunk, 64 output channels, 256-voxel tiles - were slower)
-    if (yv.W >= 32) return launch_conv<T, 32, 4, 4, 1, 1, 1, 8>(ARGS);
+    if (yv.W >= 32) return launch_conv<T, 32, 4, 4, 1, 1, 1, 8>(L, cs);
     // tiny volumes are latency bound (few workgroups, a long serial K loop): when the channel padding allows it, 2
     // k-steps per chunk halve the barrier / load round trips.  (128-voxel tiles for the 16^3 layers measured faster in
     // isolation but slower inside the network: 23.0 vs 20.9 ms per epoch.)
-    const bool k2 = CinP % (4 * Elem<T>::EPV) == 0;
-    if (yv.W >= 16) return launch_conv<T, 16, 4, 4, 1, 1, 1, 8>(ARGS);
-    if (vox <= 4096 && k2) return launch_conv<T, 8, 2, 2, 1, 1, 2>(ARGS);
-    if (vox <= 4096) return launch_conv<T, 8, 2, 2, 1, 1, 1>(ARGS);     // tiny volumes: more, smaller workgroups
-    return launch_conv<T, 8, 2, 8, 1, 1, 1, 8>(ARGS);
+    const bool k2 = L.CinP % (4 * Elem<T>::EPV) == 0;
+    if (yv.W >= 16) return launch_conv<T, 16, 4, 4, 1, 1, 1, 8>(L, cs);
+    if (vox <= 4096 && k2) return launch_conv<T, 8, 2, 2, 1, 1, 2>(L, cs);
+    if (vox <= 4096) return launch_conv<T, 8, 2, 2, 1, 1, 1>(L, cs);     // tiny volumes: more, smaller workgroups
+    return launch_conv<T, 8, 2, 8, 1, 1, 1, 8>(L, cs);
   }
   if (stride == 2) {
     // 8 waves per workgroup (one M-block each): 231 -> 153 us at 128^3 -> 64^3, 32 -> 64 channels
     if (dgtta_switches().conv_s2 == '4') {      // DGTTA_CONV_S2=4: the former 4-wave tiles
-      if (yv.W >= 16) return launch_conv<T, 16, 2, 4, 2, 1, 1>(ARGS);
-      return launch_conv<T, 8, 2, 4, 2, 1, 1>(ARGS);
+      if (yv.W >= 16) return launch_conv<T, 16, 2, 4, 2, 1, 1>(L, cs);
+      return launch_conv<T, 8, 2, 4, 2, 1, 1>(L, cs);
     }
     // two output-channel blocks per workgroup when there are that many: the input tile is staged once for 64 channels
     // (157 -> 112 us at 128^3 -> 64^3, 32 -> 64; DGTTA_CONV_S2=1: one block per workgroup, the round-1 shape)
-    if (dgtta_switches().conv_s2 != '1' && yv.W >= 32 && CoutP % 64 == 0) return launch_conv<T, 32, 4, 2, 2, 2, 1, 8>(ARGS);
-    if (yv.W >= 32) return launch_conv<T, 32, 4, 2, 2, 1, 1, 8>(ARGS);
-    if (yv.W >= 16) return launch_conv<T, 16, 2, 4, 2, 1, 1, 8>(ARGS);
-    return launch_conv<T, 8, 2, 4, 2, 1, 1, 8>(ARGS);
+    if (dgtta_switches().conv_s2 != '1' && yv.W >= 32 && L.CoutP % 64 == 0) return launch_conv<T, 32, 4, 2, 2, 2, 1, 8>(L, cs);
+    if (yv.W >= 32) return launch_conv<T, 32, 4, 2, 2, 1, 1, 8>(L, cs);
+    if (yv.W >= 16) return launch_conv<T, 16, 2, 4, 2, 1, 1, 8>(L, cs);
+    return launch_conv<T, 8, 2, 4, 2, 1, 1, 8>(L, cs);
   }
-#undef ARGS
   return DGTTA_ERR_UNSUPPORTED;
 }
 
 template <typename T>
-int dispatch_conv(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y,
-                  const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, int stride, int accumulate,
-                  hipStream_t st, double *stats = nullptr, int ntaps_src = 27, RowsGstCtx *gst = nullptr, long long xkh = 0,
-                  bool dry = false) {
-  ConvClasses cs;
-  cs.n = 1;
-  cs.kseg = 0;
-  cs.acc[0] = accumulate;
-  cs.xoff[0] = cs.yoff[0] = 0;
-  cs.taps[0] = taps;
-  return dispatch_conv_classes<T>(x, xv, w, cs, bias, y, yv, B, Cin, Cout, CinP, CoutP, stride, st, stats, ntaps_src, gst, xkh, dry);
+int dispatch_conv(const ConvLaunch &L, const Taps &taps, int stride, int accumulate) {
+  return dispatch_conv_classes<T>(L, single_class(taps, accumulate), stride);
 }
 
-
-// conv 3x3x3 weight images: imgF (N=co, K=ci) and imgB (N=ci, K=co) with REAL tap indices
+// stride-2 data gradient in one pass over dy with all 8 classes accumulated per wave (L.yv: extent of the dy lattice, strides
+// of the parity view)
 template <typename T>
-__global__ void conv_pack_image_kernel(const float *__restrict__ w, T *__restrict__ imgF, T *__restrict__ imgB, int Cin,
-                                       int Cout, int CinP, int CoutP) {
+int dgrad_s2_allcls(const ConvLaunch &L, const ConvClasses &cs) {
+  if (L.yv.W >= 32) return launch_conv<T, 32, 4, 2, 1, 1, 1, 8, true>(L, cs);
+  if (L.yv.W >= 16) return launch_conv<T, 16, 2, 4, 1, 1, 1, 8, true>(L, cs);
+  return launch_conv<T, 8, 2, 4, 1, 1, 1, 8, true>(L, cs);
+}
+
+// conv weight images: torch [Cout][Cin][ntaps] fp32 -> imgF (N = co, K = ci) and imgB (N = ci, K = co), both with the REAL tap
+// index (27 taps: kd * 9 + kh * 3 + kw)
+template <typename T>
+__global__ void conva_pack_kernel(const float *__restrict__ w, T *__restrict__ imgF, T *__restrict__ imgB, int Cin, int Cout,
+                                  int CinP, int CoutP, int ntaps) {
   constexpr int EPV = Elem<T>::EPV;
   const int CoutN = (CoutP + 31) / 32 * 32, CinN = (CinP + 31) / 32 * 32;
-  const int64_t nf = (int64_t)27 * CinP * CoutN, nb = (int64_t)27 * CoutP * CinN;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb);
-       i += (int64_t)gridDim.x * blockDim.x) {
+  const int64_t nf = (int64_t)ntaps * CinP * CoutN, nb = (int64_t)ntaps * CoutP * CinN;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (nf > nb ? nf : nb); i += (int64_t)gridDim.x * blockDim.x) {
     if (i < nf) {
-      int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), tap = (int)(i / ((int64_t)CinP * CoutN));
-      st_f<T>(imgF + conv_weight_image_index(co, ci, tap, CinP, 27, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * 27 + tap] : 0.f);
+      const int ci = (int)(i % CinP), co = (int)((i / CinP) % CoutN), tap = (int)(i / ((int64_t)CinP * CoutN));
+      st_f<T>(imgF + conv_weight_image_index(co, ci, tap, CinP, ntaps, EPV),
+              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
     }
     if (i < nb) {
-      int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), tap = (int)(i / ((int64_t)CoutP * CinN));
-      st_f<T>(imgB + conv_weight_image_index(ci, co, tap, CoutP, 27, EPV),
-              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * 27 + tap] : 0.f);
+      const int co = (int)(i % CoutP), ci = (int)((i / CoutP) % CinN), tap = (int)(i / ((int64_t)CoutP * CinN));
+      st_f<T>(imgB + conv_weight_image_index(ci, co, tap, CoutP, ntaps, EPV),
+              (ci < Cin && co < Cout) ? w[((int64_t)co * Cin + ci) * ntaps + tap] : 0.f);
     }
   }
 }
 
 }  // namespace
 
-// w_kmajor: [27][CoutP][CinP] with the K (input-channel) index contiguous; mirror: use tap 26-t.
 // upper bound of output tiles per batch sample over all tile shapes the dispatcher may pick
 int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo) {
   const int shapes[6][3] = {{4, 4, 32}, {4, 8, 16}, {2, 8, 8}, {8, 8, 8}, {4, 4, 16}, {4, 8, 8}};
@@ -542,92 +494,38 @@ int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo) {
   return best;
 }
 
+// w_kmajor: the forward or the backward weight image (27 real taps); mirror: virtual tap t uses weight tap 26 - t
 int conv3_fwd_mfma(const void *x, int ldx, const void *w_kmajor, int mirror, const float *bias, void *y, int ldy, int B,
                    int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int stride, int dtype,
                    hipStream_t st, double *stats, RowsGstCtx *gst, long long xkh, bool dry) {
   if ((xkh || dry) && (stride != 1 || dtype == DGTTA_F32)) return DGTTA_ERR_UNSUPPORTED;
   const int Do = (Di - 1) / stride + 1, Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-  const View xv = dense_view(B, Di, Hi, Wi, ldx), yv = dense_view(B, Do, Ho, Wo, ldy);
-  const Taps taps = identity_taps(mirror);
+  const ConvLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), w_kmajor, bias, y, dense_view(B, Do, Ho, Wo, ldy), B, Cin, Cout, CinP, CoutP,
+                     stats, 27, st, gst, xkh, dry};
   if (stride == 2 && !mirror && dtype != DGTTA_F32 && dgtta_switches().conv_s2 != '1' && dgtta_switches().conv_s2 != '4') {
     // the two large encoder transitions: register-operand kernel (conv_s2.hip)
-    const int rc = conv3_s2_regs(x, xv, w_kmajor, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats,
-                                 conv3_mfma_max_tiles(Do, Ho, Wo), dtype, st);
+    const int rc = conv3_s2_regs(L, conv3_mfma_max_tiles(Do, Ho, Wo), dtype);
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
   }
-  if (dtype == DGTTA_F32) {
-    if (!operand_ok<float>(x, ldx, Cin, CinP)) return DGTTA_ERR_UNSUPPORTED;
-    return dispatch_conv<float>(x, xv, w_kmajor, taps, bias, y, yv, B, Cin, Cout, CinP, CoutP, stride, 0, st, stats, 27, gst);
-  }
-  if (dtype == DGTTA_BF16) {
-    if (!operand_ok<bf16_t>(x, xkh ? 2 * ldx : ldx, Cin, CinP)) return DGTTA_ERR_UNSUPPORTED;
-    return dispatch_conv<bf16_t>(x, xv, w_kmajor, taps, bias, y, yv, B, Cin, Cout, CinP, CoutP, stride, 0, st, stats, 27, gst, xkh, dry);
-  }
-  if (dtype == DGTTA_F16) {
-    if (!operand_ok<f16_t>(x, xkh ? 2 * ldx : ldx, Cin, CinP)) return DGTTA_ERR_UNSUPPORTED;
-    return dispatch_conv<f16_t>(x, xv, w_kmajor, taps, bias, y, yv, B, Cin, Cout, CinP, CoutP, stride, 0, st, stats, 27, gst, xkh, dry);
-  }
-  return DGTTA_ERR_UNSUPPORTED;
+  if (!dtype_ok(dtype) || !operand_ok(epv_of(dtype), x, xkh ? 2 * ldx : ldx, Cin, CinP)) return DGTTA_ERR_UNSUPPORTED;
+  DISPATCH_T(dtype, return dispatch_conv<T>(L, identity_taps(mirror), stride, 0));
 }
 
 // Data gradient of a stride-2 conv: 8 parity classes of the input lattice, each a stride-1 gather of dy with the
-// 1/2/4/8 taps that reach that class.  w_kmajor = blob first half [27][CinP][CoutP] (K = co contiguous), real taps.
-template <typename T>
-static int dgrad_s2(const void *dy, int lddy, const void *w_kmajor, void *dx, int lddx, int B, int Cin, int Cout, int CinP,
-                    int CoutP, int Di, int Hi, int Wi, int accumulate, hipStream_t st) {
-  if (!operand_ok<T>(dy, lddy, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
-  const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-  const View xv = dense_view(B, Do, Ho, Wo, lddy);
-  // even extents: all 8 parity classes have the same shape -> ONE launch, class = blockIdx.z
-  ConvClasses cs;
-  cs.n = 8;
-  cs.kseg = 0;
-  View yv;
-  for (int p = 0; p < 8; ++p) {
-    const int pd = p >> 2, ph = (p >> 1) & 1, pw = p & 1;
-    long long off;
-    yv = parity_view(Di, Hi, Wi, lddx, pd, ph, pw, &off);
-    yv.sb = (long long)Di * Hi * Wi * lddx;
-    cs.xoff[p] = 0;
-    cs.yoff[p] = off;
-    cs.acc[p] = accumulate;
-    for (int t = 0; t < 27; ++t) {
-      const int k[3] = {t / 9, (t / 3) % 3, t % 3}, par[3] = {pd, ph, pw};
-      int real[3];
-      bool ok = true;
-      for (int a = 0; a < 3; ++a) {
-        if (par[a] == 0) {
-          ok = ok && (k[a] == 1);
-          real[a] = 1;
-        } else {
-          ok = ok && (k[a] >= 1);
-          real[a] = (k[a] == 1) ? 2 : 0;
-        }
-      }
-      cs.taps[p].wt[t] = ok ? (signed char)(real[0] * 9 + real[1] * 3 + real[2]) : (signed char)-1;
-    }
-  }
-  {
-    // one pass over dy with all 8 classes accumulated per wave (yv: extent of the dy lattice, strides of the parity view)
-    const int ac = dgtta_switches().dgrad_s2_allcls;      // DGTTA_DGRAD_S2_ALLCLS (tests): '0' = the 8-class launch
-    if (ac != '0' && CinP % 8 == 0) {
-      if (yv.W >= 32) return launch_conv_allcls<T, 32, 4, 2>(dy, xv, w_kmajor, cs, dx, yv, B, Cout, Cin, CoutP, CinP, st);
-      if (yv.W >= 16) return launch_conv_allcls<T, 16, 2, 4>(dy, xv, w_kmajor, cs, dx, yv, B, Cout, Cin, CoutP, CinP, st);
-      return launch_conv_allcls<T, 8, 2, 4>(dy, xv, w_kmajor, cs, dx, yv, B, Cout, Cin, CoutP, CinP, st);
-    }
-  }
-  return dispatch_conv_classes<T>(dy, xv, w_kmajor, cs, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, 1, st);
-}
-
+// 1/2/4/8 taps that reach that class (even extents: one shape for all classes -> ONE launch, class = blockIdx.z).
+// w_kmajor: the backward weight image (N = ci, K = co), real taps.
 int conv3_dgrad_s2_mfma(const void *dy, int lddy, const void *w_kmajor, void *dx, int lddx, int B, int Cin, int Cout,
                         int CinP, int CoutP, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st) {
-  if (dtype == DGTTA_F32) return dgrad_s2<float>(dy, lddy, w_kmajor, dx, lddx, B, Cin, Cout, CinP, CoutP, Di, Hi, Wi, accumulate, st);
-  if (dtype == DGTTA_BF16) return dgrad_s2<bf16_t>(dy, lddy, w_kmajor, dx, lddx, B, Cin, Cout, CinP, CoutP, Di, Hi, Wi, accumulate, st);
-  if (dtype == DGTTA_F16) return dgrad_s2<f16_t>(dy, lddy, w_kmajor, dx, lddx, B, Cin, Cout, CinP, CoutP, Di, Hi, Wi, accumulate, st);
-  return DGTTA_ERR_UNSUPPORTED;
+  if (!dtype_ok(dtype) || !operand_ok(epv_of(dtype), dy, lddy, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
+  const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
+  View yv;
+  const ConvClasses cs = dgrad_parity_classes(3, 2, 2, 2, Di, Hi, Wi, lddx, accumulate, &yv);
+  const ConvLaunch L{dy, dense_view(B, Do, Ho, Wo, lddy), w_kmajor, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, 27, st};
+  // DGTTA_DGRAD_S2_ALLCLS (tests): '0' = the 8-class launch
+  const bool allcls = dgtta_switches().dgrad_s2_allcls != '0' && CinP % 8 == 0;
+  DISPATCH_T(dtype, return allcls ? dgrad_s2_allcls<T>(L, cs) : dispatch_conv_classes<T>(L, cs, 1));
 }
 
-static size_t n32(int c) { return (size_t)(c + 31) / 32 * 32; }
 size_t convT_packed_bytes(int CinP, int CoutP, int dtype) {
   return (size_t)8 * (CinP * n32(CoutP) + CoutP * n32(CinP)) * esize(dtype);
 }
@@ -638,20 +536,14 @@ size_t conv_image_bytes(int CinP, int CoutP, int dtype) {
 size_t conv_imgB_offset_bytes(int CinP, int CoutP, int dtype) {
   return (size_t)27 * CinP * n32(CoutP) * esize(dtype);
 }
-int conv_pack_images(const float *w_t, void *img, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st) {
-  const int64_t n = (int64_t)27 * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
+int conv_pack_images(const float *w_t, void *img, int ntaps, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st) {
+  const int cmax = CinP > CoutP ? CinP : CoutP;
+  const int64_t n = (int64_t)ntaps * cmax * n32(cmax);
   const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-  void *imgB = (char *)img + conv_imgB_offset_bytes(CinP, CoutP, dtype);
-  if (dtype == DGTTA_F32)
-    hipLaunchKernelGGL((conv_pack_image_kernel<float>), dim3(blocks), dim3(256), 0, st, w_t, (float *)img, (float *)imgB, Cin,
-                       Cout, CinP, CoutP);
-  else if (dtype == DGTTA_BF16)
-    hipLaunchKernelGGL((conv_pack_image_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, w_t, (bf16_t *)img, (bf16_t *)imgB,
-                       Cin, Cout, CinP, CoutP);
-  else
-    hipLaunchKernelGGL((conv_pack_image_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, w_t, (f16_t *)img, (f16_t *)imgB, Cin,
-                       Cout, CinP, CoutP);
-  DG_CHECK_LAUNCH("conv_pack_image_kernel");
+  void *imgB = (char *)img + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((conva_pack_kernel<T>), dim3(blocks), dim3(256), 0, st, w_t, (T *)img, (T *)imgB, Cin, Cout,
+                                       CinP, CoutP, ntaps));
+  DG_CHECK_LAUNCH("conva_pack_kernel");
   return DGTTA_OK;
 }
 
@@ -686,86 +578,58 @@ int convTa_run_t(int mode, const void *in, int ldin, const float *w_t, const flo
   constexpr int EPV = Elem<T>::EPV;
   const int CinP = (Cin + 2 * EPV - 1) / (2 * EPV) * (2 * EPV), CoutP = (Cout + 2 * EPV - 1) / (2 * EPV) * (2 * EPV);
   const int no = sd * sh * sw;
-  if (mode == 0 ? !operand_ok<T>(in, ldin, Cin, CinP) : !operand_ok<T>(in, ldin, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
+  if (mode == 0 ? !operand_ok(EPV, in, ldin, Cin, CinP) : !operand_ok(EPV, in, ldin, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
   T *wf = (T *)ws, *wb = wf + (size_t)no * CinP * n32(CoutP);
   const int64_t n = (int64_t)no * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
   hipLaunchKernelGGL((convTa_pack_kernel<T>), dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, st,
                      w_t, wf, wb, Cin, Cout, CinP, CoutP, no);
   DG_CHECK_LAUNCH("convTa_pack_kernel");
   const int Do = sd * Di, Ho = sh * Hi, Wo = sw * Wi;
-  ConvClasses cs;
-  cs.kseg = 0;
+  Taps taps;
+  for (int t = 0; t < 27; ++t) taps.wt[t] = -1;
+  taps.wt[13] = 0;
   if (mode == 0) {
     // forward: the output offsets write disjoint lattices -> one pointwise launch with `no` classes
+    ConvClasses cs{};
     cs.n = no;
     View yv{};
     for (int o = 0; o < no; ++o) {
-      long long off;
       yv = lattice_view(Do, Ho, Wo, ldout, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
-                     sw == 2 ? o % 2 : 0, &off);
-      yv.sb = (long long)Do * Ho * Wo * ldout;
-      cs.xoff[o] = 0;
-      cs.yoff[o] = off;
-      cs.acc[o] = 0;
-      for (int t = 0; t < 27; ++t) cs.taps[o].wt[t] = -1;
+                        sw == 2 ? o % 2 : 0, &cs.yoff[o]);
+      cs.taps[o] = taps;
       cs.taps[o].wt[13] = (signed char)o;
     }
-    const View xv = dense_view(B, Di, Hi, Wi, ldin);
-    return dispatch_conv_classes<T>(in, xv, wf, cs, bias, out, yv, B, Cin, Cout, CinP, CoutP, 0, st, nullptr, no);
+    const ConvLaunch L{in, dense_view(B, Di, Hi, Wi, ldin), wf, bias, out, yv, B, Cin, Cout, CinP, CoutP, nullptr, no, st};
+    return dispatch_conv_classes<T>(L, cs, 0);
   }
   // data gradient: ONE pointwise GEMM with K = no x Cout, the output lattices of dout concatenated along K
-  cs.n = 1;
-  cs.acc[0] = 0;
-  cs.xoff[0] = cs.yoff[0] = 0;
-  for (int t = 0; t < 27; ++t) cs.taps[0].wt[t] = -1;
-  cs.taps[0].wt[13] = 0;
+  ConvClasses cs = single_class(taps, 0);
   cs.kseg = CoutP;
   View xv{};
-  for (int o = 0; o < no; ++o) {
-    long long off;
+  for (int o = 0; o < no; ++o)
     xv = lattice_view(Do, Ho, Wo, ldin, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0, sw == 2 ? o % 2 : 0,
-                   &off);
-    cs.segoff[o] = off;
-  }
-  xv.sb = (long long)Do * Ho * Wo * ldin;
-  const View yv = dense_view(B, Di, Hi, Wi, ldout);
-  return dispatch_conv_classes<T>(in, xv, wb, cs, nullptr, out, yv, B, Cout, Cin, no * CoutP, CinP, 0, st, nullptr, 1);
+                      &cs.segoff[o]);
+  const ConvLaunch L{in, xv, wb, nullptr, out, dense_view(B, Di, Hi, Wi, ldout), B, Cout, Cin, no * CoutP, CinP, nullptr, 1, st};
+  return dispatch_conv_classes<T>(L, cs, 0);
 }
 }  // namespace
 
-// ConvTranspose3d(k2,s2) forward / data gradient (the 8-offset case of the above).
-template <typename T>
-static int convT_run(int mode /*0 fwd, 1 dgrad*/, const void *in, int ldin, const float *w_t, const float *bias, void *out,
-                     int ldout, void *ws, int B, int Cin, int Cout, int Di, int Hi, int Wi, hipStream_t st) {
-  return convTa_run_t<T>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, st);
+int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
+               int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st) {
+  if (!dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;
+  DISPATCH_T(dtype, return convTa_run_t<T>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, st));
 }
 
+// ConvTranspose3d(k2,s2) forward / data gradient: the register-operand GEMM where it applies, else the 8-offset case of the above
 int convT_fwd_mfma(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws, int B, int Cin,
                    int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st) {
   if (ldx >= Cin && ldo >= Cout && convT_gemm_eligible(0, x, ldx, out, ldo, Cin, Cout, Wi, dtype))
     return convT_gemm_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, dtype, st);
-  if (dtype == DGTTA_F32) return convT_run<float>(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  if (dtype == DGTTA_BF16) return convT_run<bf16_t>(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  if (dtype == DGTTA_F16) return convT_run<f16_t>(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  return DGTTA_ERR_UNSUPPORTED;
+  return convTa_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, dtype, st);
 }
 int convT_dgrad_mfma(const void *dout, int lddo, const float *w_t, void *dx, int lddx, void *ws, int B, int Cin, int Cout,
                      int Di, int Hi, int Wi, int dtype, hipStream_t st) {
   if (lddo >= Cout && lddx >= Cin && convT_gemm_eligible(1, dout, lddo, dx, lddx, Cin, Cout, Wi, dtype))
     return convT_gemm_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, dtype, st);
-  if (dtype == DGTTA_F32) return convT_run<float>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  if (dtype == DGTTA_BF16) return convT_run<bf16_t>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  if (dtype == DGTTA_F16) return convT_run<f16_t>(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  return DGTTA_ERR_UNSUPPORTED;
+  return convTa_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, dtype, st);
 }
-
-int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
-               int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st) {
-#define ARGS mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, st
-  if (dtype == DGTTA_F32) return convTa_run_t<float>(ARGS);
-  if (dtype == DGTTA_BF16) return convTa_run_t<bf16_t>(ARGS);
-  if (dtype == DGTTA_F16) return convTa_run_t<f16_t>(ARGS);
-#undef ARGS
-  return DGTTA_ERR_UNSUPPORTED;
-}
-

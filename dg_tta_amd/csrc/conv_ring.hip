@@ -521,10 +521,18 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
 namespace {
 
 template <int KH>
-int ring_launch_kh(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                   int B, int Cout, double *stats, int64_t stats_cap_slots, int ntaps_src, int is_f16, hipStream_t st,
-                   RowsGstCtx *gctx, long long xkh, bool dry) {
+int ring_launch_kh(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slots, int is_f16) {
   typedef RingCfgT<KH> C;
+  const void *x = L.x, *w = L.w;
+  void *y = L.y;
+  const View &xv = L.xv, &yv = L.yv;
+  const int B = L.B, Cout = L.Cout, ntaps_src = L.ntaps_src;
+  const float *bias = L.bias;
+  double *stats = L.stats;
+  hipStream_t st = L.st;
+  RowsGstCtx *gctx = L.gst;
+  const long long xkh = L.xkh;
+  const bool dry = L.dry;
   if (xkh && (KH != 2 || xkh % 8 || xv.sw != 32)) return DGTTA_ERR_UNSUPPORTED;      // K halves as planes: 64 input channels, dense 32-channel rows
   // the buffer descriptors address one sample with 32-bit byte offsets
   const long long xb = ((long long)(xv.D - 1) * xv.sd + (long long)(xv.H - 1) * xv.sh + (long long)(xv.W - 1) * xv.sw + (xkh ? 32 : 32 * KH)) * 2;
@@ -630,14 +638,12 @@ int ring_launch_kh(const void *x, const View &xv, const void *w, const Taps &tap
 }  // namespace
 
 // Entry point used by the dispatcher in conv_mfma.hip: DGTTA_ERR_UNSUPPORTED when the shape is not this kernel's.
-int conv3_ring_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int64_t stats_cap_slots, int ntaps_src,
-                      int is_f16, hipStream_t st, RowsGstCtx *gst, long long xkh, bool dry) {
-  if (Cin != CinP || (Cin != 32 && Cin != 64) || Cout % 32 != 0 || CoutP != Cout) return DGTTA_ERR_UNSUPPORTED;
-  if (xv.D != yv.D || xv.H != yv.H || xv.W != yv.W) return DGTTA_ERR_UNSUPPORTED;
-  if (Cin == 64) {
+int conv3_ring_launch(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slots, int is_f16) {
+  if (L.Cin != L.CinP || (L.Cin != 32 && L.Cin != 64) || L.Cout % 32 != 0 || L.CoutP != L.Cout) return DGTTA_ERR_UNSUPPORTED;
+  if (L.xv.D != L.yv.D || L.xv.H != L.yv.H || L.xv.W != L.yv.W) return DGTTA_ERR_UNSUPPORTED;
+  if (L.Cin == 64) {
     if (dgtta_switches().conv_ring == '3') return DGTTA_ERR_UNSUPPORTED;      // DGTTA_CONV_RING=3: the ring for 32 input channels only
-    return ring_launch_kh<2>(x, xv, w, taps, bias, y, yv, B, Cout, stats, stats_cap_slots, ntaps_src, is_f16, st, gst, xkh, dry);
+    return ring_launch_kh<2>(L, taps, stats_cap_slots, is_f16);
   }
-  return ring_launch_kh<1>(x, xv, w, taps, bias, y, yv, B, Cout, stats, stats_cap_slots, ntaps_src, is_f16, st, gst, xkh, dry);
+  return ring_launch_kh<1>(L, taps, stats_cap_slots, is_f16);
 }

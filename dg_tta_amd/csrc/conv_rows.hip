@@ -585,10 +585,13 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
 namespace {
 
 template <int PD, int PH, int WD, int WH, typename T16>
-int launch_conv_rows(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y,
-                     const View &yv, int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src,
-                     hipStream_t st, RowsGstCtx *gctx) {
+int launch_conv_rows(const ConvLaunch &L, const Taps &taps) {
   typedef RowsCfg<PD, PH, WD, WH> Cfg;
+  const View &xv = L.xv, &yv = L.yv;
+  const int B = L.B, Cin = L.Cin, Cout = L.Cout, CinP = L.CinP, CoutP = L.CoutP;
+  const float *bias = L.bias;
+  double *stats = L.stats;
+  RowsGstCtx *gctx = L.gst;
   GstArgs ga{};
   // laboratory builds of the same kernel (libdgtta_hip_diag.so only).  DGTTA_ROWS_ABL: 1 no DMA, 3 no MFMA, 6 per-segment cycle
   // stamps, 7 the voxel-major (ragged-tile) epilogue for every tile, 8 plain (temporal) output stores; DGTTA_ROWS_VAR: '0' =
@@ -642,8 +645,8 @@ int launch_conv_rows(const void *x, const View &xv, const void *w, const Taps &t
   }();
   const int wg_per_cu = (int)((160 * 1024) / Cfg::LDS_BYTES) > 0 ? (int)((160 * 1024) / Cfg::LDS_BYTES) : 1;
   const int grid = (int)(njobs < (long long)ncu * wg_per_cu ? njobs : (long long)ncu * wg_per_cu);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, st, (const bf16_t *)x, xv, (const bf16_t *)w, taps,
-                     bias, (bf16_t *)y, yv, Cin, Cout, CinP, tW, tH, tD, nblkN, (int)njobs, stats, ntaps_src,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::NT), Cfg::LDS_BYTES, L.st, (const bf16_t *)L.x, xv, (const bf16_t *)L.w, taps,
+                     bias, (bf16_t *)L.y, yv, Cin, Cout, CinP, tW, tH, tD, nblkN, (int)njobs, stats, L.ntaps_src,
                      dgtta_switches().rows_order == '0' ? 0 : 1, ga);
   DG_CHECK_LAUNCH("conv3_rows_kernel");
   return DGTTA_OK;
@@ -652,10 +655,7 @@ int launch_conv_rows(const void *x, const View &xv, const void *w, const Taps &t
 }  // namespace
 
 // entry point used by the dispatcher in conv_mfma.hip
-int conv3_rows_launch(const void *x, const View &xv, const void *w, const Taps &taps, const float *bias, void *y, const View &yv,
-                      int B, int Cin, int Cout, int CinP, int CoutP, double *stats, int ntaps_src, int is_f16, hipStream_t st,
-                      RowsGstCtx *gst) {
-  if (is_f16)
-    return launch_conv_rows<2, 2, 2, 4, f16_t>(x, xv, w, taps, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st, gst);
-  return launch_conv_rows<2, 2, 2, 4, bf16_t>(x, xv, w, taps, bias, y, yv, B, Cin, Cout, CinP, CoutP, stats, ntaps_src, st, gst);
+int conv3_rows_launch(const ConvLaunch &L, const Taps &taps, int is_f16) {
+  if (is_f16) return launch_conv_rows<2, 2, 2, 4, f16_t>(L, taps);
+  return launch_conv_rows<2, 2, 2, 4, bf16_t>(L, taps);
 }

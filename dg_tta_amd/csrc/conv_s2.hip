@@ -172,14 +172,14 @@ __global__ __launch_bounds__(512) void conv_s2_regs_kernel(const T *__restrict__
 }
 
 template <typename T, int KC, int NBW>
-int launch_s2(const void *x, const View &xv, const void *wimg, const float *bias, void *y, const View &yv, int B, int Cout,
-              double *stats, int64_t cap_slots, hipStream_t st) {
+int launch_s2(const ConvLaunch &L, int64_t cap_slots) {
+  const View &yv = L.yv;
   constexpr int LDS = 27 * KC * NBW * 1024 + 8 * 2048;
   auto kern = conv_s2_regs_kernel<T, KC, NBW>;
   static DynLdsOnce once;
   DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(kern), LDS) == hipSuccess, DGTTA_ERR_LAUNCH,
              "conv_s2_regs: cannot raise the dynamic LDS limit to %d", LDS);
-  const int NG = Cout / (32 * NBW), nWB = cdiv(yv.W, 32);
+  const int NG = L.Cout / (32 * NBW), nWB = cdiv(yv.W, 32);
   const long long mbs = (long long)yv.D * yv.H * nWB;
   DG_REQUIRE(mbs < (1ll << 30), DGTTA_ERR_UNSUPPORTED, "conv_s2_regs: volume too large");
   long long CH = cdiv64(mbs, cap_slots);
@@ -189,11 +189,11 @@ int launch_s2(const void *x, const View &xv, const void *wimg, const float *bias
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   long long grid = (long long)cus / NG * NG;                       // one workgroup per CU, a multiple of the channel groups
-  const long long want = cdiv64((long long)B * nslots, 8) * NG;     // no more workgroups than there are jobs
+  const long long want = cdiv64((long long)L.B * nslots, 8) * NG;     // no more workgroups than there are jobs
   if (grid > want) grid = want;
   if (grid < NG) grid = NG;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, st, (const T *)x, xv, (const T *)wimg, bias, (T *)y, yv, Cout,
-                     NG, nWB, (int)mbs, (int)CH, nslots, B, stats);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, L.st, (const T *)L.x, L.xv, (const T *)L.w, L.bias, (T *)L.y, yv,
+                     L.Cout, NG, nWB, (int)mbs, (int)CH, nslots, L.B, L.stats);
   DG_CHECK_LAUNCH("conv_s2_regs_kernel");
   return DGTTA_OK;
 }
@@ -202,13 +202,15 @@ int launch_s2(const void *x, const View &xv, const void *wimg, const float *bias
 
 // Shapes served: 16-bit storage, Cin in {32, 64} unpadded, Cout a multiple of the channel group, >= 32 output columns.
 // cap_slots: statistics slots per sample the caller's buffer holds (dgtta_conv3d_stats_bytes).
-int conv3_s2_regs(const void *x, const View &xv, const void *wimg, const float *bias, void *y, const View &yv, int B, int Cin,
-                  int Cout, int CinP, int CoutP, double *stats, int64_t cap_slots, int dtype, hipStream_t st) {
+int conv3_s2_regs(const ConvLaunch &L, int64_t cap_slots, int dtype) {
+  const View &xv = L.xv, &yv = L.yv;
+  const void *x = L.x, *y = L.y;
+  const int Cin = L.Cin, Cout = L.Cout, CinP = L.CinP, CoutP = L.CoutP;
   if (dtype != DGTTA_BF16 && dtype != DGTTA_F16) return DGTTA_ERR_UNSUPPORTED;
   if (!((Cin == 32 && Cout % 64 == 0) || (Cin == 64 && Cout % 32 == 0)) || CinP != Cin || CoutP != Cout) return DGTTA_ERR_UNSUPPORTED;
   if (yv.W < 32 || xv.sw % 8 || xv.sh % 8 || xv.sd % 8 || xv.sb % 8 || ((uintptr_t)x & 15)) return DGTTA_ERR_UNSUPPORTED;
   if (yv.sw % 8 || yv.sh % 8 || yv.sd % 8 || yv.sb % 8 || ((uintptr_t)y & 15) || cap_slots < 1) return DGTTA_ERR_UNSUPPORTED;
-#define GO(TT, K, N) return launch_s2<TT, K, N>(x, xv, wimg, bias, y, yv, B, Cout, stats, cap_slots, st)
+#define GO(TT, K, N) return launch_s2<TT, K, N>(L, cap_slots)
   if (dtype == DGTTA_BF16) {
     if (Cin == 32) GO(bf16_t, 2, 2);
     GO(bf16_t, 4, 1);

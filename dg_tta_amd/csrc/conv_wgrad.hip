@@ -74,7 +74,7 @@ int wgrad_launch_classes(const void *x, const View &xv, const void *dy, const Vi
       if (rc != DGTTA_OK) return rc;
     }
     if (g == 0 && plain && sw.wgrad_ring != '0') {      // the persistent ring sweep (conv_wgrad_ring.hip; DGTTA_WGRAD_RING=0: its predecessors)
-      g = conv3_wgrad_ring_launch(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, dtype == DGTTA_F16, st, &rc, xkh);
+      g = conv3_wgrad_ring_launch(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, dtype == DGTTA_F16, st, &rc, xkh, false);
       if (rc != DGTTA_OK) return rc;
     }
     if (g > 0) {

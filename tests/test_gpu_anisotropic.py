@@ -172,7 +172,29 @@ def test_unsupported_geometry_is_rejected():
     assert rc == -2
 
 
-POOLS = [[1, 1, 1], [1, 2, 2], [1, 2, 2], [2, 2, 2]]
+# one weight-image pack serves both blobs: the kd = 3 blob of dgtta_conv3d_kpack_weights is the image region [imgF | imgB] of the
+# 3x3x3 blob, which follows its [wf | wb] of 2 * 27 * CinP * CoutP elements
+@pytest.mark.parametrize("dt", [0, 1, 2])
+def test_kpack_kd3_is_the_image_region_of_pack_weights(dt):
+    lib = _lib()
+    cin, cout = 5, 12
+    CP = 8 if dt == 0 else 16
+    cinp, coutp = _pad(cin, CP), _pad(cout, CP)
+    w = torch.randn(cout, cin, 3, 3, 3, generator=torch.Generator().manual_seed(11 + dt)).cuda().contiguous()
+    st = _stream()
+    nk, n3 = lib.dgtta_conv3d_kpacked_bytes(3, cinp, coutp, dt), lib.dgtta_conv3d_packed_bytes(cinp, coutp, dt)
+    off = 2 * 27 * cinp * coutp * TDT[dt].itemsize
+    assert nk > 0 and n3 == off + nk
+    kblob = torch.full((nk,), 0xA5, dtype=torch.uint8, device="cuda")
+    blob = torch.full((n3,), 0x5A, dtype=torch.uint8, device="cuda")
+    _check(lib.dgtta_conv3d_kpack_weights(w.data_ptr(), kblob.data_ptr(), 3, 3, 3, cin, cout, cinp, coutp, dt, st), "kpack")
+    _check(lib.dgtta_conv3d_pack_weights(w.data_ptr(), blob.data_ptr(), cin, cout, cinp, coutp, dt, st), "pack")
+    torch.cuda.synchronize()
+    assert torch.equal(kblob, blob[off:off + nk])
+    assert kblob.view(TDT[dt]).count_nonzero() == w.to(TDT[dt]).count_nonzero() * 2      # every weight once per image, padding zero
+
+
+POOLS =[[1, 1, 1], [1, 2, 2], [1, 2, 2], [2, 2, 2]]
 POOLS_121 = [[1, 1, 1], [1, 2, 1], [1, 2, 2], [2, 2, 2]]
 KERNELS = [[1, 3, 3], [1, 3, 3], [3, 3, 3], [3, 3, 3]]
 
