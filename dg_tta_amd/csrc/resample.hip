@@ -133,7 +133,90 @@ __global__ void argmax_merge_kernel(const double *__restrict__ vals, int64_t V, 
   best_idx[v] = bi;
 }
 
+// Online softmax over the class groups of the same loop (the label stays with argmax_merge_kernel): per voxel a running maximum m
+// of the scaled logits l = scale * vals, S = sum exp(l - m) and D = sum (l - m) exp(l - m).  When the maximum moves from m to m',
+// with r = exp(m - m'): S' = r S and D' = r (D + (m - m') S).  The scaled logits of the selected classes of this group are parked
+// in stash [K][V] (double: the finalize pass then owes float64 rounding only; K x V x 8 B = 17 GB at 512^3 with K = 16).
+struct SoftmaxSel {
+  int c[32];
+};
+
+__global__ void softmax_merge_kernel(const double *__restrict__ vals, int64_t V, int cg, int c0, double scale, double *__restrict__ run_max,
+                                     double *__restrict__ run_sum, double *__restrict__ run_dot, SoftmaxSel sel, int K,
+                                     double *__restrict__ stash, int first) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  double m = first ? -INFINITY : run_max[v], S = first ? 0.0 : run_sum[v], D = first ? 0.0 : run_dot[v];
+  double gm = -INFINITY;
+  for (int j = 0; j < cg; ++j) gm = fmax(gm, scale * vals[v * cg + j]);
+  if (gm > m) {
+    if (S > 0.0) {
+      const double d = m - gm, r = exp(d);
+      D = r * (D + d * S);
+      S = r * S;
+    }
+    m = gm;
+  }
+  for (int j = 0; j < cg; ++j) {
+    const double x = scale * vals[v * cg + j] - m, e = exp(x);
+    S += e;
+    D += x * e;
+  }
+  run_max[v] = m, run_sum[v] = S, run_dot[v] = D;
+#pragma unroll
+  for (int k = 0; k < 32; ++k)
+    if (k < K && sel.c[k] >= c0 && sel.c[k] < c0 + cg) stash[(int64_t)k * V + v] = scale * vals[v * cg + (sel.c[k] - c0)];
+}
+
+template <typename PT>
+__global__ void softmax_finalize_kernel(const double *__restrict__ run_max, const double *__restrict__ run_sum,
+                                        const double *__restrict__ run_dot, const double *__restrict__ stash, int64_t V, int K,
+                                        float *__restrict__ conf, float *__restrict__ entropy, PT *__restrict__ probs) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const double m = run_max[v], S = run_sum[v];
+  conf[v] = (float)(1.0 / S);
+  entropy[v] = (float)fmax(log(S) - run_dot[v] / S, 0.0);
+  for (int k = 0; k < K; ++k) st_f<PT>(probs + (int64_t)k * V + v, (float)(exp(stash[(int64_t)k * V + v] - m) / S));
+}
+
 }  // namespace
+
+extern "C" int dgtta_softmax_merge_f64(const double *vals, int64_t V, int cg, int c0, double scale, double *run_max, double *run_sum,
+                                       double *run_dot, const int *h_sel, int K, double *stash, int first, void *stream) {
+  DG_REQUIRE(vals && run_max && run_sum && run_dot && h_sel && stash, DGTTA_ERR_BADARG, "softmax_merge: null pointer");
+  DG_REQUIRE(V > 0 && cg > 0 && c0 >= 0 && scale > 0.0, DGTTA_ERR_BADARG, "softmax_merge: bad dims or scale");
+  DG_REQUIRE(K >= 1 && K <= 32, DGTTA_ERR_BADARG, "softmax_merge: 1..32 selected classes (got %d)", K);
+  SoftmaxSel sel{};
+  for (int k = 0; k < K; ++k) {
+    DG_REQUIRE(h_sel[k] >= 0, DGTTA_ERR_BADARG, "softmax_merge: selected class %d is negative", h_sel[k]);
+    for (int i = 0; i < k; ++i) DG_REQUIRE(h_sel[i] != h_sel[k], DGTTA_ERR_BADARG, "softmax_merge: class %d selected twice", h_sel[k]);
+    sel.c[k] = h_sel[k];
+  }
+  DG_REQUIRE(cdiv64(V, 256) < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "softmax_merge: too many voxels");
+  hipLaunchKernelGGL(softmax_merge_kernel, dim3((unsigned)cdiv64(V, 256)), dim3(256), 0, (hipStream_t)stream, vals, V, cg, c0, scale,
+                     run_max, run_sum, run_dot, sel, K, stash, first);
+  DG_CHECK_LAUNCH("softmax_merge_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_softmax_finalize_f64(const double *run_max, const double *run_sum, const double *run_dot, const double *stash,
+                                          int64_t V, int K, int prob_dtype, float *conf_out, float *entropy_out, void *probs_out,
+                                          void *stream) {
+  DG_REQUIRE(run_max && run_sum && run_dot && stash && conf_out && entropy_out && probs_out, DGTTA_ERR_BADARG,
+             "softmax_finalize: null pointer");
+  DG_REQUIRE(V > 0 && K >= 1 && K <= 32, DGTTA_ERR_BADARG, "softmax_finalize: bad dims");
+  DG_REQUIRE(prob_dtype == DGTTA_F32 || prob_dtype == DGTTA_F16, DGTTA_ERR_BADARG, "softmax_finalize: probabilities are fp32 or fp16");
+  DG_REQUIRE(cdiv64(V, 256) < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "softmax_finalize: too many voxels");
+  if (prob_dtype == DGTTA_F32)
+    hipLaunchKernelGGL(softmax_finalize_kernel<float>, dim3((unsigned)cdiv64(V, 256)), dim3(256), 0, (hipStream_t)stream, run_max, run_sum,
+                       run_dot, stash, V, K, conf_out, entropy_out, (float *)probs_out);
+  else
+    hipLaunchKernelGGL(softmax_finalize_kernel<f16_t>, dim3((unsigned)cdiv64(V, 256)), dim3(256), 0, (hipStream_t)stream, run_max, run_sum,
+                       run_dot, stash, V, K, conf_out, entropy_out, (f16_t *)probs_out);
+  DG_CHECK_LAUNCH("softmax_finalize_kernel");
+  return DGTTA_OK;
+}
 
 extern "C" int dgtta_logits_chunk_f64_t(const void *acc, const float *nsum, double *dst, int C, int X, int Y, int Z, int x0,
                                         int y0, int z0, int xs, int ys, int zs, int c0, int cg, int acc_dtype, void *stream) {

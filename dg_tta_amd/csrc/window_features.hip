@@ -237,12 +237,38 @@ __global__ __launch_bounds__(256) void feature_head_argmax_kernel(const float *_
 // vector-ALU kernel keeps several members' partial sums in LDS and is bound by that traffic; here a further member is 7.3 ms of MFMAs.
 constexpr int WF_WPITCH = 36;
 
-template <int NCB>      // class blocks of 32 (C <= 32 NCB)
-__global__ __launch_bounds__(256) void feature_head_argmax_mfma_kernel(const float *__restrict__ facc, int64_t member_stride,
-                                                                       const float *__restrict__ nsum, const float *__restrict__ w,
-                                                                       const float *__restrict__ bsum, int M, int C, int64_t V,
-                                                                       int64_t *__restrict__ amax) {
-  extern __shared__ __attribute__((aligned(16))) float sw[];      // [M][32 NCB][WF_WPITCH], then bsum [32 NCB]
+// The sequential scan's rule (best = -inf, class 0; strictly greater replaces; NaNs never do) over a tile's accumulators, per lane
+// half and then merged; every lane of a voxel ends with the voxel's (best, bi).
+template <int NCB>
+__device__ __forceinline__ void wf_first_max(const f32x16_t (&acc)[NCB], int C, int h, float &best, int &bi) {
+  best = -INFINITY;
+  bi = 4 * h < C ? 4 * h : 0x7fffffff;      // this half's first class
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int c = cb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+      const float x = acc[cb][q];
+      if ((cb + 1 < NCB || c < C) && x > best) {      // (only the last class block can hold padding: C > 32 (NCB - 1))
+        best = x;
+        bi = c;
+      }
+    }
+  const float ob = __shfl_xor(best, 32, 64);
+  const int oi = __shfl_xor(bi, 32, 64);
+  if (ob > best || (ob == best && oi < bi)) {
+    best = ob;
+    bi = oi;
+  }
+}
+
+// The tile loop both matrix-core head kernels run (one accumulation order: their labels are the same integers).  sw: the LDS
+// image [M][32 NCB][WF_WPITCH], then bsum [32 NCB]; epi(acc, n, v, valid, h) consumes a tile's accumulators - the UNSCALED sums
+// sum_m W_m F_m(v) + n(v) bsum of voxel v (valid = 0 on the tail lanes, which repeat the last voxel).
+template <int NCB, typename Epi>
+__device__ __forceinline__ void feature_head_tiles(const float *__restrict__ facc, int64_t member_stride, const float *__restrict__ nsum,
+                                                   const float *__restrict__ w, const float *__restrict__ bsum, int M, int C, int64_t V,
+                                                   float *sw, Epi epi) {
   float *sb = sw + (size_t)M * 32 * NCB * WF_WPITCH;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < M * 32 * NCB * WF_CIN; i += 256) {
@@ -298,28 +324,101 @@ __global__ __launch_bounds__(256) void feature_head_argmax_mfma_kernel(const flo
 #pragma unroll
       for (int s = 0; s < 4; ++s) fb[s] = fn[s];
     }
-    // the sequential scan's rule (best = -inf, class 0; strictly greater replaces; NaNs never do), per lane half and then merged
-    float best = -INFINITY;
-    int bi = 4 * h < C ? 4 * h : 0x7fffffff;      // this half's first class
+    epi(acc, n, v, t * 32 + j < V, h);
+  }
+}
+
+template <int NCB>      // class blocks of 32 (C <= 32 NCB)
+__global__ __launch_bounds__(256) void feature_head_argmax_mfma_kernel(const float *__restrict__ facc, int64_t member_stride,
+                                                                       const float *__restrict__ nsum, const float *__restrict__ w,
+                                                                       const float *__restrict__ bsum, int M, int C, int64_t V,
+                                                                       int64_t *__restrict__ amax) {
+  extern __shared__ __attribute__((aligned(16))) float sw[];      // [M][32 NCB][WF_WPITCH], then bsum [32 NCB]
+  feature_head_tiles<NCB>(facc, member_stride, nsum, w, bsum, M, C, V, sw, [&](const f32x16_t(&acc)[NCB], float, int64_t v, bool valid, int h) {
+    float best;
+    int bi;
+    wf_first_max<NCB>(acc, C, h, best, bi);
+    if (h == 0 && valid) amax[v] = bi;
+  });
+}
+
+// Head + softmax of the ensemble-MEAN logits l_c = acc_c / (M n) on the same tile loop: label (the argmax kernel's integers: the scan
+// runs on the unscaled accumulators, and a positive scale keeps their order), confidence = p[label] = 1 / S and entropy =
+// ln S - D / S with S = sum_c exp(l_c - l_max), D = sum_c (l_c - l_max) exp(l_c - l_max) - one exp and one FMA per class, one log
+// per voxel - and the probabilities of the K selected classes, plane-major ([K][V]: a lane half's 32 voxels of a class are one
+// contiguous run).  All reductions stay inside a lane plus one exchange between the lane halves.  The padding classes of the last
+// block (accumulators 0, not -inf) are masked out of every sum.  The scale is rounded once (formed in double) and applied with one
+// multiplication: two roundings on top of the dot product's.  slot: class -> row of `probs` (LDS, 128 bytes, -1 = not selected),
+// read four classes at a time - a lane's classes come in aligned runs of four.
+// Measured at 512^3 x 105 classes (profiles/tools/headprobs_bench.py): 20.1 ms with one member and one fp16 plane, 25.5 ms with 16
+// planes (argmax kernel 13.5); three members 35.5 / 40.8 ms (28.7).  The difference is the epilogue's vector instructions (about 9
+// issue slots per class and lane), which nothing overlaps at one wave per SIMD (326 registers with four class blocks); DESIGN.md.
+struct WfSel {
+  int c[32];
+};
+
+template <int NCB, typename PT>
+__global__ __launch_bounds__(256) void feature_head_softmax_mfma_kernel(const float *__restrict__ facc, int64_t member_stride,
+                                                                        const float *__restrict__ nsum, const float *__restrict__ w,
+                                                                        const float *__restrict__ bsum, int M, int C, int64_t V,
+                                                                        WfSel sel, int K, int64_t *__restrict__ label,
+                                                                        float *__restrict__ conf, float *__restrict__ entropy,
+                                                                        PT *__restrict__ probs) {
+  extern __shared__ __attribute__((aligned(16))) float sw[];      // [M][32 NCB][WF_WPITCH], bsum [32 NCB], slot [128] (bytes)
+  signed char *slot = reinterpret_cast<signed char *>(sw + (size_t)M * 32 * NCB * WF_WPITCH + 32 * NCB);
+  const int tid = threadIdx.x;
+  if (tid < 128) slot[tid] = -1;
+  __syncthreads();
+  {
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) mine = tid == k ? sel.c[k] : mine;      // (no runtime index into the kernel argument)
+    if (tid < K) slot[mine] = (signed char)tid;
+  }      // (feature_head_tiles synchronises before the first tile)
+  const double dM = (double)M;
+  feature_head_tiles<NCB>(facc, member_stride, nsum, w, bsum, M, C, V, sw, [&](const f32x16_t(&acc)[NCB], float n, int64_t v, bool valid, int h) {
+    float best;
+    int bi;
+    wf_first_max<NCB>(acc, C, h, best, bi);
+    const float inv = (float)(1.0 / (dM * (double)n));
+    const float lmax = best * inv;
+    float Sp[4] = {0.f, 0.f, 0.f, 0.f}, Dp[4] = {0.f, 0.f, 0.f, 0.f};      // four independent chains: one waits for itself
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int c = cb * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-        const float x = acc[cb][q];
-        if ((cb + 1 < NCB || c < C) && x > best) {      // (only the last class block can hold padding: C > 32 (NCB - 1))
-          best = x;
-          bi = c;
+        if (cb + 1 < NCB || c < C) {
+          const float x = acc[cb][q] * inv - lmax;
+          const float e = __expf(x);
+          Sp[q & 3] += e;
+          Dp[q & 3] = fmaf(x, e, Dp[q & 3]);
         }
       }
-    const float ob = __shfl_xor(best, 32, 64);
-    const int oi = __shfl_xor(bi, 32, 64);
-    if (ob > best || (ob == best && oi < bi)) {
-      best = ob;
-      bi = oi;
+    float S = (Sp[0] + Sp[1]) + (Sp[2] + Sp[3]), D = (Dp[0] + Dp[1]) + (Dp[2] + Dp[3]);
+    S += __shfl_xor(S, 32, 64);
+    D += __shfl_xor(D, 32, 64);
+    const float invS = 1.f / S;
+    if (valid) {
+      if (h == 0) {
+        label[v] = bi;
+        conf[v] = invS;
+        entropy[v] = fmaxf(__logf(S) - D * invS, 0.f);
+      }
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const unsigned s4 = *reinterpret_cast<const unsigned *>(slot + cb * 32 + 8 * q4 + 4 * h);
+          if (s4 == 0xffffffffu) continue;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = (int)(signed char)(s4 >> (8 * r));
+            if (k >= 0) st_f<PT>(probs + (int64_t)k * V + v, __expf(acc[cb][4 * q4 + r] * inv - lmax) * invS);
+          }
+        }
     }
-    if (h == 0 && t * 32 + j < V) amax[v] = bi;
-  }
+  });
 }
 
 // Export path (original geometry): classes c0 .. c0 + cg - 1 of the normalised ensemble logits as doubles,
@@ -486,6 +585,51 @@ extern "C" int dgtta_feature_head_argmax(const float *facc, int64_t member_strid
   hipLaunchKernelGGL(feature_head_argmax_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, facc, member_stride, nsum, w, bsum, M, C,
                      V, argmax_out);
   DG_CHECK_LAUNCH("feature_head_argmax_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_feature_head_softmax(const float *facc, int64_t member_stride, const float *nsum, const float *w, const float *bsum,
+                                          int M, int Cin, int C, int64_t V, const int *h_sel, int K, int prob_dtype, int64_t *label_out,
+                                          float *conf_out, float *entropy_out, void *probs_out, void *stream) {
+  DG_REQUIRE(facc && nsum && w && bsum && h_sel && label_out && conf_out && entropy_out && probs_out, DGTTA_ERR_BADARG,
+             "feature_head_softmax: null pointer");
+  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "feature_head_softmax: built for %d feature channels (got %d)", WF_CIN, Cin);
+  DG_REQUIRE(M >= 1 && C >= 1 && V >= 1 && (M == 1 || member_stride >= V * WF_CIN), DGTTA_ERR_BADARG, "feature_head_softmax: bad sizes");
+  DG_REQUIRE(((uintptr_t)facc & 15) == 0 && (member_stride & 3) == 0, DGTTA_ERR_BADARG, "feature_head_softmax: unaligned accumulator");
+  DG_REQUIRE(prob_dtype == DGTTA_F32 || prob_dtype == DGTTA_F16, DGTTA_ERR_BADARG, "feature_head_softmax: probabilities are fp32 or fp16");
+  DG_REQUIRE(K >= 1 && K <= 32, DGTTA_ERR_BADARG, "feature_head_softmax: 1..32 selected classes (got %d)", K);
+  WfSel sel{};
+  for (int k = 0; k < K; ++k) {
+    DG_REQUIRE(h_sel[k] >= 0 && h_sel[k] < C, DGTTA_ERR_BADARG, "feature_head_softmax: selected class %d outside [0,%d)", h_sel[k], C);
+    for (int i = 0; i < k; ++i) DG_REQUIRE(h_sel[i] != h_sel[k], DGTTA_ERR_BADARG, "feature_head_softmax: class %d selected twice", h_sel[k]);
+    sel.c[k] = h_sel[k];
+  }
+  const int ncb = (C + 31) / 32;
+  const size_t lds = ((size_t)M * 32 * ncb * WF_WPITCH + 32 * ncb) * sizeof(float) + 128;
+  DG_REQUIRE(ncb <= 4 && lds <= 160 * 1024, DGTTA_ERR_UNSUPPORTED,
+             "feature_head_softmax: %d classes x %d members: at most 128 classes and a weight image that fits the LDS", C, M);
+  static DynLdsOnce once[2][4];
+  const int64_t ntile = cdiv64(V, 32);
+  const unsigned grid = (unsigned)(cdiv64(ntile, 4) < 2048 ? cdiv64(ntile, 4) : 2048);
+#define WF_SOFTMAX(N, PT, pi)                                                                                                           \
+  do {                                                                                                                                  \
+    DG_REQUIRE(ensure_dyn_lds(once[pi][N - 1], (const void *)feature_head_softmax_mfma_kernel<N, PT>, 160 * 1024) == hipSuccess,         \
+               DGTTA_ERR_LAUNCH, "feature_head_softmax: cannot raise the dynamic LDS limit");                                           \
+    hipLaunchKernelGGL((feature_head_softmax_mfma_kernel<N, PT>), dim3(grid), dim3(256), lds, (hipStream_t)stream, facc, member_stride, \
+                       nsum, w, bsum, M, C, V, sel, K, label_out, conf_out, entropy_out, (PT *)probs_out);                              \
+  } while (0)
+#define WF_SOFTMAX_N(PT, pi)           \
+  do {                                 \
+    if (ncb == 1) WF_SOFTMAX(1, PT, pi); \
+    else if (ncb == 2) WF_SOFTMAX(2, PT, pi); \
+    else if (ncb == 3) WF_SOFTMAX(3, PT, pi); \
+    else WF_SOFTMAX(4, PT, pi);        \
+  } while (0)
+  if (prob_dtype == DGTTA_F32) WF_SOFTMAX_N(float, 0);
+  else WF_SOFTMAX_N(f16_t, 1);
+#undef WF_SOFTMAX_N
+#undef WF_SOFTMAX
+  DG_CHECK_LAUNCH("feature_head_softmax_mfma_kernel");
   return DGTTA_OK;
 }
 

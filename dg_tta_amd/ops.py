@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import check, ptr, require_cuda, stream_of
 
 F32, BF16, F16 = 0, 1, 2
+C_int = C.c_int      # (functions with a class count `C` of their own)
 
 
 def dtype_code(torch_dtype):
@@ -606,6 +607,63 @@ def feature_head_argmax(facc, nsum, w, bsum):
     check(lib.dgtta_feature_head_argmax(ptr(facc), facc.stride(0) if M > 1 else 0, ptr(nsum), ptr(w), ptr(bsum), M, 32, C, out.numel(),
                                         ptr(out), stream_of(facc.device)), "dgtta_feature_head_argmax")
     return out
+
+
+MAX_SELECTED_CLASSES = 32
+
+
+def check_selected_classes(classes, num_classes):
+    """The `sel` list of the softmax entry points as plain ints: 1..32 DISTINCT class indices in [0, num_classes), any order.
+    ValueError otherwise (checked before anything touches the GPU)."""
+    sel = [int(c) for c in classes]
+    if not 1 <= len(sel) <= MAX_SELECTED_CLASSES:
+        raise ValueError(f"classes: 1..{MAX_SELECTED_CLASSES} selected classes expected, got {len(sel)}")
+    if len(set(sel)) != len(sel):
+        raise ValueError(f"classes: duplicate class index in {sel}")
+    if min(sel) < 0 or max(sel) >= num_classes:
+        raise ValueError(f"classes: index outside [0, {num_classes}) in {sel}")
+    return sel
+
+
+def prob_dtype_code(prob_dtype):
+    if prob_dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"probabilities are stored as float32 or float16, not {prob_dtype}")
+    return F32 if prob_dtype == torch.float32 else F16
+
+
+def feature_head_softmax_supported(M, C):
+    """dgtta_feature_head_softmax takes C <= 128 and a weight image of M members that fits the LDS (the limits of
+    dgtta_feature_head_argmax's matrix-core path); anything wider belongs to the class-group path."""
+    ncb = (C + 31) // 32
+    return ncb <= 4 and (M * 32 * ncb * 36 + 32 * ncb) * 4 + 128 <= 160 * 1024
+
+
+def feature_head_softmax(facc, nsum, w, bsum, classes, prob_dtype=torch.float32):
+    """Softmax end of feature-space window accumulators (csrc/window_features.hip; definitions in include/dgtta.h, nnU-Net's from
+    memory, UNPINNED): the inputs of feature_head_argmax plus `classes` (see check_selected_classes) ->
+    (label int64 [X,Y,Z] - the integers feature_head_argmax returns -, confidence fp32 [X,Y,Z] = p[label], entropy fp32 [X,Y,Z] in
+    nats, probs prob_dtype [K,X,Y,Z] = p[classes[k]]) of p = softmax over ALL C classes of the ensemble-mean logits
+    (sum_m w[m,c] . facc[m,v] + nsum[v] bsum[c]) / (M nsum[v]).  The K maps sum to at most 1: the rest is mass on other classes."""
+    sel = check_selected_classes(classes, w.shape[-2])
+    code = prob_dtype_code(prob_dtype)
+    if facc.dim() == 4:
+        facc, w = facc[None], (w[None] if w.dim() == 2 else w)
+    if not (facc.is_cuda and facc.dtype == torch.float32 and facc[0].is_contiguous() and facc.shape[-1] == 32):
+        raise ValueError("feature_head_softmax: fp32 GPU accumulators [M,X,Y,Z,32] expected")
+    M, C = facc.shape[0], w.shape[1]
+    if tuple(w.shape) != (M, C, 32) or tuple(bsum.shape) != (C,) or tuple(nsum.shape) != tuple(facc.shape[1:4]):
+        raise ValueError("feature_head_softmax: w [M,C,32], bsum [C], nsum [X,Y,Z] expected")
+    lib = _lib.load()
+    w, bsum, nsum = w.float().contiguous(), bsum.float().contiguous(), nsum.float().contiguous()
+    shp, dev, K = facc.shape[1:4], facc.device, len(sel)
+    label = torch.empty(shp, dtype=torch.int64, device=dev)
+    conf = torch.empty(shp, dtype=torch.float32, device=dev)
+    ent = torch.empty(shp, dtype=torch.float32, device=dev)
+    probs = torch.empty((K, *shp), dtype=prob_dtype, device=dev)
+    check(lib.dgtta_feature_head_softmax(ptr(facc), facc.stride(0) if M > 1 else 0, ptr(nsum), ptr(w), ptr(bsum), M, 32, C, label.numel(),
+                                         (C_int * K)(*sel), K, code, ptr(label), ptr(conf), ptr(ent), ptr(probs), stream_of(dev)),
+          "dgtta_feature_head_softmax")
+    return label, conf, ent, probs
 
 
 def argmax_rows(acc):

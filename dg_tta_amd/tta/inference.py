@@ -165,6 +165,12 @@ class WindowFeatures:
         """Label map [X,Y,Z] (int64, padded geometry): argmax over all classes of the ensemble logits, first maximum wins."""
         return ops.feature_head_argmax(self.facc, self.nsum, self.w, self.bsum)
 
+    def softmax(self, classes, prob_dtype=torch.float32):
+        """(label int64, confidence fp32, entropy fp32 [X,Y,Z], probs prob_dtype [K,X,Y,Z]) in the padded geometry: softmax over all
+        classes of the ensemble-MEAN logits, probabilities of `classes` only (ops.feature_head_softmax; definitions unpinned).
+        `label` holds the integers argmax() returns."""
+        return ops.feature_head_softmax(self.facc, self.nsum, self.w, self.bsum, classes, prob_dtype=prob_dtype)
+
     def logits(self):
         """The accumulated ensemble logits [X,Y,Z,C] by torch (fp32) - for tests and small volumes only."""
         M, X, Y, Z, K = self.facc.shape
@@ -402,61 +408,203 @@ def export_segmentation(acc, nsum, crop, properties, plans, configuration):
     a strongly anisotropic axis), argmax'd (softmax is monotone), pasted into a zero volume of 'shape_before_cropping' at
     'bbox_used_for_cropping' and transposed back with the plans' transpose_backward.  The resampling runs on the GPU class
     group by class group with a running argmax, so the full-resolution 105-class volume never exists."""
-    from .preprocessing import separate_z
-    lib = _lib.load()
-    feats = acc if isinstance(acc, WindowFeatures) else None
-    dev = nsum.device
-    X, Y, Z, C = acc.shape
-    st = stream_of(dev)
-    label_map = (lambda: feats.argmax()) if feats is not None else (lambda: ops.argmax_rows(acc))
-    cs = [(sl.start or 0, (sl.stop if sl.stop is not None else dim) - (sl.start or 0)) for sl, dim in zip(crop, (X, Y, Z))]
-    (x0, xs), (y0, ys), (z0, zs) = cs
-    cur_shape = [xs, ys, zs]
+    C = acc.shape[3]
+    label_map = _label_map_fn(acc)
+    cs, cur_shape = _crop_extents(acc, crop)
     if properties is None:
         return label_map()[tuple(crop)].cpu().numpy()
     tgt_shape = [int(v) for v in properties["shape_after_cropping_and_before_resampling"]]
     if tgt_shape == cur_shape:
         seg = label_map()[tuple(crop)].cpu().numpy()
     else:
-        conf = _resolved_configuration(plans, configuration)
-        cur_spacing = list(conf["spacing"])
-        if len(cur_spacing) < 3:
-            cur_spacing = [properties["spacing"][0]] + cur_spacing
-        kw = conf.get("resampling_fn_probabilities_kwargs", {"order": 1, "order_z": 0})
-        order, order_z = int(kw.get("order", 1)), int(kw.get("order_z", 0))
-        if order not in (0, 1) or order_z != 0:
-            raise NotImplementedError("probability resampling is built for order 0 / 1 and order_z 0 (nnU-Net's defaults)")
-        do_sep, axis = separate_z(cur_spacing, properties["spacing"])
-        vout = tgt_shape[0] * tgt_shape[1] * tgt_shape[2]
-        best_val = torch.empty(vout, dtype=torch.float64, device=dev)
-        best_idx = torch.empty(vout, dtype=torch.int32, device=dev)
-        for c0 in range(0, C, EXPORT_CLASS_GROUP):
-            cg = min(EXPORT_CLASS_GROUP, C - c0)
-            cur = torch.empty((xs, ys, zs, cg), dtype=torch.float64, device=dev)
-            if feats is not None:
-                M = feats.facc.shape[0]
-                check(lib.dgtta_feature_logits_chunk_f64(ptr(feats.facc), feats.facc.stride(0), ptr(nsum), ptr(feats.w), ptr(feats.bsum),
-                                                         ptr(cur), M, 32, C, X, Y, Z, x0, y0, z0, xs, ys, zs, c0, cg, st),
-                      "dgtta_feature_logits_chunk_f64")
-            else:
-                check(lib.dgtta_logits_chunk_f64_t(ptr(acc), ptr(nsum), ptr(cur), C, X, Y, Z, x0, y0, z0, xs, ys, zs, c0, cg,
-                                                   _acc_code(acc), st), "dgtta_logits_chunk_f64_t")
-            for ax in range(3):          # channels-last: the class group rides in `inner` of every pass
-                n, m = cur.shape[ax], tgt_shape[ax]
-                if n == m:
-                    continue
-                shp = list(cur.shape[:3])
-                outer = int(np.prod(shp[:ax], dtype=np.int64))
-                inner = int(np.prod(shp[ax + 1:], dtype=np.int64)) * cg
-                dst = torch.empty((*shp[:ax], m, *shp[ax + 1:], cg), dtype=torch.float64, device=dev)
-                o = 0 if (do_sep and ax == axis) else order      # nearest slices along the low-resolution axis
-                check(lib.dgtta_resample_axis(ptr(cur), ptr(dst), None, 0, outer, n, m, inner, o, st), "dgtta_resample_axis")
-                cur = dst
-            check(lib.dgtta_argmax_merge_f64(ptr(cur), vout, cg, c0, ptr(best_val), ptr(best_idx), int(c0 == 0), st),
-                  "dgtta_argmax_merge_f64")
-        seg = best_idx.reshape(tgt_shape).cpu().numpy()
+        orders = _probability_resampling_orders(properties, plans, configuration)
+        merge = _RunningArgmax(tgt_shape, nsum.device)
+        for c0, cg, cur in _resampled_class_groups(acc, nsum, cs, tgt_shape, orders):
+            merge.add(cur, c0, cg)
+        seg = merge.labels()
+    return _paste_label_map(seg, C, properties, plans)
+
+
+def _label_map_fn(acc):
+    return (lambda: acc.argmax()) if isinstance(acc, WindowFeatures) else (lambda: ops.argmax_rows(acc))
+
+
+def _crop_extents(acc, crop):
+    """((x0, xs), (y0, ys), (z0, zs)) of the crop slices inside the padded accumulator, and [xs, ys, zs]."""
+    cs = [(sl.start or 0, (sl.stop if sl.stop is not None else dim) - (sl.start or 0)) for sl, dim in zip(crop, acc.shape[:3])]
+    return cs, [c[1] for c in cs]
+
+
+def _probability_resampling_orders(properties, plans, configuration):
+    """Interpolation order per axis of the plans' probability resampler: linear (or nearest), nearest slices along a strongly
+    anisotropic axis."""
+    from .preprocessing import separate_z
+    conf = _resolved_configuration(plans, configuration)
+    cur_spacing = list(conf["spacing"])
+    if len(cur_spacing) < 3:
+        cur_spacing = [properties["spacing"][0]] + cur_spacing
+    kw = conf.get("resampling_fn_probabilities_kwargs", {"order": 1, "order_z": 0})
+    order, order_z = int(kw.get("order", 1)), int(kw.get("order_z", 0))
+    if order not in (0, 1) or order_z != 0:
+        raise NotImplementedError("probability resampling is built for order 0 / 1 and order_z 0 (nnU-Net's defaults)")
+    do_sep, axis = separate_z(cur_spacing, properties["spacing"])
+    return [0 if (do_sep and ax == axis) else order for ax in range(3)]      # nearest slices along the low-resolution axis
+
+
+def _resampled_class_groups(acc, nsum, cs, tgt_shape, orders):
+    """The export loop export_segmentation and export_probabilities share: yields (c0, cg, vals) per group of EXPORT_CLASS_GROUP
+    classes, vals [*tgt_shape, cg] float64 on the GPU = the SUM over members of the window-normalised logits of classes c0..,
+    cropped back from the padding and resampled axis by axis to tgt_shape (no pass along an axis that already has its size)."""
+    lib = _lib.load()
+    feats = acc if isinstance(acc, WindowFeatures) else None
+    dev = nsum.device
+    X, Y, Z, C = acc.shape
+    st = stream_of(dev)
+    (x0, xs), (y0, ys), (z0, zs) = cs
+    for c0 in range(0, C, EXPORT_CLASS_GROUP):
+        cg = min(EXPORT_CLASS_GROUP, C - c0)
+        cur = torch.empty((xs, ys, zs, cg), dtype=torch.float64, device=dev)
+        if feats is not None:
+            M = feats.facc.shape[0]
+            check(lib.dgtta_feature_logits_chunk_f64(ptr(feats.facc), feats.facc.stride(0), ptr(nsum), ptr(feats.w), ptr(feats.bsum),
+                                                     ptr(cur), M, 32, C, X, Y, Z, x0, y0, z0, xs, ys, zs, c0, cg, st),
+                  "dgtta_feature_logits_chunk_f64")
+        else:
+            check(lib.dgtta_logits_chunk_f64_t(ptr(acc), ptr(nsum), ptr(cur), C, X, Y, Z, x0, y0, z0, xs, ys, zs, c0, cg,
+                                               _acc_code(acc), st), "dgtta_logits_chunk_f64_t")
+        for ax in range(3):          # channels-last: the class group rides in `inner` of every pass
+            n, m = cur.shape[ax], tgt_shape[ax]
+            if n == m:
+                continue
+            shp = list(cur.shape[:3])
+            outer = int(np.prod(shp[:ax], dtype=np.int64))
+            inner = int(np.prod(shp[ax + 1:], dtype=np.int64)) * cg
+            dst = torch.empty((*shp[:ax], m, *shp[ax + 1:], cg), dtype=torch.float64, device=dev)
+            check(lib.dgtta_resample_axis(ptr(cur), ptr(dst), None, 0, outer, n, m, inner, orders[ax], st), "dgtta_resample_axis")
+            cur = dst
+        yield c0, cg, cur
+
+
+class _RunningArgmax:
+    """dgtta_argmax_merge_f64 over the class groups: the label map of the resampled logits, first maximum wins."""
+
+    def __init__(self, shape, dev):
+        self.shape, self.dev = list(shape), dev
+        self.vout = int(np.prod(shape, dtype=np.int64))
+        self.best_val = torch.empty(self.vout, dtype=torch.float64, device=dev)
+        self.best_idx = torch.empty(self.vout, dtype=torch.int32, device=dev)
+
+    def add(self, vals, c0, cg):
+        check(_lib.load().dgtta_argmax_merge_f64(ptr(vals), self.vout, cg, c0, ptr(self.best_val), ptr(self.best_idx), int(c0 == 0),
+                                                 stream_of(self.dev)), "dgtta_argmax_merge_f64")
+
+    def labels(self):
+        return self.best_idx.reshape(self.shape).cpu().numpy()
+
+
+class _RunningSoftmax:
+    """dgtta_softmax_merge_f64 / dgtta_softmax_finalize_f64 over the class groups (online softmax: running maximum, sum exp and
+    sum (l - max) exp per voxel, rescaled when the maximum moves).  The scaled logits of the K selected classes wait in a float64
+    stash [K, V]: 8 K V bytes - 17 GB at 512^3 with K = 16, which the 288 GB of an MI355X carry."""
+
+    def __init__(self, shape, dev, sel, scale, prob_dtype):
+        import ctypes
+        self.shape, self.dev, self.K, self.scale, self.prob_dtype = list(shape), dev, len(sel), float(scale), prob_dtype
+        self.sel = (ctypes.c_int * len(sel))(*sel)
+        self.vout = int(np.prod(shape, dtype=np.int64))
+        self.state = torch.empty((3, self.vout), dtype=torch.float64, device=dev)
+        self.stash = torch.empty((self.K, self.vout), dtype=torch.float64, device=dev)
+
+    def add(self, vals, c0, cg):
+        m, s, d = self.state[0], self.state[1], self.state[2]
+        check(_lib.load().dgtta_softmax_merge_f64(ptr(vals), self.vout, cg, c0, self.scale, ptr(m), ptr(s), ptr(d), self.sel, self.K,
+                                                  ptr(self.stash), int(c0 == 0), stream_of(self.dev)), "dgtta_softmax_merge_f64")
+
+    def finalize(self):
+        """(confidence fp32 [*shape], entropy fp32 [*shape], probs prob_dtype [K, *shape]) on the GPU."""
+        conf = torch.empty(self.vout, dtype=torch.float32, device=self.dev)
+        ent = torch.empty(self.vout, dtype=torch.float32, device=self.dev)
+        probs = torch.empty((self.K, self.vout), dtype=self.prob_dtype, device=self.dev)
+        m, s, d = self.state[0], self.state[1], self.state[2]
+        check(_lib.load().dgtta_softmax_finalize_f64(ptr(m), ptr(s), ptr(d), ptr(self.stash), self.vout, self.K,
+                                                     ops.prob_dtype_code(self.prob_dtype), ptr(conf), ptr(ent), ptr(probs),
+                                                     stream_of(self.dev)), "dgtta_softmax_finalize_f64")
+        return conf.reshape(self.shape), ent.reshape(self.shape), probs.reshape(self.K, *self.shape)
+
+
+def _paste_label_map(seg, C, properties, plans):
     full = np.zeros(tuple(int(v) for v in properties["shape_before_cropping"]),
                     dtype=np.uint8 if C - 1 < 255 else np.uint16)
     sl = tuple(slice(int(a), int(b)) for a, b in properties["bbox_used_for_cropping"])
     full[sl] = seg
     return np.ascontiguousarray(full.transpose(plans["transpose_backward"]))
+
+
+def can_fuse_head_softmax(acc):
+    """True when dgtta_feature_head_softmax takes this accumulator (a WindowFeatures whose head it supports) - decided before any
+    work is done, as _can_accumulate_features does; everything else goes through the class-group loop."""
+    return isinstance(acc, WindowFeatures) and ops.feature_head_softmax_supported(acc.facc.shape[0], acc.shape[3])
+
+
+@torch.no_grad()
+def export_probabilities(acc, nsum, crop, properties, plans, configuration, members, classes, prob_dtype=np.float16):
+    """Softmax end of accumulated ensemble logits, in the geometry export_segmentation returns (properties None: the preprocessed
+    geometry; otherwise resampled, pasted into `shape_before_cropping` and transposed back).  Returns a dict of numpy arrays:
+
+      segmentation   the label map export_segmentation returns for the same accumulators
+      probabilities  [K, ...] `prob_dtype` (float16 or float32): p[classes[k]] - 1..32 distinct classes in any order.  The K maps sum
+                     to at most 1; the rest is mass on classes that were not selected
+      confidence     float32, p[label] of the voxel's own argmax
+      entropy        float32, -sum_c p_c ln p_c in nats, in [0, ln C]
+
+    p = softmax over ALL pretrain classes of the ensemble-MEAN logits acc / nsum / members (`members`: the number of parameter
+    sets accumulated into acc).  Resampled exports resample the logits first and take the softmax afterwards, nnU-Net's order
+    and the one the running argmax assumes.  Outside the crop box class 0 has probability 1 (confidence 1, entropy 0), consistent
+    with the zero fill of the label map.  The definitions are nnU-Net's `save_probabilities` ones from memory: UNPINNED, like the
+    window logic of this module.
+
+    Routing: dgtta_feature_head_softmax (one fused pass on the matrix cores) when acc is a WindowFeatures it supports and the
+    target shape is the preprocessed one; otherwise the class-group loop of export_segmentation with the online-softmax merge
+    (logits-space accumulators, heads wider than 128 classes, every resampled export)."""
+    C = acc.shape[3]
+    sel = ops.check_selected_classes(classes, C)
+    tdtype = {np.dtype(np.float16): torch.float16, np.dtype(np.float32): torch.float32}.get(np.dtype(prob_dtype))
+    if tdtype is None:
+        raise ValueError(f"probabilities are stored as float16 or float32, not {prob_dtype}")
+    members = int(members)
+    if members < 1 or (isinstance(acc, WindowFeatures) and acc.facc.shape[0] != members):
+        raise ValueError(f"members = {members} does not match the accumulator")
+    cs, cur_shape = _crop_extents(acc, crop)
+    tgt_shape = cur_shape if properties is None else [int(v) for v in properties["shape_after_cropping_and_before_resampling"]]
+    resample = tgt_shape != cur_shape
+    if not resample and can_fuse_head_softmax(acc):
+        label, conf, ent, probs = acc.softmax(sel, prob_dtype=tdtype)
+        seg = label[tuple(crop)].cpu().numpy()
+        conf, ent, probs = conf[tuple(crop)], ent[tuple(crop)], probs[(slice(None), *crop)]
+    else:
+        orders = _probability_resampling_orders(properties, plans, configuration) if resample else [0, 0, 0]
+        # without resampling the label is export_segmentation's own argmax of the fp32 accumulators (a float64 argmax of the
+        # normalised values could break a rounding-level tie the other way)
+        merge = _RunningArgmax(tgt_shape, nsum.device) if resample else None
+        soft = _RunningSoftmax(tgt_shape, nsum.device, sel, 1.0 / members, tdtype)
+        for c0, cg, cur in _resampled_class_groups(acc, nsum, cs, tgt_shape, orders):
+            if merge is not None:
+                merge.add(cur, c0, cg)
+            soft.add(cur, c0, cg)
+        seg = merge.labels() if resample else _label_map_fn(acc)()[tuple(crop)].cpu().numpy()
+        conf, ent, probs = soft.finalize()
+    conf, ent, probs = conf.cpu().numpy(), ent.cpu().numpy(), probs.cpu().numpy()
+    if properties is None:
+        return {"segmentation": seg, "probabilities": np.ascontiguousarray(probs), "confidence": np.ascontiguousarray(conf),
+                "entropy": np.ascontiguousarray(ent)}
+    full_shape = tuple(int(v) for v in properties["shape_before_cropping"])
+    sl = tuple(slice(int(a), int(b)) for a, b in properties["bbox_used_for_cropping"])
+    full_p = np.zeros((len(sel), *full_shape), dtype=probs.dtype)
+    if 0 in sel:
+        full_p[sel.index(0)] = 1      # outside the box: background with probability 1
+    full_c, full_e = np.ones(full_shape, dtype=np.float32), np.zeros(full_shape, dtype=np.float32)
+    full_p[(slice(None), *sl)], full_c[sl], full_e[sl] = probs, conf, ent
+    tb = [int(a) for a in plans["transpose_backward"]]
+    return {"segmentation": _paste_label_map(seg, C, properties, plans),
+            "probabilities": np.ascontiguousarray(full_p.transpose([0] + [a + 1 for a in tb])),
+            "confidence": np.ascontiguousarray(full_c.transpose(tb)), "entropy": np.ascontiguousarray(full_e.transpose(tb))}

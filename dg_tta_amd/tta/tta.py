@@ -631,15 +631,27 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
         acc, nsum, crop = predict_ensemble(image, model, params, patch_size)
     plans = getattr(predictor, "plans", None)
     original = nii is not None and plans is not None and "shape_before_cropping" in props
-    seg = export_segmentation(acc, nsum, crop, props if original else None, plans, getattr(predictor, "configuration", None))
+    save_probs = bool(config.get("inference_save_probabilities", False))
+    save_unc = bool(config.get("inference_save_uncertainty", False))
+    pretrain_idxs = get_map_idxs(label_mapping, optimized_labels, "pretrain_labels")
+    geometry = (props if original else None, plans, getattr(predictor, "configuration", None))
+    soft = None
+    if save_probs or save_unc:
+        from .inference import export_probabilities
+        soft = export_probabilities(acc, nsum, crop, *geometry, members=len(params), classes=[int(i) for i in pretrain_idxs])
+        seg = soft.pop("segmentation")      # export_segmentation's label map for the same accumulators
+    else:
+        seg = export_segmentation(acc, nsum, crop, *geometry)
     del acc, nsum
-    seg = map_label(torch.as_tensor(seg.astype(np.int64))[None],
-                    get_map_idxs(label_mapping, optimized_labels, "pretrain_labels"), input_format="argmaxed")[0]
+    seg = map_label(torch.as_tensor(seg.astype(np.int64))[None], pretrain_idxs, input_format="argmaxed")[0]
     seg = _postprocess_prediction(seg, config, device)
     # (the prediction is written in the format of the case's image, as SimpleITK's writer picks it from the file name)
-    out = Path(str(save_path / sample_id) + ((nii.get("ext") or ".nii.gz") if nii is not None else ".npy"))
+    ext = (nii.get("ext") or ".nii.gz") if nii is not None else ".npy"
+    out = Path(str(save_path / sample_id) + ext)
     out.parent.mkdir(exist_ok=True, parents=True)
     _save_label_map(out, seg.numpy().astype(np.int16), nii)
+    if soft is not None:
+        _save_soft_outputs(out.parent, Path(sample_id).name, ext, soft, optimized_labels, nii, save_probs, save_unc)
     results[(sample_id, "prediction")] = out
     bucket = "Ts" if "outputTs" in out.parent.name else ("Tr" if "outputTr" in out.parent.name else None)
     if bucket is None:
@@ -660,6 +672,23 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
         target = map_label(target[None], tta_idxs, input_format="argmaxed")[0]
         ref_path.parent.mkdir(exist_ok=True, parents=True)
         _save_label_map(ref_path, target.numpy().astype(np.int16), nii)
+
+
+def _save_soft_outputs(label_dir, case_name, ext, soft, optimized_labels, nii, save_probs, save_unc):
+    """Plan keys `inference_save_probabilities` / `inference_save_uncertainty` (not reference keys; definitions in
+    inference.export_probabilities, unpinned): files in the SIBLING directory `<label_dir>_probabilities/`, so that the directory
+    evaluate_run and postprocess_results_fn list holds what it always held.  `<case>.npz`: `probabilities` float16 [K, ...] - the
+    softmax mass of the pretrain class behind each optimized label, background first; they sum to at most 1, the rest lies on
+    unmapped classes - and `class_names`.  `<case>_confidence<ext>` / `<case>_entropy<ext>`: float32 maps with the case's header
+    (.npy for array cases).  The written label map is the post-processed one; these maps are NOT post-processed."""
+    soft_dir = label_dir.parent / (label_dir.name + "_probabilities")
+    soft_dir.mkdir(exist_ok=True, parents=True)
+    if save_probs:
+        np.savez_compressed(soft_dir / f"{case_name}.npz", probabilities=soft["probabilities"].astype(np.float16),
+                            class_names=np.asarray(list(optimized_labels)))
+    if save_unc:
+        for key in ("confidence", "entropy"):
+            _save_label_map(soft_dir / f"{case_name}_{key}{ext}", soft[key].astype(np.float32), nii)
 
 
 def _postprocess_prediction(seg, config, device):

@@ -522,6 +522,38 @@ int dgtta_feature_logits_chunk_f64(const float *facc, int64_t member_stride, con
                                    int zs, int c0, int cg, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax end of the ensemble prediction: probabilities, confidence and entropy maps beside the label map.  The reference writes
+ * label maps only (dg_tta/tta/tta.py:404-413); the definitions are nnU-Net's `save_probabilities` ones from memory, UNPINNED.
+ * For voxel v, members m = 1..M, classes c = 0..C-1:
+ *   l_c(v)     = (sum_m w[m][c] . facc[m][v] + n(v) bsum[c]) / (M n(v))     the ensemble-MEAN window-normalised logit
+ *   p          = softmax_c(l) over ALL C classes;   label = argmax_c l_c, first maximum wins
+ *   confidence = p[label] = 1 / S,   S = sum_c exp(l_c - l_max)
+ *   entropy    = -sum_c p_c ln p_c = ln S - (sum_c (l_c - l_max) exp(l_c - l_max)) / S      (nats, in [0, ln C])
+ *   probs[k]   = p[sel[k]], k < K: 1 <= K <= 32 DISTINCT classes in any order (h_sel is a HOST array; a duplicate or a class outside
+ *                [0, C) is DGTTA_ERR_BADARG).  The K planes sum to at most 1: the rest is mass on classes that were not selected.
+ *
+ * dgtta_feature_head_softmax: all of it from the feature-space accumulators in one pass on the matrix cores - the inputs of
+ *   dgtta_feature_head_argmax and the same accumulation order, so label_out holds the integers that function writes.  label_out
+ *   int64 [V], conf_out / entropy_out fp32 [V], probs_out [K][V] (plane-major) of prob_dtype DGTTA_F32 or DGTTA_F16.  C <= 128 and
+ *   a weight image (M x 128-class blocks) that fits the LDS, else DGTTA_ERR_UNSUPPORTED: the caller takes the class-group path.
+ *
+ * dgtta_softmax_merge_f64 / dgtta_softmax_finalize_f64: the same quantities for the class-group export loop (beside
+ *   dgtta_argmax_merge_f64, which keeps producing the label).  vals double [V][cg] holds classes c0.. of the SUM over members of the
+ *   normalised logits (what the *_chunk_f64 functions return, resampled or not); l = scale * vals with scale = 1 / M.  run_max,
+ *   run_sum, run_dot double [V]: the running maximum, sum exp(l - max) and sum (l - max) exp(l - max), rescaled when the maximum
+ *   moves; initialised when first != 0.  stash double [K][V] receives l of every selected class that falls in this group (fp64:
+ *   8 K V bytes, 17 GB at 512^3 with K = 16) - every selected class must lie in one of the merged groups.  finalize turns the state
+ *   into conf_out, entropy_out and probs_out as above.
+ * ------------------------------------------------------------------------------------------- */
+int dgtta_feature_head_softmax(const float *facc, int64_t member_stride, const float *nsum, const float *w, const float *bsum, int M,
+                               int Cin, int C, int64_t V, const int *h_sel, int K, int prob_dtype, int64_t *label_out, float *conf_out,
+                               float *entropy_out, void *probs_out, void *stream);
+int dgtta_softmax_merge_f64(const double *vals, int64_t V, int cg, int c0, double scale, double *run_max, double *run_sum,
+                            double *run_dot, const int *h_sel, int K, double *stash, int first, void *stream);
+int dgtta_softmax_finalize_f64(const double *run_max, const double *run_sum, const double *run_dot, const double *stash, int64_t V,
+                               int K, int prob_dtype, float *conf_out, float *entropy_out, void *probs_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Surface-distance metrics of the folder evaluation (HD95, HD, ASSD, NSD; dg_tta_amd/tta/evaluation.py).  The reference
  * delegates evaluation to nnU-Net (dg_tta/tta/tta.py:447-470) and computes none of them: the definitions are the published
  * ones, UNPINNED.  Label maps are int64 [D][H][W].
