@@ -82,7 +82,8 @@ def test_conv_mfma_bf16(case):
     assert (y.float() - y_valu.float()).abs().max() < 1.0 / 64 * y_ref.abs().max() + 1e-3
 
 
-ROWS_CASES = [  # (B, cin, cout, D, H, W): ragged tiles, several channel blocks / K-chunks, batch 2, concat-style strides
+ROWS_CASES = [  # (B, cin, cout, D, H, W): ragged tiles, several channel blocks / K-chunks, batch 2 (dense rows, ld = C; concat-style
+               # strides: test_gpu_conv_exact.py::test_strided_rows)
     (1, 32, 32, 9, 13, 45), (2, 16, 64, 5, 17, 32), (1, 64, 96, 8, 8, 70), (1, 8, 32, 4, 8, 33),
     (2, 32, 64, 32, 32, 64), (1, 16, 128, 16, 64, 32), (1, 32, 32, 36, 40, 32),      # > 256 jobs: persistent loops, block decode
 ]
