@@ -115,6 +115,11 @@ SIGNATURES = {
     "dgtta_cc_label": (I, [P, P, I, I, I, I, I, P, P, SZ, P]),
     "dgtta_cc_sizes": (I, [P, I64, P, P]),
     "dgtta_cc_filter": (I, [P, P, I, P, P, I64, I, I, I64, P, P, P, SZ, P]),
+    "dgtta_holes_ws_bytes": (SZ, [I, I, I]),
+    "dgtta_holes_fill": (I, [P, I, I, I, I, P, P, P, P, SZ, P]),
+    "dgtta_holes_member": (I, [P, I, I, I, P, I, I, I, I, I, I, I, P, P]),
+    "dgtta_holes_apply": (I, [P, I, I, I, P, P, I, I, I, I, I, I, I64, I64, P, P]),
+    "dgtta_nonzero_mask": (I, [P, I, I64, P, P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // Connected-component post-processing of a predicted label map (tta/postprocessing.py): canonical multi-label component
 // labelling under 6 / 18 / 26 connectivity, component sizes, and the keep-largest / minimum-size filter.  Everything is integer
 // valued and canonical (a component is named by its smallest linear index), so the results do not depend on the scheduling.
+// The same labelling, run on the complement of a uint8 mask, fills holes (fill_label_holes, the non-zero crop of preprocessing.py).
 #include "conv_api.h"
 
 #include <limits.h>
@@ -23,6 +24,23 @@ __device__ __forceinline__ void load_groups(int *sgroup, const int *__restrict__
   }
 }
 __device__ __forceinline__ int group_of(int64_t m, const int *sgroup, int ntab) { return (uint64_t)m < (uint64_t)ntab ? sgroup[m] : 0; }
+
+// What the labelling kernels take a voxel's group from: a label map looked up in the group table staged in LDS (cc_label), or a
+// uint8 mask whose ZERO voxels are the one group (holes_fill labels the complement).
+struct MapGroups {
+  const int64_t *map;
+  const int *group;
+  int ntab;
+  static constexpr int LDS = CC_MAXTAB;
+  __device__ __forceinline__ void load(int *sgroup) const { load_groups(sgroup, group, ntab); }
+  __device__ __forceinline__ int at(int64_t i, const int *sgroup) const { return group_of(map[i], sgroup, ntab); }
+};
+struct MaskComplement {
+  const uint8_t *mask;
+  static constexpr int LDS = 1;
+  __device__ __forceinline__ void load(int *) const {}
+  __device__ __forceinline__ int at(int64_t i, const int *) const { return mask[i] == 0; }
+};
 
 // ============================================================================ union-find
 // parent[x] <= x always, and only members of x's component are ever stored there; the larger root hangs under the smaller, so
@@ -76,12 +94,13 @@ __device__ __forceinline__ void glb_union(int *p, int a, int b) {
 // other backward neighbours inside the tile are united in LDS, and every voxel writes the GLOBAL index of its local root
 // (-1 for background).  A pair (v, n) is left out when (v - 1, n - 1) exists and has the same group on both sides: v - 1 ~ v and
 // n - 1 ~ n by their runs, and (v - 1, n - 1) is a pair of the same offset, so inside a solid organ only run starts unite.
-__global__ __launch_bounds__(256) void cc_tile_kernel(const int64_t *__restrict__ map, const int *__restrict__ group, int ntab, int D,
-                                                      int H, int W, int nnb, int tiles_h, int tiles_w, int *__restrict__ parent) {
-  __shared__ int sgroup[CC_MAXTAB];
+template <class G>
+__global__ __launch_bounds__(256) void cc_tile_kernel(const G src, int D, int H, int W, int nnb, int tiles_h, int tiles_w,
+                                                      int *__restrict__ parent) {
+  __shared__ int sgroup[G::LDS];
   __shared__ int lpar[TV];
   __shared__ unsigned short sg[TV];
-  load_groups(sgroup, group, ntab);
+  src.load(sgroup);
   const int t = blockIdx.x;
   const int d0 = t / (tiles_w * tiles_h) * TD, h0 = t / tiles_w % tiles_h * TH, w0 = t % tiles_w * TW;
   __syncthreads();
@@ -89,7 +108,7 @@ __global__ __launch_bounds__(256) void cc_tile_kernel(const int64_t *__restrict_
   for (int r = threadIdx.x / WAVE; r < TD * TH; r += 256 / WAVE) {
     const int d = d0 + r / TH, h = h0 + r % TH, w = w0 + lane;
     int g = 0;
-    if (d < D && h < H && w < W) g = group_of(map[((int64_t)d * H + h) * W + w], sgroup, ntab);
+    if (d < D && h < H && w < W) g = src.at(((int64_t)d * H + h) * W + w, sgroup);
     const int gp = __shfl_up(g, 1, WAVE);
     const unsigned long long starts = __ballot(lane == 0 || g != gp) & (~0ull >> (WAVE - 1 - lane));
     sg[r * TW + lane] = (unsigned short)g;
@@ -125,10 +144,10 @@ __global__ __launch_bounds__(256) void cc_tile_kernel(const int64_t *__restrict_
 // Border pass: the pairs (voxel, backward neighbour) that lie in two tiles, united in the global forest.  A wave takes a row
 // (d, h) at a time.  A pair leaves the tile through a lower face or, with a diagonal offset, through the upper H or W face: in a
 // row on such a D or H face every voxel is looked at, in the other rows only the voxels on the W faces, two in 64.
-__global__ __launch_bounds__(256) void cc_border_kernel(const int64_t *__restrict__ map, const int *__restrict__ group, int ntab, int D,
-                                                        int H, int W, int nnb, int *parent) {
-  __shared__ int sgroup[CC_MAXTAB];
-  load_groups(sgroup, group, ntab);
+template <class G>
+__global__ __launch_bounds__(256) void cc_border_kernel(const G src, int D, int H, int W, int nnb, int *parent) {
+  __shared__ int sgroup[G::LDS];
+  src.load(sgroup);
   __syncthreads();
   const int lane = threadIdx.x & (WAVE - 1), faces = 2 * cdiv(W, TW);
   const int64_t rows = (int64_t)D * H;
@@ -139,7 +158,7 @@ __global__ __launch_bounds__(256) void cc_border_kernel(const int64_t *__restric
       const int w = whole ? j : (j >> 1) * TW + (j & 1) * (TW - 1);
       if (w >= W || (!whole && (j & 1) && nnb == 3)) continue;
       const int64_t i = row * W + w;
-      const int g = group_of(map[i], sgroup, ntab);
+      const int g = src.at(i, sgroup);
       if (!g) continue;
       for (int k = 0; k < nnb; ++k) {
         const int dd = CC_OFF[k][0], dh = CC_OFF[k][1], dw = CC_OFF[k][2];
@@ -147,8 +166,8 @@ __global__ __launch_bounds__(256) void cc_border_kernel(const int64_t *__restric
         if (nd < 0 || nh < 0 || nh >= H || nw < 0 || nw >= W) continue;
         if (nd / TD == d / TD && nh / TH == h / TH && nw / TW == w / TW) continue;    // the tile pass had this pair
         const int64_t n = i + ((int64_t)dd * H + dh) * W + dw;
-        if (group_of(map[n], sgroup, ntab) != g) continue;
-        if (k > 0 && w > 0 && nw > 0 && group_of(map[i - 1], sgroup, ntab) == g && group_of(map[n - 1], sgroup, ntab) == g) continue;
+        if (src.at(n, sgroup) != g) continue;
+        if (k > 0 && w > 0 && nw > 0 && src.at(i - 1, sgroup) == g && src.at(n - 1, sgroup) == g) continue;
         glb_union(parent, (int)i, (int)n);
       }
     }
@@ -249,6 +268,150 @@ __global__ void cc_clear_kernel(unsigned long long *winner, unsigned long long *
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ntab; i += gridDim.x * blockDim.x) winner[i] = 0, removed[i] = 0;
 }
 
+// the forest of the components of `src` in parent[]: the tile pass, then the border pass
+template <class G>
+int cc_forest(const G src, int D, int H, int W, int connectivity, int *parent, hipStream_t st) {
+  const int nnb = connectivity == 6 ? 3 : connectivity == 18 ? 9 : 13;
+  const int tiles_d = cdiv(D, TD), tiles_h = cdiv(H, TH), tiles_w = cdiv(W, TW);
+  hipLaunchKernelGGL(cc_tile_kernel<G>, dim3((unsigned)(tiles_d * tiles_h * tiles_w)), dim3(256), 0, st, src, D, H, W, nnb, tiles_h,
+                     tiles_w, parent);
+  DG_CHECK_LAUNCH("cc_tile_kernel");
+  hipLaunchKernelGGL(cc_border_kernel<G>, dim3(gs_blocks((int64_t)D * H * WAVE, 1 << 16)), dim3(256), 0, st, src, D, H, W, nnb, parent);
+  DG_CHECK_LAUNCH("cc_border_kernel");
+  return DGTTA_OK;
+}
+
+// ============================================================================ hole filling
+// A voxel outside the mask is ENCLOSED iff its component of the complement has no voxel on any of the six faces of the volume.
+// parent[] is the forest of the complement as the border pass left it (read only from here on, each in a launch of its own).
+__device__ __forceinline__ int hf_root(const int *__restrict__ parent, int64_t i) {
+  int p = parent[i], q;
+  while ((q = parent[p]) != p) p = q;
+  return p;
+}
+
+__global__ void hf_clear_kernel(unsigned long long *n_filled, int *box) {
+  if (threadIdx.x == 0) *n_filled = 0;
+  if (box && threadIdx.x < 6) box[threadIdx.x] = threadIdx.x < 3 ? INT_MAX : -1;
+}
+
+// open[root] = 1 for every component of the complement with a voxel on a face.  A wave takes a row (d, h): all of it when the row
+// lies on a D or H face, else its two ends.  Every writer stores the same byte.
+__global__ __launch_bounds__(256) void hf_mark_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent, int D, int H, int W,
+                                                      uint8_t *open) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t rows = (int64_t)D * H;
+  for (int64_t row = blockIdx.x * (256 / WAVE) + threadIdx.x / WAVE; row < rows; row += gridDim.x * (256 / WAVE)) {
+    const int d = (int)(row / H), h = (int)(row % H);
+    const bool whole = d == 0 || d == D - 1 || h == 0 || h == H - 1;
+    for (int j = lane; j < (whole ? W : 2); j += WAVE) {
+      const int64_t i = row * W + (whole ? j : j * (W - 1));
+      if (!mask[i]) open[hf_root(parent, i)] = 1;
+    }
+  }
+}
+
+// out = mask plus its enclosed voxels; n_filled counts the enclosed ones, box (optional) is the inclusive bounding box of out.
+// A wave takes a row (d, h) at a time, so the box of what it wrote is wave uniform: the ends along W come from a ballot.
+__global__ __launch_bounds__(256) void hf_fill_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent,
+                                                      const uint8_t *__restrict__ open, int D, int H, int W, uint8_t *__restrict__ out,
+                                                      unsigned long long *n_filled, int *box) {
+  __shared__ int sbox[6];
+  __shared__ unsigned scount;
+  if (threadIdx.x < 6) sbox[threadIdx.x] = threadIdx.x < 3 ? INT_MAX : -1;
+  if (threadIdx.x == 0) scount = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t rows = (int64_t)D * H;
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+  unsigned count = 0;
+  for (int64_t row = blockIdx.x * (256 / WAVE) + threadIdx.x / WAVE; row < rows; row += gridDim.x * (256 / WAVE)) {
+    const int d = (int)(row / H), h = (int)(row % H);
+    int wlo = INT_MAX, whi = -1;
+    for (int w0 = 0; w0 < W; w0 += WAVE) {
+      const int w = w0 + lane;
+      bool member = false, enclosed = false;
+      if (w < W) {
+        const int64_t i = row * W + w;
+        member = mask[i] != 0;
+        enclosed = !member && !open[hf_root(parent, i)];
+        out[i] = member || enclosed;
+      }
+      count += __popcll(__ballot(enclosed));
+      const unsigned long long set = __ballot(member || enclosed);
+      if (set) wlo = min(wlo, w0 + __ffsll((long long)set) - 1), whi = w0 + WAVE - 1 - __clzll(set);
+    }
+    if (whi >= 0) {
+      lo[0] = min(lo[0], d), hi[0] = max(hi[0], d);
+      lo[1] = min(lo[1], h), hi[1] = max(hi[1], h);
+      lo[2] = min(lo[2], wlo), hi[2] = max(hi[2], whi);
+    }
+  }
+  if (lane == 0) {
+    atomicAdd(&scount, count);
+    if (hi[0] >= 0)
+      for (int k = 0; k < 3; ++k) atomicMin(&sbox[k], lo[k]), atomicMax(&sbox[3 + k], hi[k]);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && scount) atomicAdd(n_filled, (unsigned long long)scount);
+  if (box && threadIdx.x < 3 && sbox[3] >= 0) atomicMin(&box[threadIdx.x], sbox[threadIdx.x]), atomicMax(&box[3 + threadIdx.x], sbox[3 + threadIdx.x]);
+}
+
+// mask = 1 where group[map] != 0 (labels and entries outside the table count as 0), inside the crop box
+__global__ __launch_bounds__(256) void hf_member_kernel(const int64_t *__restrict__ map, const int *__restrict__ group, int ntab, int H, int W,
+                                                        int d0, int h0, int w0, int ch, int cw, int64_t total, uint8_t *__restrict__ mask) {
+  __shared__ int sgroup[CC_MAXTAB];
+  load_groups(sgroup, group, ntab);
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cw;
+    const int d = d0 + (int)(r / ch), h = h0 + (int)(r % ch), w = w0 + (int)(i % cw);
+    mask[i] = group_of(map[((int64_t)d * H + h) * W + w], sgroup, ntab) != 0;
+  }
+}
+
+// inside the crop box, a voxel that `filled` has and `mask` has not (an enclosed one) and whose value is `background` becomes `label`
+__global__ __launch_bounds__(256) void hf_apply_kernel(int64_t *__restrict__ map, const uint8_t *__restrict__ mask,
+                                                       const uint8_t *__restrict__ filled, int H, int W, int d0, int h0, int w0, int ch, int cw,
+                                                       int64_t total, int64_t background, int64_t label, unsigned long long *count) {
+  __shared__ unsigned scount;
+  if (threadIdx.x == 0) scount = 0;
+  __syncthreads();
+  unsigned mine = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    if (!filled[i] || mask[i]) continue;
+    const int64_t r = i / cw;
+    const int d = d0 + (int)(r / ch), h = h0 + (int)(r % ch), w = w0 + (int)(i % cw);
+    int64_t *m = map + ((int64_t)d * H + h) * W + w;
+    if (*m == background) *m = label, ++mine;
+  }
+  if (mine) atomicAdd(&scount, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && scount) atomicAdd(count, (unsigned long long)scount);
+}
+
+// ============================================================================ non-zero mask of the crop
+// mask[i] = OR over c of (data[c][i] != 0), IEEE: NaN counts as non-zero and -0.0 as zero.  Four voxels per thread (one 16-byte
+// load per channel, one 4-byte store) where n and the pointers allow it, else one.
+template <bool VEC>
+__global__ __launch_bounds__(256) void nonzero_mask_kernel(const float *__restrict__ data, int C, int64_t n, uint8_t *__restrict__ mask) {
+  const int64_t items = VEC ? n / 4 : n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (VEC) {
+      unsigned any = 0;
+      for (int c = 0; c < C; ++c) {
+        const float4 x = *(const float4 *)(data + c * n + i * 4);
+        any |= (unsigned)(x.x != 0.f) | (unsigned)(x.y != 0.f) << 8 | (unsigned)(x.z != 0.f) << 16 | (unsigned)(x.w != 0.f) << 24;
+      }
+      *(unsigned *)(mask + i * 4) = any;
+    } else {
+      bool any = false;
+      for (int c = 0; c < C; ++c) any |= data[c * n + i] != 0.f;
+      mask[i] = any;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" size_t dgtta_cc_ws_bytes(int D, int H, int W) {
@@ -270,15 +433,9 @@ extern "C" int dgtta_cc_label(const int64_t *map, const int *group, int ntab, in
              dgtta_cc_ws_bytes(D, H, W));
   DG_REQUIRE(((uintptr_t)ws & 3) == 0, DGTTA_ERR_BADARG, "cc_label: workspace must be 4-byte aligned");
   const hipStream_t st = (hipStream_t)stream;
-  const int nnb = connectivity == 6 ? 3 : connectivity == 18 ? 9 : 13;
-  const int tiles_d = cdiv(D, TD), tiles_h = cdiv(H, TH), tiles_w = cdiv(W, TW);
   int *parent = (int *)ws;
-  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)(tiles_d * tiles_h * tiles_w)), dim3(256), 0, st, map, group, ntab, D, H, W, nnb,
-                     tiles_h, tiles_w, parent);
-  DG_CHECK_LAUNCH("cc_tile_kernel");
-  hipLaunchKernelGGL(cc_border_kernel, dim3(gs_blocks((int64_t)D * H * WAVE, 1 << 16)), dim3(256), 0, st, map, group, ntab, D, H, W, nnb,
-                     parent);
-  DG_CHECK_LAUNCH("cc_border_kernel");
+  const int rc = cc_forest(MapGroups{map, group, ntab}, D, H, W, connectivity, parent, st);
+  if (rc != DGTTA_OK) return rc;
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(gs_blocks(total, 1 << 16)), dim3(256), 0, st, parent, total, cc);
   DG_CHECK_LAUNCH("cc_flatten_kernel");
   return DGTTA_OK;
@@ -315,5 +472,88 @@ extern "C" int dgtta_cc_filter(const int64_t *map, const int *group, int ntab, c
   hipLaunchKernelGGL(cc_filter_kernel, dim3(gs_blocks(n, 4096)), dim3(256), 0, st, map, group, ntab, cc, size, n, keep_largest, min_voxels,
                      background, winner, out, (unsigned long long *)removed);
   DG_CHECK_LAUNCH("cc_filter_kernel");
+  return DGTTA_OK;
+}
+
+// workspace of holes_fill: the forest (int32 per voxel), then the open flag (a byte per voxel)
+static size_t holes_forest_bytes(int D, int H, int W) { return align_up((size_t)D * (size_t)H * (size_t)W * sizeof(int), 256); }
+
+extern "C" size_t dgtta_holes_ws_bytes(int D, int H, int W) {
+  if (D <= 0 || H <= 0 || W <= 0) return 0;
+  return holes_forest_bytes(D, H, W) + align_up((size_t)D * (size_t)H * (size_t)W, 256);
+}
+
+extern "C" int dgtta_holes_fill(const uint8_t *mask, int D, int H, int W, int connectivity, uint8_t *out, int64_t *n_filled, int *box,
+                                void *ws, size_t ws_bytes, void *stream) {
+  DG_REQUIRE(mask && out && n_filled && ws && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "holes_fill: bad args");
+  DG_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, DGTTA_ERR_BADARG, "holes_fill: connectivity %d (6, 18 or 26)",
+             connectivity);
+  const int64_t total = (int64_t)D * H * W;
+  DG_REQUIRE(total < INT_MAX, DGTTA_ERR_UNSUPPORTED, "holes_fill: %d x %d x %d voxels (fewer than 2^31 - 1: components are named by int32)",
+             D, H, W);
+  DG_REQUIRE(ws_bytes >= dgtta_holes_ws_bytes(D, H, W), DGTTA_ERR_WORKSPACE, "holes_fill: workspace %zu < %zu", ws_bytes,
+             dgtta_holes_ws_bytes(D, H, W));
+  DG_REQUIRE(((uintptr_t)ws & 3) == 0 && ((uintptr_t)n_filled & 7) == 0 && ((uintptr_t)box & 3) == 0, DGTTA_ERR_BADARG,
+             "holes_fill: ws and box must be 4-byte aligned, n_filled 8-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  int *parent = (int *)ws;
+  uint8_t *open = (uint8_t *)ws + holes_forest_bytes(D, H, W);
+  const hipError_t e = hipMemsetAsync(open, 0, (size_t)total, st);
+  DG_REQUIRE(e == hipSuccess, DGTTA_ERR_LAUNCH, "holes_fill: memset failed: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(hf_clear_kernel, dim3(1), dim3(WAVE), 0, st, (unsigned long long *)n_filled, box);
+  DG_CHECK_LAUNCH("hf_clear_kernel");
+  const int rc = cc_forest(MaskComplement{mask}, D, H, W, connectivity, parent, st);
+  if (rc != DGTTA_OK) return rc;
+  const int row_blocks = gs_blocks((int64_t)D * H * WAVE, 1 << 16);
+  hipLaunchKernelGGL(hf_mark_kernel, dim3(row_blocks), dim3(256), 0, st, mask, parent, D, H, W, open);
+  DG_CHECK_LAUNCH("hf_mark_kernel");
+  hipLaunchKernelGGL(hf_fill_kernel, dim3(row_blocks), dim3(256), 0, st, mask, parent, open, D, H, W, out, (unsigned long long *)n_filled, box);
+  DG_CHECK_LAUNCH("hf_fill_kernel");
+  return DGTTA_OK;
+}
+
+// the crop box (d0, h0, w0, cd, ch, cw) must lie inside the volume
+static bool holes_box_ok(int D, int H, int W, int d0, int h0, int w0, int cd, int ch, int cw) {
+  return D > 0 && H > 0 && W > 0 && d0 >= 0 && h0 >= 0 && w0 >= 0 && cd > 0 && ch > 0 && cw > 0 && cd <= D - d0 && ch <= H - h0 && cw <= W - w0;
+}
+
+extern "C" int dgtta_holes_member(const int64_t *map, int D, int H, int W, const int *group, int ntab, int d0, int h0, int w0, int cd,
+                                  int ch, int cw, uint8_t *mask, void *stream) {
+  DG_REQUIRE(map && group && mask && ntab > 0, DGTTA_ERR_BADARG, "holes_member: bad args");
+  DG_REQUIRE(ntab <= CC_MAXTAB, DGTTA_ERR_UNSUPPORTED, "holes_member: group table of %d entries (at most %d)", ntab, CC_MAXTAB);
+  DG_REQUIRE(holes_box_ok(D, H, W, d0, h0, w0, cd, ch, cw), DGTTA_ERR_BADARG, "holes_member: box (%d, %d, %d) + (%d, %d, %d) outside %d x %d x %d",
+             d0, h0, w0, cd, ch, cw, D, H, W);
+  const int64_t total = (int64_t)cd * ch * cw;
+  hipLaunchKernelGGL(hf_member_kernel, dim3(gs_blocks(total, 4096)), dim3(256), 0, (hipStream_t)stream, map, group, ntab, H, W, d0, h0, w0,
+                     ch, cw, total, mask);
+  DG_CHECK_LAUNCH("hf_member_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_holes_apply(int64_t *map, int D, int H, int W, const uint8_t *mask, const uint8_t *filled, int d0, int h0, int w0,
+                                 int cd, int ch, int cw, int64_t background, int64_t label, int64_t *count, void *stream) {
+  DG_REQUIRE(map && mask && filled && count, DGTTA_ERR_BADARG, "holes_apply: bad args");
+  DG_REQUIRE(((uintptr_t)count & 7) == 0, DGTTA_ERR_BADARG, "holes_apply: count must be 8-byte aligned");
+  DG_REQUIRE(holes_box_ok(D, H, W, d0, h0, w0, cd, ch, cw), DGTTA_ERR_BADARG, "holes_apply: box (%d, %d, %d) + (%d, %d, %d) outside %d x %d x %d",
+             d0, h0, w0, cd, ch, cw, D, H, W);
+  const hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), st);
+  DG_REQUIRE(e == hipSuccess, DGTTA_ERR_LAUNCH, "holes_apply: memset failed: %s", hipGetErrorString(e));
+  const int64_t total = (int64_t)cd * ch * cw;
+  hipLaunchKernelGGL(hf_apply_kernel, dim3(gs_blocks(total, 4096)), dim3(256), 0, st, map, mask, filled, H, W, d0, h0, w0, ch, cw, total,
+                     background, label, (unsigned long long *)count);
+  DG_CHECK_LAUNCH("hf_apply_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_nonzero_mask(const float *data, int C, int64_t n, uint8_t *mask, void *stream) {
+  DG_REQUIRE(data && mask && C > 0 && n > 0, DGTTA_ERR_BADARG, "nonzero_mask: bad args");
+  DG_REQUIRE(((uintptr_t)data & 3) == 0, DGTTA_ERR_BADARG, "nonzero_mask: data must be 4-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  if (n % 4 == 0 && ((uintptr_t)data & 15) == 0 && ((uintptr_t)mask & 3) == 0)
+    hipLaunchKernelGGL(nonzero_mask_kernel<true>, dim3(gs_blocks(n / 4, 1 << 16)), dim3(256), 0, st, data, C, n, mask);
+  else
+    hipLaunchKernelGGL(nonzero_mask_kernel<false>, dim3(gs_blocks(n, 1 << 16)), dim3(256), 0, st, data, C, n, mask);
+  DG_CHECK_LAUNCH("nonzero_mask_kernel");
   return DGTTA_OK;
 }

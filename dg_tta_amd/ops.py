@@ -847,6 +847,86 @@ def cc_filter(label_map, group, cc, size, keep_largest=True, min_voxels=0, backg
     return res, removed
 
 
+# ------------------------------------------------------------------------------------------------ hole filling
+def _mask3(t, name, what="mask"):
+    require_cuda(t)
+    if t.dim() != 3 or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"{name}: contiguous uint8 {what} [D,H,W] expected")
+    return t
+
+
+def holes_ws_bytes(d, h, w):
+    return int(_lib.load().dgtta_holes_ws_bytes(int(d), int(h), int(w)))
+
+
+def fill_holes(mask, connectivity=6, out=None, ws=None, return_box=False):
+    """(filled uint8 [D,H,W], n_filled) of a uint8 membership mask (non-zero = member): the mask plus its enclosed voxels, those
+    whose component of the complement under `connectivity` (6, 18, 26) touches none of the six faces of the volume
+    (csrc/components.hip).  Connectivity 6 is scipy.ndimage.binary_fill_holes.  n_filled: the number of enclosed voxels, a 0-dim
+    int64 tensor on the device (reading it synchronises).  `out` (uint8, at least D*H*W elements) and `ws` (uint8, at least
+    holes_ws_bytes(D,H,W)) let a caller reuse its buffers.  return_box: a third result, int32 [6] on the device = the inclusive
+    bounding box of `filled` (lo d, h, w, hi d, h, w; lo > hi when it is empty)."""
+    _mask3(mask, "fill_holes")
+    if isinstance(connectivity, bool) or connectivity not in (6, 18, 26):
+        raise ValueError(f"fill_holes: connectivity {connectivity!r} (6, 18 or 26)")
+    lib = _lib.load()
+    d, h, w = mask.shape
+    n = d * h * w
+    filled = (torch.empty(n, dtype=torch.uint8, device=mask.device) if out is None
+              else _cc_buffer(out, n, torch.uint8, mask.device, "fill_holes", "out")).view(d, h, w)
+    nbytes = lib.dgtta_holes_ws_bytes(d, h, w)
+    if ws is None:
+        ws = _ws(nbytes, mask.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < nbytes or ws.device != mask.device:
+        raise ValueError("fill_holes: ws must be a uint8 buffer of at least holes_ws_bytes(D,H,W) bytes on the mask's device")
+    n_filled = torch.empty((), dtype=torch.int64, device=mask.device)
+    box = torch.empty(6, dtype=torch.int32, device=mask.device) if return_box else None
+    check(lib.dgtta_holes_fill(ptr(mask), d, h, w, int(connectivity), ptr(filled), ptr(n_filled), ptr(box), ptr(ws), ws.numel(),
+                               stream_of(mask.device)), "dgtta_holes_fill")
+    return (filled, n_filled, box) if return_box else (filled, n_filled)
+
+
+def holes_member(label_map, group, box):
+    """uint8 [cd,ch,cw]: 1 where group[label] != 0 (the table rule of cc_label) inside the crop box (d0, h0, w0, cd, ch, cw) of an
+    int64 label map."""
+    _label_map3(label_map, "holes_member")
+    _group_table(group, label_map, "holes_member")
+    d, h, w = label_map.shape
+    d0, h0, w0, cd, ch, cw = (int(v) for v in box)
+    mask = torch.empty((cd, ch, cw), dtype=torch.uint8, device=label_map.device)
+    check(_lib.load().dgtta_holes_member(ptr(label_map), d, h, w, ptr(group), group.numel(), d0, h0, w0, cd, ch, cw, ptr(mask),
+                                         stream_of(label_map.device)), "dgtta_holes_member")
+    return mask
+
+
+def holes_apply(label_map, mask, filled, box, background, label):
+    """IN PLACE on the int64 label map: inside the crop box (d0, h0, w0, cd, ch, cw) a voxel that `filled` has and `mask` has not
+    (both uint8 [cd,ch,cw]) and whose value is `background` becomes `label`.  Returns the number of voxels changed, a 0-dim
+    int64 tensor on the device."""
+    _label_map3(label_map, "holes_apply")
+    d, h, w = label_map.shape
+    d0, h0, w0, cd, ch, cw = (int(v) for v in box)
+    for t, what in ((mask, "mask"), (filled, "filled")):
+        _mask3(t, "holes_apply", what)
+        if tuple(t.shape) != (cd, ch, cw) or t.device != label_map.device:
+            raise ValueError(f"holes_apply: {what} must have the box's shape {(cd, ch, cw)} on the map's device")
+    count = torch.empty((), dtype=torch.int64, device=label_map.device)
+    check(_lib.load().dgtta_holes_apply(ptr(label_map), d, h, w, ptr(mask), ptr(filled), d0, h0, w0, cd, ch, cw, int(background),
+                                        int(label), ptr(count), stream_of(label_map.device)), "dgtta_holes_apply")
+    return count
+
+
+def nonzero_mask(data):
+    """uint8 [*spatial] = OR over the channels of (data[c] != 0) for float32 data [C, *spatial]: IEEE comparison, so NaN counts as
+    non-zero and -0.0 as zero, as numpy's `!=` does."""
+    require_cuda(data)
+    if data.dim() < 2 or data.dtype != torch.float32 or not data.is_contiguous() or data.numel() == 0:
+        raise ValueError("nonzero_mask: contiguous float32 data [C, ...] expected")
+    mask = torch.empty(data.shape[1:], dtype=torch.uint8, device=data.device)
+    check(_lib.load().dgtta_nonzero_mask(ptr(data), data.shape[0], mask.numel(), ptr(mask), stream_of(data.device)), "dgtta_nonzero_mask")
+    return mask
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

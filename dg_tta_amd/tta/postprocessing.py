@@ -15,7 +15,12 @@ Labels must lie in [0, 1024) to be looked at (the kernels' table size); volumes 
 Plan keys (all optional, none is written by prepare_tta): `postprocessing_keep_largest_component` (false | true | "foreground" |
 a list of indices into / names from `optimized_labels`, a nested list being a region), `postprocessing_min_component_voxels`
 (int, default 0), `postprocessing_connectivity` (6 | 18 | 26, default 26).  With one of the first two set, run_tta filters every
-prediction before it is written."""
+prediction before it is written.
+
+Hole filling (fill_label_holes, the same file of kernels run on the complement of an organ) is the other half: a pocket of
+background inside an organ becomes the organ.  Plan keys `postprocessing_fill_holes` (false | true | a list as above; "foreground"
+names no label to fill with and is refused) and `postprocessing_fill_holes_connectivity` (6 | 18 | 26, default 6 = scipy's
+binary_fill_holes); run_tta fills after it has filtered.  UNPINNED as well."""
 import numpy as np
 import torch
 
@@ -144,34 +149,90 @@ def remove_all_but_largest_component_from_segmentation(segmentation, labels_or_r
     return ret
 
 
+def fill_label_holes(label_map, labels_or_regions=None, connectivity=6, background=0, device="cuda"):
+    """(filled map, {group: filled voxels}).  The complement of keep_largest_components: a pocket of `background` inside an organ
+    becomes the organ.  This project's definition, UNPINNED against any implementation: the entries (an int, or a tuple of ints
+    = a region; None = every non-zero label present, ascending) are processed in the listed order, each on the result of the one
+    before.  For an entry with labels L, S = isin(map, L); a voxel outside S is enclosed iff its component of the complement of S
+    under `connectivity` (6 = scipy.ndimage.binary_fill_holes, 18, 26) touches no face of the volume; every enclosed voxel whose
+    value is `background` becomes the entry's FIRST label, enclosed voxels of another label (a lesion inside the organ) keep it.
+    Labels outside [0, 1024) are never members of S.  Containers, dtypes and the dictionary's keys as in keep_largest_components.
+    Each entry runs inside the bounding box of L, whose faces stand for the volume's: everything outside the box is complement
+    and reaches the border, so the result is the whole volume's."""
+    connectivity = _check_connectivity(connectivity)
+    if isinstance(labels_or_regions, str):
+        raise ValueError(f"postprocessing: {labels_or_regions!r} names no label to fill with; list labels or regions")
+    seg, back = _to_device(label_map, device)
+    boxes = ops.label_bboxes(seg, seg, MAX_LABELS).cpu().numpy()
+    if labels_or_regions is None:
+        entries = [(l, (l,)) for l in range(1, MAX_LABELS) if boxes[l, 0] <= boxes[l, 3]]
+    else:
+        entries = _entries(labels_or_regions)
+    # the entries are applied in place: never to the caller's memory (an int64 tensor on the device comes through as it is)
+    out = seg.clone() if isinstance(label_map, torch.Tensor) and seg.data_ptr() == label_map.data_ptr() else seg
+    ws, counts = None, {}
+    for key, labels in entries:
+        present = [l for l in labels if boxes[l, 0] <= boxes[l, 3]]
+        if not present:         # nothing of L in the map: filling changes no box, so the boxes taken before the loop hold
+            counts[key] = 0
+            continue
+        lo, hi = boxes[present, :3].min(0), boxes[present, 3:].max(0)
+        box = (*lo.tolist(), *(hi - lo + 1).tolist())
+        table = torch.zeros(max(labels) + 1, dtype=torch.int32)
+        table[list(labels)] = 1
+        mask = ops.holes_member(out, table.to(out.device), box)
+        nbytes = ops.holes_ws_bytes(*mask.shape)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+        filled, _ = ops.fill_holes(mask, connectivity, ws=ws)
+        counts[key] = ops.holes_apply(out, mask, filled, box, background, labels[0])
+    return back(out), {key: int(v) for key, v in counts.items()}
+
+
 # ---------------------------------------------------------------------------------------------- plan keys (host logic)
-def postprocessing_groups(config):
-    """The `labels_or_regions` of keep_largest_components that the plan key `postprocessing_keep_largest_component` asks for, in the
-    index space of `optimized_labels` (the label values of a written prediction): None for false / absent, every foreground index
-    for true, "foreground", or the listed entries - an index or a name, a nested list of them being a region."""
-    key = config.get("postprocessing_keep_largest_component", False)
+def _plan_groups(config, key_name, foreground):
+    """The `labels_or_regions` that the plan key `key_name` asks for, in the index space of `optimized_labels` (the label values of
+    a written prediction): None for false / absent, every foreground index for true, "foreground" where the key takes it, or the
+    listed entries - an index or a name, a nested list of them being a region."""
+    key = config.get(key_name, False)
     names = list(config["optimized_labels"])
     if key is None or key is False:
         return None
     if key is True:
         return list(range(1, len(names)))
-    if key == "foreground":
+    if key == "foreground" and foreground:
         return "foreground"
     if not isinstance(key, (list, tuple)):
-        raise ValueError(f"postprocessing_keep_largest_component: {key!r} (false, true, \"foreground\" or a list expected)")
+        takes = "false, true, \"foreground\" or a list" if foreground else "false, true or a list"
+        raise ValueError(f"{key_name}: {key!r} ({takes} expected)")
 
     def index(x):
         if isinstance(x, str):
             if x not in names:
-                raise ValueError(f"postprocessing_keep_largest_component: label name {x!r} is not in optimized_labels {names}")
+                raise ValueError(f"{key_name}: label name {x!r} is not in optimized_labels {names}")
             return names.index(x)
         if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < len(names):
-            raise ValueError(f"postprocessing_keep_largest_component: label index {x!r} is not in optimized_labels "
-                             f"(0 to {len(names) - 1})")
+            raise ValueError(f"{key_name}: label index {x!r} is not in optimized_labels (0 to {len(names) - 1})")
         return int(x)
     groups = [tuple(index(x) for x in e) if isinstance(e, (list, tuple)) else index(e) for e in key]
     _entries(groups)        # duplicates are reported here, not at the first case
     return groups
+
+
+def postprocessing_groups(config):
+    """The `labels_or_regions` of keep_largest_components that the plan key `postprocessing_keep_largest_component` asks for."""
+    return _plan_groups(config, "postprocessing_keep_largest_component", foreground=True)
+
+
+def fill_holes_settings(config):
+    """None when the plan asks for no hole filling, else the keyword arguments of fill_label_holes: `postprocessing_fill_holes`
+    (false | true | a list as for the keep-largest key; "foreground" names no label to fill with and is refused) and
+    `postprocessing_fill_holes_connectivity` (6 | 18 | 26, default 6)."""
+    connectivity = _check_connectivity(config.get("postprocessing_fill_holes_connectivity", 6))
+    groups = _plan_groups(config, "postprocessing_fill_holes", foreground=False)
+    if groups is None:
+        return None
+    return dict(labels_or_regions=groups, connectivity=connectivity)
 
 
 def postprocessing_settings(config):

@@ -6,8 +6,10 @@ foreground intensity statistics, ZScoreNormalization), resampling to the configu
 orders (image cubic spline, labels linear per label with a 0.5 threshold, nearest along a strongly anisotropic axis).
 
 The resampling - the only part with real arithmetic volume - runs on the GPU (csrc/resample.hip: separable spline passes
-with scipy.ndimage.zoom / skimage.resize semantics, float64 like the reference); cropping and normalisation are a few
-numpy passes on the host, as in nnU-Net.  nnunetv2 is not installed here: restated from its published behaviour, parity
+with scipy.ndimage.zoom / skimage.resize semantics, float64 like the reference), and so do the non-zero mask of the crop, its
+hole filling and its box (crop_to_nonzero_gpu, csrc/components.hip; the host crop_to_nonzero stays as nnU-Net has it and is
+what the GPU crop is tested against, element for element); normalisation is a few numpy passes on the host, as in
+nnU-Net.  nnunetv2 is not installed here: restated from its published behaviour, parity
 checked against oracle/preprocessing.py (scipy) only.  Reading: NIfTI-1 via nifti_io (SimpleITK order [z,y,x])."""
 import numpy as np
 import torch
@@ -46,6 +48,30 @@ def crop_to_nonzero(data, seg, nonzero_label=-1):
     sl = tuple(slice(a, b) for a, b in bbox)
     data = data[(slice(None),) + sl]
     mask = mask[sl][None]
+    if seg is not None:
+        seg = seg[(slice(None),) + sl].copy()
+        seg[(seg == 0) & (~mask)] = nonzero_label
+    else:
+        seg = np.where(mask, 0, nonzero_label).astype(np.int8)
+    return data, seg, bbox
+
+
+def crop_to_nonzero_gpu(data, seg, device, nonzero_label=-1):
+    """crop_to_nonzero with the mask, its hole filling and its bounding box on the GPU (csrc/components.hip: ops.nonzero_mask,
+    ops.fill_holes); equal to the host function in every element and dtype, by test.  data: float32 numpy [C,X,Y,Z]; only the
+    mask inside the box comes back from the device, data and seg are cut on the host."""
+    if not isinstance(data, np.ndarray) or data.dtype != np.float32 or data.ndim != 4:
+        raise ValueError(f"crop_to_nonzero_gpu: float32 numpy data [C,X,Y,Z] expected, got {getattr(data, 'shape', None)} "
+                         f"{getattr(data, 'dtype', type(data))}")
+    raw = ops.nonzero_mask(torch.from_numpy(np.ascontiguousarray(data)).to(device))
+    filled, _, box = ops.fill_holes(raw, 6, return_box=True)
+    box = box.cpu().tolist()
+    if box[0] > box[3]:
+        raise ValueError("crop_to_nonzero_gpu: every voxel of the case is zero, there is no box to crop to")
+    bbox = [[box[k], box[3 + k] + 1] for k in range(3)]
+    sl = tuple(slice(a, b) for a, b in bbox)
+    data = data[(slice(None),) + sl]
+    mask = filled[sl].contiguous().cpu().numpy().astype(bool)[None]
     if seg is not None:
         seg = seg[(slice(None),) + sl].copy()
         seg[(seg == 0) & (~mask)] = nonzero_label
@@ -142,7 +168,11 @@ def run_case_npy(data, seg, spacing, plans, configuration, device="cuda"):
         seg = seg.transpose([0] + [i + 1 for i in tf])
     spacing = [float(spacing[i]) for i in tf]
     props = {"spacing": spacing, "shape_before_cropping": tuple(data.shape[1:])}
-    data, seg, bbox = crop_to_nonzero(data, seg)
+    # the hole-filling kernels name components by int32; a larger volume (there is none in practice) takes nnU-Net's host passes
+    if torch.device(device).type == "cuda" and data.ndim == 4 and data[0].size < 2 ** 31 - 1:
+        data, seg, bbox = crop_to_nonzero_gpu(data, seg, device)
+    else:
+        data, seg, bbox = crop_to_nonzero(data, seg)
     props["bbox_used_for_cropping"] = bbox
     props["shape_after_cropping_and_before_resampling"] = tuple(data.shape[1:])
     target = list(conf["spacing"])

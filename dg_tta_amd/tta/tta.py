@@ -692,18 +692,22 @@ def _save_soft_outputs(label_dir, case_name, ext, soft, optimized_labels, nii, s
 
 
 def _postprocess_prediction(seg, config, device):
-    """The connected-component filter that the plan keys `postprocessing_*` ask for (postprocessing.py), applied to a mapped
-    prediction [D,H,W]; `seg` itself, without a GPU call, when none of them asks for anything."""
-    from .postprocessing import keep_largest_components, postprocessing_settings
-    settings = postprocessing_settings(config)
-    if settings is None:
-        return seg
-    out, removed = keep_largest_components(seg, device=device, **settings)
+    """The connected-component filter and then the hole filling that the plan keys `postprocessing_*` ask for (postprocessing.py),
+    applied to a mapped prediction [D,H,W]; `seg` itself, without a GPU call, when none of them asks for anything."""
+    from .postprocessing import fill_holes_settings, fill_label_holes, keep_largest_components, postprocessing_settings
+    settings, fill = postprocessing_settings(config), fill_holes_settings(config)
     names = config["optimized_labels"]
-    print("Post-processing removed voxels: " + ", ".join(
-        f"{'+'.join(names[l] for l in k) if isinstance(k, tuple) else names[k] if isinstance(k, int) else k}={v}"
-        for k, v in removed.items()))
-    return out
+
+    def per_group(counts):
+        return ", ".join(f"{'+'.join(names[l] for l in k) if isinstance(k, tuple) else names[k] if isinstance(k, int) else k}={v}"
+                         for k, v in counts.items())
+    if settings is not None:
+        seg, removed = keep_largest_components(seg, device=device, **settings)
+        print("Post-processing removed voxels: " + per_group(removed))
+    if fill is not None:
+        seg, filled = fill_label_holes(seg, device=device, **fill)
+        print("Post-processing filled voxels: " + per_group(filled))
+    return seg
 
 
 def evaluate_run(save_path, config, modifier_fn_module, device="cuda"):

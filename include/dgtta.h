@@ -620,6 +620,35 @@ int dgtta_cc_sizes(const int *cc, int64_t n, int *size, void *stream);
 int dgtta_cc_filter(const int64_t *map, const int *group, int ntab, const int *cc, const int *size, int64_t n, int keep_largest,
                     int min_voxels, int64_t background, int64_t *out, int64_t *removed, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Hole filling (csrc/components.hip): the same labelling on the COMPLEMENT of a uint8 membership mask [D][H][W] (non-zero =
+ * member).  A voxel outside the mask is enclosed iff its component of the complement under `connectivity` has no voxel on any
+ * of the six faces of the volume; an axis of extent 1 or 2 therefore encloses nothing.  With connectivity 6 this is
+ * scipy.ndimage.binary_fill_holes (18 / 26: structure = generate_binary_structure(3, 2) / (3, 3)); equal to scipy's by test.
+ * n = D*H*W must be below 2^31 - 1.
+ *
+ * holes_fill: out uint8 [n] = 1 on the mask and its enclosed voxels, else 0; must not overlap mask.  n_filled (8-byte
+ * aligned) = the number of enclosed voxels.  box: NULL, or int32 [6] = the inclusive bounding box of out (lo d, h, w, hi d,
+ * h, w; lo > hi when out is empty).  Both are cleared here.  ws: dgtta_holes_ws_bytes(D, H, W) bytes, 4-byte aligned (the
+ * forest and one flag byte per voxel).  Integer valued: the same on every run.
+ *
+ * holes_member / holes_apply: one entry of fill_label_holes (tta/postprocessing.py) inside a crop box (d0, h0, w0) +
+ * (cd, ch, cw) of an int64 label map, whose faces then count as the volume's.  member: mask uint8 [cd][ch][cw] = 1 where
+ * group[map] != 0 (the table rule of cc_label).  apply: IN PLACE, a voxel of the box with filled != 0, mask == 0 and
+ * map == background becomes `label`; count (8-byte aligned, cleared here) = the voxels changed.
+ *
+ * nonzero_mask: mask uint8 [n] = OR over c of (data[c][i] != 0) for float32 data [C][n], with IEEE comparison: NaN counts as
+ * non-zero, -0.0 as zero (numpy's `!=`).  The mask of nnU-Net's crop_to_nonzero before its holes are filled.
+ * ------------------------------------------------------------------------------------------- */
+size_t dgtta_holes_ws_bytes(int D, int H, int W);
+int dgtta_holes_fill(const uint8_t *mask, int D, int H, int W, int connectivity, uint8_t *out, int64_t *n_filled, int *box, void *ws,
+                     size_t ws_bytes, void *stream);
+int dgtta_holes_member(const int64_t *map, int D, int H, int W, const int *group, int ntab, int d0, int h0, int w0, int cd, int ch,
+                       int cw, uint8_t *mask, void *stream);
+int dgtta_holes_apply(int64_t *map, int D, int H, int W, const uint8_t *mask, const uint8_t *filled, int d0, int h0, int w0, int cd,
+                      int ch, int cw, int64_t background, int64_t label, int64_t *count, void *stream);
+int dgtta_nonzero_mask(const float *data, int C, int64_t n, uint8_t *mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
