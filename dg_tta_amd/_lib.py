@@ -46,6 +46,9 @@ SIGNATURES = {
     "dgtta_adamw_step": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I64), I, F, F, F, F, F,
                              I, F, P, P]),
     "dgtta_grads_nonfinite": (I, [C.POINTER(P), C.POINTER(I64), I, P, P]),
+    "dgtta_grad_sumsq_ws_bytes": (SZ, [I64, I]),
+    "dgtta_grad_sumsq": (I, [C.POINTER(P), C.POINTER(I64), I, P, P, SZ, P]),
+    "dgtta_sgd_step": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I64), I, F, F, F, I, I, F, P, F, P, P]),
     "dgtta_conv3d_packed_bytes": (SZ, [I, I, I]),
     "dgtta_conv3d_pack_weights": (I, [P, P, I, I, I, I, I, P]),
     "dgtta_conv3d_stats_bytes": (SZ, [I, I, I, I, I]),

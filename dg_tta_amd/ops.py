@@ -570,6 +570,70 @@ def grads_nonfinite(grads, flag):
     check(lib.dgtta_grads_nonfinite(hg, hn, n, ptr(flag), stream_of(grads[0].device)), "dgtta_grads_nonfinite")
 
 
+# ------------------------------------------------------------------------------------------------ clipped SGD
+def grad_sumsq_ws_bytes(total_elements, ntensors):
+    return int(_lib.load().dgtta_grad_sumsq_ws_bytes(int(total_elements), int(ntensors)))
+
+
+def grad_sumsq(grads, out=None, ws=None):
+    """Sum of squares of every element of `grads` (fp32 GPU tensors, None entries skipped) -> fp32 device scalar `out`;
+    bit-reproducible (csrc/sgd.hip).  ws: uint8 workspace of grad_sumsq_ws_bytes(total elements, len) bytes, allocated
+    when not given."""
+    lib = _lib.load()
+    grads = [g for g in grads if g is not None]
+    require_cuda(*grads)
+    require_cuda(out, ws)
+    if not grads and out is None:
+        raise ValueError("grad_sumsq: no gradient and no `out` to tell the device from")
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError("grad_sumsq: contiguous fp32 gradients expected")
+    device = grads[0].device if grads else out.device
+    n = len(grads)
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=device)
+    elif out.dtype != torch.float32 or out.numel() != 1:
+        raise ValueError("grad_sumsq: `out` is one fp32 element")
+    need = grad_sumsq_ws_bytes(sum(g.numel() for g in grads), n)
+    if ws is None:
+        ws = _ws(need, device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"grad_sumsq: `ws` is a contiguous uint8 tensor of at least {need} bytes")
+    hg = (C.c_void_p * max(n, 1))(*[g.data_ptr() for g in grads])
+    hn = (C.c_int64 * max(n, 1))(*[g.numel() for g in grads])
+    check(lib.dgtta_grad_sumsq(hg, hn, n, ptr(out), ptr(ws), ws.numel(), stream_of(device)), "dgtta_grad_sumsq")
+    return out
+
+
+def sgd_step(params, grads, bufs, lr, momentum=0.99, weight_decay=3e-5, nesterov=True, first_step=False, grad_scale=1.0,
+             sumsq=None, max_norm=12.0, skip_flag=None):
+    """One multi-tensor clipped SGD step (csrc/sgd.hip; formula in include/dgtta.h).  sumsq: the device scalar of
+    grad_sumsq over ALL gradients of the step (None: no clipping); first_step: `bufs` are written, not read; skipped on
+    the device when skip_flag (int32 device scalar) is non-zero."""
+    lib = _lib.load()
+    n = len(params)
+    if n == 0:
+        return
+    require_cuda(*params)
+    require_cuda(*grads)
+    require_cuda(*bufs)
+    require_cuda(sumsq, skip_flag)
+    for p, g, b in zip(params, grads, bufs):
+        for t in (p, g, b):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError("sgd_step: contiguous fp32 tensors expected")
+        if (g is not None and g.numel() != p.numel()) or b.numel() != p.numel():
+            raise ValueError("sgd_step: a gradient or momentum buffer does not have its parameter's element count")
+    P = C.c_void_p * n
+    hp = P(*[p.data_ptr() for p in params])
+    hg = P(*[(g.data_ptr() if g is not None else None) for g in grads])
+    hb = P(*[b.data_ptr() for b in bufs])
+    hn = (C.c_int64 * n)(*[p.numel() for p in params])
+    check(lib.dgtta_sgd_step(hp, hg, hb, hn, n, float(lr), float(momentum), float(weight_decay), int(bool(nesterov)),
+                             int(bool(first_step)), float(grad_scale), ptr(sumsq), float(max_norm), ptr(skip_flag),
+                             stream_of(params[0].device)), "dgtta_sgd_step")
+
+
 # ------------------------------------------------------------------------------------------------ eval helpers
 def argmax_dice(logits, labels=None):
     """argmax over channels (+ per-label counts for hard Dice, tta.py:321, torch_utils.py:107-117).

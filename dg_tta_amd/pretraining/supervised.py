@@ -20,7 +20,8 @@ def pretrain_supervised(net, cases, patch_size, label_to_class, steps, batch=2, 
     one-hot label channels, the layout get_batch reads).  label_to_class: int64 tensor, dataset label id (0 = background,
     i = label channel i) -> class index of the network output (pretrain class ids; with `net.selected_classes` set:
     positions in the selection).  Draws come from the thread's generators (utils.rng_scope / the global ones) in a fixed
-    order, so a seed reproduces the weights.  `optimizer`: continue with this HipAdamW (its moments) instead of a fresh one.
+    order, so a seed reproduces the weights.  `optimizer`: continue with this HipAdamW (its moments) instead of a fresh one, or train with
+    optim.HipSGD (nnU-Net's optimiser; the caller steps its PolyLRScheduler between calls).
     deep_supervision: net.deep_supervision is on for the duration and the loss is ops.deep_supervision_loss (the reported
     per-step loss is the weighted sum); False: it is off for the duration, also on a net that came with it on; ds_weights:
     per-output weights instead of nnU-Net's (which drop the lowest resolution).

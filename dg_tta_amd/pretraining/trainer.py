@@ -1,0 +1,352 @@
+"""`dgtta pretrain`: source-domain training of a DG trainer's network on this engine, from a dataset folder to
+`nnUNet_results/<Dataset>/<trainer>__nnUNetPlans__<configuration>/fold_<k>/checkpoint_final.pth` - the file
+`dgtta prepare_tta <numeric id>` looks for (tta/config_log_utils.py) and `load_network` reads.  The reference dispatches
+this step into `nnUNetv2_train` (dg_tta/run.py pretrain); nnunetv2 is not needed here.  What nnU-Net's trainer does around
+the network is restated from memory of nnunetv2 2.2 (UNPINNED): SGD with Nesterov momentum 0.99, weight decay 3e-5,
+gradient-norm clipping at 12 (optim.HipSGD, csrc/sgd.hip), polynomial learning rate from 1e-2 stepped per epoch
+(optim.PolyLRScheduler), 250 training + 50 validation iterations per epoch, 33 % of a batch centred on foreground,
+DC+CE loss with deep supervision (ops.deep_supervision_loss as it stands: the Dice term per sample, whatever the plans'
+`batch_dice` says), online pseudo-Dice from the validation batches.
+
+REDUCED AUGMENTATION: the DG trainers' own augmentation runs (GIN / MIND forward pre-hooks; for the *_MultiRes trainers
+SimulateDiscreteLowResolutionTransform with the reference's arguments, nnUNetTrainer_GIN_MIND_MultiRes.py:61-67), mirroring
+is off as those trainers set it, but nnU-Net's rotation / scaling and noise / blur / brightness / contrast / gamma
+transforms are NOT applied.  Experiment planning is out of scope: nnUNetPlans.json must exist.  Random streams are not
+part of a checkpoint: a continued run draws differently from an uninterrupted one."""
+import json
+import os
+import re
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..optim import HipSGD, PolyLRScheduler
+from ..synthetic import he_init_
+from ..tta.config_log_utils import maybe_convert_to_dataset_name, nnunet_path
+from ..tta.nnunet_utils import unet_cfg_from_plans
+from ..tta.torch_utils import as_label_map_case, get_batch, release_resident
+from ..unet import HipPlainConvUNet
+from ..utils import disable_internal_augmentation, numpy_rng
+from .discrete_downsampling import SimulateDiscreteLowResolutionTransform
+from .hooks import register_dg_hooks, trainer_spec
+
+DG_TRAINERS = tuple(f"nnUNetTrainer_{n}{m}" for m in ("", "_MultiRes") for n in ("GIN", "MIND", "GIN_MIND"))
+INITIAL_LR = 1e-2
+OVERSAMPLE_FOREGROUND = 0.33
+MAX_LOCATIONS_PER_CLASS = 10000
+SAVE_EVERY = 50
+RESIDENT_CASES = 64          # cases kept in HBM by get_batch's volume cache; trimmed at epoch ends
+REDUCED_AUGMENTATION_NOTE = (
+    "pretrain: REDUCED AUGMENTATION - the trainer's own GIN / MIND hooks (and, for *_MultiRes, the discrete low-resolution "
+    "transform) run, mirroring is off as the DG trainers set it; nnU-Net's rotation / scaling and noise / blur / brightness / "
+    "contrast / gamma transforms are not applied by this engine.")
+
+
+# ------------------------------------------------------------------------------------------------ host logic (no GPU)
+def is_forced_foreground(j, batch_size, oversample=OVERSAMPLE_FOREGROUND):
+    """nnU-Net's oversampling rule: batch item j is centred on foreground when j >= round(B * (1 - oversample))."""
+    return not j < round(batch_size * (1 - oversample))
+
+
+def make_splits(case_names, n_splits=5, seed=12345):
+    """Seeded n-fold split of the sorted case names: numpy RandomState(seed).permutation, cut into n_splits nearly equal
+    parts; part k is the validation set of fold k.  NOT sklearn's KFold(shuffle=True) that nnU-Net uses: the folds of an
+    nnU-Net run on the same data differ (copy its splits_final.json to reproduce them).  The validation sets partition
+    the cases; with fewer cases than folds the last folds have none."""
+    names = sorted(case_names)
+    perm = np.random.RandomState(seed).permutation(len(names))
+    splits = []
+    for part in np.array_split(perm, n_splits):
+        val = {names[i] for i in part.tolist()}
+        splits.append({"train": [n for n in names if n not in val], "val": sorted(val)})
+    return splits
+
+
+def fold_folder_name(fold):
+    return f"fold_{fold}"
+
+
+def class_locations(seg, max_per_class=MAX_LOCATIONS_PER_CLASS, seed=1234):
+    """{class id > 0: int array [n, 3] of (D, H, W) voxels}, at most max_per_class per class, drawn once per case with a
+    seeded generator (nnU-Net samples them at preprocessing time in the same way)."""
+    flat = np.asarray(seg).reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    vals, starts = np.unique(flat[order], return_index=True)
+    ends = list(starts[1:]) + [flat.size]
+    rs = np.random.RandomState(seed)
+    out = {}
+    for v, a, b in zip(vals.tolist(), starts.tolist(), ends):
+        if v <= 0:
+            continue
+        idx = order[a:b]
+        if idx.size > max_per_class:
+            idx = idx[rs.choice(idx.size, max_per_class, replace=False)]
+        out[int(v)] = np.stack(np.unravel_index(idx, np.asarray(seg).shape), axis=1)
+    return out
+
+
+def draw_center(locations, rng):
+    """A random voxel of a random foreground class present in the case; None when the case has no foreground (the patch
+    is then drawn at random, as nnU-Net does)."""
+    classes = sorted(locations)
+    if not classes:
+        return None
+    loc = locations[classes[int(rng.randint(len(classes)))]]
+    return tuple(int(x) for x in loc[int(rng.randint(len(loc)))])
+
+
+def _configuration(plans, configuration):
+    conf = plans["configurations"][configuration]
+    while "inherits_from" in conf:
+        parent = dict(plans["configurations"][conf["inherits_from"]])
+        parent.update({k: v for k, v in conf.items() if k != "inherits_from"})
+        conf = parent
+    return conf
+
+
+def load_dataset_files(dataset_name):
+    """(plans, dataset_json, preprocessed dataset folder, raw dataset folder or None)."""
+    pre = Path(nnunet_path("nnUNet_preprocessed")) / dataset_name
+    raw = Path(os.environ["nnUNet_raw"]) / dataset_name if os.environ.get("nnUNet_raw") else None
+    plans_file = pre / "nnUNetPlans.json"
+    if not plans_file.is_file():
+        raise FileNotFoundError(
+            f"{plans_file} not found: `dgtta pretrain` trains from existing plans and does no experiment planning.  Put the "
+            f"nnUNetPlans.json of this dataset there (nnUNetv2_plan_and_preprocess writes it; the plans.json of a model trained "
+            f"on comparable data, with its patch size and spacing, works too).")
+    with open(plans_file) as f:
+        plans = json.load(f)
+    for folder in (pre, raw):
+        if folder is not None and (folder / "dataset.json").is_file():
+            with open(folder / "dataset.json") as f:
+                return plans, json.load(f), pre, raw
+    raise FileNotFoundError(f"dataset.json found neither in {pre} nor in {raw}")
+
+
+def find_cases(data_dir, raw, file_ending):
+    """{case name: (npz path, raw image file or None, raw label file or None)} from the preprocessed folder and imagesTr."""
+    cases = {}
+    if data_dir.is_dir():
+        for p in sorted(data_dir.glob("*.npz")):
+            cases[p.name[:-4]] = (p, None, None)
+    if raw is not None and (raw / "imagesTr").is_dir():
+        for p in sorted((raw / "imagesTr").iterdir()):
+            m = re.match(r"(.*)_0000" + re.escape(file_ending) + "$", p.name)
+            if m and m.group(1) not in cases:
+                cases[m.group(1)] = (data_dir / f"{m.group(1)}.npz", p, raw / "labelsTr" / f"{m.group(1)}{file_ending}")
+    return cases
+
+
+# ------------------------------------------------------------------------------------------------ cases
+class _Case:
+    def __init__(self, name, data, seg):
+        seg = np.where(seg < 0, 0, seg)                 # nnU-Net's "outside the non-zero mask" label (-1) trains as background
+        self.name = name
+        self.tensor = as_label_map_case(torch.from_numpy(np.ascontiguousarray(data[0], dtype=np.float32)),
+                                        torch.from_numpy(np.ascontiguousarray(seg[0], dtype=np.float32)))
+        self.locations = class_locations(seg[0])
+
+
+def load_case(name, entry, plans, configuration, device):
+    """Reads <case>.npz (keys `data` [C, D, H, W], `seg` [1, D, H, W]); a missing file is made from the raw image + label
+    with tta/preprocessing.run_case and written first, so there is one code path.  (nnU-Net's per-case .pkl of geometry
+    properties is not written: training does not read it.)"""
+    npz, img, lbl = entry
+    if not npz.is_file():
+        if img is None or not Path(lbl).is_file():
+            raise FileNotFoundError(f"case {name}: neither {npz} nor a raw image + label pair")
+        from ..tta.preprocessing import run_case
+        data, seg, _ = run_case([img], lbl, plans, configuration, device)
+        npz.parent.mkdir(parents=True, exist_ok=True)
+        np.savez_compressed(npz, data=data.astype(np.float32), seg=seg)
+    with np.load(npz) as z:
+        data, seg = z["data"], z["seg"]
+    if data.shape[0] != 1:
+        raise NotImplementedError(f"case {name}: {data.shape[0]} image channels; the DG trainers' hooks take one")
+    return _Case(name, data, seg)
+
+
+def build_network(plans, dataset_json, configuration, trainer_name, act_dtype=torch.float32, seed=7):
+    """The network `train_fold` starts from: topology from the plans, the trainer's input channels, nnU-Net's He
+    initialisation drawn from `seed`, deep supervision on.  No hooks registered."""
+    in_ch, _ = trainer_spec(trainer_name)
+    cfg, patch = unet_cfg_from_plans(plans, dataset_json, configuration, in_ch)
+    net = he_init_(HipPlainConvUNet(cfg, act_dtype=act_dtype, deep_supervision=True), seed=seed)
+    return net, patch
+
+
+def _sample(cases, batch_size, patch, device, multires):
+    rng = numpy_rng()
+    picks = [cases[int(i)] for i in rng.choice(len(cases), batch_size)]
+    imgs, labels = [], []
+    with torch.no_grad():
+        for j, case in enumerate(picks):
+            center = draw_center(case.locations, rng) if is_forced_foreground(j, batch_size) else None
+            im, lb = get_batch([case.tensor], [0], patch, None, device, centers=[center])
+            imgs.append(im[0][0])                          # [1, D, H, W]
+            labels.append(lb[0])
+        if multires is not None:
+            multires(data=imgs)
+    return torch.stack(imgs), torch.cat(labels, dim=0)[:, 0], picks
+
+
+# ------------------------------------------------------------------------------------------------ the loop
+def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iterations_per_epoch=250, val_iterations=50,
+               device="cuda", act_dtype=torch.float32, continue_training=False, seed=None):
+    """Trains one fold and writes the model folder (module docstring).  dataset: numeric id or folder name; fold: 0..4 or
+    "all".  Returns the path of checkpoint_final.pth."""
+    if trainer_name not in DG_TRAINERS:
+        raise ValueError(f"trainer {trainer_name}: one of {', '.join(DG_TRAINERS)} expected")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("dg_tta_amd trains on the MI355X only (no CPU fallback)")
+    fold = "all" if str(fold) == "all" else int(fold)
+    dataset_name = maybe_convert_to_dataset_name(dataset)
+    plans, dataset_json, pre, raw = load_dataset_files(dataset_name)
+    conf = _configuration(plans, configuration)
+    data_dir = pre / conf.get("data_identifier", f"{plans.get('plans_name', 'nnUNetPlans')}_{configuration}")
+    entries = find_cases(data_dir, raw, dataset_json.get("file_ending", ".nii.gz"))
+    if not entries:
+        raise FileNotFoundError(f"no training case: neither *.npz in {data_dir} nor images in {raw}/imagesTr")
+    splits_file = pre / "splits_final.json"
+    if fold == "all":
+        train_names = val_names = sorted(entries)
+    else:
+        if splits_file.is_file():
+            with open(splits_file) as f:
+                splits = json.load(f)
+        else:
+            splits = make_splits(sorted(entries))
+            with open(splits_file, "w") as f:
+                json.dump(splits, f, indent=4)
+        if not 0 <= fold < len(splits):
+            raise ValueError(f"fold {fold}: {splits_file} has {len(splits)} folds")
+        train_names, val_names = splits[fold]["train"], splits[fold]["val"]
+        if not val_names:
+            print(f"pretrain: fold {fold} has no validation case ({len(entries)} cases): validating on the training cases")
+            val_names = train_names
+    missing = sorted((set(train_names) | set(val_names)) - set(entries))
+    if missing:
+        raise FileNotFoundError(f"{splits_file} names cases that are not in the dataset: {missing[:6]}")
+
+    out_dir = Path(nnunet_path("nnUNet_results")) / dataset_name / f"{trainer_name}__nnUNetPlans__{configuration}"
+    fold_dir = out_dir / fold_folder_name(fold)
+    fold_dir.mkdir(parents=True, exist_ok=True)
+    with open(out_dir / "plans.json", "w") as f:
+        json.dump(plans, f, indent=4)
+    with open(out_dir / "dataset.json", "w") as f:
+        json.dump(dataset_json, f, indent=4)
+
+    if seed is not None:
+        torch.manual_seed(seed)
+        torch.cuda.manual_seed(seed)
+        np.random.seed(seed)
+    net, patch = build_network(plans, dataset_json, configuration, trainer_name, act_dtype,
+                               seed=seed if seed is not None else int(np.random.randint(2 ** 31 - 1)))
+    batch_size = int(conf["batch_size"])
+    num_classes = net.cfg["num_classes"]
+    net = net.to(device)
+    for p in net.parameters():
+        p.requires_grad_(True)
+    opt = HipSGD(net.parameters(), lr=INITIAL_LR, grad_scale=net.loss_scale)
+    log = dict(train_losses=[], val_losses=[], mean_fg_dice=[], lrs=[])
+    start_epoch = 0
+    if continue_training:
+        src = next((p for p in (fold_dir / "checkpoint_latest.pth", fold_dir / "checkpoint_final.pth") if p.is_file()), None)
+        if src is None:
+            raise FileNotFoundError(f"continue_training: no checkpoint_latest.pth / checkpoint_final.pth in {fold_dir}")
+        ck = torch.load(src, map_location="cpu", weights_only=False)
+        net.load_state_dict(ck["network_weights"])
+        opt.load_state_dict(ck["optimizer_state"])
+        opt.grad_scale = float((ck.get("grad_scaler_state") or {}).get("scale", opt.grad_scale))
+        start_epoch, log = int(ck["current_epoch"]), {k: list(ck["logging"][k]) for k in log}
+        print(f"pretrain: continuing from {src} at epoch {start_epoch} (random streams are not restored)")
+    sched = PolyLRScheduler(opt, INITIAL_LR, num_epochs)
+    multires = None
+    if trainer_name.endswith("_MultiRes"):
+        multires = SimulateDiscreteLowResolutionTransform(zoom_range=(1 / 6, 1 / 4, 1 / 2), zoom_axes_invidually=True,
+                                                          per_channel=False, p_per_channel=1.0, order_downsample=0,
+                                                          order_upsample=3, p_per_sample=0.5, ignore_axes=None)
+
+    loaded = {}
+
+    def cases_of(names):
+        for n in names:
+            if n not in loaded:
+                loaded[n] = load_case(n, entries[n], plans, configuration, device)
+        return [loaded[n] for n in names]
+
+    train_cases, val_cases = cases_of(train_names), cases_of(val_names)
+
+    def save(name, epoch):
+        torch.save({"network_weights": {k: v.detach().cpu() for k, v in net.state_dict().items()},
+                    "optimizer_state": opt.state_dict(), "current_epoch": epoch, "trainer_name": trainer_name,
+                    "init_args": dict(plans=plans, configuration=configuration, fold=fold, dataset_json=dataset_json),
+                    "inference_allowed_mirroring_axes": None, "logging": log,
+                    "grad_scaler_state": {"scale": opt.grad_scale}}, fold_dir / name)
+
+    handles = register_dg_hooks(net, trainer_name)          # switches the internal augmentation on, as the trainers do
+    recent = {}                                             # case name -> last epoch it was sampled in
+    try:
+        with open(fold_dir / "training_log.txt", "a") as logf:
+            for epoch in range(start_epoch, num_epochs):
+                t0 = time.time()
+                lr = sched.step(epoch)
+                net.train()
+                tr_losses = []
+                for _ in range(iterations_per_epoch):
+                    if opt.resolve_overflow():             # (reads a flag only on the guarded fp16 path)
+                        print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
+                    imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires)
+                    loss, _ = ops.deep_supervision_loss(net(imgs), target)
+                    torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
+                                                                          device=device))
+                    opt.step()
+                    opt.zero_grad(set_to_none=True)
+                    tr_losses.append(loss.detach())
+                    recent.update((c.name, epoch) for c in picks)
+                net.eval()
+                va_losses, counts = [], torch.zeros((3, num_classes), dtype=torch.int64, device=device)
+                with torch.no_grad():
+                    for _ in range(val_iterations):
+                        imgs, target, picks = _sample(val_cases, batch_size, patch, device, None)
+                        outs = net(imgs)
+                        loss, _ = ops.deep_supervision_loss(outs, target)
+                        va_losses.append(loss)
+                        counts += ops.argmax_dice(outs[0], target)[1]
+                        recent.update((c.name, epoch) for c in picks)
+                # the one read-back of the epoch: mean losses and the per-class pseudo-Dice 2 TP / (2 TP + FP + FN) summed over
+                # the validation batches (counts rows: predicted, reference, both)
+                nan = torch.full((1,), float("nan"), dtype=torch.float64, device=device)
+                dice = 2.0 * counts[2, 1:].double() / (counts[0, 1:] + counts[1, 1:]).double()
+                host = torch.cat([torch.stack(tr_losses).double().mean()[None] if tr_losses else nan,
+                                  torch.stack(va_losses).double().mean()[None] if va_losses else nan, dice]).cpu()
+                fg = host[2:][~torch.isnan(host[2:])]
+                mean_dice = float(fg.mean()) if fg.numel() else float("nan")
+                log["train_losses"].append(float(host[0]))
+                log["val_losses"].append(float(host[1]))
+                log["mean_fg_dice"].append(mean_dice)
+                log["lrs"].append(lr)
+                logf.write(f"epoch {epoch} lr {lr:.6g} train_loss {float(host[0]):.4f} val_loss {float(host[1]):.4f} "
+                           f"pseudo_dice {mean_dice:.4f} loss_scale {opt.grad_scale:g} skipped_steps {opt.skipped_steps} "
+                           f"time {time.time() - t0:.1f}s\n")
+                logf.flush()
+                if len(recent) > RESIDENT_CASES:            # the stream is drained here: trim the volume cache
+                    old = sorted(recent, key=recent.get)[:len(recent) - RESIDENT_CASES]
+                    release_resident([loaded[n].tensor for n in old])
+                    for n in old:
+                        del recent[n]
+                if (epoch + 1) % SAVE_EVERY == 0 and epoch + 1 < num_epochs:
+                    save("checkpoint_latest.pth", epoch + 1)
+        opt.resolve_overflow()
+        save("checkpoint_latest.pth", max(num_epochs, start_epoch))
+        save("checkpoint_final.pth", max(num_epochs, start_epoch))
+    finally:
+        for h in handles:
+            h.remove()
+        disable_internal_augmentation()
+        release_resident([c.tensor for c in loaded.values()])
+    return fold_dir / "checkpoint_final.pth"

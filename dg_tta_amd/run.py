@@ -1,6 +1,7 @@
 """`dgtta` command line — same sub-commands, positional arguments and option names as the reference's dg_tta/run.py
-(prepare_tta :71-118, run_tta :120-209).  `inject_trainers` / `pretrain` dispatch into nnU-Net training and are out of
-scope for this engine.  Extra, optional: `run_tta --gpus N` fans out one process per GPU
+(prepare_tta :71-118, run_tta :120-209).  `pretrain` takes the arguments of `nnUNetv2_train`, which the reference dispatches
+into, and trains on this engine (pretraining/trainer.py); `inject_trainers` patches an installed nnunetv2 and has nothing
+to do here.  Extra, optional: `run_tta --gpus N` fans out one process per GPU
 (sample-sharded, no collectives), `--dtype {fp32,bf16,fp16}` (default fp32 = the reference's precision).
 """
 import argparse
@@ -67,6 +68,7 @@ class DGTTAProgram:
         parser = argparse.ArgumentParser(description="DG-TTA for nnUNetv2 (MI355X engine)", usage="""dgtta <command> [<args>]
 
         Commands are:
+        pretrain        Pre-train on the source dataset (GIN / MIND trainers)
         prepare_tta     Prepare test-time adaptation
         run_tta         Run test-time adaptation
         """)
@@ -79,11 +81,39 @@ class DGTTAProgram:
         getattr(self, args.command)()
 
     def inject_trainers(self):
-        raise SystemExit("inject_trainers patches an installed nnunetv2 for source-domain pre-training; "
-                         "use the reference package for that step (out of scope of the TTA engine).")
+        raise SystemExit("inject_trainers patches an installed nnunetv2 so that nnUNetv2_train finds the DG trainers; "
+                         "nothing is injected here: `dgtta pretrain` trains on this engine and no longer needs it.")
+
+    @staticmethod
+    def _pretrain_parser():
+        from .pretraining.trainer import DG_TRAINERS
+        parser = argparse.ArgumentParser(description="Pre-train a DG trainer's network on the source dataset (positional "
+                                         "arguments, -tr and --c as in nnUNetv2_train)", usage="dgtta pretrain [-h]")
+        parser.add_argument("dataset_id", help="Dataset name or numeric id of the source dataset")
+        parser.add_argument("configuration", help="Configuration of nnUNetPlans.json, e.g. 3d_fullres")
+        parser.add_argument("fold", help="Fold of the 5-fold split, 0..4, or 'all'")
+        parser.add_argument("-tr", dest="trainer", required=True, choices=DG_TRAINERS, help="DG trainer")
+        parser.add_argument("--num_epochs", type=int, default=1000)
+        parser.add_argument("--iterations_per_epoch", type=int, default=250)
+        parser.add_argument("--val_iterations", type=int, default=50)
+        parser.add_argument("--device", help="Device to be used", default="cuda")
+        parser.add_argument("--dtype", choices=["fp32", "fp16", "bf16"], default=DEFAULT_DTYPE, help="activation storage")
+        parser.add_argument("--c", dest="continue_training", action="store_true",
+                            help="continue from fold_<k>/checkpoint_latest.pth")
+        parser.add_argument("--seed", type=int, default=None, help="seeds the initialisation and every random draw")
+        return parser
 
     def pretrain(self):
-        raise SystemExit("pretrain dispatches into nnUNetv2_train; use the reference package (out of scope here).")
+        args = self._pretrain_parser().parse_args(self.argv[2:])
+        if args.fold != "all" and not args.fold.isnumeric():
+            raise SystemExit(f"pretrain: fold {args.fold!r} is neither a number nor 'all'")
+        from .pretraining.trainer import REDUCED_AUGMENTATION_NOTE, train_fold
+        print(REDUCED_AUGMENTATION_NOTE)
+        final = train_fold(args.dataset_id, args.configuration, args.fold, args.trainer, num_epochs=args.num_epochs,
+                           iterations_per_epoch=args.iterations_per_epoch, val_iterations=args.val_iterations,
+                           device=torch.device(args.device), continue_training=args.continue_training, seed=args.seed,
+                           act_dtype={"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype])
+        print(f"pretrain: wrote {final}")
 
     def prepare_tta(self):
         parser = argparse.ArgumentParser(description="Prepare DG-TTA", usage="dgtta prepare_tta [-h]")

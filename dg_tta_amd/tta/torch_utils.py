@@ -25,7 +25,9 @@ def _resident(data, device):
     img = data[0][None, None].float().contiguous().to(device)
     mn = data[0].min().reshape(1).float().to(device)                  # torch_utils.py:58
     lab = None
-    if data[1:].numel() != 0:
+    if getattr(data, "dgtta_label_map", False):                       # as_label_map_case: channel 1 IS the label map
+        lab = data[1][None, None].float().contiguous().to(device)
+    elif data[1:].numel() != 0:
         segs = data[1:][None]
         # get_argmaxed_segs (torch_utils.py:79-82) commutes with nearest sampling: apply it once to the volume
         lab = torch.cat([(segs.sum(1, keepdim=True) < 1.0).float(), segs.float()], dim=1).argmax(1, keepdim=True)
@@ -47,10 +49,39 @@ def release_resident(tensor_list=None):
         del _VOLUME_CACHE[key]
 
 
-def get_batch(tensor_list, batch_idxs, patch_size, fixed_patch_idx=None, device="cuda"):
+def as_label_map_case(image, label_map):
+    """A case for get_batch held as image + integer label map ([2, D, H, W] fp32) instead of image + one one-hot channel per
+    label: what pre-training on a 105-class dataset can afford.  The returned tensor carries a mark that _resident reads;
+    an unmarked tensor is read as before."""
+    data = torch.stack([image.float(), label_map.float()]).contiguous()
+    data.dgtta_label_map = True
+    return data
+
+
+def center_to_offset(center, shape, patch_size):
+    """Patch centred on voxel `center` of a volume of `shape` -> the normalised offset get_batch puts into its affine, in
+    (D, H, W) order.  nnU-Net's rule: the patch starts at center - patch // 2, moved so that it stays inside the volume
+    (start in [0, shape - patch]); along an axis where the volume is not larger than the patch the offset is 0, the
+    centred patch get_batch draws there too.  With start s, output voxel i reads source voxel s + i exactly (an integer
+    crop): normalised, align_corners=False, that is the offset (2 s + patch) / shape - 1.  Host arithmetic only."""
+    out = []
+    for c, s, p in zip(center, shape, patch_size):
+        c, s, p = int(c), int(s), int(p)
+        if s <= p:
+            out.append(0.0)
+            continue
+        start = min(max(c - p // 2, 0), s - p)
+        out.append((2 * start + p) / s - 1.0)
+    return out
+
+
+def get_batch(tensor_list, batch_idxs, patch_size, fixed_patch_idx=None, device="cuda", centers=None):
     """Reference: torch_utils.py:13-76.  Random (torch.rand(3) on the CPU generator) or centre patch via affine
-    resampling; image trilinear with the (x - min) + min trick, labels nearest."""
+    resampling; image trilinear with the (x - min) + min trick, labels nearest.
+    centers (optional, pre-training's foreground oversampling): per batch item None or a (D, H, W) voxel; such an item's
+    patch is the integer crop centred there (center_to_offset) and draws no random offset."""
     assert fixed_patch_idx in range(8) or fixed_patch_idx is None or fixed_patch_idx == "center"
+    assert centers is None or len(centers) == len(batch_idxs)
     device = torch.device(device)
     b_img, b_label = [], []
     t_patch = torch.as_tensor(patch_size)
@@ -59,11 +90,16 @@ def get_batch(tensor_list, batch_idxs, patch_size, fixed_patch_idx=None, device=
     patch_affine = scales.diag()
     for b in range(len(batch_idxs)):
         data = tensor_list[batch_idxs[b]]
-        if fixed_patch_idx != "center":
+        if centers is not None and centers[b] is not None:
+            ranged = torch.tensor(center_to_offset(centers[b], t_shape.tolist(), t_patch.tolist()))
+            patch_affine[:, -1] = torch.cat([ranged.flip(0), torch.tensor([1.0])], dim=0)
+        elif fixed_patch_idx != "center":
             rand_offset = 2.0 * torch.rand(3, generator=cpu_generator()) - 1.0
             offset_range = ((t_shape - t_patch) / t_shape).clip(min=0.0)
             ranged = rand_offset * offset_range
             patch_affine[:, -1] = torch.cat([ranged.flip(0), torch.tensor([1.0])], dim=0)
+        elif centers is not None:            # a centre patch after an item that set an offset
+            patch_affine[:, -1] = torch.tensor([0.0, 0.0, 0.0, 1.0])
         theta = upload_async([patch_affine[:3][None].float().contiguous()], device)[0]
         img, mn, lab = _resident(data, device)
         b_img.append(ops.affine_sample(img, theta, patch_size, "zeros", "bilinear", sub_const=mn))

@@ -238,6 +238,27 @@ int dgtta_adamw_step(float *const *h_p, const float *const *h_g, float *const *h
 int dgtta_grads_nonfinite(const float *const *h_g, const int64_t *h_n, int ntensors, int *flag, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * nnU-Net's optimiser step [3P nnunetv2==2.2.1 nnUNetTrainer, from memory: UNPINNED], the one `nnUNetv2_train` runs for
+ * the reference's trainers (dg_tta/run.py pretrain): torch.nn.utils.clip_grad_norm_(parameters, 12) followed by
+ * torch.optim.SGD(lr, weight_decay=3e-5, momentum=0.99, nesterov=True), dampening 0.  h_* are HOST arrays as above; tensors
+ * whose h_g[i] is NULL are skipped and do not enter the norm.
+ * dgtta_grad_sumsq: *out (device fp32) = sum over all gradient elements of g*g, of the gradients AS STORED (loss scale
+ * included).  Bit-reproducible from run to run: per-workgroup partials (double) in ws, added in a fixed order; no floating-
+ * point atomics.  ws: dgtta_grad_sumsq_ws_bytes(sum of the element counts, ntensors) bytes, 8-byte aligned.
+ * dgtta_sgd_step, per element (no operation fused):
+ *   norm = sqrt(*sumsq) / grad_scale;  coef = min(1, max_norm / (norm + 1e-6))      (coef = 1 when sumsq is NULL)
+ *   g' = (g / grad_scale) * coef;  d = g' + weight_decay * p;  buf = first_step ? d : momentum * buf + d
+ *   p -= lr * (nesterov ? d + momentum * buf : buf)
+ * first_step != 0: the momentum buffers are written, never read (torch creates them as a copy of d on a parameter's first
+ * step).  sumsq is read on the device.  skip_if_nonzero as in dgtta_adamw_step: p and buf stay untouched. */
+size_t dgtta_grad_sumsq_ws_bytes(int64_t total_elements, int ntensors);
+int dgtta_grad_sumsq(const float *const *h_g, const int64_t *h_n, int ntensors, float *out, void *ws, size_t ws_bytes,
+                     void *stream);
+int dgtta_sgd_step(float *const *h_p, const float *const *h_g, float *const *h_buf, const int64_t *h_n, int ntensors,
+                   float lr, float momentum, float weight_decay, int nesterov, int first_step, float grad_scale,
+                   const float *sumsq, float max_norm, const int *skip_if_nonzero, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * nnUNet PlainConvUNet building blocks (third-party dynamic-network-architectures==0.2, built at
  * dg_tta/pretraining/nnUNetTrainer_GIN_MIND.py:46-53 from plans.json:279-401): Conv3d 3x3x3 (pad 1,
  * stride 1|2, bias) -> InstanceNorm3d(eps, affine) -> LeakyReLU(0.01); ConvTranspose3d k2 s2;
