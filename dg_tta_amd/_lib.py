@@ -123,7 +123,18 @@ SIGNATURES = {
     "dgtta_holes_member": (I, [P, I, I, I, P, I, I, I, I, I, I, I, P, P]),
     "dgtta_holes_apply": (I, [P, I, I, I, P, P, I, I, I, I, I, I, I64, I64, P, P]),
     "dgtta_nonzero_mask": (I, [P, I, I64, P, P]),
+    "dgtta_bspline3_prefilter": (I, [P, P, I, I, I, P]),
+    "dgtta_patch_sample_aug": (I, [P, I, I, I, I, I, P, P, P]),
 }
+
+
+
+class PatchItem(C.Structure):
+    """DgttaPatchItem of include/dgtta.h."""
+    _fields_ = [("image", P), ("label", P), ("D", I), ("H", I), ("W", I), ("map", F * 12)]
+
+
+PATCH_MAX_ITEMS = 16
 
 _lib = None
 _load_error = None

@@ -991,6 +991,62 @@ def nonzero_mask(data):
     return mask
 
 
+# ------------------------------------------------------------------------------------------------ spatial augmentation
+def _volume3(t, name, what):
+    t = t.reshape(t.shape[-3:]) if t.dim() > 3 and t.numel() == t.shape[-3] * t.shape[-2] * t.shape[-1] else t
+    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+        raise ValueError(f"{name}: {what} must be a contiguous float32 volume [D, H, W] (leading axes of extent 1 allowed)")
+    return t
+
+
+def bspline3_prefilter(volume):
+    """scipy.ndimage.spline_filter(volume, order=3, mode="mirror") in fp32 (csrc/spatial_aug.hip): the cubic B-spline
+    coefficients sample_patches_aug(order=3) reads.  volume: float32 [D, H, W] on the GPU -> a new tensor of that shape."""
+    require_cuda(volume)
+    src = _volume3(volume, "bspline3_prefilter", "volume")
+    dst = torch.empty_like(src)
+    d, h, w = src.shape
+    check(_lib.load().dgtta_bspline3_prefilter(ptr(src), ptr(dst), d, h, w, stream_of(src.device)), "dgtta_bspline3_prefilter")
+    return dst.reshape(volume.shape)
+
+
+def sample_patches_aug(coefs, label_maps, maps, patch_size, order=3):
+    """One launch that samples len(coefs) <= 16 patches through affine voxel maps (csrc/spatial_aug.hip, include/dgtta.h).
+    coefs: per item the float32 volume the image is read from - B-spline coefficients (bspline3_prefilter) for order 3, the
+    raw volume for order 1; label_maps: per item the label map as float32 values, same shape; maps: per item a 3 x 4 [A | t]
+    (anything numpy converts; rounded to fp32): output voxel v reads source position A v + t, (D, H, W) order, voxel units.
+    Items may differ in volume shape.  Returns (image float32 [B, 1, *patch_size], labels int64 [B, *patch_size])."""
+    import numpy as np
+    n = len(coefs)
+    if not (1 <= n <= _lib.PATCH_MAX_ITEMS and len(label_maps) == n and len(maps) == n):
+        raise ValueError(f"sample_patches_aug: 1..{_lib.PATCH_MAX_ITEMS} items with one label map and one map each (got {n}, "
+                         f"{len(label_maps)}, {len(maps)})")
+    if order not in (1, 3):
+        raise ValueError(f"sample_patches_aug: order {order} not in (1, 3)")
+    pd, ph, pw = (int(p) for p in patch_size)
+    items = (_lib.PatchItem * n)()
+    keep = []
+    for b in range(n):
+        require_cuda(coefs[b], label_maps[b])
+        img, lab = _volume3(coefs[b], "sample_patches_aug", "an image"), _volume3(label_maps[b], "sample_patches_aug", "a label map")
+        if img.shape != lab.shape or img.device != lab.device or img.device != coefs[0].device:
+            raise ValueError(f"sample_patches_aug: item {b}: image {tuple(img.shape)} and label map {tuple(lab.shape)} must agree "
+                             f"in shape and lie on one device")
+        m = np.asarray(maps[b], dtype=np.float64)
+        if m.shape != (3, 4) or not np.isfinite(m).all():
+            raise ValueError(f"sample_patches_aug: item {b}: a finite 3 x 4 map expected")
+        keep += [img, lab]
+        items[b].image, items[b].label = img.data_ptr(), lab.data_ptr()
+        items[b].D, items[b].H, items[b].W = (int(s) for s in img.shape)
+        items[b].map[:] = m.astype(np.float32).reshape(-1).tolist()
+    device = coefs[0].device
+    image = torch.empty((n, 1, pd, ph, pw), dtype=torch.float32, device=device)
+    labels = torch.empty((n, pd, ph, pw), dtype=torch.int64, device=device)
+    check(_lib.load().dgtta_patch_sample_aug(items, n, pd, ph, pw, int(order), ptr(image), ptr(labels), stream_of(device)),
+          "dgtta_patch_sample_aug")
+    return image, labels
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

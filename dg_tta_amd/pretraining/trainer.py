@@ -11,8 +11,10 @@ DC+CE loss with deep supervision (ops.deep_supervision_loss as it stands: the Di
 REDUCED AUGMENTATION: the DG trainers' own augmentation runs (GIN / MIND forward pre-hooks; for the *_MultiRes trainers
 SimulateDiscreteLowResolutionTransform with the reference's arguments, nnUNetTrainer_GIN_MIND_MultiRes.py:61-67), mirroring
 is off as those trainers set it, but nnU-Net's rotation / scaling and noise / blur / brightness / contrast / gamma
-transforms are NOT applied.  Experiment planning is out of scope: nnUNetPlans.json must exist.  Random streams are not
-part of a checkpoint: a continued run draws differently from an uninterrupted one."""
+transforms are NOT applied.  `augmentation="spatial"` (`--augmentation spatial`) adds the rotation / scaling
+(pretraining/spatial.py, csrc/spatial_aug.hip); the intensity transforms stay missing.  Experiment planning is out of
+scope: nnUNetPlans.json must exist.  Random streams are not part of a checkpoint: a continued run draws differently from
+an uninterrupted one."""
 import json
 import os
 import re
@@ -27,11 +29,12 @@ from ..optim import HipSGD, PolyLRScheduler
 from ..synthetic import he_init_
 from ..tta.config_log_utils import maybe_convert_to_dataset_name, nnunet_path
 from ..tta.nnunet_utils import unet_cfg_from_plans
-from ..tta.torch_utils import as_label_map_case, get_batch, release_resident
+from ..tta.torch_utils import _resident, as_label_map_case, get_batch, release_resident, resident_spline
 from ..unet import HipPlainConvUNet
 from ..utils import disable_internal_augmentation, numpy_rng
 from .discrete_downsampling import SimulateDiscreteLowResolutionTransform
 from .hooks import register_dg_hooks, trainer_spec
+from .spatial import SpatialAugmentation, patch_start, sampling_map
 
 DG_TRAINERS = tuple(f"nnUNetTrainer_{n}{m}" for m in ("", "_MultiRes") for n in ("GIN", "MIND", "GIN_MIND"))
 INITIAL_LR = 1e-2
@@ -43,6 +46,13 @@ REDUCED_AUGMENTATION_NOTE = (
     "pretrain: REDUCED AUGMENTATION - the trainer's own GIN / MIND hooks (and, for *_MultiRes, the discrete low-resolution "
     "transform) run, mirroring is off as the DG trainers set it; nnU-Net's rotation / scaling and noise / blur / brightness / "
     "contrast / gamma transforms are not applied by this engine.")
+SPATIAL_AUGMENTATION_NOTE = (
+    "pretrain: SPATIAL AUGMENTATION - nnU-Net's rotation / scaling is applied (cubic B-spline image, order-1 labels; "
+    "pretraining/spatial.py) beside the trainer's own GIN / MIND hooks (and, for *_MultiRes, the discrete low-resolution "
+    "transform), mirroring is off as the DG trainers set it; nnU-Net's noise / blur / brightness / contrast / gamma "
+    "transforms are not applied by this engine.")
+AUGMENTATIONS = ("reduced", "spatial")
+MAX_AUG_ITEMS = 16           # items per ops.sample_patches_aug launch
 
 
 # ------------------------------------------------------------------------------------------------ host logic (no GPU)
@@ -178,16 +188,58 @@ def build_network(plans, dataset_json, configuration, trainer_name, act_dtype=to
     return net, patch
 
 
-def _sample(cases, batch_size, patch, device, multires):
-    rng = numpy_rng()
+def _plan_batch(cases, batch_size, patch, spatial, rng):
+    """The draws of one augmented batch, in stream order: the case picks, then per item its centre (draw_center for a
+    forced-foreground item, else - or when the case has no foreground - a uniformly drawn voxel) and its spatial draw.
+    Returns [(case, centre, A or None)]."""
     picks = [cases[int(i)] for i in rng.choice(len(cases), batch_size)]
-    imgs, labels = [], []
-    with torch.no_grad():
-        for j, case in enumerate(picks):
-            center = draw_center(case.locations, rng) if is_forced_foreground(j, batch_size) else None
+    plan = []
+    for j, case in enumerate(picks):
+        center = draw_center(case.locations, rng) if is_forced_foreground(j, batch_size) else None
+        if center is None:
+            center = tuple(int(rng.randint(n)) for n in case.tensor.shape[-3:])
+        plan.append((case, center, spatial.draw(patch, rng)))
+    return plan
+
+
+def _sample_spatial(cases, batch_size, patch, device, spatial):
+    """Items whose draw is None are the integer crop of get_batch(..., centers=); all others of the batch leave ONE
+    ops.sample_patches_aug launch (16 items per launch, should a batch be larger)."""
+    plan = _plan_batch(cases, batch_size, patch, spatial, numpy_rng())
+    imgs, labels, aug = [None] * batch_size, [None] * batch_size, []
+    for j, (case, center, a) in enumerate(plan):
+        if a is None:
             im, lb = get_batch([case.tensor], [0], patch, None, device, centers=[center])
-            imgs.append(im[0][0])                          # [1, D, H, W]
-            labels.append(lb[0])
+            imgs[j], labels[j] = im[0][0], lb[0]
+        else:
+            aug.append(j)
+    for k in range(0, len(aug), MAX_AUG_ITEMS):
+        chunk = aug[k:k + MAX_AUG_ITEMS]
+        coefs, labs, maps = [], [], []
+        for j in chunk:
+            case, center, a = plan[j]
+            coefs.append(resident_spline(case.tensor, device))
+            labs.append(_resident(case.tensor, device)[2])
+            maps.append(sampling_map(a, patch_start(center, case.tensor.shape[-3:], patch), patch))
+        im, lb = ops.sample_patches_aug(coefs, labs, maps, patch, order=3)
+        for i, j in enumerate(chunk):
+            imgs[j], labels[j] = im[i], lb[i][None, None]
+    return imgs, labels, [p[0] for p in plan]
+
+
+def _sample(cases, batch_size, patch, device, multires, spatial=None):
+    with torch.no_grad():
+        if spatial is not None:
+            imgs, labels, picks = _sample_spatial(cases, batch_size, patch, device, spatial)
+        else:
+            rng = numpy_rng()
+            picks = [cases[int(i)] for i in rng.choice(len(cases), batch_size)]
+            imgs, labels = [], []
+            for j, case in enumerate(picks):
+                center = draw_center(case.locations, rng) if is_forced_foreground(j, batch_size) else None
+                im, lb = get_batch([case.tensor], [0], patch, None, device, centers=[center])
+                imgs.append(im[0][0])                          # [1, D, H, W]
+                labels.append(lb[0])
         if multires is not None:
             multires(data=imgs)
     return torch.stack(imgs), torch.cat(labels, dim=0)[:, 0], picks
@@ -195,9 +247,17 @@ def _sample(cases, batch_size, patch, device, multires):
 
 # ------------------------------------------------------------------------------------------------ the loop
 def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iterations_per_epoch=250, val_iterations=50,
-               device="cuda", act_dtype=torch.float32, continue_training=False, seed=None):
+               device="cuda", act_dtype=torch.float32, continue_training=False, seed=None, augmentation="reduced"):
     """Trains one fold and writes the model folder (module docstring).  dataset: numeric id or folder name; fold: 0..4 or
-    "all".  Returns the path of checkpoint_final.pth."""
+    "all".  augmentation: "reduced" (module docstring), "spatial" (adds nnU-Net's rotation / scaling to the training
+    batches, pretraining/spatial.py; validation batches are never augmented) or a SpatialAugmentation to draw from.
+    Returns the path of checkpoint_final.pth."""
+    if isinstance(augmentation, SpatialAugmentation):
+        spatial = augmentation
+    elif augmentation in AUGMENTATIONS:
+        spatial = SpatialAugmentation() if augmentation == "spatial" else None
+    else:
+        raise ValueError(f"augmentation {augmentation!r}: one of {', '.join(AUGMENTATIONS)} expected")
     if trainer_name not in DG_TRAINERS:
         raise ValueError(f"trainer {trainer_name}: one of {', '.join(DG_TRAINERS)} expected")
     device = torch.device(device)
@@ -300,7 +360,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                 for _ in range(iterations_per_epoch):
                     if opt.resolve_overflow():             # (reads a flag only on the guarded fp16 path)
                         print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
-                    imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires)
+                    imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial)
                     loss, _ = ops.deep_supervision_loss(net(imgs), target)
                     torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
                                                                           device=device))

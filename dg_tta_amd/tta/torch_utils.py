@@ -9,6 +9,7 @@ from .. import ops
 from ..utils import cpu_generator, upload_async
 
 _VOLUME_CACHE = {}
+_SPLINE_CACHE = {}
 
 
 def _resident(data, device):
@@ -37,16 +38,33 @@ def _resident(data, device):
     return img, mn, lab
 
 
+def resident_spline(data, device):
+    """Cubic B-spline coefficients [1,1,Dv,Hv,Wv] fp32 of a case's resident image (ops.bspline3_prefilter), for pre-training's
+    rotation / scaling augmentation: built on first use and kept beside the volume under the same rule - a hit requires the
+    same tensor object at the same version; release_resident frees it with the volume."""
+    import weakref
+    key = (id(data), str(device))
+    hit = _SPLINE_CACHE.get(key)
+    if hit is not None and hit[0]() is data and hit[1] == data._version:
+        return hit[2]
+    coef = ops.bspline3_prefilter(_resident(data, device)[0])
+    _SPLINE_CACHE[key] = (weakref.ref(data), data._version, coef)
+    weakref.finalize(data, _SPLINE_CACHE.pop, key, None)
+    return coef
+
+
 def release_resident(tensor_list=None):
-    """Frees the device copies of cached volumes: those of `tensor_list` (tta_main, after each sample), or all of them.
-    Entries are never evicted behind a running epoch's back: kernels enqueued on the input-pipeline stream may still
-    read them."""
+    """Frees the device copies of cached volumes (and their spline coefficients): those of `tensor_list` (tta_main, after
+    each sample), or all of them.  Entries are never evicted behind a running epoch's back: kernels enqueued on the
+    input-pipeline stream may still read them."""
     if tensor_list is None:
         _VOLUME_CACHE.clear()
+        _SPLINE_CACHE.clear()
         return
     ids = {id(t) for t in tensor_list}
-    for key in [k for k in _VOLUME_CACHE if k[0] in ids]:
-        del _VOLUME_CACHE[key]
+    for cache in (_VOLUME_CACHE, _SPLINE_CACHE):
+        for key in [k for k in cache if k[0] in ids]:
+            del cache[key]
 
 
 def as_label_map_case(image, label_map):

@@ -670,6 +670,36 @@ int dgtta_holes_apply(int64_t *map, int D, int H, int W, const uint8_t *mask, co
                       int ch, int cw, int64_t background, int64_t label, int64_t *count, void *stream);
 int dgtta_nonzero_mask(const float *data, int C, int64_t n, uint8_t *mask, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rotation / scaling augmentation of pre-training (csrc/spatial_aug.hip, dg_tta_amd/pretraining/spatial.py): patches sampled
+ * through an affine voxel map the way nnU-Net 2.2 samples them with scipy.ndimage.map_coordinates (restated from memory,
+ * UNPINNED).  Volumes are fp32 [D][H][W] with fewer than 2^31 voxels.
+ *
+ * bspline3_prefilter: dst = scipy.ndimage.spline_filter(src, order=3, mode="mirror") in fp32: along every axis gain 6, pole
+ * sqrt(3) - 2, the causal and anticausal recursion with the mirror initialisation (its sum cut after 64 terms, below fp32
+ * resolution); an axis of extent 1 is left as it is.  dst may be src.  Three launches; once per case.
+ *
+ * patch_sample_aug: items is a HOST array of n_items <= DGTTA_PATCH_MAX_ITEMS descriptors, copied into the kernel arguments
+ * (nothing is read from it after the call returns).  Output voxel v = (d, h, w) of item b reads the source position
+ *     x = map[0..2] . v + map[3],  map[4..6] . v + map[7],  map[8..10] . v + map[11]         (D, H, W order, voxel units)
+ * evaluated in double from the fp32 entries, which must be finite.  image float [B][1][PD][PH][PW]:
+ * map_coordinates(order, mode="constant", cval=0) - 0 when x leaves [0, n - 1] on any axis, else the (order + 1)^3 taps
+ * around x with mirrored tap indices; order 3 reads it.image as B-spline COEFFICIENTS (bspline3_prefilter), order 1 as the raw
+ * volume.  labels int64 [B][PD][PH][PW] from it.label (a label map stored as fp32 values): of the 8 trilinear corners of x,
+ * those outside the volume carry label 0; the mass of a label is the sum of the weights of the corners that carry it; the
+ * result is the largest label > 0 whose mass is >= 0.5, else 0.  order: 1 or 3 (DGTTA_ERR_UNSUPPORTED otherwise).  One launch.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_PATCH_MAX_ITEMS 16
+typedef struct DgttaPatchItem {
+  const float *image; /* device: coefficients (order 3) or raw volume (order 1) */
+  const float *label; /* device: label map */
+  int D, H, W;
+  float map[12];      /* row-major 3 x 4 [A | t] */
+} DgttaPatchItem;
+int dgtta_bspline3_prefilter(const float *src, float *dst, int D, int H, int W, void *stream);
+int dgtta_patch_sample_aug(const DgttaPatchItem *items, int n_items, int PD, int PH, int PW, int order, float *image,
+                           int64_t *labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
