@@ -75,23 +75,9 @@ def build_asan(verbose=False):
                   capture=not verbose)
 
 
-DIAG_DIR = CSRC.parents[1] / "build" / "diag"
-DIAG_LIB = CSRC.parents[1] / "profiles" / "tools" / "libdgtta_hip_diag.so"
-
-
-def build_diag(verbose=False):
-    """The LABORATORY build (-DDGTTA_DIAG): the same sources plus the timing-model / cycle-stamp instantiations and the
-    DGTTA_*_ABL, DGTTA_ROWS_VAR, DGTTA_RING_NT, DGTTA_WGRAD_RING_CLK switches that select them (results wrong by
-    construction, stamps written behind the caller's buffers).  It lands beside the scripts that use it
-    (profiles/tools/, loaded through DGTTA_LIB) and never in the package: the product library has none of this."""
-    return _build(DIAG_DIR, [*FLAGS, "-DDGTTA_DIAG"], DIAG_LIB, verbose=verbose)
-
-
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan(verbose=True))
-    elif "--diag" in sys.argv:
-        print(build_diag(verbose=True))
     else:
         build(force="--force" in sys.argv)
         print(LIB)

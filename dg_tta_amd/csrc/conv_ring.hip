@@ -83,10 +83,8 @@ __device__ __forceinline__ unsigned pack2_pk<bf16_t>(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
 
-template <bool NT_ST>
 __device__ __forceinline__ void store16_buf(u32x4_t rsrc, unsigned voff, unsigned soff, u32x4_t val) {
-  if (NT_ST) asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt" ::"v"(val), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-  else asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(val), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+  asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" ::"v"(val), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 
 // the n youngest vector-memory operations may stay in flight; n above the 40 cases is clamped, not dropped to vmcnt(0) as
@@ -104,10 +102,7 @@ struct RingGst {
   unsigned bytes;
 };
 
-// ABL (diagnostic builds, DGTTA_RING_ABL; results are wrong for 1 and 2): 1 no DMA after a job's first four planes, 2 no stores,
-// 3 a step's DMA pieces issued in one burst behind the barrier instead of one per input row, 6 per-segment cycle stamps and
-// the in-kernel clock, written behind the statistics (profiles/tools/ring_stamps.py)
-template <typename T16, bool NT_ST, int ABL = 0, bool GST = false, int KH = 1>
+template <typename T16, bool GST = false, int KH = 1>
 __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16_t *__restrict__ x, View xv, const bf16_t *__restrict__ w,
                                                                  Taps taps, const float *__restrict__ bias, bf16_t *__restrict__ y,
                                                                  View yv, int Cout, int tilesW, int tilesH, int nblkN, int nseg,
@@ -140,21 +135,6 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
 
   uint4 wreg[KH][27];
   int nb_loaded = -1;
-  // ABL 6 (diagnostic): cycle stamps per segment - 0 job prologue, 1 rows 0..6, 2 wait + barrier, 3 rows 7..15, 4 epilogue
-  unsigned long long tseg[5] = {0, 0, 0, 0, 0}, tprev = 0, t_begin = 0, rt_begin = 0;
-  auto stamp = [&](int i) {
-    if (ABL == 6) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_sched_barrier(0);
-      tseg[i] += t - tprev;
-      tprev = t;
-    }
-  };
-  if (ABL == 6) {
-    t_begin = __builtin_amdgcn_s_memtime();
-    rt_begin = __builtin_amdgcn_s_memrealtime();
-  }
   const int G = gridDim.x;
   const bool xcd_order = (G % 8) == 0;
   const int rounds = (njobs + G - 1) / G;
@@ -309,12 +289,8 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
         const auto p1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
         const u32x4_t val = {p0[0], p1[0], p0[1], p1[1]};
         const unsigned soff = (unsigned)(((long long)odg * yv.sd + (long long)ohg * yv.sh + (long long)ow0 * yv.sw + n0) * 2);
-        if (ABL != 2) {
-          store16_buf<NT_ST>(ry, ooff, soff, val);
-          ++issued;
-        } else {
-          asm volatile("" ::"v"(val), "s"(soff));
-        }
+        store16_buf(ry, ooff, soff, val);
+        ++issued;
         if (GST && goff != RSRC_OOB) {       // (a voxel beyond W contributes nothing)
           const u32x4_t yq = gy[oh];
 #pragma unroll
@@ -371,7 +347,9 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
             for (int r = 0; r < 4; ++r) acc[od][oh][hf][r] = bv[r];
     };
     int mark_cur = 0, mark_nxt = 0;
-    auto issue_group = [&](int pr, int ip) {
+    // (always_inline: with 64 input channels the 13 pieces are above the inliner's threshold, and an out-of-line copy would take
+    // the descriptor and the LDS address in vector registers, which the DMA's scalar operands do not accept)
+    auto issue_group = [&](int pr, int ip) __attribute__((always_inline)) {
 #pragma unroll
       for (int i = 0; i < C::NPW; ++i) issued += issue_piece(i, pr, ip);
       return issued;
@@ -388,22 +366,16 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
       for (int rs = RS0; rs < RS1; ++rs) {
         const int dz = rs >> 2, hy = rs & 3;
         if (BAR7 && rs == 7) {
-          stamp(1);
           ring_wait_all_but(issued - mark_cur);
           lds_barrier();
-          stamp(2);
         }
         // the row's DMA piece (wave-uniform branches) first; then ONE basic block: the six (twelve) fragment reads of row rs + 1
         // dealt out BETWEEN the MFMAs of row rs.  Round 5: with the reads in front of the MFMAs and the DMA between them, a wave
         // issued no MFMA for ~150 cycles per row - hidden by the SIMD's second wave with 32 input channels, plain idle time of
         // the matrix pipe with 64 (one wave per SIMD): profiles/r05_ab.txt.
-        if (DMA0 >= 0 && more) {
-          if (ABL == 3) {
-            if (rs == DMA0) mark_nxt = issue_group(prn, 2 * k + 4);
-          } else if (rs >= DMA0 && rs < DMA0 + C::NPW) {
-            issued += issue_piece(rs - DMA0, prn, 2 * k + 4);
-            if (rs == DMA0 + C::NPW - 1) mark_nxt = issued;
-          }
+        if (DMA0 >= 0 && more && rs >= DMA0 && rs < DMA0 + C::NPW) {
+          issued += issue_piece(rs - DMA0, prn, 2 * k + 4);
+          if (rs == DMA0 + C::NPW - 1) mark_nxt = issued;
         }
         if (GST && rs == 8) load_gy(k, 0);
         if (GST && rs == 12) load_gy(k, 1);
@@ -431,7 +403,6 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
           else ring_sched_interleave<24 * KH, 6 * KH>();
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (rs == 15) stamp(3);
         if (rs == 10 || rs == 11 || rs == 14 || rs == 15) epilogue_row(k, (rs >> 2) - 2, (rs & 3) - 2);
       }
     };
@@ -439,21 +410,18 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
     typedef std::integral_constant<int, 16> I16;
 
     lds_barrier();      // every wave is done with the previous job's planes
-    if (ABL == 6) tprev = __builtin_amdgcn_s_memtime();
     const int mark_p = issue_group(0, 0);
     mark_cur = issue_group(1, 2);      // planes 2, 3: needed behind M_0
     ring_wait_all_but(issued - mark_p);
     lds_barrier();      // planes 0, 1 are there
-    stamp(0);
     int kk = 0;         // k mod 3: ring pair that holds the step's first two planes
     {
       for (int k = 0; k < nsteps; ++k) {
-        const bool more = k + 1 < nsteps && ABL != 1;
+        const bool more = k + 1 < nsteps;
         mark_nxt = issued;
         init_acc();
         load_row(0, kk, fr[0]);
         rows(I0{}, I16{}, std::true_type{}, I0{}, k, kk, more);
-        stamp(4);
         mark_cur = mark_nxt;
         kk = kk == 2 ? 0 : kk + 1;
       }
@@ -508,12 +476,6 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
       if (blockIdx.x == 0 && tid == 0 && rd == 0) reinterpret_cast<long long *>(stats)[0] = nblk;
     }
   }
-  if (ABL == 6 && stats && lane == 0) {      // behind everything the finalize kernels read (profiles/tools/ring_stamps.py knows the place)
-    double *o = stats + (1 << 20) + ((size_t)blockIdx.x * C::NW + wave) * 8;
-    for (int i = 0; i < 5; ++i) o[i] = (double)tseg[i];
-    o[5] = (double)(__builtin_amdgcn_s_memtime() - t_begin);
-    o[6] = (double)(__builtin_amdgcn_s_memrealtime() - rt_begin);
-  }
 }
 
 }  // namespace
@@ -541,12 +503,11 @@ int ring_launch_kh(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slot
   if (xv.sw % 8 || xv.sh % 8 || xv.sd % 8 || xv.sb % 8 || yv.sw % 8 || yv.sh % 8 || yv.sd % 8 || yv.sb % 8 || ((uintptr_t)x & 15) ||
       ((uintptr_t)y & 15))
     return DGTTA_ERR_UNSUPPORTED;
-  static int ncu_dev = [] {
+  static int ncu = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  const int ncu = DG_LAB_NCU(ncu_dev);
   const int tW = cdiv(yv.W, C::TW), tH = cdiv(yv.H, C::TH), nblkN = Cout / 32;
   const int steps_total = (yv.D + 1) / 2;
   const long long ncol = (long long)B * nblkN * tW * tH;
@@ -568,11 +529,10 @@ int ring_launch_kh(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slot
   if (njobs >= (1ll << 31)) return DGTTA_ERR_UNSUPPORTED;
   // a data gradient that is asked to leave the InstanceNorm backward sums of the previous block (dgtta_conv3d_k3_dgrad_gstats)
   RingGst ga{};
-  const int abl = DG_LAB(ring_abl);      // laboratory builds (libdgtta_hip_diag.so only): timing models and cycle stamps
   const long long gb = gctx ? ((long long)(yv.D - 1) * yv.H * yv.W * gctx->ldy + (long long)(yv.H - 1) * yv.W * gctx->ldy +
                                (long long)(yv.W - 1) * gctx->ldy + Cout) * 2 : 0;
   const bool gst_on = gctx && !stats && !bias && gctx->ldy % 8 == 0 && ((uintptr_t)gctx->y & 15) == 0 && gb < (1ll << 31) &&
-                      (int64_t)tW * tH * nseg <= stats_cap_slots && abl < 0;
+                      (int64_t)tW * tH * nseg <= stats_cap_slots;
   if (gst_on) {
     ga.y = (const bf16_t *)gctx->y;
     ga.v = dense_view(B, yv.D, yv.H, yv.W, (int)gctx->ldy);
@@ -586,12 +546,9 @@ int ring_launch_kh(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slot
   }
   if (dry) return DGTTA_OK;      // (dgtta_conv3d_k3_blocked_supported: would this launch be taken?)
   const int grid = (int)(njobs < ncu ? njobs : ncu);
-  // DGTTA_RING_NT=1 (diagnostic build): non-temporal output stores (measured 5 % slower: the two 32-byte halves of a voxel come
-  // from two waves and merge in L2)
-  const bool nt = DG_LAB(ring_nt) == '1';
-#define RING_LAUNCH(T16, NTS, ABLV, GSTV)                                                                                     \
+#define RING_LAUNCH(T16, GSTV)                                                                                                \
   do {                                                                                                                        \
-    auto kern = conv3_ring_kernel<T16, NTS, ABLV, GSTV, KH>;                                                                  \
+    auto kern = conv3_ring_kernel<T16, GSTV, KH>;                                                                             \
     static DynLdsOnce once;                                                                                                   \
     DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(kern), C::LDS_BYTES) == hipSuccess, DGTTA_ERR_LAUNCH,      \
                "conv3_ring: cannot raise the dynamic LDS limit to %d", C::LDS_BYTES);                                         \
@@ -599,38 +556,15 @@ int ring_launch_kh(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slot
                        (bf16_t *)y, yv, Cout, tW, tH, nblkN, nseg, sps, (int)njobs, stats, ntaps_src, (unsigned)xb,           \
                        (unsigned)yb, ga, xkh);                                                                                \
   } while (0)
-  bool diag = false;
-#ifdef DGTTA_DIAG
-  if constexpr (KH == 1) {      // diagnostic builds exist for the fp16 / 32-channel instantiation only; exact values only
-    if (is_f16 && (abl == '1' || abl == '2' || abl == '3')) {
-      diag = true;
-      if (abl == '1') RING_LAUNCH(f16_t, false, 1, false);
-      else if (abl == '2') RING_LAUNCH(f16_t, false, 2, false);
-      else RING_LAUNCH(f16_t, false, 3, false);
-    } else if (is_f16 && abl == '6') {
-      // cycle stamps go to stats + 2^20 doubles, past what dgtta_conv3d_stats_bytes covers: only profiles/tools/ring_stamps.py,
-      // which allocates that area itself, may ask for this build (it does not exist in the product library)
-      diag = true;
-      RING_LAUNCH(f16_t, false, 6, false);
-    }
-    if (!diag && nt) {
-      diag = true;
-      if (is_f16) RING_LAUNCH(f16_t, true, 0, false);
-      else RING_LAUNCH(bf16_t, true, 0, false);
-    }
-  }
-#endif
-  if (diag) {
-  } else if (gst_on) {
-    if (is_f16) RING_LAUNCH(f16_t, false, 0, true);
-    else RING_LAUNCH(bf16_t, false, 0, true);
+  if (gst_on) {
+    if (is_f16) RING_LAUNCH(f16_t, true);
+    else RING_LAUNCH(bf16_t, true);
   } else if (is_f16) {
-    RING_LAUNCH(f16_t, false, 0, false);
+    RING_LAUNCH(f16_t, false);
   } else {
-    RING_LAUNCH(bf16_t, false, 0, false);
+    RING_LAUNCH(bf16_t, false);
   }
 #undef RING_LAUNCH
-  (void)nt;
   DG_CHECK_LAUNCH("conv3_ring_kernel");
   return DGTTA_OK;
 }

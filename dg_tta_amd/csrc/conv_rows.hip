@@ -1,7 +1,6 @@
 // Row-reuse 3x3x3 convolution kernel (bf16, stride 1) -- see the block comment below.
 #include "conv_common.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -35,17 +34,12 @@ struct RowsCfg {
   static constexpr size_t LDS_BYTES = 2 * A_BYTES + B_BYTES + RED_BYTES;
 };
 
-// VAR (round 3, bit mask; default 5 = 1 | 4, DGTTA_ROWS_VAR=0: the round-2 kernel): 1 = the next job's coordinates come from a mixed-radix
-// counter (a few scalar adds) instead of ten integer divisions on the CU's one scalar unit, which all 8 waves queued on
-// (stamps: 5.7 % of the kernel); 2 = the DMA pieces of the next chunk are issued in the first 5/8 of the MFMA loop, so
-// that they have landed when the loop ends (measured: no gain, not in the default); 4 = the 27 weight fragments are read from LDS just in time inside the MFMA
-// loop (taps (kd,kh) in order of first use) instead of in a block before it, and the barrier that frees the weight
-// buffer for the next chunk's DMA sits in the middle of the loop.  Stamps (128^3 32->32): each feature shortens its own
-// segment (job decode 13.7 k -> 8.6 k cycles per wave, weight reload + barriers 31.9 k -> 17.1 k of 238 k) and the MFMA
-// loop of the lock-stepped waves absorbs most of it; net 1.5-2.5 % per launch.  Also tried in round 3 and dropped: the A image
-// filled as flat 1-KiB pieces crossing row boundaries (12 instead of 20 piece issues per wave and phase): 8 % SLOWER -
-// the per-lane row select and address arithmetic cost more than the issue slots they save.
-// GST (round 3): the launch is the DATA GRADIENT of a conv whose input was z = LeakyReLU(InstanceNorm(y_prev)): the
+// Two things keep the scalar unit and the LDS out of the MFMA loop's way (what each bought, and the variants that were
+// measured and dropped: DESIGN.md).  The next job's coordinates come from a mixed-radix counter (a few scalar adds)
+// instead of ten integer divisions on the CU's one scalar unit, which all 8 waves queued on.  The 27 weight fragments are
+// read from LDS just in time inside the MFMA loop (taps (kd,kh) in order of first use), and the barrier that frees the
+// weight buffer for the next chunk's DMA sits in the middle of the loop.
+// GST: the launch is the DATA GRADIENT of a conv whose input was z = LeakyReLU(InstanceNorm(y_prev)): the
 // epilogue also accumulates the statistics the InstanceNorm backward of that previous layer needs,
 //   sum_v g'  and  sum_v g' * y_prev   with  g' = gz * lrelu'(A y_prev + B),  A = gamma * rstd,  B = beta - mean * A
 // (sum g' xhat = rstd (sum g' y - mean sum g')), from the gz values it is about to store (rounded, as the apply pass reads
@@ -58,7 +52,7 @@ struct GstArgs {
   float slope;
 };
 
-template <int PD, int PH, int WD, int WH, int ABL = 0, typename T16 = bf16_t, int VAR = 0, bool GST = false>   // ABL: diagnostic ablation
+template <int PD, int PH, int WD, int WH, typename T16 = bf16_t, bool GST = false>
 __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *__restrict__ x, View xv,
                                                                  const bf16_t *__restrict__ w, Taps taps,
                                                                  const float *__restrict__ bias, bf16_t *__restrict__ y,
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
     if (i < 2 * NPR) {
       const int row = wave + (i >> 1) * NW;          // wave-uniform
       const bool tail = i & 1;
-      if (row < Cfg::NROW && (!tail || lane < 4) && !(ABL == 7 && tail)) {
+      if (row < Cfg::NROW && (!tail || lane < 4)) {
         const int dz = row / IH, hy = row % IH;
         const int gd = q.od0 - 1 + dz, gh = q.oh0 - 1 + hy;
         const int g = tail ? t_g : m_g, gw = q.ow0 - 1 + (tail ? t_wx : m_wx);
@@ -176,7 +170,6 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
                         c < cin_lim;
         const bf16_t *rowp = x + (long long)q.b * xv.sb + gd * xv.sd + gh * xv.sh;      // scalar part
         const void *src = ok ? (const void *)(rowp + gw * xv.sw + c) : (const void *)&g_zero16;
-        if (ABL == 1 || ABL == 4 || (ABL == 9 && dz >= 4)) return;      // 9: timing model of a D-ring (4 new planes of 6)
         dma16_to_lds(src, lds_addr_of(sAb + (size_t)buf * Cfg::A_BYTES + (row * Cfg::RB + (tail ? 64 : 0)) * 16));
       }
     } else {
@@ -185,7 +178,6 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
         const int wt = my_wt[i - 2 * NPR];
         const void *src = wt >= 0 ? (const void *)(w + ((((long long)(q.n0 / 32) * nk + kc) * ntaps_src + wt) * 64 + lane) * 8)
                                   : (const void *)&g_zero16;
-        if (ABL == 1 || ABL == 5) return;
         dma16_to_lds(src, lds_addr_of(sBb + tap * 1024));
       }
     }
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
     abase[kw] = ((wd * PD) * IH + wh * PH) * Cfg::RB + (col < 32 ? h * 32 + col : 64 + h * 2 + (col - 32));
   }
 
-  // mixed-radix job counter (VAR & 1): digits (nb_lo, td_lo, th_lo, td_hi, th_hi, nb_hi, tw | b) of the current job index
+  // mixed-radix job counter: digits (nb_lo, td_lo, th_lo, td_hi, th_hi, nb_hi, tw | b) of the current job index
   // and of the stride between this workgroup's jobs; advancing = digit-wise add with carry, all on wave-uniform values
   int dg[8], sdg[8];
   const int rad[7] = {NBL, TDL, THL, tdH, thH, nbH, tilesW};
@@ -241,24 +233,8 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
 #pragma unroll
   for (int i = 0; i < NPIECE; ++i) issue_piece(cur, 0, 0, i);
   int kc = 0, jn = jbeg;
-  unsigned long long tseg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;     // ABL 6: cycle stamps per segment (diagnostic)
-  auto stamp = [&](int k) {
-    if (ABL == 6) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_sched_barrier(0);
-      tseg[k] += t - tprev;
-      tprev = t;
-    }
-  };
-  unsigned long long t_begin = 0, rt_begin = 0;      // ABL 6: in-kernel clock = d(s_memtime) / d(s_memrealtime) x 100 MHz
-  if (ABL == 6) {
-    tprev = t_begin = __builtin_amdgcn_s_memtime();
-    rt_begin = __builtin_amdgcn_s_memrealtime();
-  }
   for (int p = 0; p < nph; ++p) {
     dma_wait_all();
-    stamp(0);                 // waiting for the DMA
     lds_barrier();            // chunk p has landed; every wave is done with phase p-1
     uint4 breg[27];
     const uint4 *sB = reinterpret_cast<const uint4 *>(sBb);
@@ -266,13 +242,8 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) breg[(kd * 3 + kh) * 3 + kw] = sB[((kd * 3 + kh) * 3 + kw) * 64 + lane];
     };
-    if (VAR & 4) {
-      static_assert(!(VAR & 4) || (PD == 2 && PH == 2), "the just-in-time weight schedule is written for 2 x 2 patches");
-      load_b(0, 0);
-    } else {
-#pragma unroll
-      for (int t = 0; t < 27; ++t) breg[t] = sB[t * 64 + lane];
-    }
+    static_assert(PD == 2 && PH == 2, "the just-in-time weight schedule is written for 2 x 2 patches");
+    load_b(0, 0);
     if (kc == 0) {            // bias of this job, fetched while no DMA is in flight (its wait would drain them)
       const int co = cur.n0 + r;
       bv = (bias && co < Cout) ? bias[co] : 0.f;
@@ -289,17 +260,14 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
         gst_newrun = false;         // (published by the barriers between here and the epilogue)
       }
     }
-    if (!(VAR & 4)) lds_barrier();            // B buffer is free again (VAR & 4: in the middle of the MFMA loop)
-    stamp(1);                 // barrier + B fragments + barrier
     // prefetch the next phase (next K-chunk of this job, or chunk 0 of the next job)
     Job nxt = cur;
     int kn = kc + 1;
     if (kn == nk) {
       kn = 0;
-      if (p + 1 < nph) nxt = ((VAR & 1) && order != 0) ? advance() : decode(jn + jstep);
+      if (p + 1 < nph) nxt = order != 0 ? advance() : decode(jn + jstep);
     }
     const bool more = p + 1 < nph;
-    stamp(2);
 
     if (kc == 0) {          // accumulators start at the bias of this lane's output channel (column re of every row)
 #pragma unroll
@@ -315,54 +283,46 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
       for (int dz = 0; dz < PD + 2; ++dz)
 #pragma unroll
         for (int hy = 0; hy < PH + 2; ++hy) {
-          if (VAR & 4) {
-            // weight fragments just in time: tap row (kd, kh) is first used at input row (dz, hy) = (kd, kh); row step rs
-            // reads the fragments whose first use is 1-3 steps ahead.  After step 7 every wave holds all 27: the barrier
-            // at step 8 frees the weight buffer, the DMA pieces of the next weight chunk are issued after it.
-            const int rs = dz * (PH + 2) + hy;
-            constexpr int sched[8][2] = {{0, 1}, {0, 2}, {1, 0}, {1, 1}, {1, 2}, {2, 0}, {2, 1}, {2, 2}};
-            if (rs < 8) {
-              __builtin_amdgcn_sched_barrier(0);
-              load_b(sched[rs][0], sched[rs][1]);
-            } else if (rs == 8) {
-              __builtin_amdgcn_sched_barrier(0);
-              lds_barrier();
-            }
+          // weight fragments just in time: tap row (kd, kh) is first used at input row (dz, hy) = (kd, kh); row step rs
+          // reads the fragments whose first use is 1-3 steps ahead.  After step 7 every wave holds all 27: the barrier
+          // at step 8 frees the weight buffer, the DMA pieces of the next weight chunk are issued after it.
+          const int rs = dz * (PH + 2) + hy;
+          constexpr int sched[8][2] = {{0, 1}, {0, 2}, {1, 0}, {1, 1}, {1, 2}, {2, 0}, {2, 1}, {2, 2}};
+          if (rs < 8) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_b(sched[rs][0], sched[rs][1]);
+          } else if (rs == 8) {
+            __builtin_amdgcn_sched_barrier(0);
+            lds_barrier();
           }
 #pragma unroll
           for (int kw = 0; kw < 3; ++kw) {
             const uint4 af = sA[abase[kw] + (dz * IH + hy) * Cfg::RB];
-            {   // spread this wave's DMA pieces of the next chunk over the A-read steps (VAR & 2: over the first 5/8 of
-                // them; the weight pieces - the last ones - then still come after the barrier of step 24)
+            {   // spread this wave's DMA pieces of the next chunk over the A-read steps (the weight pieces - the last
+                // ones - come after the barrier of step 24)
               constexpr int NSTEP = (PD + 2) * (PH + 2) * 3;
-              constexpr int NISSUE = (VAR & 2) ? NSTEP * 5 / 8 : NSTEP;
-              static_assert(!(VAR & 4) || (2 * NPR * NISSUE) / NPIECE + 1 > 24, "weight pieces must follow the mid-loop barrier");
+              static_assert((2 * NPR * NSTEP) / NPIECE + 1 > 24, "weight pieces must follow the mid-loop barrier");
               const int step = (dz * (PH + 2) + hy) * 3 + kw;
 #pragma unroll
               for (int i = 0; i < NPIECE; ++i)
-                if (step == (i * NISSUE) / NPIECE + 1 && more) issue_piece(nxt, kn, (p + 1) & 1, i);
+                if (step == (i * NSTEP) / NPIECE + 1 && more) issue_piece(nxt, kn, (p + 1) & 1, i);
             }
 #pragma unroll
             for (int kd = 0; kd < 3; ++kd)
 #pragma unroll
               for (int kh = 0; kh < 3; ++kh) {
                 const int od = dz - kd, oh = hy - kh;
-                if (od >= 0 && od < PD && oh >= 0 && oh < PH) {
-                  if (ABL == 3) acc[od][oh][0] += __uint_as_float(af.x ^ breg[(kd * 3 + kh) * 3 + kw].x);
-                  else mfma_step<T16>(af, breg[(kd * 3 + kh) * 3 + kw], acc[od][oh]);
-                }
+                if (od >= 0 && od < PD && oh >= 0 && oh < PH) mfma_step<T16>(af, breg[(kd * 3 + kh) * 3 + kw], acc[od][oh]);
               }
           }
         }
     }
 
-    stamp(3);                 // MFMA loop
     if (kc == nk - 1) {
       // ---- epilogue of job `cur`: convert, transpose through LDS (this phase's A buffer, one 8-KiB slab per wave) so
       //      that a lane stores 16 bytes = 8 channels of a voxel; per-channel sum / sum of squares of the unrounded
       //      values for the following InstanceNorm, kept in registers over the jobs of one (sample, channel block) run.
       lds_barrier();          // every wave has finished reading this phase's A buffer
-      stamp(5);               // (diagnostic) barrier skew
       // lane-derived epilogue indices are rebuilt from a laundered lane id: otherwise the compiler hoists them out of
       // the phase loop, keeps them live across the MFMA phase and spills (a scratch reload's wait drains the DMA)
       int le = lane;
@@ -371,7 +331,7 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
       const int co = cur.n0 + re;
       unsigned char *slabb = sAb + (size_t)(p & 1) * Cfg::A_BYTES + wave * (PD * PH * 2048);
       const bool full = cur.od0 + Cfg::TD <= Do && cur.oh0 + Cfg::TH <= Ho && cur.ow0 + 32 <= Wo && cur.n0 + 32 <= Cout;
-      if (full && ABL != 7) {
+      if (full) {
         // Fast path (whole tile inside the volume).  The MFMA leaves a lane with ONE channel (re) and 16 voxels, 4
         // consecutive ones per q group: the slab is CHANNEL-major [32 ch][32 voxels] bf16 (64-byte rows), written 8 bytes
         // (4 voxels) at a time - 4 ds_write_b64 + 8 packed converts per accumulator instead of 16 2-byte writes and 16
@@ -453,9 +413,8 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
             const int ow = cur.ow0 + 16 * vb + li;
             // NON-TEMPORAL store: the output streams through L2 instead of displacing the input lines, whose second
             // 16-channel half is fetched one phase later.  PMC, 128^3 32->32, one sample: FETCH 353 -> 197 MB (134 MB
-            // of input; the rest is the D-halo of consecutive jobs), WRITE unchanged (DGTTA_ROWS_ABL=8: plain stores)
-            if (ABL == 8) *reinterpret_cast<uint4 *>(orow + ow * yv.sw) = val;
-            else if (ABL != 2) st16_nt(orow + ow * yv.sw, val);
+            // of input; the rest is the D-halo of consecutive jobs), WRITE unchanged
+            st16_nt(orow + ow * yv.sw, val);
           }
         };
         // (a wave reads back only its own slab: LDS operations of one wave complete in order); the read-back and stores
@@ -490,7 +449,6 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
             }
           }
         }
-        stamp(7);               // (diagnostic) slab reads + global stores
       } else {
         // ragged tile: voxel-major slab [32 voxels][32 ch] with 2-byte writes and per-element bounds
         bf16_t *slab = reinterpret_cast<bf16_t *>(slabb);
@@ -511,7 +469,6 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
               }
             }
           }
-        stamp(6);
 #pragma unroll
         for (int i = 0; i < PD; ++i)
 #pragma unroll
@@ -523,11 +480,10 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
               const int m = t * 16 + (le >> 2), cq = (le & 3) * 8;
               const uint4 val = *reinterpret_cast<const uint4 *>(slab + (i * PH + j) * 1024 + m * 32 + cq);
               const int ow = cur.ow0 + m;
-              if (ABL != 2 && od < Do && oh < Ho && ow < Wo && cur.n0 + cq < Cout)
+              if (od < Do && oh < Ho && ow < Wo && cur.n0 + cq < Cout)
                 *reinterpret_cast<uint4 *>(orow + ow * yv.sw + cq) = val;
             }
           }
-        stamp(7);
       }
       if (stats) {
         // the partial sums of a run of jobs over one (sample, channel block) are flushed once, into the slot of the run's
@@ -564,19 +520,11 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
         if (blockIdx.x == 0 && tid == 0 && p == nk - 1) reinterpret_cast<long long *>(stats)[0] = tiles_per_b;
       }
     }
-    stamp(4);                 // epilogue
     kc = kn;
     if (kn == 0) {
       cur = nxt;
       jn += jstep;
     }
-  }
-  if (ABL == 6 && stats && lane == 0) {
-    for (int k = 0; k < 8; ++k) stats[4096 + ((size_t)blockIdx.x * NW + wave) * 8 + k] = (double)tseg[k];
-    stats[4096 + (size_t)gridDim.x * NW * 8 + ((size_t)blockIdx.x * NW + wave) * 2 + 0] =
-        (double)(__builtin_amdgcn_s_memtime() - t_begin);
-    stats[4096 + (size_t)gridDim.x * NW * 8 + ((size_t)blockIdx.x * NW + wave) * 2 + 1] =
-        (double)(__builtin_amdgcn_s_memrealtime() - rt_begin);
   }
 }
 
@@ -593,15 +541,9 @@ int launch_conv_rows(const ConvLaunch &L, const Taps &taps) {
   double *stats = L.stats;
   RowsGstCtx *gctx = L.gst;
   GstArgs ga{};
-  // laboratory builds of the same kernel (libdgtta_hip_diag.so only).  DGTTA_ROWS_ABL: 1 no DMA, 3 no MFMA, 6 per-segment cycle
-  // stamps, 7 the voxel-major (ragged-tile) epilogue for every tile, 8 plain (temporal) output stores; DGTTA_ROWS_VAR: '0' =
-  // the round-2 kernel, default = feature mask 5
-  const int abl = DG_LAB(rows_abl);
-  const int var = DG_LAB(rows_var);
   // eligible: no forward statistics asked for, every tile whole, whole 32-channel blocks
   const bool gst_on = gctx && !stats && !bias && yv.D % Cfg::TD == 0 && yv.H % Cfg::TH == 0 && yv.W % 32 == 0 && Cout % 32 == 0 &&
-                      CoutP == Cout && gctx->ldy % 8 == 0 && ((uintptr_t)gctx->y & 15) == 0 && abl < 0 &&
-                      var != '7' && var != '0';      // (those builds have no GST form)
+                      CoutP == Cout && gctx->ldy % 8 == 0 && ((uintptr_t)gctx->y & 15) == 0;
   if (gst_on) {
     ga.y = (const bf16_t *)gctx->y;
     ga.v = dense_view(B, yv.D, yv.H, yv.W, (int)gctx->ldy);
@@ -612,28 +554,10 @@ int launch_conv_rows(const ConvLaunch &L, const Taps &taps) {
     stats = gctx->out;
     gctx->produced = 1;
   }
-  auto kern = conv3_rows_kernel<PD, PH, WD, WH, 0, T16, 5>;
-  static DynLdsOnce once[16];
-  int slot = 0;
-  if (gst_on) kern = conv3_rows_kernel<PD, PH, WD, WH, 0, T16, 5, true>, slot = 15;
-#ifdef DGTTA_DIAG
-  if (var == '0') kern = conv3_rows_kernel<PD, PH, WD, WH, 0, T16, 0>, slot = 6;
-  if (std::is_same<T16, bf16_t>::value) {      // diagnostic builds exist for the bf16 instantiation only
-    if (var == '7') kern = conv3_rows_kernel<PD, PH, WD, WH, 0, T16, 7>, slot = 7;
-    if (abl == '1') kern = conv3_rows_kernel<PD, PH, WD, WH, 1, T16, 0>, slot = 1;
-    if (abl == '3') kern = conv3_rows_kernel<PD, PH, WD, WH, 3, T16, 0>, slot = 2;
-    if (abl == '6') {
-      kern = conv3_rows_kernel<PD, PH, WD, WH, 6, T16, 5>, slot = 3;
-      if (var == '0') kern = conv3_rows_kernel<PD, PH, WD, WH, 6, T16, 0>, slot = 9;
-    }
-    if (abl == '7') kern = conv3_rows_kernel<PD, PH, WD, WH, 7, T16, 0>, slot = 4;
-    if (abl == '4') kern = conv3_rows_kernel<PD, PH, WD, WH, 4, T16, 0>, slot = 12;
-    if (abl == '5') kern = conv3_rows_kernel<PD, PH, WD, WH, 5, T16, 0>, slot = 13;
-    if (abl == '9') kern = conv3_rows_kernel<PD, PH, WD, WH, 9, T16, 0>, slot = 14;
-    if (abl == '8') kern = conv3_rows_kernel<PD, PH, WD, WH, 8, T16, 0>, slot = 5;
-  }
-#endif
-  DG_REQUIRE(ensure_dyn_lds(once[slot], reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess,
+  auto kern = conv3_rows_kernel<PD, PH, WD, WH, T16>;
+  static DynLdsOnce once_plain, once_gst;
+  if (gst_on) kern = conv3_rows_kernel<PD, PH, WD, WH, T16, true>;
+  DG_REQUIRE(ensure_dyn_lds(gst_on ? once_gst : once_plain, reinterpret_cast<const void *>(kern), (int)Cfg::LDS_BYTES) == hipSuccess,
              DGTTA_ERR_LAUNCH, "conv3_rows: cannot raise the dynamic LDS limit to %zu", (size_t)Cfg::LDS_BYTES);
   const int tW = cdiv(yv.W, 32), tH = cdiv(yv.H, Cfg::TH), tD = cdiv(yv.D, Cfg::TD), nblkN = cdiv(CoutP, 32);
   const long long njobs = (long long)tW * tH * tD * nblkN * B;

@@ -15,7 +15,7 @@
 //   * the accumulators live across all jobs of the workgroup: one slab per workgroup (<= 256 per channel-block pair), the two
 //     row halves of a tap are added through LDS once, at the very end.
 // Measured (MI355X, fp16, 8 x 128^3, 200 back-to-back launches, same box): 32 -> 32 0.948 -> 0.933 ms, 64 -> 32 1.96 -> 1.81 ms
-// (one dy stream per channel-block pair less halo).  Stamps (profiles/tools/wring_clock.py): in-kernel clock 1.87-1.98 GHz, MFMA
+// (one dy stream per channel-block pair less halo).  Stamps (profiles/r04_wring_clock.txt): in-kernel clock 1.87-1.98 GHz, MFMA
 // busy 60 % of the wave time, 19 % at the barrier (the older wave of a SIMD pair 30 %, the younger 8 %).  Timing models (wrong
 // results): without the DMA inside the sweep the cycles fall 8 % and the CLOCK rises from 1.98 to 2.39 GHz (0.82 -> 0.64 ms);
 // without the LDS operand reads -16 % cycles at 2.21 GHz: the sweep is power bound, and what it spends on moving its two
@@ -89,8 +89,7 @@ __device__ __forceinline__ bool wr_reuse_stored(int wq, int i, bool pair, int ha
 // registers.  16 + 4 instead of 28 + 4 operand reads per row half and k-step: the sweep was bound by the LDS read rate
 // (512 KiB per CU and slice = 4096 clk against 3584 clk of MFMA), not by the matrix pipe.  With PAIR the
 // pair slot s < 3 holds tap kh = s of columns 2 wq (rows 0..15) and 2 wq + 1 (rows 16..31), slot 3 the ninth column's tap.
-template <typename T16, bool MF16, bool CLK = false, bool PAIR = false, bool REUSE = false>      // MF16: v_mfma_f32_16x16x32 (K = the row's 32 voxels) instead of 32x32x16;
-                                                                           // CLK (diagnostic): cycle / real-time stamps behind the slabs
+template <typename T16, bool MF16, bool PAIR = false, bool REUSE = false>      // MF16: v_mfma_f32_16x16x32 (K = the row's 32 voxels) instead of 32x32x16
 __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf16_t *__restrict__ x, View xv, const bf16_t *__restrict__ dy,
                                                                        View yv, float *__restrict__ slabs, int Cin, int Cout, int tilesW,
                                                                        int tilesH, int nseg, int DR, int cobs, int njobs, unsigned x_bytes,
@@ -100,11 +99,6 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char *sX = smem, *sY = smem + WR::NXS * WR::X_SLICE_B;
   const unsigned lds0 = lds_addr_of(smem);
-  unsigned long long t_begin = 0, rt_begin = 0, t_wait = 0;
-  if (CLK) {
-    t_begin = __builtin_amdgcn_s_memtime();
-    rt_begin = __builtin_amdgcn_s_memrealtime();
-  }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rh = wave & 1, wq = wave >> 1;      // row half, tap residue
   const int D = yv.D, H = yv.H, W = yv.W;
@@ -255,11 +249,8 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
     // four magic-number divisions and seven slot selects - sat between the barrier and the slice's first operand read)
     int xr0 = (d_begin + WR::NXS) % WR::NXS, yr0 = (d_begin + WR::NYS) % WR::NYS;
     for (int d = d_begin; d < d_end; ++d) {
-      unsigned long long tw0 = 0;
-      if (CLK) tw0 = __builtin_amdgcn_s_memtime();
       vm_wait_all_but<10>(issued - mark_cur);      // this wave's pieces of x(d + 1), dy(d) have landed ...
       lds_barrier();                           // ... and everyone's; every wave is done with slice d - 1
-      if (CLK) t_wait += __builtin_amdgcn_s_memtime() - tw0;
       const bool more = d + 2 < d_end;         // x(d + 3), dy(d + 2): first read in slice d + 2
       int mark_new = issued;
       const unsigned char *ys0 = sY + yr0 * WR::Y_SLICE_B + rh * 4 * WR::Y_ROW_B;
@@ -406,12 +397,6 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
     }
   }
 
-  if (CLK && lane == 0) {
-    float *o = slabs + (int64_t)gridDim.y * gridDim.x * (27 * 1024) + ((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * WR::NW + wave) * 4;
-    o[0] = (float)(__builtin_amdgcn_s_memtime() - t_begin);
-    o[1] = (float)(__builtin_amdgcn_s_memrealtime() - rt_begin);
-    o[2] = (float)t_wait;
-  }
   // the two row halves of a tap: waves with rh = 1 hand their accumulators over through LDS, which overlays the rings.  A
   // workgroup whose LAST job has a single slice (DR == 1 or a one-slice tail segment) has only waited for the first three of
   // its prologue's four DMA groups: drain them all before the overlay is written (free for every other job: already drained)
@@ -502,10 +487,10 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
   if (ncol * yv.D < 4ll * ncu * 8 / pairs && sw != '1' && sw != '5' && sw != '6')
     return 0;      // (=1 / =5 / =6: forced, for the tests; 5 = forced, one tap per MFMA for Cin <= 16 and no operand reuse; 6 = forced, no operand reuse)
   if (dry) return G;      // (dgtta_conv3d_k3_blocked_supported: would this launch be taken?)
-#define WR_LAUNCH(T16, MF, CK) WR_LAUNCH_P(T16, MF, CK, false, false)
-#define WR_LAUNCH_P(T16, MF, CK, PR, RU)                                                                                          \
+#define WR_LAUNCH(T16, MF) WR_LAUNCH_P(T16, MF, false, false)
+#define WR_LAUNCH_P(T16, MF, PR, RU)                                                                                           \
   do {                                                                                                                         \
-    auto kern = conv3_wgrad_ring_kernel<T16, MF, CK, PR, RU>;                                                                      \
+    auto kern = conv3_wgrad_ring_kernel<T16, MF, PR, RU>;                                                                      \
     static DynLdsOnce once;                                                                                                    \
     if (ensure_dyn_lds(once, reinterpret_cast<const void *>(kern), WR_LDS_TOTAL) != hipSuccess) {                              \
       dgtta_set_error("wgrad_ring: cannot raise the dynamic LDS limit to %d", WR_LDS_TOTAL);                                   \
@@ -521,34 +506,23 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
   const bool mf16 = sw == '4';
   // operands shared between neighbouring rows (REUSE; DGTTA_WGRAD_RING=6: its predecessor)
   const bool reuse = !mf16 && sw != '5' && sw != '6';
-  bool lab = false;
   // Cin <= 16 (the first layer): two taps per MFMA (DGTTA_WGRAD_RING=5: the one-tap form, its predecessor)
   if (Cin <= 16 && !mf16 && sw != '5') {
-    lab = true;
     if (is_f16) {
-      if (reuse) WR_LAUNCH_P(f16_t, false, false, true, true);
-      else WR_LAUNCH_P(f16_t, false, false, true, false);
+      if (reuse) WR_LAUNCH_P(f16_t, false, true, true);
+      else WR_LAUNCH_P(f16_t, false, true, false);
     } else {
-      if (reuse) WR_LAUNCH_P(bf16_t, false, false, true, true);
-      else WR_LAUNCH_P(bf16_t, false, false, true, false);
+      if (reuse) WR_LAUNCH_P(bf16_t, false, true, true);
+      else WR_LAUNCH_P(bf16_t, false, true, false);
     }
-  }
-#ifdef DGTTA_DIAG
-  if (!lab && is_f16 && DG_LAB(wgrad_ring_lab) == '6') {      // DGTTA_WGRAD_RING_CLK=6: cycle stamps BEHIND the slabs; only
-    lab = true;                                        // profiles/tools/wring_clock.py, which allocates that area, asks for it
-    if (reuse) WR_LAUNCH_P(f16_t, false, true, false, true);
-    else WR_LAUNCH(f16_t, false, true);
-  }
-#endif
-  if (lab) {
   } else if (is_f16) {
-    if (mf16) WR_LAUNCH(f16_t, true, false);
-    else if (reuse) WR_LAUNCH_P(f16_t, false, false, false, true);
-    else WR_LAUNCH(f16_t, false, false);
+    if (mf16) WR_LAUNCH(f16_t, true);
+    else if (reuse) WR_LAUNCH_P(f16_t, false, false, true);
+    else WR_LAUNCH(f16_t, false);
   } else {
-    if (mf16) WR_LAUNCH(bf16_t, true, false);
-    else if (reuse) WR_LAUNCH_P(bf16_t, false, false, false, true);
-    else WR_LAUNCH(bf16_t, false, false);
+    if (mf16) WR_LAUNCH(bf16_t, true);
+    else if (reuse) WR_LAUNCH_P(bf16_t, false, false, true);
+    else WR_LAUNCH(bf16_t, false);
   }
 #undef WR_LAUNCH
 #undef WR_LAUNCH_P

@@ -50,7 +50,7 @@ __global__ void convT_frag_pack_kernel(const float *__restrict__ w, T *__restric
 template <typename T, int MODE, int KSP, int NBR>
 __global__ __launch_bounds__(512) void convT_gemm_kernel(const T *__restrict__ in, int ldin, const T *__restrict__ wfrag,
                                                         const float *__restrict__ bias, T *__restrict__ out, int ldout,
-                                                        int Di, int Hi, int Wi, int Cout, int nWB, long long nMB, int abl) {
+                                                        int Di, int Hi, int Wi, int Cout, int nWB, long long nMB) {
   constexpr int R = MODE == 0 ? 4 : 1, S = MODE == 0 ? 1 : 4, NF = R * NBR * S * KSP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4 *sW = reinterpret_cast<uint4 *>(smem);
@@ -105,10 +105,7 @@ __global__ __launch_bounds__(512) void convT_gemm_kernel(const T *__restrict__ i
 #pragma unroll
         for (int s = 0; s < S; ++s)
 #pragma unroll
-          for (int ks = 0; ks < KSP; ++ks) {
-            if (abl == 3) acc[0] += __uint_as_float(xa[s][ks].x);
-            else mfma_step<T>(wf[(s * KSP + ks) << 6], xa[s][ks], acc);
-          }
+          for (int ks = 0; ks < KSP; ++ks) mfma_step<T>(wf[(s * KSP + ks) << 6], xa[s][ks], acc);
         // lane (voxel r, half h) holds channels 8j + 4h .. +3 of the block: through a per-wave slab [32 voxels][72 bytes]
         // (pitch 72: the 8-byte writes of 32 voxels hit 64 distinct banks) so that 4 consecutive lanes store the 64
         // contiguous bytes of one voxel - 8-byte stores straight from the accumulator layout ran at 2.7 TB/s
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(512) void convT_gemm_kernel(const T *__restrict__ i
           T *o;
           if (MODE == 0) o = out + (orow + 2 * wv + c0 / Cout) * ldout + c0 % Cout;
           else o = out + (orow + wv) * ldout + c0;
-          if (wv < Wi && (abl != 2 || val.x == 0x12345u)) *reinterpret_cast<uint4 *>(o) = val;
+          if (wv < Wi) *reinterpret_cast<uint4 *>(o) = val;
         }
       }
     }
@@ -150,8 +147,7 @@ int launch_gemm(const void *in, int ldin, const T *blob, const float *bias, void
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long want = cdiv64(nMB, 8), cap = (long long)cus * (LDS <= 64 * 1024 ? 2 : 1);
   hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(512), LDS, st, (const T *)in, ldin, blob, bias,
-                     (T *)out, ldout, Di, Hi, Wi, Cout, nWB, nMB,
-                     DG_LAB(convt_gemm_abl) >= '2' ? DG_LAB(convt_gemm_abl) - '0' : 0);      // timing models: diagnostic build only
+                     (T *)out, ldout, Di, Hi, Wi, Cout, nWB, nMB);
   DG_CHECK_LAUNCH("convT_gemm_kernel");
   return DGTTA_OK;
 }

@@ -450,7 +450,7 @@ __device__ __forceinline__ float quad_xor_add(float v, int which) {     // v + (
   return v + __int_as_float(o);
 }
 
-template <typename T, bool ABL = false>
+template <typename T>
 __global__ __launch_bounds__(256) void head_warp_fwd_kernel(const T *__restrict__ z, const float *__restrict__ theta,
                                                             const float *__restrict__ w, const float *__restrict__ bias,
                                                             const int *__restrict__ sel, int nsel, float *__restrict__ out,
@@ -486,8 +486,7 @@ __global__ __launch_bounds__(256) void head_warp_fwd_kernel(const T *__restrict_
         const int xx = cr.x0 + (k & 1), yy = cr.y0 + ((k >> 1) & 1), zz = cr.z0 + (k >> 2);
         inb[k] = (unsigned)xx < (unsigned)W && (unsigned)yy < (unsigned)H && (unsigned)zz < (unsigned)D;
         const int xc = min(max(xx, 0), W - 1), yc = min(max(yy, 0), H - 1), zc = min(max(zz, 0), D - 1);
-        // (abl: timing diagnostic DGTTA_WARP_ABL=1 - every corner read lands in a 2 x 4 x 16-voxel block that stays in L1)
-        const int64_t sv = ABL ? (((int64_t)(zc & 1) * H + (yc & 3)) * W + (xc & 15)) : (((int64_t)zc * H + yc) * W + xc);
+        const int64_t sv = ((int64_t)zc * H + yc) * W + xc;
         t[k] = *reinterpret_cast<const uint4 *>(zb + sv * HW_CIN + g * 8);
       }
 #pragma unroll
@@ -622,7 +621,7 @@ __global__ __launch_bounds__(256) void head_warp_fwd_mfma_kernel(const T *__rest
 // Measured beside it and NOT kept (profiles/r06_ab.txt): W^T on the fp32 matrix cores through a class-major LDS slab (same
 // bits, but 82 instead of 80 registers = 5 instead of 6 waves per SIMD: 1.96 ms) and a chunked gather with 2 or 3 lines'
 // candidate rows in flight (2.14 / 2.17 ms: the candidate search is the cost, not the round trips - more slots, more search).
-template <typename T, bool ABL = false, bool G16 = false>
+template <typename T, bool G16 = false>
 __global__ __launch_bounds__(256, 6) void head_warp_bwd_kernel(const void *__restrict__ gdst_, const float *__restrict__ theta,
                                                             const float *__restrict__ w, const int *__restrict__ sel,
                                                             int nsel, T *__restrict__ gz, unsigned short *__restrict__ d16,
@@ -706,8 +705,7 @@ __global__ __launch_bounds__(256, 6) void head_warp_bwd_kernel(const void *__res
         for (int wq = w0; wq <= w1; ++wq) {
           float wt;
           if (!corner_weight(wq, yc, zc, wt)) continue;
-          const int64_t grow = (ABL ? (((int64_t)(d & 1) * H + (h & 3)) * W + (wq & 15)) * nsel
-                                    : ((int64_t)b * V + ((int64_t)d * H + h) * W + wq) * nsel);
+          const int64_t grow = ((int64_t)b * V + ((int64_t)d * H + h) * W + wq) * nsel;
           if (G16) {
             const unsigned short *gp = gdst16 + grow;
 #pragma unroll
@@ -978,19 +976,10 @@ extern "C" int dgtta_seghead_warp_fwd(const void *z, const float *w, const float
   const int gx = cdiv(W * 4, 256), gy = cdiv(H, WARP_ROWS);
   const int64_t nblk = (int64_t)gx * gy * D * B;
   DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "seghead_warp_fwd: too many tiles");
-#define HWF_LAUNCH(T, A)                                                                                                   \
-  hipLaunchKernelGGL((head_warp_fwd_kernel<T, A>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const T *)z, \
+#define HWF_LAUNCH(T)                                                                                                   \
+  hipLaunchKernelGGL((head_warp_fwd_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const T *)z,  \
                      theta, w, bias, sel, nsel, out, D, H, W, tta_grid_algebra, gx, gy)
-  bool lab = false;
-#ifdef DGTTA_DIAG
-  if (DG_LAB(warp_abl) == '1') {      // timing model (every gather read L1-resident): results wrong by construction
-    lab = true;
-    if (dtype == DGTTA_BF16) HWF_LAUNCH(bf16_t, true);
-    else HWF_LAUNCH(f16_t, true);
-  }
-#endif
-  if (lab) {
-  } else if (dgtta_switches().headwarp_mfma != '0') {      // round 6: the head on the fp32 matrix cores (DGTTA_HEADWARP_MFMA=0: the FMA chain)
+  if (dgtta_switches().headwarp_mfma != '0') {      // round 6: the head on the fp32 matrix cores (DGTTA_HEADWARP_MFMA=0: the FMA chain)
     if (dtype == DGTTA_BF16)
       hipLaunchKernelGGL((head_warp_fwd_mfma_kernel<bf16_t>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
                          (const bf16_t *)z, theta, w, bias, sel, nsel, out, D, H, W, tta_grid_algebra, gx, gy);
@@ -998,9 +987,9 @@ extern "C" int dgtta_seghead_warp_fwd(const void *z, const float *w, const float
       hipLaunchKernelGGL((head_warp_fwd_mfma_kernel<f16_t>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
                          (const f16_t *)z, theta, w, bias, sel, nsel, out, D, H, W, tta_grid_algebra, gx, gy);
   } else if (dtype == DGTTA_BF16) {
-    HWF_LAUNCH(bf16_t, false);
+    HWF_LAUNCH(bf16_t);
   } else {
-    HWF_LAUNCH(f16_t, false);
+    HWF_LAUNCH(f16_t);
   }
 #undef HWF_LAUNCH
   DG_CHECK_LAUNCH("head_warp_fwd_kernel");
@@ -1032,24 +1021,15 @@ static int seghead_warp_bwd_impl(const void *z, const void *gout, int gout16, co
   const int gx = cdiv(W, 16), gy = cdiv(H, 4);
   const int64_t nblk = (int64_t)gx * gy * cdiv(D, 4) * B;
   DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "seghead_warp_bwd: too many tiles");
-#define HWB_LAUNCH(T, A, G)                                                                                               \
-  hipLaunchKernelGGL((head_warp_bwd_kernel<T, A, G>), dim3((unsigned)nblk), dim3(256), 0, st, gout, theta, w, sel, nsel, \
+#define HWB_LAUNCH(T, G)                                                                                            \
+  hipLaunchKernelGGL((head_warp_bwd_kernel<T, G>), dim3((unsigned)nblk), dim3(256), 0, st, gout, theta, w, sel, nsel, \
                      (T *)gz, d16, db_sel ? bias_partial : nullptr, D, H, W, tta_grid_algebra, gx, gy)
-  bool lab = false;
-#ifdef DGTTA_DIAG
-  if (DG_LAB(warp_abl) == '1' && !gout16) {      // timing model: results wrong by construction
-    lab = true;
-    if (dtype == DGTTA_BF16) HWB_LAUNCH(bf16_t, true, false);
-    else HWB_LAUNCH(f16_t, true, false);
-  }
-#endif
-  if (lab) {
-  } else if (dtype == DGTTA_BF16) {
-    if (gout16) HWB_LAUNCH(bf16_t, false, true);
-    else HWB_LAUNCH(bf16_t, false, false);
+  if (dtype == DGTTA_BF16) {
+    if (gout16) HWB_LAUNCH(bf16_t, true);
+    else HWB_LAUNCH(bf16_t, false);
   } else {
-    if (gout16) HWB_LAUNCH(f16_t, false, true);
-    else HWB_LAUNCH(f16_t, false, false);
+    if (gout16) HWB_LAUNCH(f16_t, true);
+    else HWB_LAUNCH(f16_t, false);
   }
 #undef HWB_LAUNCH
   DG_CHECK_LAUNCH("head_warp_bwd_kernel");

@@ -38,10 +38,10 @@ struct AccRun<float> {
       r[j] = i < n ? ap[i] : 0.f;
     }
   }
-  __device__ __forceinline__ void add_store(float *ap, int n, const float *tile) {
+  __device__ __forceinline__ void add_store(float *ap, int n, const float *tile, int t = (int)threadIdx.x) {      // t: thread index
 #pragma unroll
     for (int j = 0; j < HA_RUN; ++j) {
-      const int i = (int)threadIdx.x + 256 * j;
+      const int i = t + 256 * j;
       if (i < n) ap[i] = r[j] + tile[i];
     }
   }
@@ -63,12 +63,12 @@ struct AccRun<f16_t> {
       r[j] = v;
     }
   }
-  __device__ __forceinline__ void add_store(f16_t *ap, int n, const float *tile) {
+  __device__ __forceinline__ void add_store(f16_t *ap, int n, const float *tile, int t = (int)threadIdx.x) {
     const int h0 = (int)(((uintptr_t)ap >> 1) & 1);
     unsigned short *hp = reinterpret_cast<unsigned short *>(ap);
 #pragma unroll
     for (int j = 0; j < HA_RUN2; ++j) {
-      const int e0 = 2 * ((int)threadIdx.x + 256 * j) - h0;
+      const int e0 = 2 * (t + 256 * j) - h0;
       const bool v0 = e0 >= 0 && e0 < n, v1 = e0 + 1 < n;
       const unsigned short lo = v0 ? f32_to_f16(f16_to_f32((unsigned short)(r[j] & 0xffffu)) + tile[e0]) : (unsigned short)0;
       const unsigned short hi = v1 ? f32_to_f16(f16_to_f32((unsigned short)(r[j] >> 16)) + tile[e0 + 1]) : (unsigned short)0;
@@ -83,8 +83,7 @@ template <typename T, typename ACC>
 __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
                                                               ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0,
-                                                              int abl) {
+                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   // the head's weights are the same for every lane of a wave (a wave = 64 voxels x one class at a time): they are read
@@ -105,14 +104,14 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
     ACC *ap = acc + vg * C;
     const int n = nv * C;
     AccRun<ACC> run;
-    if (abl != 2) run.load(ap, n);           // (abl: timing diagnostics, DGTTA_HA_ABL - 1: no logits, 2: no accumulator traffic)
+    run.load(ap, n);
     float ns = 0.f, gs = 0.f;
     if (nsum && (int)threadIdx.x < nv) {
       ns = nsum[vg + threadIdx.x];
       gs = gauss[((int64_t)pd * PH + ph) * PW + pw0 + threadIdx.x];
     }
     __syncthreads();                                              // previous tile consumed
-    if (vox < nv && abl != 1) {
+    if (vox < nv) {
       float xr[HA_CIN];
       const uint4 *zr = reinterpret_cast<const uint4 *>(z + p * HA_CIN);
 #pragma unroll
@@ -126,7 +125,11 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
       }
     }
     __syncthreads();
-    if (abl != 2) run.add_store(ap, n, tile);
+    // the stores' indices are rebuilt from a laundered thread id: shared with the loads above, the compiler keeps the run's 28
+    // offsets and lane masks live across the FMA chain (26 registers more) and waits for each store before the next
+    int ts = (int)threadIdx.x;
+    asm volatile("" : "+v"(ts));
+    run.add_store(ap, n, tile, ts);
     if (nsum && (int)threadIdx.x < nv) nsum[vg + threadIdx.x] = ns + gs;
   }
 }
@@ -145,8 +148,7 @@ template <typename T, typename ACC>
 __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
                                                               ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0,
-                                                              int abl) {
+                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
   float gq[4], gq_n[4];
   float ns = 0.f, gs = 0.f, ns_n = 0.f, gs_n = 0.f;
   auto fetch = [&](const TilePos &t, AccRun<ACC> &rn, uint4 *zz, float *gg, float &nss, float &gss) {
-    if (abl != 2) rn.load(acc + t.vg * C, t.n);
+    rn.load(acc + t.vg * C, t.n);
     nss = 0.f;
     gss = 0.f;
     if (nsum && (int)threadIdx.x < t.nv) {
@@ -232,31 +234,29 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
     const bool more = blk + (int)gridDim.x < nblk;
     if (more) fetch(tile_pos(blk + gridDim.x), run_n, zb_n, gq_n, ns_n, gs_n);
     __syncthreads();                                              // previous tile consumed
-    if (abl != 1) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int cg = wv + 4 * j;
-        if (cg * 16 < C) {                                        // wave-uniform
+    for (int j = 0; j < 2; ++j) {
+      const int cg = wv + 4 * j;
+      if (cg * 16 < C) {                                        // wave-uniform
 #pragma unroll
-          for (int vgp = 0; vgp < 4; ++vgp) {
-            f32x4_t d = {0.f, 0.f, 0.f, 0.f};
-            mfma16<T>(wa[j][2], zb[vgp], d);
-            mfma16<T>(wa[j][1], zb[vgp], d);
-            mfma16<T>(wa[j][0], zb[vgp], d);
-            const int vox = vgp * 16 + ln;
-            if (vox < t.nv) {
+        for (int vgp = 0; vgp < 4; ++vgp) {
+          f32x4_t d = {0.f, 0.f, 0.f, 0.f};
+          mfma16<T>(wa[j][2], zb[vgp], d);
+          mfma16<T>(wa[j][1], zb[vgp], d);
+          mfma16<T>(wa[j][0], zb[vgp], d);
+          const int vox = vgp * 16 + ln;
+          if (vox < t.nv) {
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int k = cg * 16 + lq * 4 + r;
-                if (k < C) tile[vox * C + k] = (d[r] + bq[j][r]) * gq[vgp];
-              }
+            for (int r = 0; r < 4; ++r) {
+              const int k = cg * 16 + lq * 4 + r;
+              if (k < C) tile[vox * C + k] = (d[r] + bq[j][r]) * gq[vgp];
             }
           }
         }
       }
     }
     __syncthreads();
-    if (abl != 2) run.add_store(acc + t.vg * C, t.n, tile);
+    run.add_store(acc + t.vg * C, t.n, tile);
     if (nsum && (int)threadIdx.x < t.nv) nsum[t.vg + threadIdx.x] = ns + gs;
     if (more) {
       run = run_n;
@@ -290,7 +290,6 @@ extern "C" int dgtta_seghead_window_accumulate_t(const void *z, const float *w, 
   static DynLdsOnce once[8];
   const dim3 grid((unsigned)(nblk < 2048 ? nblk : 2048));
   hipStream_t st = (hipStream_t)stream;
-  const int abl = DG_LAB(ha_abl) == '1' ? 1 : (DG_LAB(ha_abl) == '2' ? 2 : 0);      // timing models: diagnostic build only
   const bool fma = dgtta_switches().ha_mfma == '0';
 #define HA_LAUNCH(IDX, T, ACC)                                                                                               \
   do {                                                                                                                       \
@@ -299,10 +298,10 @@ extern "C" int dgtta_seghead_window_accumulate_t(const void *z, const float *w, 
                "seghead_window_accumulate: cannot raise the dynamic LDS limit");                                             \
     if (fma)                                                                                                                 \
       hipLaunchKernelGGL((head_accumulate_fma_kernel<T, ACC>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,       \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, abl);                                         \
+                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0);                                              \
     else                                                                                                                     \
       hipLaunchKernelGGL((head_accumulate_kernel<T, ACC>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,           \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, abl);                                         \
+                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0);                                              \
   } while (0)
   if (dtype == DGTTA_BF16 && acc_dtype == DGTTA_F32) HA_LAUNCH(0, bf16_t, float);
   else if (dtype == DGTTA_BF16) HA_LAUNCH(1, bf16_t, f16_t);
