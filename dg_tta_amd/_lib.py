@@ -125,6 +125,10 @@ SIGNATURES = {
     "dgtta_nonzero_mask": (I, [P, I, I64, P, P]),
     "dgtta_bspline3_prefilter": (I, [P, P, I, I, I, P]),
     "dgtta_patch_sample_aug": (I, [P, I, I, I, I, I, P, P, P]),
+    "dgtta_intensity_stats_ws_bytes": (SZ, [I, I64]),
+    "dgtta_intensity_stats": (I, [P, I, I64, C.POINTER(I), I, P, P, SZ, P]),
+    "dgtta_intensity_map": (I, [P, P, I, I64, P, I, P, P, P]),
+    "dgtta_gauss_blur3": (I, [P, P, P, I, I, I, I, P, I, P]),
 }
 
 
@@ -135,6 +139,21 @@ class PatchItem(C.Structure):
 
 
 PATCH_MAX_ITEMS = 16
+
+
+class IntensityItem(C.Structure):
+    """DgttaIntensityItem of include/dgtta.h."""
+    _fields_ = [("item", I), ("mode", I), ("negate", I), ("noise_b", I), ("a", F), ("s", F), ("seed_lo", C.c_uint32),
+                ("seed_hi", C.c_uint32), ("off_lo", C.c_uint32), ("off_hi", C.c_uint32)]
+
+
+class BlurItem(C.Structure):
+    """DgttaBlurItem of include/dgtta.h."""
+    _fields_ = [("item", I), ("radius", I), ("taps", F * 9)]
+
+
+INTENSITY_MAX_ITEMS = 16
+IMAP_LINEAR, IMAP_CONTRAST, IMAP_GAMMA, IMAP_RESTORE = 0, 1, 2, 3
 
 _lib = None
 _load_error = None

@@ -1047,6 +1047,164 @@ def sample_patches_aug(coefs, label_maps, maps, patch_size, order=3):
     return image, labels
 
 
+# ------------------------------------------------------------------------------------------------ intensity augmentation
+IMAP_MODES = {"linear": _lib.IMAP_LINEAR, "contrast": _lib.IMAP_CONTRAST, "gamma": _lib.IMAP_GAMMA, "restore": _lib.IMAP_RESTORE}
+
+
+def _intensity_batch(x, name, what="x"):
+    """(B, D, H, W) of a batch [B, (1,) D, H, W] the intensity kernels take; ValueError for anything else."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError(f"{name}: `{what}` must be a CUDA tensor (there is no CPU fallback)")
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"{name}: `{what}` must be a non-empty contiguous float32 tensor")
+    if not (x.dim() == 4 or (x.dim() == 5 and x.shape[1] == 1)):
+        raise ValueError(f"{name}: `{what}` must be [B, 1, D, H, W] or [B, D, H, W] (got {tuple(x.shape)})")
+    return (int(x.shape[0]), *(int(s) for s in x.shape[-3:]))
+
+
+def _intensity_items(items, b, name):
+    items = [int(i) for i in items]
+    if not 1 <= len(items) <= _lib.INTENSITY_MAX_ITEMS:
+        raise ValueError(f"{name}: 1..{_lib.INTENSITY_MAX_ITEMS} items per launch (got {len(items)})")
+    if len(set(items)) != len(items) or min(items) < 0 or max(items) >= b:
+        raise ValueError(f"{name}: items {items} must be distinct indices into a batch of {b}")
+    return items
+
+
+def _intensity_params(values, n, name, what):
+    import math
+    values = [float(v) for v in values]
+    if len(values) != n or not all(math.isfinite(v) for v in values):
+        raise ValueError(f"{name}: {n} finite `{what}` expected (got {values})")
+    return values
+
+
+def _intensity_stats_arg(t, b, like, name, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != like.device or t.dtype != torch.float64 or \
+            not t.is_contiguous() or tuple(t.shape) != (b, 4):
+        raise ValueError(f"{name}: `{what}` must be a contiguous float64 CUDA tensor [{b}, 4] on the batch's device")
+    return t
+
+
+def _intensity_out(x, out, name):
+    if out is None:
+        return x
+    _intensity_batch(out, name, "out")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"{name}: `out` must have the shape and device of `x`")
+    return out
+
+
+def intensity_stats_ws_bytes(n_items, voxels):
+    return int(_lib.load().dgtta_intensity_stats_ws_bytes(int(n_items), int(voxels)))
+
+
+def intensity_stats(x, items, out=None, ws=None):
+    """Per item of `items` (indices into the batch x [B, 1, D, H, W], float32) its min, max, mean and population standard
+    deviation -> out[item] of a float64 tensor [B, 4] on the device; rows of other items are left as they are (csrc/
+    intensity_aug.hip; bit-reproducible, no read-back).  ws: uint8 workspace of intensity_stats_ws_bytes(len(items), voxels)."""
+    b, d, h, w = _intensity_batch(x, "intensity_stats")
+    items = _intensity_items(items, b, "intensity_stats")
+    v = d * h * w
+    out = torch.empty((b, 4), dtype=torch.float64, device=x.device) if out is None else _intensity_stats_arg(out, b, x, "intensity_stats", "out")
+    need = intensity_stats_ws_bytes(len(items), v)
+    if ws is None:
+        ws = _ws(need, x.device)
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"intensity_stats: `ws` is a contiguous uint8 CUDA tensor of at least {need} bytes")
+    h_items = (C.c_int * len(items))(*items)
+    check(_lib.load().dgtta_intensity_stats(ptr(x), b, v, h_items, len(items), ptr(out), ptr(ws), ws.numel(), stream_of(x.device)),
+          "dgtta_intensity_stats")
+    return out
+
+
+def intensity_map(x, items, mode, a=None, s=None, keys=None, offset=0, noise_index=None, negate=False, stats=None, stats2=None,
+                  out=None):
+    """One elementwise pass over the items `items` of the batch x [B, 1, D, H, W] (float32), formulas in include/dgtta.h:
+      mode "linear"    x * a + s * n(v): a (default 1) and s (default 0: no noise) per item; keys: per item the 64-bit Philox
+                       key of its noise, offset: counter words 2 and 3, noise_index: per item counter word 1 (default: the
+                       item's index in the batch);
+      mode "contrast"  clip((x - mean) * a + mean, min, max) with the item's row of `stats`;
+      mode "gamma"     ((x - lo) / (r + 1e-7))^a * r + lo from `stats`; negate: of the negated item (not negated back);
+      mode "restore"   (x - mean2) / (std2 + 1e-8) * std + mean with `stats` (before the power) and `stats2` (after); negate:
+                       the mean of the negated item, and the result negated back.
+    stats / stats2: float64 [B, 4] as intensity_stats writes them, read on the device.  Writes `out` (default: x itself, in
+    place); items that are not named are neither read nor written.  Returns out."""
+    name = "intensity_map"
+    b, d, h, w = _intensity_batch(x, name)
+    items = _intensity_items(items, b, name)
+    n = len(items)
+    if mode not in IMAP_MODES:
+        raise ValueError(f"{name}: mode {mode!r} not in {sorted(IMAP_MODES)}")
+    out = _intensity_out(x, out, name)
+    a = _intensity_params([1.0] * n if a is None else a, n, name, "a")
+    s = _intensity_params([0.0] * n if s is None else s, n, name, "s")
+    if mode != "linear":
+        stats = _intensity_stats_arg(stats, b, x, name, "stats")
+        if any(v != 0.0 for v in s):
+            raise ValueError(f"{name}: noise belongs to mode 'linear'")
+    if mode == "restore":
+        stats2 = _intensity_stats_arg(stats2, b, x, name, "stats2")
+    if mode == "gamma" and not all(v > 0.0 for v in a):
+        raise ValueError(f"{name}: gamma exponents must be positive (got {a})")
+    keys = [0] * n if keys is None else [_u64(k) for k in keys]
+    noise_index = items if noise_index is None else [int(i) for i in noise_index]
+    if len(keys) != n or len(noise_index) != n or any(not 0 <= i < 2 ** 31 for i in noise_index):
+        raise ValueError(f"{name}: one key and one noise index in [0, 2^31) per item expected")
+    off = _u64(offset)
+    desc = (_lib.IntensityItem * n)()
+    for k in range(n):
+        desc[k].item, desc[k].mode, desc[k].negate, desc[k].noise_b = items[k], IMAP_MODES[mode], int(bool(negate)), noise_index[k]
+        desc[k].a, desc[k].s = a[k], s[k]
+        desc[k].seed_lo, desc[k].seed_hi = keys[k] & 0xFFFFFFFF, keys[k] >> 32
+        desc[k].off_lo, desc[k].off_hi = off & 0xFFFFFFFF, off >> 32
+    check(_lib.load().dgtta_intensity_map(ptr(x), ptr(out), b, d * h * w, desc, n, ptr(stats) if mode != "linear" else None,
+                                          ptr(stats2) if mode == "restore" else None, stream_of(x.device)), "dgtta_intensity_map")
+    return out
+
+
+def gauss_blur_taps(sigma):
+    """(radius, taps) of scipy.ndimage.gaussian_filter(sigma, truncate=4) for 0 < sigma <= 1: radius = int(4 sigma + 0.5) in
+    1 .. 4 (sigma < 0.125 keeps the one-voxel radius the kernel needs; its outer taps are then below 1e-13),
+    taps = exp(-x^2 / (2 sigma^2)) / sum in float64, rounded to float32."""
+    import numpy as np
+    sigma = float(sigma)
+    if not 0.0 < sigma <= 1.0:        # false for NaN
+        raise ValueError(f"gauss_blur3: sigma {sigma} outside (0, 1]")
+    radius = max(int(4.0 * sigma + 0.5), 1)
+    xs = np.arange(-radius, radius + 1, dtype=np.float64)
+    t = np.exp(-0.5 / (sigma * sigma) * xs ** 2)
+    return radius, (t / t.sum()).astype(np.float32)
+
+
+def gauss_blur3(x, items, sigmas, out=None, scratch=None):
+    """scipy.ndimage.gaussian_filter(x[item, 0], sigma, mode="reflect", truncate=4) for the items `items` of the batch x
+    [B, 1, D, H, W] (float32) with one sigma in (0, 1] each, separable in fp32 (csrc/intensity_aug.hip; three launches).
+    Writes `out` (default: x itself, in place); `scratch`: a float32 tensor of x's shape that is neither x nor out (allocated
+    when not given).  Items that are not named are neither read nor written.  Returns out."""
+    name = "gauss_blur3"
+    b, d, h, w = _intensity_batch(x, name)
+    items = _intensity_items(items, b, name)
+    sigmas = list(sigmas)
+    if len(sigmas) != len(items):
+        raise ValueError(f"{name}: one sigma per item expected")
+    out = _intensity_out(x, out, name)
+    if scratch is None:
+        scratch = torch.empty_like(x)
+    else:
+        _intensity_batch(scratch, name, "scratch")
+        if scratch.shape != x.shape or scratch.device != x.device or scratch.data_ptr() in (x.data_ptr(), out.data_ptr()):
+            raise ValueError(f"{name}: `scratch` must have x's shape and device and be a buffer of its own")
+    desc = (_lib.BlurItem * len(items))()
+    for k, (item, sigma) in enumerate(zip(items, sigmas)):
+        radius, taps = gauss_blur_taps(sigma)
+        desc[k].item, desc[k].radius = item, radius
+        desc[k].taps[:len(taps)] = taps.tolist()
+    check(_lib.load().dgtta_gauss_blur3(ptr(x), ptr(out), ptr(scratch), b, d, h, w, desc, len(items), stream_of(x.device)),
+          "dgtta_gauss_blur3")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

@@ -12,7 +12,11 @@ REDUCED AUGMENTATION: the DG trainers' own augmentation runs (GIN / MIND forward
 SimulateDiscreteLowResolutionTransform with the reference's arguments, nnUNetTrainer_GIN_MIND_MultiRes.py:61-67), mirroring
 is off as those trainers set it, but nnU-Net's rotation / scaling and noise / blur / brightness / contrast / gamma
 transforms are NOT applied.  `augmentation="spatial"` (`--augmentation spatial`) adds the rotation / scaling
-(pretraining/spatial.py, csrc/spatial_aug.hip); the intensity transforms stay missing.  Experiment planning is out of
+(pretraining/spatial.py, csrc/spatial_aug.hip); the intensity transforms stay missing.  `augmentation="full"`
+(`--augmentation full`) adds both: the rotation / scaling and nnU-Net's noise / blur / brightness / contrast / low-resolution /
+gamma chain (pretraining/intensity.py, csrc/intensity_aug.hip), with the *_MultiRes trainers' discrete low-resolution transform
+in the chain's low-resolution slot, where the reference puts it.  What `full` still lacks against nnU-Net: elastic deformation
+(nnU-Net's default switches it off too) and mirroring (the DG trainers switch it off).  Experiment planning is out of
 scope: nnUNetPlans.json must exist.  Random streams are not part of a checkpoint: a continued run draws differently from
 an uninterrupted one."""
 import json
@@ -34,6 +38,7 @@ from ..unet import HipPlainConvUNet
 from ..utils import disable_internal_augmentation, numpy_rng
 from .discrete_downsampling import SimulateDiscreteLowResolutionTransform
 from .hooks import register_dg_hooks, trainer_spec
+from .intensity import IntensityAugmentation
 from .spatial import SpatialAugmentation, patch_start, sampling_map
 
 DG_TRAINERS = tuple(f"nnUNetTrainer_{n}{m}" for m in ("", "_MultiRes") for n in ("GIN", "MIND", "GIN_MIND"))
@@ -51,7 +56,13 @@ SPATIAL_AUGMENTATION_NOTE = (
     "pretraining/spatial.py) beside the trainer's own GIN / MIND hooks (and, for *_MultiRes, the discrete low-resolution "
     "transform), mirroring is off as the DG trainers set it; nnU-Net's noise / blur / brightness / contrast / gamma "
     "transforms are not applied by this engine.")
-AUGMENTATIONS = ("reduced", "spatial")
+FULL_AUGMENTATION_NOTE = (
+    "pretrain: FULL AUGMENTATION - nnU-Net's rotation / scaling (cubic B-spline image, order-1 labels; pretraining/spatial.py) "
+    "and its intensity chain - Gaussian noise, Gaussian blur, brightness, contrast, simulated low resolution, inverted gamma, "
+    "gamma (pretraining/intensity.py) - are applied to the training batches beside the trainer's own GIN / MIND hooks; for "
+    "*_MultiRes the discrete low-resolution transform takes the chain's low-resolution slot.  Not applied: elastic deformation "
+    "and mirroring (off as the DG trainers set it).")
+AUGMENTATIONS = ("reduced", "spatial", "full")
 MAX_AUG_ITEMS = 16           # items per ops.sample_patches_aug launch
 
 
@@ -227,7 +238,9 @@ def _sample_spatial(cases, batch_size, patch, device, spatial):
     return imgs, labels, [p[0] for p in plan]
 
 
-def _sample(cases, batch_size, patch, device, multires, spatial=None):
+def _sample(cases, batch_size, patch, device, multires, spatial=None, *, intensity=None):
+    """One batch.  intensity: an IntensityAugmentation whose chain runs on the stacked images after the sampling; the
+    *_MultiRes transform then runs inside it (stage 5) instead of after the sampling."""
     with torch.no_grad():
         if spatial is not None:
             imgs, labels, picks = _sample_spatial(cases, batch_size, patch, device, spatial)
@@ -240,6 +253,9 @@ def _sample(cases, batch_size, patch, device, multires, spatial=None):
                 im, lb = get_batch([case.tensor], [0], patch, None, device, centers=[center])
                 imgs.append(im[0][0])                          # [1, D, H, W]
                 labels.append(lb[0])
+        if intensity is not None:
+            plan = intensity.draw(batch_size, patch, discrete_lowres=multires)
+            return intensity.apply(torch.stack(imgs), plan), torch.cat(labels, dim=0)[:, 0], picks
         if multires is not None:
             multires(data=imgs)
     return torch.stack(imgs), torch.cat(labels, dim=0)[:, 0], picks
@@ -250,12 +266,22 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                device="cuda", act_dtype=torch.float32, continue_training=False, seed=None, augmentation="reduced"):
     """Trains one fold and writes the model folder (module docstring).  dataset: numeric id or folder name; fold: 0..4 or
     "all".  augmentation: "reduced" (module docstring), "spatial" (adds nnU-Net's rotation / scaling to the training
-    batches, pretraining/spatial.py; validation batches are never augmented) or a SpatialAugmentation to draw from.
-    Returns the path of checkpoint_final.pth."""
+    batches, pretraining/spatial.py; validation batches are never augmented), "full" (the rotation / scaling plus nnU-Net's
+    intensity chain, pretraining/intensity.py), or the objects to draw from: a SpatialAugmentation, an IntensityAugmentation
+    or a (SpatialAugmentation, IntensityAugmentation) pair.  Returns the path of checkpoint_final.pth."""
+    spatial = intensity = None
     if isinstance(augmentation, SpatialAugmentation):
         spatial = augmentation
-    elif augmentation in AUGMENTATIONS:
-        spatial = SpatialAugmentation() if augmentation == "spatial" else None
+    elif isinstance(augmentation, IntensityAugmentation):
+        intensity = augmentation
+    elif isinstance(augmentation, (tuple, list)) and len(augmentation) == 2 and isinstance(augmentation[0], SpatialAugmentation) \
+            and isinstance(augmentation[1], IntensityAugmentation):
+        spatial, intensity = augmentation
+    elif isinstance(augmentation, str) and augmentation in AUGMENTATIONS:
+        if augmentation != "reduced":
+            spatial = SpatialAugmentation()
+        if augmentation == "full":
+            intensity = IntensityAugmentation()
     else:
         raise ValueError(f"augmentation {augmentation!r}: one of {', '.join(AUGMENTATIONS)} expected")
     if trainer_name not in DG_TRAINERS:
@@ -360,7 +386,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                 for _ in range(iterations_per_epoch):
                     if opt.resolve_overflow():             # (reads a flag only on the guarded fp16 path)
                         print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
-                    imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial)
+                    imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial, intensity=intensity)
                     loss, _ = ops.deep_supervision_loss(net(imgs), target)
                     torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
                                                                           device=device))

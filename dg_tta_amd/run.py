@@ -101,16 +101,17 @@ class DGTTAProgram:
         parser.add_argument("--c", dest="continue_training", action="store_true",
                             help="continue from fold_<k>/checkpoint_latest.pth")
         parser.add_argument("--seed", type=int, default=None, help="seeds the initialisation and every random draw")
-        parser.add_argument("--augmentation", choices=["reduced", "spatial"], default="reduced",
-                            help="spatial: nnU-Net's rotation / scaling on the training batches")
+        parser.add_argument("--augmentation", choices=["reduced", "spatial", "full"], default="reduced",
+                            help="spatial: nnU-Net's rotation / scaling on the training batches; full: that plus its noise / blur / "
+                                 "brightness / contrast / low-resolution / gamma chain")
         return parser
 
     def pretrain(self):
         args = self._pretrain_parser().parse_args(self.argv[2:])
         if args.fold != "all" and not args.fold.isnumeric():
             raise SystemExit(f"pretrain: fold {args.fold!r} is neither a number nor 'all'")
-        from .pretraining.trainer import REDUCED_AUGMENTATION_NOTE, SPATIAL_AUGMENTATION_NOTE, train_fold
-        print(SPATIAL_AUGMENTATION_NOTE if args.augmentation == "spatial" else REDUCED_AUGMENTATION_NOTE)
+        from .pretraining.trainer import FULL_AUGMENTATION_NOTE, REDUCED_AUGMENTATION_NOTE, SPATIAL_AUGMENTATION_NOTE, train_fold
+        print({"spatial": SPATIAL_AUGMENTATION_NOTE, "full": FULL_AUGMENTATION_NOTE}.get(args.augmentation, REDUCED_AUGMENTATION_NOTE))
         final = train_fold(args.dataset_id, args.configuration, args.fold, args.trainer, num_epochs=args.num_epochs,
                            iterations_per_epoch=args.iterations_per_epoch, val_iterations=args.val_iterations,
                            device=torch.device(args.device), continue_training=args.continue_training, seed=args.seed, augmentation=args.augmentation,

@@ -700,6 +700,74 @@ int dgtta_bspline3_prefilter(const float *src, float *dst, int D, int H, int W, 
 int dgtta_patch_sample_aug(const DgttaPatchItem *items, int n_items, int PD, int PH, int PW, int order, float *image,
                            int64_t *labels, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Intensity augmentation of pre-training (csrc/intensity_aug.hip, dg_tta_amd/pretraining/intensity.py): the kernels under
+ * nnU-Net's noise / blur / brightness / contrast / gamma transforms (restated from memory of nnunetv2 2.2 / batchgenerators,
+ * UNPINNED).  x is a batch [B][V] of fp32 items, V = D*H*W < 2^31 voxels each.  Every entry point takes a HOST array of
+ * n_items <= DGTTA_INTENSITY_MAX_ITEMS descriptors that is copied into the kernel arguments (nothing is uploaded, nothing is
+ * read from it after the call returns); `item` is the index of the batch item a descriptor works on.  A batch item that no
+ * descriptor names is neither read nor written.  No operation below is fused into an FMA.
+ *
+ * intensity_stats: stats[item][4] = (min, max, mean, population standard deviation) of the item, as doubles on the device.
+ * min / max are the exact fp32 values.  With the pivot p = the item's first voxel, S1 = sum (x - p) and S2 = sum (x - p)^2 are
+ * formed in double (x - p and its square of two fp32 values are exact or rounded once in double): one partial per workgroup of
+ * 4096 voxels in `ws`, added in a fixed order by one last workgroup;
+ *     mean = p + S1 / V,   std = sqrt(max(S2 / V - (S1 / V)^2, 0))
+ * so a constant item has std = 0 exactly.  No floating-point atomics: the same bits on every run.
+ * ws: dgtta_intensity_stats_ws_bytes(n_items, V) bytes, 8-byte aligned.  Two launches.
+ *
+ * intensity_map: dst[item] = f(src[item]) voxel by voxel, one launch, mode and parameters per descriptor.  dst may be src.
+ * Statistics are read on the device from `stats` (and `stats2`), rows [item][4] as intensity_stats writes them, each value
+ * rounded to fp32 ONCE; all per-voxel arithmetic is fp32 in the order written:
+ *   DGTTA_IMAP_LINEAR    y = x * a + s * n(v)              (s == 0: y = x * a, the generator is not called)
+ *   DGTTA_IMAP_CONTRAST  mean, lo, hi = fp32(stats mean, min, max);  y = min(max((x - mean) * a + mean, lo), hi)
+ *   DGTTA_IMAP_GAMMA     negate = 0: lo = fp32(min);  negate = 1: x = -x, lo = -fp32(max);  r = fp32(max - min) (the
+ *                        difference taken in double);  y = powf((x - lo) / (r + 1e-7f), a) * r + lo
+ *                        (y is NOT negated back: the statistics of the next step are those of the negated item)
+ *   DGTTA_IMAP_RESTORE   mn = fp32(stats mean) (negate = 1: -fp32(stats mean)), sd = fp32(stats std), mn2, sd2 = fp32(stats2
+ *                        mean, std);  y = (x - mn2) / (sd2 + 1e-8f) * sd + mn;  negate = 1: y = -y
+ * 1e-7f / 1e-8f are the fp32 values nearest 1e-7 / 1e-8.  stats is needed by every mode but LINEAR, stats2 by RESTORE.
+ * The noise n(v) of voxel v (index inside the item) is counter-based, Philox4x32-10 + Box-Muller exactly as the seeded MIND
+ * noise above (csrc/philox.h), one Philox call per four voxels:
+ *   (x0,x1,x2,x3) = Philox4x32-10(counter = (v >> 2, noise_b, off_lo, off_hi), key = (seed_lo, seed_hi))
+ *   v & 3 == 0: sqrt(-2 ln u0) cos(2 pi u1)   1: sqrt(-2 ln u0) sin(2 pi u1)   2, 3: the same from (u2, u3)
+ * It depends on (seed, offset, noise_b, v) only: an item launched alone with the same noise_b draws the same field.  There is
+ * no noise tensor and no generator state.
+ *
+ * gauss_blur3: scipy.ndimage.gaussian_filter(item, sigma, order=0, mode="reflect", truncate=4) for sigma <= 1, separable, the
+ * axes in the order D, H, W: out[i] = sum_{k = 0 .. 2 radius} taps[k] * in[reflect(i + k - radius)] added in ascending k in fp32,
+ * reflect(j) = j mod 2n, mirrored (2n - 1 - j) when >= n - correct for extents shorter than the radius too.  taps: the caller's
+ * 2 radius + 1 <= 9 normalised weights (float64 exp(-x^2 / (2 sigma^2)) / sum, rounded to fp32), radius = int(4 sigma + 0.5)
+ * in 1 .. 4.  Three launches: D pass src -> scratch, H pass scratch -> dst, W pass dst -> dst (a whole row is staged in LDS
+ * before it is written; W <= 2048).  dst may be src; scratch [B][V] is neither.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_INTENSITY_MAX_ITEMS 16
+#define DGTTA_IMAP_LINEAR 0
+#define DGTTA_IMAP_CONTRAST 1
+#define DGTTA_IMAP_GAMMA 2
+#define DGTTA_IMAP_RESTORE 3
+typedef struct DgttaIntensityItem {
+  int item;    /* index in the batch */
+  int mode;    /* DGTTA_IMAP_* */
+  int negate;  /* GAMMA: negate the input; RESTORE: negate the output */
+  int noise_b; /* LINEAR: counter word 1 of the noise */
+  float a;     /* LINEAR: multiplier; CONTRAST: factor; GAMMA: exponent */
+  float s;     /* LINEAR: noise scale */
+  uint32_t seed_lo, seed_hi, off_lo, off_hi; /* LINEAR: Philox key and counter words 2, 3 */
+} DgttaIntensityItem;
+typedef struct DgttaBlurItem {
+  int item;   /* index in the batch */
+  int radius; /* 1 .. 4 */
+  float taps[9];
+} DgttaBlurItem;
+size_t dgtta_intensity_stats_ws_bytes(int n_items, int64_t V);
+int dgtta_intensity_stats(const float *x, int B, int64_t V, const int *h_items, int n_items, double *stats, void *ws,
+                          size_t ws_bytes, void *stream);
+int dgtta_intensity_map(const float *src, float *dst, int B, int64_t V, const DgttaIntensityItem *h_items, int n_items,
+                        const double *stats, const double *stats2, void *stream);
+int dgtta_gauss_blur3(const float *src, float *dst, float *scratch, int B, int D, int H, int W, const DgttaBlurItem *h_items,
+                      int n_items, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
