@@ -8,7 +8,11 @@ matrix product per row of three taps, written out.  Activations are channels las
     dw[co][ci][tap] = sum_{b, vo} x[b][s vo + tap - 1][ci] dy[b][vo][co]          db[co] = sum_{b, vo} dy[b][vo][co]
     out[b][2 v + o][co] = bias[co] + sum_ci x[b][v][ci] w[ci][co][o]              (transposed conv, o in {0, 1}^3)
 
-The second half is what tests/test_gpu_conv_exact.py and tests/test_conv_ref.py share: operands on which every kernel must be
+Beside them the anisotropic layers of conv_aniso.hip in the same style (conva_*, convTa_*): kernel (kd, 3, 3) with kd = 1 | 3, padding
+(kd // 2, 1, 1), one stride per axis, and the transposed conv with kernel = stride in {1, 2}^3.
+
+The second half is what tests/test_gpu_conv_exact.py, tests/test_gpu_aniso_exact.py and tests/test_conv_ref.py share: operands on
+which every kernel must be
 EXACT.  x, w and dy are drawn from {-1, 0, 1} and the bias from small integers, so every product is exact, every fp32 partial
 sum is an integer far below 2^24 whatever the order, and every output is an integer that bf16 (|v| <= 256) and fp16 hold
 exactly: a kernel's result must then torch.equal the float64 one.  The case lists live here so that the CPU test can check
@@ -120,6 +124,127 @@ def convT_wgrad(x, dout):
     xf = x.to(F64).reshape(-1, cin)
     for od, oh, ow in _offsets():
         dw[:, :, od, oh, ow] = xf.t() @ dout[:, od::2, oh::2, ow::2].to(F64).reshape(-1, cout)
+    return dw
+
+
+# ------------------------------------------------------------------------------------------------ the anisotropic operators
+# dg_tta_amd/csrc/conv_aniso.hip: kernel (kd, 3, 3) with kd in {1, 3}, padding (kd // 2, 1, 1), stride (sd, sh, sw) in {1, 2}^3, and
+# the transposed conv with kernel = stride.  Per axis, with k the kernel extent, p = k // 2 and s the stride:
+#     y[vo] = bias + sum_{tap, ci} x[s vo + tap - p] w[tap]          out extent (n + 2 p - k) // s + 1
+#     out[s v + o][co] = bias[co] + sum_ci x[v][ci] w[ci][co][o]     (transposed conv, o in [0, sd) x [0, sh) x [0, sw))
+def out_extent_k(n, k, stride):
+    return (n + 2 * (k // 2) - k) // stride + 1
+
+
+def aniso_out_dims(in_dims, kd, stride):
+    return tuple(out_extent_k(n, k, s) for n, k, s in zip(in_dims, (kd, 3, 3), stride))
+
+
+def _pad_k(x, kd):
+    B, D, H, W, C = x.shape
+    pd = kd // 2
+    xp = torch.zeros(B, D + 2 * pd, H + 2, W + 2, C, dtype=x.dtype)
+    xp[:, pd:pd + D, 1:-1, 1:-1] = x
+    return xp
+
+
+def _unpad_k(xp, kd):
+    pd = kd // 2
+    return xp[:, pd:xp.shape[1] - pd, 1:-1, 1:-1].contiguous()
+
+
+def _tap_view_a(xp, td, th, tw, out_dims, stride):
+    """_tap_view with one step per axis."""
+    (Do, Ho, Wo), (sd, sh, sw) = out_dims, stride
+    return xp[:, td:td + sd * (Do - 1) + 1:sd, th:th + sh * (Ho - 1) + 1:sh, tw:tw + sw * (Wo - 1) + 1:sw]
+
+
+def _row_view_a(xp, td, th, out_dims, stride):
+    """_row_view with one step per axis: the three kw taps of row (td, th), [B, Do, Ho, Wo, 3 C] ordered (kw, c)."""
+    B, _, _, _, C = xp.shape
+    sb, sd, sh, sw, sc = xp.stride()
+    return xp.as_strided((B, *out_dims, 3 * C), (sb, stride[0] * sd, stride[1] * sh, stride[2] * sw, sc),
+                         xp.storage_offset() + td * sd + th * sh)
+
+
+def _rows_k(kd):
+    return [(td, th) for td in range(kd) for th in range(3)]
+
+
+def conva_fwd(x, w, bias=None, stride=(1, 1, 1)):
+    """x [B, D, H, W, Cin], w [Cout, Cin, kd, 3, 3] -> [B, Do, Ho, Wo, Cout]."""
+    C, kd = x.shape[-1], w.shape[2]
+    od = aniso_out_dims(x.shape[1:4], kd, stride)
+    xp = _pad_k(x.to(F64), kd)
+    w = w.to(F64)
+    y = torch.zeros(x.shape[0], *od, w.shape[0], dtype=F64)
+    for td, th in _rows_k(kd):
+        y += _row_view_a(xp, td, th, od, stride) @ w[:, :, td, th, :].permute(2, 1, 0).reshape(3 * C, -1)    # [(kw, ci), co]
+    return y if bias is None else y + bias.to(F64)
+
+
+def conva_dgrad(dy, w, in_dims, stride=(1, 1, 1)):
+    B, (D, H, W) = dy.shape[0], in_dims
+    w = w.to(F64)
+    C, kd = w.shape[1], w.shape[2]
+    od = aniso_out_dims(in_dims, kd, stride)
+    assert tuple(dy.shape[1:4]) == od
+    dxp = torch.zeros(B, D + 2 * (kd // 2), H + 2, W + 2, C, dtype=F64)
+    for td, th in _rows_k(kd):
+        t = dy.to(F64) @ w[:, :, td, th, :].permute(0, 2, 1).reshape(-1, 3 * C)                              # [co, (kw, ci)]
+        for tw in range(3):
+            _tap_view_a(dxp, td, th, tw, od, stride).add_(t[..., tw * C:(tw + 1) * C])
+    return _unpad_k(dxp, kd)
+
+
+def conva_wgrad(x, dy, kd, stride=(1, 1, 1)):
+    od = tuple(dy.shape[1:4])
+    assert od == aniso_out_dims(x.shape[1:4], kd, stride)
+    C = x.shape[-1]
+    xp = _pad_k(x.to(F64), kd)
+    g = dy.to(F64).reshape(-1, dy.shape[-1])
+    dw = torch.zeros(dy.shape[-1], C, kd, 3, 3, dtype=F64)
+    for td, th in _rows_k(kd):
+        dw[:, :, td, th, :] = (g.t() @ _row_view_a(xp, td, th, od, stride).reshape(-1, 3 * C)).reshape(-1, 3, C).permute(0, 2, 1)
+    return dw
+
+
+def conva_dbias(dy):
+    return conv3_dbias(dy)
+
+
+def _offsets_s(stride):
+    return [(od, oh, ow) for od in range(stride[0]) for oh in range(stride[1]) for ow in range(stride[2])]
+
+
+def convTa_fwd(x, w, bias=None):
+    """x [B, D, H, W, Cin], w [Cin, Cout, sd, sh, sw] (kernel = stride) -> [B, sd D, sh H, sw W, Cout]."""
+    B, D, H, W, _ = x.shape
+    w = w.to(F64)
+    sd, sh, sw = w.shape[2:]
+    out = torch.zeros(B, sd * D, sh * H, sw * W, w.shape[1], dtype=F64)
+    for od, oh, ow in _offsets_s((sd, sh, sw)):
+        out[:, od::sd, oh::sh, ow::sw] = x.to(F64) @ w[:, :, od, oh, ow]
+    return out if bias is None else out + bias.to(F64)
+
+
+def convTa_dgrad(dout, w):
+    w = w.to(F64)
+    sd, sh, sw = w.shape[2:]
+    B, Do, Ho, Wo, _ = dout.shape
+    dx = torch.zeros(B, Do // sd, Ho // sh, Wo // sw, w.shape[0], dtype=F64)
+    for od, oh, ow in _offsets_s((sd, sh, sw)):
+        dx += dout[:, od::sd, oh::sh, ow::sw].to(F64) @ w[:, :, od, oh, ow].t()
+    return dx
+
+
+def convTa_wgrad(x, dout, stride):
+    cin, cout = x.shape[-1], dout.shape[-1]
+    sd, sh, sw = stride
+    dw = torch.zeros(cin, cout, sd, sh, sw, dtype=F64)
+    xf = x.to(F64).reshape(-1, cin)
+    for od, oh, ow in _offsets_s(stride):
+        dw[:, :, od, oh, ow] = xf.t() @ dout[:, od::sd, oh::sh, ow::sw].to(F64).reshape(-1, cout)
     return dw
 
 
@@ -257,3 +382,76 @@ def gstats_problem(case):
     dx = conv3_dgrad(dy, w, (D, H, W), 1)
     s0, s1 = gstats_sums(dx, y_prev, mean, rstd, gamma, beta, GSTATS_SLOPE)
     return dict(dy=dy, w=w, y_prev=y_prev, gamma=gamma, beta=beta, mean=mean, rstd=rstd, dx=dx, s0=s0, s1=s1)
+
+
+# ------------------------------------------------------------------------------------------------ anisotropic cases
+# what tests/test_gpu_aniso_exact.py runs and tests/test_conv_ref.py checks the conditions of; every conv case with both kd and
+# all eight strides, every transposed case with the seven strides that are not (1, 1, 1)
+ANISO_KDS = (1, 3)
+ANISO_STRIDES = [(sd, sh, sw) for sd in (1, 2) for sh in (1, 2) for sw in (1, 2)]
+ANISO_CONVT_STRIDES = [s for s in ANISO_STRIDES if s != (1, 1, 1)]
+# Wo 72 / 36: the 32-wide tile (sd = 1) and the 16-wide one (sd = 2), ragged in W, H, D, Cin (16-channel K chunk) and Cout (32), 18 tiles at
+# stride 1 | Wo 28 / 14: the 16- and the 8-wide tile, Cin 12 (the first layer's ragged row), batch 2, 40 tiles at stride 1 (the XCD
+# swizzle) | the 8-wide tile at sw = 1, Cout < 32, one tile along D | odd extents: forward only where a strided axis is odd | Wo 40 /
+# 20: the one tile the four above leave out, 16-wide with sd = 1 and sw = 2 (and the 16-wide tile under several data-gradient classes)
+ANISO_CONV_CASES = [(1, 24, 40, 6, 10, 72), (2, 12, 32, 6, 20, 28), (1, 16, 8, 4, 6, 12), (1, 16, 32, 5, 7, 13), (1, 8, 16, 4, 6, 40)]
+# batch 2 with Cin 24 and odd extents | Cin 40 > 32, ragged against it | rows of 36 voxels (the 32-wide tile) with Cin = 2 x 32
+ANISO_CONVT_CASES = [(2, 24, 16, 3, 5, 7), (1, 40, 24, 4, 6, 18), (1, 64, 32, 2, 4, 36)]
+
+
+def aniso_grads_defined(case, stride):
+    """The library's data and weight gradient ask for an even input extent along every strided axis."""
+    return all(s == 1 or n % 2 == 0 for n, s in zip(case[3:], stride))
+
+
+def _stride_code(stride):
+    return (stride[0] - 1) * 4 + (stride[1] - 1) * 2 + (stride[2] - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def aniso_conv_problem(case, kd, stride):
+    """conv_problem for kernel (kd, 3, 3) and stride (sd, sh, sw); dx is None where the library refuses the data gradient."""
+    B, cin, cout, D, H, W = case
+    g = _gen(case, 100 + 10 * kd + _stride_code(stride))
+    p = densities(cin, cout)
+    od = aniso_out_dims((D, H, W), kd, stride)
+    x = ternary((B, D, H, W, cin), p["x"], g)
+    w = ternary((cout, cin, kd, 3, 3), p["w_fwd"], g)
+    bias = integers((cout,), -BIAS_RANGE, BIAS_RANGE, g)
+    dy = ternary((B, *od, cout), p["dy"], g)
+    wd = ternary((cout, cin, kd, 3, 3), p["w_dgrad"], g)
+    base = integers((B, D, H, W, cin), -BASE_RANGE, BASE_RANGE, g)
+    dx = conva_dgrad(dy, wd, (D, H, W), stride) if aniso_grads_defined(case, stride) else None
+    return dict(x=x, w=w, bias=bias, dy=dy, wd=wd, base=base, y=conva_fwd(x, w, bias, stride), dx=dx, od=od)
+
+
+@functools.lru_cache(maxsize=None)
+def aniso_wgrad_problem(case, kd, stride):
+    B, cin, cout, D, H, W = case
+    assert aniso_grads_defined(case, stride)
+    g = _gen(case, 300 + 10 * kd + _stride_code(stride))
+    p = densities(cin, cout)
+    od = aniso_out_dims((D, H, W), kd, stride)
+    x = ternary((B, D, H, W, cin), p["x"], g)
+    dy = ternary((B, *od, cout), p["dy"], g)
+    base_w = integers((cout, cin, kd, 3, 3), -BASE_RANGE, BASE_RANGE, g)
+    base_b = integers((cout,), -BASE_RANGE, BASE_RANGE, g)
+    return dict(x=x, dy=dy, base_w=base_w, base_b=base_b, dw=conva_wgrad(x, dy, kd, stride), db=conva_dbias(dy), od=od)
+
+
+@functools.lru_cache(maxsize=None)
+def aniso_convT_problem(case, stride):
+    """convT_problem for kernel = stride: the output is the first Cout channels of a concat buffer of 2 Cout, dcat its gradient."""
+    B, cin, cout, D, H, W = case
+    sd, sh, sw = stride
+    g = _gen(case, 500 + _stride_code(stride))
+    x = ternary((B, D, H, W, cin), 2.0 / 3, g)
+    w = ternary((cin, cout, sd, sh, sw), min(2.0 / 3, 32.0 / cin), g)
+    bias = integers((cout,), -BIAS_RANGE, BIAS_RANGE, g)
+    dcat = ternary((B, sd * D, sh * H, sw * W, 2 * cout), 2.0 / 3, g)
+    wd = ternary((cin, cout, sd, sh, sw), min(2.0 / 3, 32.0 / cout), g)
+    base_w = integers((cin, cout, sd, sh, sw), -BASE_RANGE, BASE_RANGE, g)
+    base_b = integers((cout,), -BASE_RANGE, BASE_RANGE, g)
+    dout = dcat[..., :cout]
+    return dict(x=x, w=w, bias=bias, dcat=dcat, wd=wd, base_w=base_w, base_b=base_b, out=convTa_fwd(x, w, bias),
+                dx=convTa_dgrad(dout, wd), dw=convTa_wgrad(x, dout, stride), db=conv3_dbias(dout))
