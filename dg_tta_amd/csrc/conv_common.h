@@ -1,9 +1,10 @@
 // Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
-// convt_gemm.hip, conv_aniso.hip, conv_wgrad_ring.hip and, through conv_wgrad_common.h, the other weight-gradient units):
+// convt_gemm.hip, conv_aniso.hip and, through conv_wgrad_common.h, the weight-gradient units):
 // operand descriptors and views, the launch descriptor of the forward / data-gradient dispatch chains (ConvLaunch) and the
 // launchers that take it, the class tables (single_class, dgrad_parity_classes), tile geometry and the weight image index.
-// Pointer-level functions are declared in conv_api.h, what only the weight-gradient units share in conv_wgrad_common.h; the device
-// primitives that are not about convolutions (vector types, MFMA wrappers, LDS-DMA) live in gfx950.h.
+// Pointer-level functions are declared in conv_api.h; what only the weight-gradient units share - their launch descriptor
+// (WgradLaunch), launchers and class tables - in conv_wgrad_common.h; the device primitives that are not about convolutions
+// (vector types, MFMA wrappers, LDS-DMA) live in gfx950.h.
 #pragma once
 #include "conv_api.h"
 #include "gfx950.h"
@@ -60,17 +61,14 @@ struct ConvLaunch {
 }  // namespace dgconv
 using namespace dgconv;
 
-// Launchers of the specialised kernels that the dispatchers of conv_mfma.hip / conv_wgrad.hip try first; the conv ones return
-// DGTTA_ERR_UNSUPPORTED for a launch they do not take, conv3_wgrad_ring_launch its slab count (0: nothing launched).
+// Launchers of the specialised kernels that the dispatchers of conv_mfma.hip try first; they return DGTTA_ERR_UNSUPPORTED for a
+// launch they do not take.
 // conv_rows.hip: row-reuse kernel
 int conv3_rows_launch(const ConvLaunch &L, const Taps &taps, int is_f16);
 // conv_ring.hip: D-ring kernel
 int conv3_ring_launch(const ConvLaunch &L, const Taps &taps, int64_t stats_cap_slots, int is_f16);
 // conv_s2.hip: register-operand kernel of the two large stride-2 encoder transitions (L.w: the forward weight image)
 int conv3_s2_regs(const ConvLaunch &L, int64_t cap_slots, int dtype);
-// conv_wgrad_ring.hip: ring sweep of the weight gradient (xkh, dry: as in ConvLaunch)
-int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B,
-                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh, bool dry);
 
 namespace {
 

@@ -1,7 +1,8 @@
 // Weight gradients of the 3x3x3 convolutions on the matrix cores: the host side.  Launch plans, workspace sizes, the choice of
 // the kernel (conv_wgrad_ring.hip, conv_wgrad_flat.hip, conv_wgrad_rows.hip, conv_wgrad_s2.hip) and of the slab reduction
-// (conv_wgrad_reduce.hip), the parity-class decompositions of strided convs and the fp32 weight gradient as six 16-bit launches.
-// convt_wgrad.hip (transposed convs) and head_wgrad.hip (1x1x1 head) come in through wgrad_launch_classes / wgrad_launch.
+// (conv_wgrad_reduce.hip) for one WgradLaunch, and the fp32 weight gradient as six 16-bit launches.  The pointer-level entry
+// points fill a WgradLaunch / WgradOut pair and a class table (wgrad_single_class, wgrad_parity_classes); convt_wgrad.hip
+// (transposed convs) and head_wgrad.hip (1x1x1 head) come in through wgrad_launch_classes with theirs.
 #include "conv_wgrad_common.h"
 
 WgradPlan wgrad_plan(int B, int Cin, int Cout, int D, int H, int W, int ncls, int tileW, int tileH) {
@@ -25,10 +26,8 @@ WgradPlan wgrad_plan(int B, int Cin, int Cout, int D, int H, int W, int ncls, in
 size_t conv3_wgrad_mfma_ws_bytes(int B, int Cin, int Cout, int D, int H, int W) {
   WgradPlan p1 = wgrad_plan(B, Cin, Cout, D, H, W, 1, 32, WT::TH), p8 = wgrad_plan(B, Cin, Cout, D, H, W, 8, 32, WT::TH),
             p2 = wgrad_plan(B, Cin, Cout, D, H, W, 1, WT2::TWO, WT2::TH);
-  size_t a = (size_t)p1.units * p1.cibs * p1.cobs, b = (size_t)8 * p8.units * p8.cibs * p8.cobs,
-         c = (size_t)p2.units * p2.cibs * p2.cobs;
-  a = a > b ? a : b;
-  return (a > c ? a : c) * 27 * 1024 * sizeof(float);
+  const size_t a = wgrad_slab_bytes(p1, 1), b = wgrad_slab_bytes(p8, 8), c = wgrad_slab_bytes(p2, 1);
+  return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
 // units a workgroup sweeps into one slab: as many as keep >= `slots` workgroups in the launch (at most 4; DGTTA_WGRAD_UPW=1:
@@ -43,139 +42,80 @@ static int units_per_workgroup(int64_t units, int64_t gy, int slots) {
   return u < 1 ? 1 : (int)u;
 }
 
-int wgrad_launch_classes(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B,
-                         int Cin, int Cout, const WgradClasses &wc, const RealTaps &reals, long long s_co, long long s_ci,
-                         long long s_tap, int accumulate, int dtype, hipStream_t st, long long xkh, bool split_leg) {
-  if (!wgrad_dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;      // (esize() below takes every other dtype for 16-bit)
-  const int esz = (int)esize(dtype), EPV = 16 / esz;
+int wgrad_launch_classes(const WgradLaunch &L, const WgradOut &out, const WgradClasses &wc, const RealTaps &reals) {
+  if (!wgrad_dtype_ok(L.dtype)) return DGTTA_ERR_UNSUPPORTED;      // (esize() below takes every other dtype for 16-bit)
+  const int esz = (int)esize(L.dtype), EPV = 16 / esz;
+  const View &xv = L.xv, &yv = L.yv;
   // Cin may be ragged (first layer: 12 channels in rows of 16): the pad channels only feed gradient rows ci >= Cin,
   // which the reduction never writes.  The rows must be long enough to be read in whole 16-byte groups.
-  if (Cout % EPV || xv.sw % EPV || yv.sw % EPV || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15) ||
-      xv.sw < (xkh ? 32 : (Cin + EPV - 1) / EPV * EPV))      // (x as 32-channel planes: rows of one block)
+  if (L.Cout % EPV || xv.sw % EPV || yv.sw % EPV || ((uintptr_t)L.x & 15) || ((uintptr_t)L.dy & 15) ||
+      xv.sw < (L.xkh ? 32 : (L.Cin + EPV - 1) / EPV * EPV))      // (x as 32-channel planes: rows of one block)
     return DGTTA_ERR_UNSUPPORTED;
   for (int c = 0; c < wc.n; ++c)
     if ((wc.xoff[c] * (long long)esz) % 16 || (wc.yoff[c] * (long long)esz) % 16) return DGTTA_ERR_UNSUPPORTED;
-  if (xkh && (esz != 2 || dgtta_switches().wgrad_tr == '0' || dgtta_switches().wgrad_ring == '0')) return DGTTA_ERR_UNSUPPORTED;
-  WgradPlan p = wgrad_plan(B, Cin, Cout, yv.D, yv.H, yv.W, wc.n, 32, WT::TH);
-  const size_t need = (size_t)wc.n * p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
-  if (ws_bytes < need || p.units >= (1ll << 31) || p.cibs * p.cobs > 65535) return DGTTA_ERR_UNSUPPORTED;
-  float *slabs = (float *)ws;
+  const DgttaSwitches &sw = dgtta_switches();
+  if (L.xkh && (esz != 2 || sw.wgrad_tr == '0' || sw.wgrad_ring == '0')) return DGTTA_ERR_UNSUPPORTED;
+  WgradPlan p = wgrad_plan(L.B, L.Cin, L.Cout, yv.D, yv.H, yv.W, wc.n, 32, WT::TH);
+  if (L.ws_bytes < wgrad_slab_bytes(p, wc.n) || p.units >= (1ll << 31) || p.cibs * p.cobs > 65535) return DGTTA_ERR_UNSUPPORTED;
   int64_t nslab = p.units;            // partial slabs per (channel-block pair, class)
   int rc = DGTTA_OK;
-  const DgttaSwitches &sw = dgtta_switches();
   if (esz == 2 && sw.wgrad_tr != '0') {        // DGTTA_WGRAD_TR=0 (tests): the register-transpose predecessor
     const bool plain = wc.n == 1 && wc.mask[0] == 0x7ffffffu && wc.xoff[0] == 0 && wc.yoff[0] == 0;
     // planes of W <= 16 as flat runs (DGTTA_WGRAD_FLAT=0: the kernels below).  Not for the six launches of an fp32 weight
     // gradient (split_leg): that path's fixtures compare label maps and Adam update signs of near-tied values bit for bit
     // with the reference run, i.e. they are pinned on the summation order of the kernels below
     int64_t g = 0;
-    if (plain && !xkh && !split_leg && sw.wgrad_flat != '0') {
-      g = wgrad_flat_launch(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, dtype, st, &rc);
+    if (plain && !L.xkh && !L.split_leg && sw.wgrad_flat != '0') {
+      g = wgrad_flat_launch(L, &rc);
       if (rc != DGTTA_OK) return rc;
     }
     if (g == 0 && plain && sw.wgrad_ring != '0') {      // the persistent ring sweep (conv_wgrad_ring.hip; DGTTA_WGRAD_RING=0: its predecessors)
-      g = conv3_wgrad_ring_launch(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, dtype == DGTTA_F16, st, &rc, xkh, false);
+      g = conv3_wgrad_ring_launch(L, &rc);
       if (rc != DGTTA_OK) return rc;
     }
     if (g > 0) {
       nslab = g;
-    } else if (xkh) {
+    } else if (L.xkh) {
       return DGTTA_ERR_UNSUPPORTED;      // only the ring sweep reads x as 32-channel planes
-    } else if (plain && Cout >= 64 && sw.wgrad_tr8 != '0') {      // DGTTA_WGRAD_TR8=0 (tests): always the 4-wave kernel
+    } else if (plain && L.Cout >= 64 && sw.wgrad_tr8 != '0') {      // DGTTA_WGRAD_TR8=0 (tests): always the 4-wave kernel
       const int upw = units_per_workgroup(p.units, (int64_t)p.cibs * ((p.cobs + 1) / 2), 256);      // one 8-wave workgroup per CU
       nslab = cdiv64(p.units, upw);
-      rc = conv3_wgrad_tr8_launch(x, xv, dy, yv, slabs, Cin, Cout, p, upw, nslab, dtype, st);
+      rc = conv3_wgrad_tr8_launch(L, p, upw, nslab);
     } else {
       // two 4-wave workgroups per CU; class launches keep one unit per workgroup (their classes carry 1..8 taps: many
       // small workgroups balance that, 4 units each measured 1.5x slower)
       const int upw = plain ? units_per_workgroup(p.units, (int64_t)p.cibs * p.cobs, 512) : 1;
       nslab = cdiv64(p.units, upw);
-      rc = conv3_wgrad_tr_launch(x, xv, dy, yv, slabs, Cin, Cout, p, wc, plain, upw, nslab, dtype, st);
+      rc = conv3_wgrad_tr_launch(L, p, wc, plain, upw, nslab);
     }
   } else {
-    rc = conv3_wgrad_mfma_launch(x, xv, dy, yv, slabs, Cin, Cout, p, wc, dtype, st);
+    rc = conv3_wgrad_mfma_launch(L, p, wc);
   }
   if (rc != DGTTA_OK) return rc;
-  return wgrad_reduce_launch(slabs, dw, Cin, Cout, p, wc.n, nslab, accumulate, reals, wc.n == 1 ? &reals.t[0] : nullptr, s_co, s_ci,
-                             s_tap, st);
+  return wgrad_reduce_launch(L, out, p, wc.n, nslab, reals);
 }
 
-int wgrad_launch(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B, int Cin,
-                 int Cout, unsigned tapmask, const Taps &real, long long s_co, long long s_ci, long long s_tap, int accumulate,
-                 int dtype, hipStream_t st, long long xkh, bool split_leg) {
-  WgradClasses wc;
-  wc.n = 1;
-  wc.mask[0] = tapmask;
-  wc.xoff[0] = wc.yoff[0] = 0;
+// 3x3x3 conv, stride 1 or 2 (even extents).  L.xv: x at full resolution, L.yv: dy
+static int wgrad_conv(const WgradLaunch &L, const WgradOut &out, int stride) {
   RealTaps reals;
-  reals.t[0] = real;
-  return wgrad_launch_classes(x, xv, dy, yv, dw, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, s_tap, accumulate, dtype, st, xkh,
-                              split_leg);
-}
-
-static int wgrad_conv(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B,
-                      int Cin, int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st,
-                      long long xkh = 0, bool split_leg = false) {
-  const long long s_co = (long long)Cin * 27, s_ci = 27, s_tap = 1;
-  if (stride == 1) {
-    const View xv = dense_view(B, Di, Hi, Wi, ldx), yv = dense_view(B, Di, Hi, Wi, lddy);
-    return wgrad_launch(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, 0x7ffffffu, identity_taps(0), s_co, s_ci, s_tap, accumulate,
-                        dtype, st, xkh, split_leg);
-  }
-  if (xkh) return DGTTA_ERR_UNSUPPORTED;
-  // stride 2: x[2*vo + tap - 1] lives on parity sub-lattices of x; per axis parity 0 <- tap 1 (offset 0),
-  // parity 1 <- tap 0 (offset -1) and tap 2 (offset 0).  Each real tap belongs to exactly one of the 8 classes.
-  const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-  const View yv = dense_view(B, Do, Ho, Wo, lddy);
-  if (dtype != DGTTA_F32) {
+  if (stride == 1) return wgrad_launch_classes(L, out, wgrad_single_class(0x7ffffffu, identity_taps(0), &reals), reals);
+  if (L.xkh) return DGTTA_ERR_UNSUPPORTED;
+  if (L.dtype != DGTTA_F32) {
     // one pass over x (full resolution tile) and dy with all 27 taps: conv3_wgrad_tr_s2_kernel
     const int one = dgtta_switches().wgrad_s2_onepass;      // DGTTA_WGRAD_S2_ONEPASS=0 (tests): the 8-class launch
-    const View xfull = dense_view(B, Di, Hi, Wi, ldx);
-    WgradPlan p = wgrad_plan(B, Cin, Cout, Do, Ho, Wo, 1, WT2::TWO, WT2::TH);
-    const size_t need = (size_t)p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
-    const bool ok = Cout % 8 == 0 && ldx % 8 == 0 && lddy % 8 == 0 && !((uintptr_t)x & 15) && !((uintptr_t)dy & 15) &&
-                    ldx >= (Cin + 7) / 8 * 8 && ws_bytes >= need && p.units < (1ll << 31) && p.cibs * p.cobs <= 65535;
-    if (ok && one != '0') {
+    WgradPlan p = wgrad_plan(L.B, L.Cin, L.Cout, L.yv.D, L.yv.H, L.yv.W, 1, WT2::TWO, WT2::TH);
+    if (wgrad_onepass_ok(L, p) && one != '0') {
       // two output-channel blocks share the x tile (DGTTA_WGRAD_S2_ONEPASS=1: one)
-      const int rc = conv3_wgrad_s2_launch(x, xfull, dy, yv, (float *)ws, Cin, Cout, p, p.cobs % 2 == 0 && Cout % 64 == 0 && one != '1',
-                                           dtype, st);
+      const int rc = conv3_wgrad_s2_launch(L, p, p.cobs % 2 == 0 && L.Cout % 64 == 0 && one != '1');
       if (rc != DGTTA_OK) return rc;
-      RealTaps ident;
-      ident.t[0] = identity_taps(0);
-      return wgrad_reduce_launch((const float *)ws, dw_t, Cin, Cout, p, 1, p.units, accumulate, ident, &ident.t[0], s_co, s_ci, s_tap, st);
+      reals.t[0] = identity_taps(0);
+      return wgrad_reduce_launch(L, out, p, 1, p.units, reals);
     }
   }
-  WgradClasses wc;
-  RealTaps reals;
-  wc.n = 8;
-  View xv;
-  for (int p = 0; p < 8; ++p) {
-    const int par[3] = {p >> 2, (p >> 1) & 1, p & 1};
-    long long off;
-    xv = parity_view(Di, Hi, Wi, ldx, par[0], par[1], par[2], &off);   // even extents: same shape for all classes
-    xv.sb = (long long)Di * Hi * Wi * ldx;
-    wc.xoff[p] = off;
-    wc.yoff[p] = 0;
-    unsigned mask = 0;
-    for (int t = 0; t < 27; ++t) {
-      const int k[3] = {t / 9, (t / 3) % 3, t % 3};
-      int rl[3];
-      bool ok = true;
-      for (int a = 0; a < 3; ++a) {
-        if (par[a] == 0) {
-          ok = ok && (k[a] == 1);
-          rl[a] = 1;
-        } else {
-          ok = ok && (k[a] <= 1);
-          rl[a] = (k[a] == 0) ? 0 : 2;
-        }
-      }
-      reals.t[p].wt[t] = ok ? (signed char)(rl[0] * 9 + rl[1] * 3 + rl[2]) : (signed char)-1;
-      if (ok) mask |= 1u << t;
-    }
-    wc.mask[p] = mask;
-  }
-  return wgrad_launch_classes(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, s_tap, accumulate, dtype, st);
+  // x[2*vo + tap - 1] lives on the parity sub-lattices of x: 8 classes of a stride-1 problem
+  WgradLaunch C = L;
+  const WgradClasses wc = wgrad_parity_classes(3, 2, 2, 2, L.xv.D, L.xv.H, L.xv.W, (int)L.xv.sw, &reals, &C.xv);
+  return wgrad_launch_classes(C, out, wc, reals);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -242,37 +182,29 @@ size_t conv3_wgrad_split_extra_bytes(int B, int Cin, int Cout, int D, int H, int
   return 3 * wgrad_split_plane_bytes(B, Cin, D * stride, H * stride, W * stride) + 3 * wgrad_split_plane_bytes(B, Cout, D, H, W);
 }
 
-// carves the three x planes and the three dy planes out of `planes` and fills them (one streaming pass per operand)
-int wgrad_split_planes(const float *x, int ldx, int Cin, int64_t rows_x, size_t plane_x_bytes, const float *dy, int lddy, int Cout,
-                       int64_t rows_y, size_t plane_y_bytes, void *planes, bf16_t *xs[3], bf16_t *gs[3], hipStream_t st) {
-  const int ldxs = (Cin + 7) / 8 * 8, ldys = (Cout + 7) / 8 * 8;
+// carves the three x planes and the three dy planes out of the workspace behind the slab region, fills them (one streaming pass
+// per operand) and runs the six products in their fixed order
+int wgrad_f32_split(const SplitOperand &x, const SplitOperand &dy, void *ws, size_t ws_bytes, size_t slab_bytes, int accumulate,
+                    hipStream_t st, const WgradSplitLeg &leg) {
+  const size_t px = wgrad_split_plane_bytes(x.B, x.C, x.D, x.H, x.W), py = wgrad_split_plane_bytes(dy.B, dy.C, dy.D, dy.H, dy.W);
+  if (dy.C % 8 || dgtta_switches().wgrad_f32_split == '0' || ws_bytes < slab_bytes + 3 * px + 3 * py) return DGTTA_ERR_UNSUPPORTED;
+  const int ldxs = (x.C + 7) / 8 * 8, ldys = (dy.C + 7) / 8 * 8;
+  const int64_t rows_x = (int64_t)x.B * x.D * x.H * x.W, rows_y = (int64_t)dy.B * dy.D * dy.H * dy.W;
+  char *planes = (char *)ws + slab_bytes;
+  bf16_t *xs[3], *gs[3];
   for (int i = 0; i < 3; ++i) {
-    xs[i] = (bf16_t *)((char *)planes + i * plane_x_bytes);
-    gs[i] = (bf16_t *)((char *)planes + 3 * plane_x_bytes + i * plane_y_bytes);
+    xs[i] = (bf16_t *)(planes + i * px);
+    gs[i] = (bf16_t *)(planes + 3 * px + i * py);
   }
   const int64_t tx = rows_x * (ldxs / 8), ty = rows_y * (ldys / 8);
-  hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)(cdiv64(tx, 256) < 8192 ? cdiv64(tx, 256) : 8192)), dim3(256), 0, st, x, ldx,
-                     Cin, ldxs, rows_x, xs[0], xs[1], xs[2]);
-  hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)(cdiv64(ty, 256) < 8192 ? cdiv64(ty, 256) : 8192)), dim3(256), 0, st, dy,
-                     lddy, Cout, ldys, rows_y, gs[0], gs[1], gs[2]);
+  hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)(cdiv64(tx, 256) < 8192 ? cdiv64(tx, 256) : 8192)), dim3(256), 0, st, x.p, x.ld,
+                     x.C, ldxs, rows_x, xs[0], xs[1], xs[2]);
+  hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)(cdiv64(ty, 256) < 8192 ? cdiv64(ty, 256) : 8192)), dim3(256), 0, st, dy.p,
+                     dy.ld, dy.C, ldys, rows_y, gs[0], gs[1], gs[2]);
   DG_CHECK_LAUNCH("split3_bf16_kernel");
-  return DGTTA_OK;
-}
-
-// Di, Hi, Wi: input extent; stride 1 or 2 (even extents)
-static int wgrad_conv_f32_split(const float *x, int ldx, const float *dy, int lddy, float *dw_t, void *ws, size_t slab_bytes,
-                                void *planes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int stride, int accumulate,
-                                hipStream_t st) {
-  const int ldxs = (Cin + 7) / 8 * 8, ldys = (Cout + 7) / 8 * 8;
-  const int D = Di / stride, H = Hi / stride, W = Wi / stride;
-  const int64_t rows_x = (int64_t)B * Di * Hi * Wi, rows = (int64_t)B * D * H * W;
-  bf16_t *xs[3], *gs[3];
-  int rc = wgrad_split_planes(x, ldx, Cin, rows_x, wgrad_split_plane_bytes(B, Cin, Di, Hi, Wi), dy, lddy, Cout, rows,
-                              wgrad_split_plane_bytes(B, Cout, D, H, W), planes, xs, gs, st);
-  if (rc != DGTTA_OK) return rc;
+  constexpr int PAIRS[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};      // (x plane, dy plane), in this order
   for (int q = 0; q < 6; ++q) {
-    rc = wgrad_conv(xs[WGRAD_SPLIT_PAIRS[q][0]], ldxs, gs[WGRAD_SPLIT_PAIRS[q][1]], ldys, dw_t, ws, slab_bytes, B, Cin, Cout,
-                    Di, Hi, Wi, stride, (accumulate || q > 0) ? 1 : 0, DGTTA_BF16, st, 0, true);
+    const int rc = leg(xs[PAIRS[q][0]], ldxs, gs[PAIRS[q][1]], ldys, (accumulate || q > 0) ? 1 : 0);
     if (rc != DGTTA_OK) return rc;        // (q == 0: nothing written yet, the caller falls back to the fp32 kernel)
   }
   return DGTTA_OK;
@@ -282,23 +214,28 @@ int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw
                      int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st, long long xkh) {
   if (stride != 1 && stride != 2) return DGTTA_ERR_UNSUPPORTED;
   if (stride == 2 && ((Di | Hi | Wi) & 1)) return DGTTA_ERR_UNSUPPORTED;   // odd extents: leave to the general kernel
+  const int Do = Di / stride, Ho = Hi / stride, Wo = Wi / stride;
+  WgradLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), dy, dense_view(B, Do, Ho, Wo, lddy), B, Cin, Cout, dtype, ws, ws_bytes, st};
+  L.xkh = xkh;
+  const WgradOut out{dw_t, (long long)Cin * 27, 27, 1, accumulate};
   if (dtype == DGTTA_F32) {
     if (xkh) return DGTTA_ERR_UNSUPPORTED;      // (x as 32-channel planes: 16-bit storage only)
     // the caller offered the split workspace (dgtta_conv3d_wgrad_split_ws_bytes) behind the plain one: six 16-bit launches
     // (DGTTA_WGRAD_F32_SPLIT=0: the fp32 MFMA kernel, its predecessor)
-    const int Do = Di / stride, Ho = Hi / stride, Wo = Wi / stride;
-    const size_t base = conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, Do, Ho, Wo);
-    const size_t slab = align_up(base, 256);
-    if (Cout % 8 == 0 && dgtta_switches().wgrad_f32_split != '0' &&
-        ws_bytes >= slab + conv3_wgrad_split_extra_bytes(B, Cin, Cout, Do, Ho, Wo, stride)) {
-      const int rc = wgrad_conv_f32_split((const float *)x, ldx, (const float *)dy, lddy, dw_t, ws, slab, (char *)ws + slab, B, Cin,
-                                          Cout, Di, Hi, Wi, stride, accumulate, st);
-      if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
-    }
-    return wgrad_conv(x, ldx, dy, lddy, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, stride, accumulate, dtype, st);
+    const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, Do, Ho, Wo), 256);
+    const SplitOperand sx{(const float *)x, ldx, Cin, B, Di, Hi, Wi}, sy{(const float *)dy, lddy, Cout, B, Do, Ho, Wo};
+    const int rc = wgrad_f32_split(sx, sy, ws, ws_bytes, slab, accumulate, st,
+                                   [&](const bf16_t *xs, int ldxs, const bf16_t *gs, int ldys, int acc) {
+      WgradLaunch leg = L;
+      leg.x = xs, leg.xv = dense_view(B, Di, Hi, Wi, ldxs), leg.dy = gs, leg.yv = dense_view(B, Do, Ho, Wo, ldys);
+      leg.dtype = DGTTA_BF16, leg.ws_bytes = slab, leg.split_leg = true;
+      return wgrad_conv(leg, WgradOut{dw_t, out.s_co, out.s_ci, out.s_tap, acc}, stride);
+    });
+    if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
+  } else if (!wgrad_dtype_ok(dtype)) {
+    return DGTTA_ERR_UNSUPPORTED;
   }
-  if (!wgrad_dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;
-  return wgrad_conv(x, ldx, dy, lddy, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, stride, accumulate, dtype, st, xkh);
+  return wgrad_conv(L, out, stride);
 }
 // would the weight gradient of a stride-1 conv on these dims take x as 32-channel planes (only the ring sweep does)?
 bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int dtype) {
@@ -307,22 +244,19 @@ bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int d
   const View xv = dense_view(B, D, H, W, 32), yv = dense_view(B, D, H, W, Cout);
   int rc = DGTTA_OK;
   const size_t ws_bytes = conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, D, H, W);
-  const int g = conv3_wgrad_ring_launch((const void *)16, xv, (const void *)16, yv, nullptr, ws_bytes, B, Cin, Cout, dtype == DGTTA_F16, nullptr,
-                                        &rc, (long long)B * D * H * W * 32, true);
+  WgradLaunch L{(const void *)16, xv, (const void *)16, yv, B, Cin, Cout, dtype, nullptr, ws_bytes, nullptr};
+  L.xkh = (long long)B * D * H * W * 32, L.dry = true;
+  const int g = conv3_wgrad_ring_launch(L, &rc);
   return rc == DGTTA_OK && g > 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Weight gradients of the anisotropic layers (conv_aniso.hip) on the class-masked kernels (conv_wgrad_rows.hip).
-//   conv [kd][3][3], strides (sd, sh, sw) in {1, 2}:  dW[co][ci][t] = sum_{b,vo} dy[vo][co] x[s vo + t - pad][ci] per axis.
-//   A strided axis splits x into its two parity lattices: parity p at virtual offset u (-1, 0, +1) carries the real tap
-//   t = s u + p + pad where 0 <= t < k (stride 1: t = u + pad).  One class per parity combination that carries a tap (1 to 8),
-//   each a stride-1 problem over dy's lattice whose mask holds exactly the virtual taps with a real tap: the kernels multiply
-//   those only, and the fixed-order slab reduction writes them into torch layout [Cout][Cin][kd * 9].
-//   Strided axes need even input extents (every parity lattice then has dy's extent).
+// Weight gradients of the anisotropic layers (conv_aniso.hip) on the class-masked kernels (conv_wgrad_rows.hip): the classes of
+// wgrad_parity_classes - the kernels multiply only the virtual taps with a real tap, and the fixed-order slab reduction writes
+// them into torch layout [Cout][Cin][kd * 9].
 size_t wgrad_classes_bytes(int B, int Cin, int Cout, int D, int H, int W, int ncls) {
   const WgradPlan p = wgrad_plan(B, Cin, Cout, D, H, W, ncls, 32, WT::TH);
-  return (size_t)ncls * p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
+  return wgrad_slab_bytes(p, ncls);
 }
 
 // slabs for any class count 1..8 on a dy lattice of D x H x W (the plan's D split depends on the class count)
@@ -337,42 +271,10 @@ size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W) {
 
 int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
                      int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
-  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
   const int Do = (Di + 2 * (kd / 2) - kd) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
-  const View yv = dense_view(B, Do, Ho, Wo, lddy);
-  WgradClasses wc;
+  WgradLaunch L{x, View{}, dy, dense_view(B, Do, Ho, Wo, lddy), B, Cin, Cout, dtype, ws, ws_bytes, st};
   RealTaps reals;
-  wc.n = 0;
-  for (int c = 0; c < sd * sh * sw; ++c) {
-    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
-    unsigned mask = 0;
-    Taps rt;
-    for (int t = 0; t < 27; ++t) {
-      const int u[3] = {t / 9 - 1, (t / 3) % 3 - 1, t % 3 - 1};
-      int real[3];
-      bool ok = true;
-      for (int a = 0; a < 3; ++a) {
-        real[a] = ss[a] * u[a] + par[a] + ks[a] / 2;
-        ok = ok && real[a] >= 0 && real[a] < ks[a];
-      }
-      rt.wt[t] = ok ? (signed char)(real[0] * 9 + real[1] * 3 + real[2]) : (signed char)-1;
-      if (ok) mask |= 1u << t;
-    }
-    if (!mask) continue;            // kd = 1 along a strided D: the odd planes carry no tap
-    wc.xoff[wc.n] = ((long long)par[0] * Hi * Wi + (long long)par[1] * Wi + par[2]) * ldx;
-    wc.yoff[wc.n] = 0;
-    wc.mask[wc.n] = mask;
-    reals.t[wc.n] = rt;
-    ++wc.n;
-  }
-  View xv = dense_view(B, Di, Hi, Wi, ldx);      // the parity lattices: steps s, extent of dy
-  xv.sd *= sd;
-  xv.sh *= sh;
-  xv.sw *= sw;
-  xv.D = Di / sd;
-  xv.H = Hi / sh;
-  xv.W = Wi / sw;
+  const WgradClasses wc = wgrad_parity_classes(kd, sd, sh, sw, Di, Hi, Wi, ldx, &reals, &L.xv);
   if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Do, Ho, Wo, wc.n)) return DGTTA_ERR_WORKSPACE;
-  const long long s_co = (long long)Cin * kd * 9, s_ci = kd * 9;
-  return wgrad_launch_classes(x, xv, dy, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, s_co, s_ci, 1, accumulate, dtype, st);
+  return wgrad_launch_classes(L, WgradOut{dw_t, (long long)Cin * kd * 9, kd * 9, 1, accumulate}, wc, reals);
 }

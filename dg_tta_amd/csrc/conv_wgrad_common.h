@@ -1,11 +1,14 @@
-// Shared declarations of the weight-gradient translation units (conv_wgrad.hip: host dispatch; conv_wgrad_rows.hip,
-// conv_wgrad_flat.hip, conv_wgrad_s2.hip, convt_wgrad.hip, conv_wgrad_reduce.hip, head_wgrad.hip: kernels and their launchers):
-// the launch descriptors, the launchers that cross files (each declared here, once; the defining file includes this header)
-// and the weight-gradient device helpers that more than one kernel file uses (the MFMA wrappers and tr_operand: gfx950.h).
+// Shared declarations of the weight-gradient translation units (conv_wgrad.hip: host dispatch; conv_wgrad_ring.hip,
+// conv_wgrad_rows.hip, conv_wgrad_flat.hip, conv_wgrad_s2.hip, convt_wgrad.hip, conv_wgrad_reduce.hip, head_wgrad.hip: kernels and
+// their launchers): the kernels' by-value descriptors, the launch and output descriptors of the host chain (WgradLaunch, WgradOut)
+// and the launchers that take them (each declared here, once; the defining file includes this header), the class tables
+// (wgrad_single_class, wgrad_parity_classes) and the weight-gradient device helpers that more than one kernel file uses (the MFMA
+// wrappers and tr_operand: gfx950.h).
 // All kernels leave fp32 partial slabs [27 taps][32 ci][32 co], one per workgroup and channel-block pair; wgrad_reduce_launch
 // sums them in a fixed order.
 #pragma once
 #include "conv_common.h"
+#include <functional>
 #include <type_traits>
 
 namespace dgconv {
@@ -23,56 +26,141 @@ struct WgradPlan {
   int tW, tH, nsd, DR, cibs, cobs;
   int64_t units;
 };
+
+// One weight-gradient launch as the host chain hands it down: the operands and their views (yv: the lattice the plan tiles),
+// batch and channel counts, the storage type, the slab region and the stream.  Every launcher writes its slabs at ws.  Riders:
+//   xkh != 0: x holds its 32-channel blocks as dense planes xkh elements apart - only conv3_wgrad_ring_launch reads that layout;
+//   split_leg: one of the six launches of an fp32 weight gradient - wgrad_launch_classes keeps those off the flat kernel;
+//   dry: no launch, conv3_wgrad_ring_launch only answers whether it would take the call (conv3_wgrad_blocked_ok).
+struct WgradLaunch {
+  const void *x;
+  View xv;
+  const void *dy;
+  View yv;
+  int B, Cin, Cout, dtype;
+  void *ws;
+  size_t ws_bytes;
+  hipStream_t st;
+  long long xkh = 0;
+  bool split_leg = false;
+  bool dry = false;
+};
+// where the slab reduction writes: dw[co * s_co + ci * s_ci + real_tap * s_tap] (+)=
+struct WgradOut {
+  float *dw;
+  long long s_co, s_ci, s_tap;
+  int accumulate;
+};
+// one fp32 operand of a split weight gradient: rows [B * D * H * W][ld] with C channels used
+struct SplitOperand {
+  const float *p;
+  int ld, C, B, D, H, W;
+};
 }  // namespace dgconv
 
 // the storage types the weight-gradient entry points take; anything else is DGTTA_ERR_UNSUPPORTED (no error text)
 static inline bool wgrad_dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
+// slab region of a launch of plan p with ncls classes
+static inline size_t wgrad_slab_bytes(const WgradPlan &p, int ncls) {
+  return (size_t)ncls * p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
+}
+// do the one-pass 16-bit kernels (conv_wgrad_s2.hip, convT_wgrad_tr_kernel) take this launch under their single-class plan p?
+static inline bool wgrad_onepass_ok(const WgradLaunch &L, const WgradPlan &p) {
+  return L.Cout % 8 == 0 && L.xv.sw % 8 == 0 && L.yv.sw % 8 == 0 && !((uintptr_t)L.x & 15) && !((uintptr_t)L.dy & 15) &&
+         L.xv.sw >= (L.Cin + 7) / 8 * 8 && L.ws_bytes >= wgrad_slab_bytes(p, 1) && p.units < (1ll << 31) && p.cibs * p.cobs <= 65535;
+}
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad.hip
 // plan of a launch with ncls classes over tiles of tileW x tileH voxels (32 x 4: the stride-1 kernels; WT2::TWO x WT2::TH: the
 // one-pass stride-2 and transposed-conv kernels)
 WgradPlan wgrad_plan(int B, int Cin, int Cout, int D, int H, int W, int ncls, int tileW, int tileH);
 size_t wgrad_classes_bytes(int B, int Cin, int Cout, int D, int H, int W, int ncls);
-// class launch of the stride-1 kernels + slab reduction into dw[co*s_co + ci*s_ci + real_tap*s_tap]; wgrad_launch: one class
-int wgrad_launch_classes(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B,
-                         int Cin, int Cout, const WgradClasses &wc, const RealTaps &reals, long long s_co, long long s_ci,
-                         long long s_tap, int accumulate, int dtype, hipStream_t st, long long xkh = 0, bool split_leg = false);
-int wgrad_launch(const void *x, const View &xv, const void *dy, const View &yv, float *dw, void *ws, size_t ws_bytes, int B, int Cin,
-                 int Cout, unsigned tapmask, const Taps &real, long long s_co, long long s_ci, long long s_tap, int accumulate,
-                 int dtype, hipStream_t st, long long xkh = 0, bool split_leg = false);
-// fp32 operands as three bf16 planes each (exact three-term splits): plane size, the two split passes, the order of the six products
+// class launch of the stride-1 kernels (the first that takes it: flat, ring, tr8, tr; fp32 or DGTTA_WGRAD_TR=0: mfma) + slab reduction
+int wgrad_launch_classes(const WgradLaunch &L, const WgradOut &out, const WgradClasses &wc, const RealTaps &reals);
+// fp32 operands as three bf16 planes each (exact three-term splits): plane size, and the driver of the six 16-bit launches.  It
+// carves the planes out of ws behind slab_bytes, fills them and calls leg(x plane, its ld, dy plane, its ld, accumulate) for the
+// products (0,0) (0,1) (1,0) (0,2) (1,1) (2,0), accumulating from the second on.  DGTTA_ERR_UNSUPPORTED, nothing written: the
+// split does not apply (Cout % 8, DGTTA_WGRAD_F32_SPLIT=0, workspace without the planes) or the first leg refused
 size_t wgrad_split_plane_bytes(int B, int C, int D, int H, int W);
-int wgrad_split_planes(const float *x, int ldx, int Cin, int64_t rows_x, size_t plane_x_bytes, const float *dy, int lddy, int Cout,
-                       int64_t rows_y, size_t plane_y_bytes, void *planes, bf16_t *xs[3], bf16_t *gs[3], hipStream_t st);
-constexpr int WGRAD_SPLIT_PAIRS[6][2] = {{0, 0}, {0, 1}, {1, 0}, {0, 2}, {1, 1}, {2, 0}};      // (x plane, dy plane), in this order
+typedef std::function<int(const bf16_t *x, int ldx, const bf16_t *dy, int lddy, int accumulate)> WgradSplitLeg;
+int wgrad_f32_split(const SplitOperand &x, const SplitOperand &dy, void *ws, size_t ws_bytes, size_t slab_bytes, int accumulate,
+                    hipStream_t st, const WgradSplitLeg &leg);
+
+// ---------------------------------------------------------------------------------------------------- conv_wgrad_ring.hip
+// persistent ring sweep of plain 16-bit launches; returns its slab count per channel-block pair (0: not taken, nothing launched)
+int conv3_wgrad_ring_launch(const WgradLaunch &L, int *rc);
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad_rows.hip
-// stride-1 kernels; one slab per workgroup at slabs[(class, pair, blockIdx.x)].  dtype: the storage type (tr / tr8: 16-bit only)
-int conv3_wgrad_mfma_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                            const WgradPlan &p, const WgradClasses &wc, int dtype, hipStream_t st);
-int conv3_wgrad_tr_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                          const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab, int dtype, hipStream_t st);
-int conv3_wgrad_tr8_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                           const WgradPlan &p, int upw, int64_t nslab, int dtype, hipStream_t st);
+// stride-1 kernels; one slab per workgroup at slabs[(class, pair, blockIdx.x)] (tr / tr8: 16-bit storage only)
+int conv3_wgrad_mfma_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc);
+int conv3_wgrad_tr_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab);
+int conv3_wgrad_tr8_launch(const WgradLaunch &L, const WgradPlan &p, int upw, int64_t nslab);
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad_flat.hip
 // planes of W <= 16; returns the number of slabs per channel-block pair (0: shape not taken)
-int64_t wgrad_flat_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B, int Cin,
-                          int Cout, int dtype, hipStream_t st, int *rc);
+int64_t wgrad_flat_launch(const WgradLaunch &L, int *rc);
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad_s2.hip
-// one-pass stride-2 kernels (x at full resolution); two_blocks: the 8-wave kernel that shares the x tile between two
+// one-pass stride-2 kernels (L.xv: x at full resolution); two_blocks: the 8-wave kernel that shares the x tile between two
 // output-channel blocks
-int conv3_wgrad_s2_launch(const void *x, const View &xfull, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                          const WgradPlan &p, bool two_blocks, int dtype, hipStream_t st);
+int conv3_wgrad_s2_launch(const WgradLaunch &L, const WgradPlan &p, bool two_blocks);
 
 // ---------------------------------------------------------------------------------------------------- conv_wgrad_reduce.hip
-// dw (+)= sum over the nslab slabs of every pair, fixed order; ncls slab sets with the tap tables reals.t[0 .. ncls).  `dense`
-// (optional): the one table of a single-class launch, offered to the dense-layout kernel
-int wgrad_reduce_launch(const float *slabs, float *dw, int Cin, int Cout, const WgradPlan &p, int ncls, int64_t nslab, int accumulate,
-                        const RealTaps &reals, const Taps *dense, long long s_co, long long s_ci, long long s_tap, hipStream_t st);
+// out (+)= sum over the nslab slabs (at L.ws) of every pair, fixed order; ncls slab sets with the tap tables reals.t[0 .. ncls).  The
+// one table of a single-class launch is offered to the dense-layout kernel
+int wgrad_reduce_launch(const WgradLaunch &L, const WgradOut &out, const WgradPlan &p, int ncls, int64_t nslab, const RealTaps &reals);
 
 namespace {
+
+// one class over the whole operands (offsets 0) with the virtual taps of tapmask; *reals: its real-tap table
+inline WgradClasses wgrad_single_class(unsigned tapmask, const Taps &real, RealTaps *reals) {
+  WgradClasses wc{};
+  wc.n = 1;
+  wc.mask[0] = tapmask;
+  reals->t[0] = real;
+  return wc;
+}
+
+// Weight gradient of a [kd, 3, 3] conv with strides (sd, sh, sw) in {1, 2}^3 as stride-1 problems over dy's lattice (the counterpart
+// of dgrad_parity_classes, conv_common.h):  dW[co][ci][t] = sum_{b,vo} dy[vo][co] x[s vo + t - pad][ci] per axis.  A strided axis
+// splits x into its two parity lattices: parity p at virtual offset u (-1, 0, +1) carries the real tap t = s u + p + pad where
+// 0 <= t < k (stride 1: t = u + pad; kd = 3, stride 2: parity 0 carries tap 1, parity 1 taps 0 and 2).  One class per parity
+// combination that carries a tap (1 to 8, parities flattened in D, H, W order), its mask exactly the virtual taps with a real tap
+// (*reals) - each real tap belongs to one class.  *xv: the lattices' common view (steps s, extent of dy, batch stride of the dense
+// volume); strided axes need even input extents.
+inline WgradClasses wgrad_parity_classes(int kd, int sd, int sh, int sw, int Di, int Hi, int Wi, int ldx, RealTaps *reals, View *xv) {
+  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+  WgradClasses wc{};
+  for (int c = 0; c < sd * sh * sw; ++c) {
+    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
+    unsigned mask = 0;
+    Taps rt;
+    for (int t = 0; t < 27; ++t) {
+      const int u[3] = {t / 9 - 1, (t / 3) % 3 - 1, t % 3 - 1};
+      int real[3];
+      bool ok = true;
+      for (int a = 0; a < 3; ++a) {
+        real[a] = ss[a] * u[a] + par[a] + ks[a] / 2;
+        ok = ok && real[a] >= 0 && real[a] < ks[a];
+      }
+      rt.wt[t] = ok ? (signed char)(real[0] * 9 + real[1] * 3 + real[2]) : (signed char)-1;
+      if (ok) mask |= 1u << t;
+    }
+    if (!mask) continue;            // kd = 1 along a strided D: the odd planes carry no tap
+    wc.xoff[wc.n] = ((long long)par[0] * Hi * Wi + (long long)par[1] * Wi + par[2]) * ldx;
+    wc.mask[wc.n] = mask;
+    reals->t[wc.n] = rt;
+    ++wc.n;
+  }
+  *xv = dense_view(1, Di, Hi, Wi, ldx);
+  xv->sd *= sd;
+  xv->sh *= sh;
+  xv->sw *= sw;
+  xv->D = Di / sd;
+  xv->H = Hi / sh;
+  xv->W = Wi / sw;
+  return wc;
+}
 
 // Workgroups are dispatched round robin over the 8 XCDs (each with its own L2), units are columns of the volume whose x
 // tiles overlap their H neighbours' by the halo rows: give every XCD a CONTIGUOUS range of units, so that the halo is

@@ -194,9 +194,10 @@ __global__ __launch_bounds__(256, PIPE ? 1 : 2) void conv3_wgrad_flat_kernel(con
 
 // launch plan of conv3_wgrad_flat_kernel; returns the number of slabs per channel-block pair (0: shape not taken)
 template <typename T16>
-int64_t flat_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B, int Cin,
-                    int Cout, hipStream_t st, int *rc) {
+int64_t flat_launch(const WgradLaunch &L, int *rc) {
   *rc = DGTTA_OK;
+  const View &xv = L.xv, &yv = L.yv;
+  const int B = L.B, Cin = L.Cin, Cout = L.Cout;
   const int D = yv.D, H = yv.H, W = yv.W;
   if (W > 16 || xv.D != D || xv.H != H || xv.W != W) return 0;
   const int P = W + 2, NCH = cdiv(H * P, 16);
@@ -230,7 +231,7 @@ int64_t flat_launch(const void *x, const View &xv, const void *dy, const View &y
   // slabs per pair: fill the chip once (two workgroups per CU in the non-PIPE form); every slab is 110 KB written and read
   // again, so no more than that
   int64_t want = (int64_t)ncu * (pipe ? 1 : 2) / wgs_y;
-  const int64_t fit = (int64_t)(ws_bytes / ((size_t)pairs * 27 * 1024 * sizeof(float)));
+  const int64_t fit = (int64_t)(L.ws_bytes / ((size_t)pairs * 27 * 1024 * sizeof(float)));
   if (fit < 1) return 0;
   if (want > fit) want = fit;
   if (want < 1) want = 1;
@@ -249,8 +250,8 @@ int64_t flat_launch(const void *x, const View &xv, const void *dy, const View &y
     *rc = DGTTA_ERR_LAUNCH;
     return 0;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nslab, (unsigned)wgs_y), dim3(256), lds, st, (const bf16_t *)x, xv,
-                     (const bf16_t *)dy, yv, slabs, Cin, Cout, cobs, nseg, DR, upw, units, P, NCH, XS, G);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nslab, (unsigned)wgs_y), dim3(256), lds, L.st, (const bf16_t *)L.x, xv,
+                     (const bf16_t *)L.dy, yv, (float *)L.ws, Cin, Cout, cobs, nseg, DR, upw, units, P, NCH, XS, G);
   if (hipGetLastError() != hipSuccess) {
     dgtta_set_error("conv3_wgrad_flat_kernel: launch failed");
     *rc = DGTTA_ERR_LAUNCH;
@@ -261,8 +262,6 @@ int64_t flat_launch(const void *x, const View &xv, const void *dy, const View &y
 
 }  // namespace
 
-int64_t wgrad_flat_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B, int Cin,
-                          int Cout, int dtype, hipStream_t st, int *rc) {
-  return dtype == DGTTA_F16 ? flat_launch<f16_t>(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, st, rc)
-                            : flat_launch<bf16_t>(x, xv, dy, yv, slabs, ws_bytes, B, Cin, Cout, st, rc);
+int64_t wgrad_flat_launch(const WgradLaunch &L, int *rc) {
+  return L.dtype == DGTTA_F16 ? flat_launch<f16_t>(L, rc) : flat_launch<bf16_t>(L, rc);
 }

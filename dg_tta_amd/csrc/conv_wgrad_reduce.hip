@@ -123,19 +123,20 @@ static bool reduce_taps_ok(const Taps *real, const float *dw, int Cin, long long
   return true;
 }
 
-int wgrad_reduce_launch(const float *slabs, float *dw, int Cin, int Cout, const WgradPlan &p, int ncls, int64_t nslab, int accumulate,
-                        const RealTaps &reals, const Taps *dense, long long s_co, long long s_ci, long long s_tap, hipStream_t st) {
+int wgrad_reduce_launch(const WgradLaunch &L, const WgradOut &out, const WgradPlan &p, int ncls, int64_t nslab, const RealTaps &reals) {
+  const float *slabs = (const float *)L.ws;
+  const int Cin = L.Cin, Cout = L.Cout;
   const int64_t rrows = (int64_t)27 * Cin * ((Cout + 31) / 32);
   const int npairs = p.cibs * p.cobs;
   if (nslab >= 64)
-    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3((unsigned)rrows, (unsigned)ncls), dim3(256), 0, st, slabs, dw, Cin, Cout, p.cobs,
-                       npairs, (int)nslab, accumulate, reals, s_co, s_ci, s_tap);
-  else if (reduce_taps_ok(dense, dw, Cin, s_ci, s_tap))
-    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)((Cin / 8) * ((Cout + 31) / 32))), dim3(256), 0, st, slabs, dw, Cin,
-                       Cout, p.cobs, (int)nslab, accumulate, s_co);
+    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3((unsigned)rrows, (unsigned)ncls), dim3(256), 0, L.st, slabs, out.dw, Cin, Cout, p.cobs,
+                       npairs, (int)nslab, out.accumulate, reals, out.s_co, out.s_ci, out.s_tap);
+  else if (reduce_taps_ok(ncls == 1 ? &reals.t[0] : nullptr, out.dw, Cin, out.s_ci, out.s_tap))
+    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)((Cin / 8) * ((Cout + 31) / 32))), dim3(256), 0, L.st, slabs, out.dw, Cin,
+                       Cout, p.cobs, (int)nslab, out.accumulate, out.s_co);
   else
-    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)cdiv64(rrows, 8), (unsigned)ncls), dim3(256), 0, st, slabs, dw, Cin,
-                       Cout, p.cobs, npairs, (int)nslab, accumulate, reals, s_co, s_ci, s_tap);
+    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)cdiv64(rrows, 8), (unsigned)ncls), dim3(256), 0, L.st, slabs, out.dw, Cin,
+                       Cout, p.cobs, npairs, (int)nslab, out.accumulate, reals, out.s_co, out.s_ci, out.s_tap);
   DG_CHECK_LAUNCH("wgrad_reduce_kernel");
   return DGTTA_OK;
 }

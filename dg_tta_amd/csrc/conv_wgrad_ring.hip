@@ -24,9 +24,8 @@
 // four of a wave's seven x operands per row are the previous row's registers; the next iteration's operand reads placed between
 // the MFMAs; ring slots as counters; DMA pieces without branches.  32 -> 32: 0.886 -> 0.80 ms per 8 x 128^3 launch (1155 TFLOP/s),
 // 74 % of the wave time in MFMAs at 1.62 GHz (profiles/r05_ab.txt); DGTTA_WGRAD_RING=6 / =5 select the forms before.
-#include "conv_common.h"
+#include "conv_wgrad_common.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -444,9 +443,11 @@ __global__ __launch_bounds__(WR::NW * 64) void conv3_wgrad_ring_kernel(const bf1
 
 // Entry point used by wgrad_launch_classes (conv_wgrad.hip): plain stride-1 launches with 16-bit storage.  Returns the number
 // of slabs per channel-block pair it wrote (> 0), or 0 if the shape is not this kernel's (then nothing was launched).
-int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, size_t ws_bytes, int B,
-                            int Cin, int Cout, int is_f16, hipStream_t st, int *rc, long long xkh, bool dry) {
+int conv3_wgrad_ring_launch(const WgradLaunch &L, int *rc) {
   *rc = DGTTA_OK;
+  const View &xv = L.xv, &yv = L.yv;
+  const int B = L.B, Cin = L.Cin, Cout = L.Cout;
+  const long long xkh = L.xkh;
   if (Cout % 32 != 0 || xv.D != yv.D || xv.H != yv.H || xv.W != yv.W) return 0;
   if (xkh && (xkh % 8 || xv.sw != 32 || Cin % 32)) return 0;      // channel blocks as planes: dense 32-channel rows
   const int cibs = cdiv(Cin, 32), cobs = Cout / 32;
@@ -481,12 +482,12 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
   const long long njobs = ncol * nseg;
   if (njobs >= (1ll << 31)) return 0;
   if (njobs < G) G = (int)njobs;
-  if (ws_bytes < (size_t)pairs * G * 27 * 1024 * sizeof(float)) return 0;
+  if (L.ws_bytes < (size_t)pairs * G * 27 * 1024 * sizeof(float)) return 0;
   // small problems stay with the many-small-workgroups kernels: a persistent sweep needs a few slices per job to amortise its prologue
   const char sw = dgtta_switches().wgrad_ring;
   if (ncol * yv.D < 4ll * ncu * 8 / pairs && sw != '1' && sw != '5' && sw != '6')
     return 0;      // (=1 / =5 / =6: forced, for the tests; 5 = forced, one tap per MFMA for Cin <= 16 and no operand reuse; 6 = forced, no operand reuse)
-  if (dry) return G;      // (dgtta_conv3d_k3_blocked_supported: would this launch be taken?)
+  if (L.dry) return G;      // (dgtta_conv3d_k3_blocked_supported: would this launch be taken?)
 #define WR_LAUNCH(T16, MF) WR_LAUNCH_P(T16, MF, false, false)
 #define WR_LAUNCH_P(T16, MF, PR, RU)                                                                                           \
   do {                                                                                                                         \
@@ -497,9 +498,9 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
       *rc = DGTTA_ERR_LAUNCH;                                                                                                  \
       return 0;                                                                                                                \
     }                                                                                                                          \
-    hipLaunchKernelGGL(kern, dim3((unsigned)G, (unsigned)pairs), dim3(WR::NW * 64), WR_LDS_TOTAL, st, (const bf16_t *)x, xv,  \
-                       (const bf16_t *)dy, yv, slabs, Cin, Cout, tW, tH, nseg, DR, cobs, (int)njobs, (unsigned)xb, (unsigned)yb, \
-                       xkh);                                                                                                   \
+    hipLaunchKernelGGL(kern, dim3((unsigned)G, (unsigned)pairs), dim3(WR::NW * 64), WR_LDS_TOTAL, L.st, (const bf16_t *)L.x, xv, \
+                       (const bf16_t *)L.dy, yv, (float *)L.ws, Cin, Cout, tW, tH, nseg, DR, cobs, (int)njobs, (unsigned)xb,       \
+                       (unsigned)yb, xkh);                                                                                     \
   } while (0)
   // DGTTA_WGRAD_RING=4: the v_mfma_f32_16x16x32 form (conflict-free after the half swap above; measured within +-2 % of the
   // 32x32x16 form on three boxes, which is the default: 36 registers less and no swizzle)
@@ -507,6 +508,7 @@ int conv3_wgrad_ring_launch(const void *x, const View &xv, const void *dy, const
   // operands shared between neighbouring rows (REUSE; DGTTA_WGRAD_RING=6: its predecessor)
   const bool reuse = !mf16 && sw != '5' && sw != '6';
   // Cin <= 16 (the first layer): two taps per MFMA (DGTTA_WGRAD_RING=5: the one-tap form, its predecessor)
+  const bool is_f16 = L.dtype == DGTTA_F16;
   if (Cin <= 16 && !mf16 && sw != '5') {
     if (is_f16) {
       if (reuse) WR_LAUNCH_P(f16_t, false, true, true);

@@ -487,41 +487,38 @@ __global__ __launch_bounds__(512, 1) void conv3_wgrad_tr8_kernel(const bf16_t *_
 }
 
 template <typename T>
-int mfma_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout, const WgradPlan &p,
-                const WgradClasses &wc, hipStream_t st) {
+int mfma_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc) {
   auto kern = conv3_wgrad_mfma_kernel<T>;
   static DynLdsOnce mf_once;
   DG_REQUIRE(ensure_dyn_lds(mf_once, reinterpret_cast<const void *>(kern), (int)WG<T>::LDS_BYTES) == hipSuccess,
              DGTTA_ERR_LAUNCH, "wgrad_mfma: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(kern, dim3((unsigned)p.units, (unsigned)(p.cibs * p.cobs), (unsigned)wc.n), dim3(256), WG<T>::LDS_BYTES,
-                     st, (const T *)x, xv, (const T *)dy, yv, slabs, Cin, Cout, p.tW, p.tH, p.nsd, p.DR, p.cobs, wc);
+                     L.st, (const T *)L.x, L.xv, (const T *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW, p.tH, p.nsd, p.DR, p.cobs, wc);
   DG_CHECK_LAUNCH("conv3_wgrad_mfma_kernel");
   return DGTTA_OK;
 }
 
 template <typename T16>
-int tr_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout, const WgradPlan &p,
-              const WgradClasses &wc, bool plain, int upw, int64_t nslab, hipStream_t st) {
+int tr_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab) {
   auto ktr = plain ? conv3_wgrad_tr_kernel<false, T16> : conv3_wgrad_tr_kernel<true, T16>;
   static DynLdsOnce tr_once[2];
   DG_REQUIRE(ensure_dyn_lds(tr_once[plain], reinterpret_cast<const void *>(ktr), (int)WT::LDS_BYTES) == hipSuccess,
              DGTTA_ERR_LAUNCH, "wgrad_tr: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(ktr, dim3((unsigned)nslab, (unsigned)(p.cibs * p.cobs), (unsigned)wc.n), dim3(256), WT::LDS_BYTES,
-                     st, (const bf16_t *)x, xv, (const bf16_t *)dy, yv, slabs, Cin, Cout, p.tW, p.tH, p.nsd,
+                     L.st, (const bf16_t *)L.x, L.xv, (const bf16_t *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW, p.tH, p.nsd,
                      p.DR, p.cobs, wc, upw, (int)p.units, dgtta_switches().wgrad_xcd != '0');
   DG_CHECK_LAUNCH("conv3_wgrad_tr_kernel");
   return DGTTA_OK;
 }
 
 template <typename T16>
-int tr8_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout, const WgradPlan &p,
-               int upw, int64_t nslab, hipStream_t st) {
+int tr8_launch(const WgradLaunch &L, const WgradPlan &p, int upw, int64_t nslab) {
   static DynLdsOnce a8;
   DG_REQUIRE(ensure_dyn_lds(a8, reinterpret_cast<const void *>(conv3_wgrad_tr8_kernel<T16>), (int)WT8::LDS_BYTES) ==
                  hipSuccess, DGTTA_ERR_LAUNCH, "wgrad_tr8: cannot raise the dynamic LDS limit");
   const int64_t gy = (int64_t)p.cibs * ((p.cobs + 1) / 2);
   hipLaunchKernelGGL(conv3_wgrad_tr8_kernel<T16>, dim3((unsigned)nslab, (unsigned)gy), dim3(512),
-                     WT8::LDS_BYTES, st, (const bf16_t *)x, xv, (const bf16_t *)dy, yv, slabs, Cin, Cout, p.tW, p.tH,
+                     WT8::LDS_BYTES, L.st, (const bf16_t *)L.x, L.xv, (const bf16_t *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW, p.tH,
                      p.nsd, p.DR, p.cobs, upw, (int)p.units, dgtta_switches().wgrad_xcd != '0');
   DG_CHECK_LAUNCH("conv3_wgrad_tr8_kernel");
   return DGTTA_OK;
@@ -529,21 +526,15 @@ int tr8_launch(const void *x, const View &xv, const void *dy, const View &yv, fl
 
 }  // namespace
 
-int conv3_wgrad_mfma_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                            const WgradPlan &p, const WgradClasses &wc, int dtype, hipStream_t st) {
-  if (dtype == DGTTA_F32) return mfma_launch<float>(x, xv, dy, yv, slabs, Cin, Cout, p, wc, st);
-  if (dtype == DGTTA_F16) return mfma_launch<f16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, wc, st);
-  return mfma_launch<bf16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, wc, st);
+int conv3_wgrad_mfma_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc) {
+  if (L.dtype == DGTTA_F32) return mfma_launch<float>(L, p, wc);
+  return L.dtype == DGTTA_F16 ? mfma_launch<f16_t>(L, p, wc) : mfma_launch<bf16_t>(L, p, wc);
 }
 
-int conv3_wgrad_tr_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                          const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab, int dtype, hipStream_t st) {
-  return dtype == DGTTA_F16 ? tr_launch<f16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, wc, plain, upw, nslab, st)
-                            : tr_launch<bf16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, wc, plain, upw, nslab, st);
+int conv3_wgrad_tr_launch(const WgradLaunch &L, const WgradPlan &p, const WgradClasses &wc, bool plain, int upw, int64_t nslab) {
+  return L.dtype == DGTTA_F16 ? tr_launch<f16_t>(L, p, wc, plain, upw, nslab) : tr_launch<bf16_t>(L, p, wc, plain, upw, nslab);
 }
 
-int conv3_wgrad_tr8_launch(const void *x, const View &xv, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                           const WgradPlan &p, int upw, int64_t nslab, int dtype, hipStream_t st) {
-  return dtype == DGTTA_F16 ? tr8_launch<f16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, upw, nslab, st)
-                            : tr8_launch<bf16_t>(x, xv, dy, yv, slabs, Cin, Cout, p, upw, nslab, st);
+int conv3_wgrad_tr8_launch(const WgradLaunch &L, const WgradPlan &p, int upw, int64_t nslab) {
+  return L.dtype == DGTTA_F16 ? tr8_launch<f16_t>(L, p, upw, nslab) : tr8_launch<bf16_t>(L, p, upw, nslab);
 }

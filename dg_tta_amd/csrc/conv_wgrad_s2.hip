@@ -281,20 +281,19 @@ __global__ __launch_bounds__(512, 2) void conv3_wgrad_tr_s2x_kernel(const bf16_t
 }
 
 template <typename T16>
-int s2_launch(const void *x, const View &xfull, const void *dy, const View &yv, float *slabs, int Cin, int Cout, const WgradPlan &p,
-              bool two_blocks, hipStream_t st) {
+int s2_launch(const WgradLaunch &L, const WgradPlan &p, bool two_blocks) {
   static DynLdsOnce once, once_x;
   if (two_blocks) {
     DG_REQUIRE(ensure_dyn_lds(once_x, reinterpret_cast<const void *>(conv3_wgrad_tr_s2x_kernel<T16>), (int)WT2X::LDS_BYTES) ==
                    hipSuccess, DGTTA_ERR_LAUNCH, "wgrad_tr_s2x: cannot raise the dynamic LDS limit");
     hipLaunchKernelGGL(conv3_wgrad_tr_s2x_kernel<T16>, dim3((unsigned)p.units, (unsigned)(p.cibs * (p.cobs / 2))), dim3(512),
-                       WT2X::LDS_BYTES, st, (const bf16_t *)x, xfull, (const bf16_t *)dy, yv, slabs, Cin, Cout, p.tW,
+                       WT2X::LDS_BYTES, L.st, (const bf16_t *)L.x, L.xv, (const bf16_t *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW,
                        p.tH, p.nsd, p.DR, p.cobs);
   } else {
     DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(conv3_wgrad_tr_s2_kernel<T16>), (int)WT2::LDS_BYTES) ==
                    hipSuccess, DGTTA_ERR_LAUNCH, "wgrad_tr_s2: cannot raise the dynamic LDS limit");
     hipLaunchKernelGGL(conv3_wgrad_tr_s2_kernel<T16>, dim3((unsigned)p.units, (unsigned)(p.cibs * p.cobs)), dim3(256),
-                       WT2::LDS_BYTES, st, (const bf16_t *)x, xfull, (const bf16_t *)dy, yv, slabs, Cin, Cout, p.tW,
+                       WT2::LDS_BYTES, L.st, (const bf16_t *)L.x, L.xv, (const bf16_t *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW,
                        p.tH, p.nsd, p.DR, p.cobs);
   }
   DG_CHECK_LAUNCH("conv3_wgrad_tr_s2_kernel");
@@ -303,8 +302,6 @@ int s2_launch(const void *x, const View &xfull, const void *dy, const View &yv, 
 
 }  // namespace
 
-int conv3_wgrad_s2_launch(const void *x, const View &xfull, const void *dy, const View &yv, float *slabs, int Cin, int Cout,
-                          const WgradPlan &p, bool two_blocks, int dtype, hipStream_t st) {
-  return dtype == DGTTA_F16 ? s2_launch<f16_t>(x, xfull, dy, yv, slabs, Cin, Cout, p, two_blocks, st)
-                            : s2_launch<bf16_t>(x, xfull, dy, yv, slabs, Cin, Cout, p, two_blocks, st);
+int conv3_wgrad_s2_launch(const WgradLaunch &L, const WgradPlan &p, bool two_blocks) {
+  return L.dtype == DGTTA_F16 ? s2_launch<f16_t>(L, p, two_blocks) : s2_launch<bf16_t>(L, p, two_blocks);
 }

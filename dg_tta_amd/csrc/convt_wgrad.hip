@@ -189,98 +189,68 @@ __global__ __launch_bounds__(256) void convT_bias_finalize_kernel(const float *_
 }  // namespace
 
 // ConvTranspose3d with kernel = stride (sd, sh, sw): dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[s v + o][co], one single-tap class
-// per output offset o = (od * sh + oh) * sw + ow (the dout lattice at that offset)
-static int convT_wgrad_classes(const void *x, const View &xv, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
-                               int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype,
-                               hipStream_t st) {
+// per output offset o = (od * sh + oh) * sw + ow (the dout lattice at that offset).  L.xv: the input lattice, L.yv: dout at full
+// resolution
+static int convT_wgrad_classes(const WgradLaunch &L, float *dw_t, int sd, int sh, int sw, int accumulate) {
   const int no = sd * sh * sw;
-  WgradClasses wc;
+  WgradLaunch C = L;
+  WgradClasses wc{};
   RealTaps reals;
   wc.n = no;
-  View yv{};
   for (int o = 0; o < no; ++o) {
-    long long off;
-    yv = lattice_view(sd * Di, sh * Hi, sw * Wi, lddo, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
-                      sw == 2 ? o % 2 : 0, &off);
-    wc.xoff[o] = 0;
-    wc.yoff[o] = off;
+    C.yv = lattice_view(L.yv.D, L.yv.H, L.yv.W, (int)L.yv.sw, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
+                        sw == 2 ? o % 2 : 0, &wc.yoff[o]);
     wc.mask[o] = 1u << 13;
     for (int t = 0; t < 27; ++t) reals.t[o].wt[t] = -1;
     reals.t[o].wt[13] = (signed char)o;
   }
-  return wgrad_launch_classes(x, xv, dout, yv, dw_t, ws, ws_bytes, B, Cin, Cout, wc, reals, no, (long long)Cout * no, 1, accumulate,
-                              dtype, st);
+  return wgrad_launch_classes(C, WgradOut{dw_t, no, (long long)L.Cout * no, 1, accumulate}, wc, reals);
 }
 
 // one-pass kernel with NCI input-channel blocks per workgroup; bp: room for the bias partials or nullptr
 template <typename T16, int NCI>
-static int convT_tr_launch(const void *x, const View &xv, const void *dout, const View &yfull, float *slabs, int Cin, int Cout,
-                           const WgradPlan &p, float *bp, hipStream_t st) {
+static int convT_tr_launch(const WgradLaunch &L, const WgradPlan &p, float *bp) {
   static DynLdsOnce once;
   DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(convT_wgrad_tr_kernel<T16, NCI>), (int)WT3<NCI>::LDS_BYTES) ==
                  hipSuccess, DGTTA_ERR_LAUNCH, "convT_wgrad_tr: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL((convT_wgrad_tr_kernel<T16, NCI>), dim3((unsigned)p.units, (unsigned)(cdiv(p.cibs, NCI) * p.cobs)), dim3(256),
-                     WT3<NCI>::LDS_BYTES, st, (const bf16_t *)x, xv, (const bf16_t *)dout, yfull, slabs, Cin, Cout, p.tW, p.tH,
-                     p.nsd, p.DR, p.cobs, p.cibs, bp);
+                     WT3<NCI>::LDS_BYTES, L.st, (const bf16_t *)L.x, L.xv, (const bf16_t *)L.dy, L.yv, (float *)L.ws, L.Cin, L.Cout, p.tW,
+                     p.tH, p.nsd, p.DR, p.cobs, p.cibs, bp);
   DG_CHECK_LAUNCH("convT_wgrad_tr_kernel");
   return DGTTA_OK;
 }
 
-// ConvTranspose3d k2 s2 weight gradient: dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[2v+o][co]  (one pass, or 8 single-tap launches)
-static int convT_wgrad(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
-                       int Cin, int Cout, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st, float *bias_part,
-                       size_t bias_part_bytes, int *bias_units) {
+// ConvTranspose3d k2 s2 weight gradient: dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[2v+o][co]  (one pass, or 8 single-tap launches).
+// L.xv: the input lattice, L.yv: dout at full resolution
+static int convT_wgrad(const WgradLaunch &L, float *dw_t, int accumulate, float *bias_part, size_t bias_part_bytes, int *bias_units) {
   if (bias_units) *bias_units = 0;
-  const View xv = dense_view(B, Di, Hi, Wi, ldx);
-  if (dtype != DGTTA_F32) {
+  if (L.dtype != DGTTA_F32) {
     const int one = dgtta_switches().convt_wgrad_onepass;      // DGTTA_CONVT_WGRAD_ONEPASS=0 (tests): the 8-class launch
-    const View yfull = dense_view(B, 2 * Di, 2 * Hi, 2 * Wi, lddo);
-    WgradPlan p = wgrad_plan(B, Cin, Cout, Di, Hi, Wi, 1, WT2::TWO, WT2::TH);      // same tile shape (2 rows x 16 voxels) on the input lattice
-    const size_t need = (size_t)p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
-    const bool ok = Cout % 8 == 0 && ldx % 8 == 0 && lddo % 8 == 0 && !((uintptr_t)x & 15) && !((uintptr_t)dout & 15) &&
-                    ldx >= (Cin + 7) / 8 * 8 && ws_bytes >= need && p.units < (1ll << 31) && p.cibs * p.cobs <= 65535;
-    if (ok && one != '0') {
+    WgradPlan p = wgrad_plan(L.B, L.Cin, L.Cout, L.xv.D, L.xv.H, L.xv.W, 1, WT2::TWO, WT2::TH);      // same tile shape (2 rows x 16 voxels) on the input lattice
+    if (wgrad_onepass_ok(L, p) && one != '0') {
       // bias partials [unit][32 cobs] ride along when the caller offers room for them
       float *bp = (bias_part && bias_units && bias_part_bytes >= (size_t)p.units * p.cobs * 32 * sizeof(float)) ? bias_part : nullptr;
       if (bp) *bias_units = (int)p.units;
-      const bool f16 = dtype == DGTTA_F16;
+      const bool f16 = L.dtype == DGTTA_F16;
       int rc;
       if (p.cibs >= 2)      // two input-channel blocks share a dout tile
-        rc = f16 ? convT_tr_launch<f16_t, 2>(x, xv, dout, yfull, (float *)ws, Cin, Cout, p, bp, st)
-                 : convT_tr_launch<bf16_t, 2>(x, xv, dout, yfull, (float *)ws, Cin, Cout, p, bp, st);
+        rc = f16 ? convT_tr_launch<f16_t, 2>(L, p, bp) : convT_tr_launch<bf16_t, 2>(L, p, bp);
       else
-        rc = f16 ? convT_tr_launch<f16_t, 1>(x, xv, dout, yfull, (float *)ws, Cin, Cout, p, bp, st)
-                 : convT_tr_launch<bf16_t, 1>(x, xv, dout, yfull, (float *)ws, Cin, Cout, p, bp, st);
+        rc = f16 ? convT_tr_launch<f16_t, 1>(L, p, bp) : convT_tr_launch<bf16_t, 1>(L, p, bp);
       if (rc != DGTTA_OK) return rc;
       RealTaps rt;
       for (int t = 0; t < 27; ++t) rt.t[0].wt[t] = (signed char)(t < 8 ? t : -1);      // slab tap slot o -> dw_t[..][o]
       // (dw_t[ci][co][8] is not the dense 27-tap layout, so this ends in the row kernels)
-      return wgrad_reduce_launch((const float *)ws, dw_t, Cin, Cout, p, 1, p.units, accumulate, rt, &rt.t[0], 8, (long long)Cout * 8, 1, st);
+      return wgrad_reduce_launch(L, WgradOut{dw_t, 8, (long long)L.Cout * 8, 1, accumulate}, p, 1, p.units, rt);
     }
   }
-  return convT_wgrad_classes(x, xv, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, accumulate, dtype, st);
+  return convT_wgrad_classes(L, dw_t, 2, 2, 2, accumulate);
 }
 
-// fp32 transposed-conv weight gradient as six launches of the 16-bit kernel on exact three-term bf16 splits (see
-// wgrad_conv_f32_split in conv_wgrad.hip): extra bytes behind the slab region = 3 planes of x (input lattice) and 3 of dout (output lattice)
+// fp32 transposed-conv weight gradient as six launches of the 16-bit kernel on exact three-term bf16 splits (wgrad_f32_split,
+// conv_wgrad.hip): extra bytes behind the slab region = 3 planes of x (input lattice) and 3 of dout (output lattice)
 size_t convT_wgrad_split_extra_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi) {
   return 3 * wgrad_split_plane_bytes(B, Cin, Di, Hi, Wi) + 3 * wgrad_split_plane_bytes(B, Cout, 2 * Di, 2 * Hi, 2 * Wi);
-}
-
-static int convT_wgrad_f32_split(const float *x, int ldx, const float *dout, int lddo, float *dw_t, void *ws, size_t slab_bytes,
-                                 void *planes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int accumulate, hipStream_t st) {
-  const int ldxs = (Cin + 7) / 8 * 8, ldys = (Cout + 7) / 8 * 8;
-  const int64_t rows_x = (int64_t)B * Di * Hi * Wi, rows = rows_x * 8;
-  bf16_t *xs[3], *gs[3];
-  int rc = wgrad_split_planes(x, ldx, Cin, rows_x, wgrad_split_plane_bytes(B, Cin, Di, Hi, Wi), dout, lddo, Cout, rows,
-                              wgrad_split_plane_bytes(B, Cout, 2 * Di, 2 * Hi, 2 * Wi), planes, xs, gs, st);
-  if (rc != DGTTA_OK) return rc;
-  for (int q = 0; q < 6; ++q) {
-    rc = convT_wgrad(xs[WGRAD_SPLIT_PAIRS[q][0]], ldxs, gs[WGRAD_SPLIT_PAIRS[q][1]], ldys, dw_t, ws, slab_bytes, B, Cin, Cout,
-                     Di, Hi, Wi, (accumulate || q > 0) ? 1 : 0, DGTTA_BF16, st, nullptr, 0, nullptr);
-    if (rc != DGTTA_OK) return rc;        // (q == 0: nothing written yet, the caller falls back to the fp32 kernel)
-  }
-  return DGTTA_OK;
 }
 
 // bias_part / bias_units (optional): room for [units][ceil(Cout / 32) * 32] floats; *bias_units > 0 on return means the launch left
@@ -289,20 +259,24 @@ int convT_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *
                      int Cin, int Cout, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st, float *bias_part,
                      size_t bias_part_bytes, int *bias_units) {
   if (bias_units) *bias_units = 0;
+  const View xv = dense_view(B, Di, Hi, Wi, ldx), yfull = dense_view(B, 2 * Di, 2 * Hi, 2 * Wi, lddo);
+  const WgradLaunch L{x, xv, dout, yfull, B, Cin, Cout, dtype, ws, ws_bytes, st};
   if (dtype == DGTTA_F32) {
     // the caller offered the split workspace (dgtta_convT3d_bwd_split_ws_bytes): six 16-bit launches (DGTTA_WGRAD_F32_SPLIT=0: never)
     const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, Di, Hi, Wi), 256);
-    if (Cout % 8 == 0 && dgtta_switches().wgrad_f32_split != '0' &&
-        ws_bytes >= slab + convT_wgrad_split_extra_bytes(B, Cin, Cout, Di, Hi, Wi)) {
-      const int rc = convT_wgrad_f32_split((const float *)x, ldx, (const float *)dout, lddo, dw_t, ws, slab, (char *)ws + slab, B, Cin,
-                                           Cout, Di, Hi, Wi, accumulate, st);
-      if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
-    }
-    return convT_wgrad(x, ldx, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, accumulate, dtype, st, nullptr, 0, nullptr);
+    const SplitOperand sx{(const float *)x, ldx, Cin, B, Di, Hi, Wi}, sy{(const float *)dout, lddo, Cout, B, 2 * Di, 2 * Hi, 2 * Wi};
+    const int rc = wgrad_f32_split(sx, sy, ws, ws_bytes, slab, accumulate, st,
+                                   [&](const bf16_t *xs, int ldxs, const bf16_t *gs, int ldys, int acc) {
+      WgradLaunch leg = L;
+      leg.x = xs, leg.xv = dense_view(B, Di, Hi, Wi, ldxs), leg.dy = gs, leg.yv = dense_view(B, 2 * Di, 2 * Hi, 2 * Wi, ldys);
+      leg.dtype = DGTTA_BF16, leg.ws_bytes = slab;
+      return convT_wgrad(leg, dw_t, acc, nullptr, 0, nullptr);
+    });
+    if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
+    return convT_wgrad(L, dw_t, accumulate, nullptr, 0, nullptr);
   }
   if (!wgrad_dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;
-  return convT_wgrad(x, ldx, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, accumulate, dtype, st, bias_part,
-                     bias_part_bytes, bias_units);
+  return convT_wgrad(L, dw_t, accumulate, bias_part, bias_part_bytes, bias_units);
 }
 
 int convT_bias_finalize(const float *part, int units, int Cout, float *db, int accumulate, hipStream_t st) {
@@ -315,6 +289,7 @@ int convT_bias_finalize(const float *part, int units, int Cout, float *db, int a
 int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
                       int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
   if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Di, Hi, Wi, sd * sh * sw)) return DGTTA_ERR_WORKSPACE;
-  const View xv = dense_view(B, Di, Hi, Wi, ldx);
-  return convT_wgrad_classes(x, xv, dout, lddo, dw_t, ws, ws_bytes, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, accumulate, dtype, st);
+  const View xv = dense_view(B, Di, Hi, Wi, ldx), yfull = dense_view(B, sd * Di, sh * Hi, sw * Wi, lddo);
+  const WgradLaunch L{x, xv, dout, yfull, B, Cin, Cout, dtype, ws, ws_bytes, st};
+  return convT_wgrad_classes(L, dw_t, sd, sh, sw, accumulate);
 }

@@ -116,14 +116,15 @@ int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *
   if (rows % 128 || rows / 128 >= (1ll << 30)) return DGTTA_ERR_UNSUPPORTED;
   const int D = (int)(rows / 128);
   if (ws_bytes < head_wgrad_mfma_ws_bytes(Cin, nsel, rows)) return DGTTA_ERR_UNSUPPORTED;
+  // the class kernels' form: one class with the centre tap alone over the folded rows, reduced into dw[k][ci]
   Taps real;
   for (int t = 0; t < 27; ++t) real.wt[t] = -1;
   real.wt[13] = 0;
-  const View xv = dense_view(1, D, 4, 32, ldx);
-  if (dtype == DGTTA_F32) {
-    const View yv = dense_view(1, D, 4, 32, lddo);
-    return wgrad_launch(x, xv, dout, yv, dw_sel, ws, ws_bytes, 1, Cin, nsel, 1u << 13, real, Cin, 1, 0, accumulate, dtype, st);
-  }
+  RealTaps reals;
+  const WgradClasses wc = wgrad_single_class(1u << 13, real, &reals);
+  const WgradOut out{dw_sel, Cin, 1, 0, accumulate};
+  WgradLaunch L{x, dense_view(1, D, 4, 32, ldx), dout, dense_view(1, D, 4, 32, lddo), 1, Cin, nsel, dtype, ws, ws_bytes, st};
+  if (dtype == DGTTA_F32) return wgrad_launch_classes(L, out, wc, reals);
   if (dtype == DGTTA_BF16 || dtype == DGTTA_F16) {
     const size_t cbytes = align_up((size_t)rows * nsel * 2, 256);
     unsigned short *d16 = (unsigned short *)ws;
@@ -159,9 +160,9 @@ int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *
       DG_CHECK_LAUNCH("pointwise_wgrad_finalize_kernel");
       return DGTTA_OK;
     }
-    const View yv = dense_view(1, D, 4, 32, nsel);
-    return wgrad_launch(x, xv, d16, yv, dw_sel, (char *)ws + cbytes, ws_bytes - cbytes, 1, Cin, nsel, 1u << 13, real, Cin, 1, 0,
-                        accumulate, dtype, st);
+    L.dy = d16, L.yv = dense_view(1, D, 4, 32, nsel);      // the 16-bit copy; slabs behind it
+    L.ws = (char *)ws + cbytes, L.ws_bytes = ws_bytes - cbytes;
+    return wgrad_launch_classes(L, out, wc, reals);
   }
   return DGTTA_ERR_UNSUPPORTED;
 }
