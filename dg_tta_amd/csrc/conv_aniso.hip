@@ -276,16 +276,9 @@ int run_conva_dt(int dtype, const ConvLaunch &L, const ConvClasses &cs, int kd, 
   DISPATCH_T(dtype, return run_conva<T>(L, cs, kd, sd, sh, sw));
 }
 
-bool stride_ok(int s) { return s == 1 || s == 2; }
-bool kernel_ok(int kd, int sd, int sh, int sw) { return (kd == 1 || kd == 3) && stride_ok(sd) && stride_ok(sh) && stride_ok(sw); }
-bool dims_ok(int B, int Cin, int Cout, int D, int H, int W) {
-  return B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0 && Cin <= (1 << 16) && Cout <= (1 << 16);
-}
-
-bool convt_strides_ok(int sd, int sh, int sw) { return stride_ok(sd) && stride_ok(sh) && stride_ok(sw) && sd * sh * sw > 1; }
-
 }  // namespace
 
+// (the shared checks of conv_api.h with cap: this family bounds the channel counts at 2^16)
 extern "C" size_t dgtta_conv3d_kpacked_bytes(int kd, int CinP, int CoutP, int dtype) {
   if ((kd != 1 && kd != 3) || CinP <= 0 || CoutP <= 0 || CinP > (1 << 16) || CoutP > (1 << 16) || !dtype_ok(dtype)) return 0;
   return (size_t)kd * 9 * ((size_t)CinP * n32(CoutP) + (size_t)CoutP * n32(CinP)) * esize(dtype);
@@ -301,143 +294,130 @@ extern "C" int dgtta_conv3d_kpack_weights(const float *w_t, void *wpack, int kd,
   DG_REQUIRE(dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED, "conv3d_kpack_weights: dtype %d", dtype);
   DG_REQUIRE(CinP % conv_granule(dtype) == 0 && CoutP % conv_granule(dtype) == 0, DGTTA_ERR_BADARG,
              "conv3d_kpack_weights: padded channel counts must be multiples of %d", conv_granule(dtype));
-  return conv_pack_images(w_t, wpack, kd * 9, Cin, Cout, CinP, CoutP, dtype, (hipStream_t)stream);
+  const ConvProblem P{0, Cin, Cout, CinP, CoutP, 0, 0, 0, kd, 1, 1, 1, dtype, (hipStream_t)stream};
+  return conv_pack_images(P, w_t, wpack);
 }
 
 extern "C" int dgtta_conv3d_fwd(const void *x, int ldx, const void *wpack, const float *bias, void *y, int ldy, void *stats, int B,
                                 int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw,
                                 int dtype, void *stream) {
-  DG_REQUIRE(x && wpack && y, DGTTA_ERR_BADARG, "conv3d_fwd: null pointer");
-  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && CinP >= Cin && CoutP >= Cout, DGTTA_ERR_BADARG, "conv3d_fwd: bad dims");
-  DG_REQUIRE(ldx >= Cin && ldy >= Cout, DGTTA_ERR_BADARG, "conv3d_fwd: ld < C");
-  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_fwd: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
+  static const char fn[] = "conv3d_fwd";
+  const ConvProblem P{B, Cin, Cout, CinP, CoutP, Di, Hi, Wi, kd, sd, sh, sw, dtype, (hipStream_t)stream};
+  CONV_REQUIRE_PTRS(fn, x && wpack && y);
+  CONV_REQUIRE_DIMS(fn, P, true, true);
+  CONV_REQUIRE_LD(fn, ldx >= Cin && ldy >= Cout);
+  CONV_REQUIRE_KERNEL(fn, P);
   DG_REQUIRE(operand_ok(epv_of(dtype), x, ldx, Cin, CinP), DGTTA_ERR_UNSUPPORTED,
              "conv3d_fwd: x must be 16-byte aligned with rows of whole 16 bytes, CinP a multiple of %d", conv_granule(dtype));
-  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
   Taps taps;
-  for (int t = 0; t < 27; ++t) taps.wt[t] = (signed char)(t < kd * 9 ? t : -1);
-  const ConvLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), wpack, bias, y, dense_view(B, Do, Ho, Wo, ldy), B, Cin, Cout, CinP, CoutP,
-                     (double *)stats, kd * 9, (hipStream_t)stream};
+  for (int t = 0; t < 27; ++t) taps.wt[t] = (signed char)(t < P.ntaps() ? t : -1);
+  const ConvLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), wpack, bias, y, dense_view(B, P.Do(), P.Ho(), P.Wo(), ldy), B, Cin, Cout, CinP,
+                     CoutP, (double *)stats, P.ntaps(), P.st};
   return run_conva_dt(dtype, L, single_class(taps, 0), kd, sd, sh, sw);
 }
 
 extern "C" int dgtta_conv3d_dgrad(const void *dy, int lddy, const void *wpack, void *dx, int lddx, int B, int Cin, int Cout, int CinP,
                                   int CoutP, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype,
                                   void *stream) {
-  DG_REQUIRE(dy && wpack && dx, DGTTA_ERR_BADARG, "conv3d_dgrad: null pointer");
-  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && CinP >= Cin && CoutP >= Cout, DGTTA_ERR_BADARG, "conv3d_dgrad: bad dims");
-  DG_REQUIRE(lddx >= Cin && lddy >= Cout, DGTTA_ERR_BADARG, "conv3d_dgrad: ld < C");
-  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_dgrad: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
-  DG_REQUIRE((sd == 1 || Di % 2 == 0) && (sh == 1 || Hi % 2 == 0) && (sw == 1 || Wi % 2 == 0), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_dgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
+  static const char fn[] = "conv3d_dgrad";
+  const ConvProblem P{B, Cin, Cout, CinP, CoutP, Di, Hi, Wi, kd, sd, sh, sw, dtype, (hipStream_t)stream};
+  CONV_REQUIRE_PTRS(fn, dy && wpack && dx);
+  CONV_REQUIRE_DIMS(fn, P, true, true);
+  CONV_REQUIRE_LD(fn, lddx >= Cin && lddy >= Cout);
+  CONV_REQUIRE_KERNEL(fn, P);
+  CONV_REQUIRE_EVEN(fn, P);
   DG_REQUIRE(operand_ok(epv_of(dtype), dy, lddy, Cout, CoutP), DGTTA_ERR_UNSUPPORTED,
              "conv3d_dgrad: dy must be 16-byte aligned with rows of whole 16 bytes, CoutP a multiple of %d", conv_granule(dtype));
-  const int ntaps = kd * 9;
-  const void *imgB = (const char *)wpack + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
-  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
+  const void *imgB = (const char *)wpack + (size_t)P.ntaps() * CinP * n32(CoutP) * esize(dtype);
   // one stride-1 class per parity of the strided axes
   View yv;
-  const ConvClasses cs = dgrad_parity_classes(kd, sd, sh, sw, Di, Hi, Wi, lddx, accumulate, &yv);
-  const ConvLaunch L{dy, dense_view(B, Do, Ho, Wo, lddy), imgB, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, ntaps,
-                     (hipStream_t)stream};
+  const ConvClasses cs = dgrad_parity_classes(P, lddx, accumulate, &yv);
+  const ConvProblem G = dgrad_as_fwd(P);
+  const ConvLaunch L{dy, dense_view(B, P.Do(), P.Ho(), P.Wo(), lddy), imgB, nullptr, dx, yv, B, G.Cin, G.Cout, G.CinP, G.CoutP, nullptr,
+                     P.ntaps(), P.st};
   return run_conva_dt(dtype, L, cs, kd, 1, 1, 1);
 }
 
-// workspace: [bias partials][weight-gradient slabs]
+// workspace: [bias partials][weight-gradient slabs] (conv_wgrad_ws_layout)
 extern "C" size_t dgtta_conv3d_kwgrad_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw) {
-  if (!dims_ok(B, Cin, Cout, Di, Hi, Wi) || !kernel_ok(kd, sd, sh, sw)) return 0;
-  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
-  return align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256) +
-         align_up(conva_wgrad_ws_bytes(B, Cin, Cout, Do, Ho, Wo), 256);
+  const ConvProblem P{B, Cin, Cout, Cin, Cout, Di, Hi, Wi, kd, sd, sh, sw, DGTTA_F32, nullptr};
+  if (!conv_dims_ok(P, true) || !kernel_ok(P)) return 0;
+  return conv_wgrad_ws_layout(P, true).total();
 }
 
 extern "C" int dgtta_conv3d_wgrad(const void *x, int ldx, const void *dy, int lddy, float *dw_t, float *db, void *ws, size_t ws_bytes,
                                   int B, int Cin, int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate,
                                   int dtype, void *stream) {
-  DG_REQUIRE(x && dy && dw_t && ws, DGTTA_ERR_BADARG, "conv3d_wgrad: null pointer");
-  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && lddy >= Cout, DGTTA_ERR_BADARG, "conv3d_wgrad: bad dims");
-  DG_REQUIRE(kernel_ok(kd, sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_wgrad: kernel %dx3x3, stride (%d,%d,%d), dtype %d not supported", kd, sd, sh, sw, dtype);
-  DG_REQUIRE((sd == 1 || Di % 2 == 0) && (sh == 1 || Hi % 2 == 0) && (sw == 1 || Wi % 2 == 0), DGTTA_ERR_UNSUPPORTED,
-             "conv3d_wgrad: strided axes need even input extents (%dx%dx%d)", Di, Hi, Wi);
-  DG_REQUIRE(ws_bytes >= dgtta_conv3d_kwgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi, kd, sd, sh, sw), DGTTA_ERR_WORKSPACE,
-             "conv3d_wgrad: workspace too small");
-  const int Do = out_dim(Di, sd, kd), Ho = out_dim(Hi, sh, 3), Wo = out_dim(Wi, sw, 3);
-  const size_t bias_bytes = align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Do * Ho * Wo), 256);
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = conva_wgrad_mfma(x, ldx, dy, lddy, dw_t, (char *)ws + bias_bytes, ws_bytes - bias_bytes, B, Cin, Cout, Di, Hi, Wi,
-                                  kd, sd, sh, sw, accumulate, dtype, st);
+  static const char fn[] = "conv3d_wgrad";
+  const ConvProblem P{B, Cin, Cout, Cin, Cout, Di, Hi, Wi, kd, sd, sh, sw, dtype, (hipStream_t)stream};
+  CONV_REQUIRE_PTRS(fn, x && dy && dw_t && ws);
+  CONV_REQUIRE_DIMS(fn, P, true, ldx >= Cin && lddy >= Cout);
+  CONV_REQUIRE_KERNEL(fn, P);
+  CONV_REQUIRE_EVEN(fn, P);
+  const ConvWsLayout lay = conv_wgrad_ws_layout(P, true);
+  CONV_REQUIRE_WS(fn, ws_bytes, lay.total());
+  const int rc = conva_wgrad_mfma(P, Src{x, ldx}, Src{dy, lddy}, dw_t, lay.main_of(ws, ws_bytes), accumulate);
   if (rc == DGTTA_ERR_UNSUPPORTED)
     dgtta_set_error("conv3d_wgrad: operands not taken by the MFMA kernel (16-byte aligned rows, Cout a multiple of %d)",
                     dtype == DGTTA_F32 ? 4 : 8);
   if (rc != DGTTA_OK) return rc;
-  if (db) return conv_bias_grad(dy, lddy, db, ws, B, Cout, (int64_t)Do * Ho * Wo, accumulate, dtype, st);
+  if (db) return conv_bias_grad(dy, lddy, db, ws, B, Cout, P.out_vox(), accumulate, dtype, P.st);
   return DGTTA_OK;
 }
 
 // ---- ConvTranspose3d with kernel = stride (sd, sh, sw) in {1, 2}^3, not all 1:
 //      out[b][s*v + o][co] = bias[co] + sum_ci x[b][v][ci] w[ci][co][o]
 extern "C" size_t dgtta_convT3d_s_fwd_ws_bytes(int Cin, int Cout, int sd, int sh, int sw, int dtype) {
-  if (Cin <= 0 || Cout <= 0 || Cin > (1 << 16) || Cout > (1 << 16) || !convt_strides_ok(sd, sh, sw) || !dtype_ok(dtype)) return 0;
+  const ConvProblem P{1, Cin, Cout, Cin, Cout, 1, 1, 1, sd, sd, sh, sw, dtype, nullptr};
+  if (!conv_dims_ok(P, true) || !convt_strides_ok(P) || !dtype_ok(dtype)) return 0;
   return convT_pack_region(Cin, Cout, dtype);
 }
 
 extern "C" int dgtta_convT3d_s_fwd(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws,
                                    size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype,
                                    void *stream) {
-  DG_REQUIRE(x && w_t && out && ws, DGTTA_ERR_BADARG, "convT3d_s_fwd: null pointer");
-  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && ldo >= Cout, DGTTA_ERR_BADARG, "convT3d_s_fwd: bad dims");
-  DG_REQUIRE(convt_strides_ok(sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
-             "convT3d_s_fwd: kernel = stride (%d,%d,%d), dtype %d not supported", sd, sh, sw, dtype);
-  DG_REQUIRE(ws_bytes >= dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, dtype), DGTTA_ERR_WORKSPACE,
-             "convT3d_s_fwd: workspace too small");
-  const int rc = convTa_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, dtype, (hipStream_t)stream);
+  static const char fn[] = "convT3d_s_fwd";
+  const ConvProblem P{B, Cin, Cout, Cin, Cout, Di, Hi, Wi, sd, sd, sh, sw, dtype, (hipStream_t)stream};
+  CONV_REQUIRE_PTRS(fn, x && w_t && out && ws);
+  CONV_REQUIRE_DIMS(fn, P, true, ldx >= Cin && ldo >= Cout);
+  CONV_REQUIRE_CONVT_STRIDES(fn, P);
+  CONV_REQUIRE_WS(fn, ws_bytes, convT_pack_region(Cin, Cout, dtype));
+  const int rc = convTa_run(P, 0, Src{x, ldx}, w_t, bias, Dst{out, ldo}, ws);
   if (rc == DGTTA_ERR_UNSUPPORTED) dgtta_set_error("convT3d_s_fwd: x must be 16-byte aligned with rows of whole 16 bytes");
   return rc;
 }
 
-// workspace: [bias partials][packed weights][weight-gradient slabs]
-static size_t convTa_bias_region(int B, int Cout, int Di, int Hi, int Wi, int no) {
-  return align_up(conv_bias_grad_ws_bytes(B, Cout, (int64_t)Di * Hi * Wi * no), 256);
-}
-
+// workspace: [bias partials][packed weights][weight-gradient slabs] (convT_bwd_ws_layout)
 extern "C" size_t dgtta_convT3d_s_bwd_ws_bytes(int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw) {
-  if (!dims_ok(B, Cin, Cout, Di, Hi, Wi) || !convt_strides_ok(sd, sh, sw)) return 0;
-  return convTa_bias_region(B, Cout, Di, Hi, Wi, sd * sh * sw) + dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, DGTTA_F32) +
-         align_up(conva_wgrad_ws_bytes(B, Cin, Cout, Di, Hi, Wi), 256);
+  const ConvProblem P{B, Cin, Cout, Cin, Cout, Di, Hi, Wi, sd, sd, sh, sw, DGTTA_F32, nullptr};
+  if (!conv_dims_ok(P, true) || !convt_strides_ok(P)) return 0;
+  return convT_bwd_ws_layout(P, true).total();
 }
 
 extern "C" int dgtta_convT3d_s_bwd(const void *x, int ldx, const void *dout, int lddo, const float *w_t, void *dx, int lddx, float *dw_t,
                                    float *db, void *ws, size_t ws_bytes, int B, int Cin, int Cout, int Di, int Hi, int Wi, int sd, int sh,
                                    int sw, int accumulate, int dtype, void *stream) {
-  DG_REQUIRE(x && dout && w_t && ws, DGTTA_ERR_BADARG, "convT3d_s_bwd: null pointer");
-  DG_REQUIRE(dims_ok(B, Cin, Cout, Di, Hi, Wi) && ldx >= Cin && lddo >= Cout, DGTTA_ERR_BADARG, "convT3d_s_bwd: bad dims");
-  DG_REQUIRE(convt_strides_ok(sd, sh, sw) && dtype_ok(dtype), DGTTA_ERR_UNSUPPORTED,
-             "convT3d_s_bwd: kernel = stride (%d,%d,%d), dtype %d not supported", sd, sh, sw, dtype);
-  DG_REQUIRE(ws_bytes >= dgtta_convT3d_s_bwd_ws_bytes(B, Cin, Cout, Di, Hi, Wi, sd, sh, sw), DGTTA_ERR_WORKSPACE,
-             "convT3d_s_bwd: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int no = sd * sh * sw;
-  void *ws_bias = ws;
-  void *ws_pack = (char *)ws + convTa_bias_region(B, Cout, Di, Hi, Wi, no);
-  void *ws_main = (char *)ws_pack + dgtta_convT3d_s_fwd_ws_bytes(Cin, Cout, sd, sh, sw, DGTTA_F32);
-  const size_t main_bytes = ws_bytes - ((char *)ws_main - (char *)ws);
+  static const char fn[] = "convT3d_s_bwd";
+  const ConvProblem P{B, Cin, Cout, Cin, Cout, Di, Hi, Wi, sd, sd, sh, sw, dtype, (hipStream_t)stream};
+  const Src xs{x, ldx}, dos{dout, lddo};
+  CONV_REQUIRE_PTRS(fn, x && dout && w_t && ws);
+  CONV_REQUIRE_DIMS(fn, P, true, ldx >= Cin && lddo >= Cout);
+  CONV_REQUIRE_CONVT_STRIDES(fn, P);
+  const ConvWsLayout lay = convT_bwd_ws_layout(P, true);
+  CONV_REQUIRE_WS(fn, ws_bytes, lay.total());
   if (dx) {
     DG_REQUIRE(lddx >= Cin, DGTTA_ERR_BADARG, "convT3d_s_bwd: lddx < Cin");
-    const int rc = convTa_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws_pack, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, dtype, st);
+    const int rc = convTa_run(P, 1, dos, w_t, nullptr, Dst{dx, lddx}, lay.pack_of(ws));
     if (rc == DGTTA_ERR_UNSUPPORTED) dgtta_set_error("convT3d_s_bwd: dout must be 16-byte aligned with rows of whole 16 bytes");
     if (rc != DGTTA_OK) return rc;
   }
   if (dw_t) {
-    const int rc = convTa_wgrad_mfma(x, ldx, dout, lddo, dw_t, ws_main, main_bytes, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, accumulate,
-                                     dtype, st);
+    const int rc = convTa_wgrad_mfma(P, xs, dos, dw_t, lay.main_of(ws, ws_bytes), accumulate);
     if (rc == DGTTA_ERR_UNSUPPORTED)
       dgtta_set_error("convT3d_s_bwd: operands not taken by the MFMA kernel (16-byte aligned rows, Cout a multiple of %d)",
                       dtype == DGTTA_F32 ? 4 : 8);
     if (rc != DGTTA_OK) return rc;
   }
-  if (db) return conv_bias_grad(dout, lddo, db, ws_bias, B, Cout, (int64_t)Di * Hi * Wi * no, accumulate, dtype, st);
+  if (db) return conv_bias_grad(dout, lddo, db, ws, B, Cout, P.t_vox(), accumulate, dtype, P.st);
   return DGTTA_OK;
 }

@@ -1,9 +1,11 @@
 // Shared declarations of the MFMA convolution translation units (conv_mfma.hip, conv_rows.hip, conv_ring.hip, conv_s2.hip,
 // convt_gemm.hip, conv_aniso.hip and, through conv_wgrad_common.h, the weight-gradient units):
 // operand descriptors and views, the launch descriptor of the forward / data-gradient dispatch chains (ConvLaunch) and the
-// launchers that take it, the class tables (single_class, dgrad_parity_classes), tile geometry and the weight image index.
-// Pointer-level functions are declared in conv_api.h; what only the weight-gradient units share - their launch descriptor
-// (WgradLaunch), launchers and class tables - in conv_wgrad_common.h; the device primitives that are not about convolutions
+// launchers that take it, the views of a volume and its sub-lattices (dense_view, lattice_view) with the one decode of a class
+// index into parities (class_parity), the class tables (single_class, dgrad_parity_classes), tile geometry and the weight image
+// index.  Pointer-level functions and the problem descriptor they take (ConvProblem, which the entry points fill and the
+// pointer-level functions turn into a ConvLaunch) are declared in conv_api.h; what only the weight-gradient units share - their
+// launch descriptor (WgradLaunch), launchers and class tables - in conv_wgrad_common.h; the device primitives that are not about convolutions
 // (vector types, MFMA wrappers, LDS-DMA) live in gfx950.h.
 #pragma once
 #include "conv_api.h"
@@ -40,8 +42,9 @@ struct ConvClasses {
 // are the GEMM's K, Cout / CoutP its N), the InstanceNorm partial sums to leave (or null), the tap count of the weight image
 // and the stream.  The three riders concern the ring / row-reuse launchers only:
 //   gst: InstanceNorm-backward context of dgtta_conv3d_k3_dgrad_gstats;
-//   xkh != 0: x holds its two 32-channel K halves as dense planes xkh elements apart - only the ring kernel reads that layout;
-//   dry: no launch, DGTTA_OK iff the ring kernel would take this call (dgtta_conv3d_k3_blocked_supported).
+//   xkh != 0: x holds its two 32-channel K halves as dense planes xkh elements apart - only the ring kernel reads that layout
+//             (Src::kh of the pointer-level functions);
+//   dry: no launch, DGTTA_OK iff the ring kernel would take this call (ConvProblem::dry, dgtta_conv3d_k3_blocked_supported).
 struct ConvLaunch {
   const void *x;
   View xv;
@@ -134,21 +137,23 @@ inline View dense_view(int B, int D, int H, int W, int ld) {
   v.W = W;
   return v;
 }
-// sub-lattice of a dense volume with per-axis steps (sd,sh,sw) at offsets (pd,ph,pw): elements s*v+p
-View lattice_view(int D, int H, int W, int ld, int sd, int sh, int sw, int pd, int ph, int pw, long long *offset) {
-  View v = dense_view(1, D, H, W, ld);
-  *offset = ((long long)pd * H * W + (long long)ph * W + pw) * ld;
-  v.sd *= sd;
-  v.sh *= sh;
-  v.sw *= sw;
-  v.D = (D - pd + sd - 1) / sd;
-  v.H = (H - ph + sh - 1) / sh;
-  v.W = (W - pw + sw - 1) / sw;
-  return v;
+// Parities of class (or output offset) c of a layer with strides (sd, sh, sw) in {1, 2}^3: the classes number the parity
+// combinations of the strided axes, flattened in D, H, W order (torch's flattening of a kernel = stride); an axis of stride 1 has
+// parity 0.  The one place that knows this numbering.
+struct Parity { int p[3]; };      // D, H, W
+inline Parity class_parity(int c, int sd, int sh, int sw) {
+  return {{sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0}};
 }
-// sub-lattice of parity (pd,ph,pw) of a dense volume: elements 2v+p
-View parity_view(int D, int H, int W, int ld, int pd, int ph, int pw, long long *offset) {
-  return lattice_view(D, H, W, ld, 2, 2, 2, pd, ph, pw, offset);
+// sub-lattice of class c of the dense volume `full` (its sb is kept) with per-axis steps (sd, sh, sw): elements s * v + parity
+inline View lattice_view(const View &full, int sd, int sh, int sw, int c, long long *offset) {
+  const Parity par = class_parity(c, sd, sh, sw);
+  View v = full;
+  *offset = par.p[0] * full.sd + par.p[1] * full.sh + par.p[2] * full.sw;
+  v.sd *= sd, v.sh *= sh, v.sw *= sw;
+  v.D = (full.D - par.p[0] + sd - 1) / sd;
+  v.H = (full.H - par.p[1] + sh - 1) / sh;
+  v.W = (full.W - par.p[2] + sw - 1) / sw;
+  return v;
 }
 
 inline int epv_of(int dtype) { return dtype == DGTTA_F32 ? 4 : 8; }      // Elem<T>::EPV of a runtime dtype
@@ -177,22 +182,23 @@ inline ConvClasses single_class(const Taps &taps, int accumulate) {
 // of the strided axes (class index = parities flattened in D, H, W order), writing the sub-lattice s * j + p of dx (*yv: its
 // view - with even strided extents one shape serves all classes).  Per axis the virtual tap v (0..k-1) reads dy[j + v - k/2]
 // and carries weight tap t = p + k/2 - s * (v - k/2) where 0 <= t < k.
-inline ConvClasses dgrad_parity_classes(int kd, int sd, int sh, int sw, int Di, int Hi, int Wi, int lddx, int accumulate, View *yv) {
+inline ConvClasses dgrad_parity_classes(const ConvProblem &P, int lddx, int accumulate, View *yv) {
   ConvClasses cs{};
-  cs.n = sd * sh * sw;
-  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+  cs.n = P.noff();
+  const int ks[3] = {P.kd, 3, 3}, ss[3] = {P.sd, P.sh, P.sw};
+  const View full = dense_view(P.B, P.Di, P.Hi, P.Wi, lddx);
   for (int c = 0; c < cs.n; ++c) {
-    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
-    *yv = lattice_view(Di, Hi, Wi, lddx, sd, sh, sw, par[0], par[1], par[2], &cs.yoff[c]);
+    const Parity par = class_parity(c, P.sd, P.sh, P.sw);
+    *yv = lattice_view(full, P.sd, P.sh, P.sw, c, &cs.yoff[c]);
     cs.acc[c] = accumulate;
     for (int t = 0; t < 27; ++t) cs.taps[c].wt[t] = -1;
-    for (int v = 0; v < kd * 9; ++v) {
+    for (int v = 0; v < P.ntaps(); ++v) {
       const int vv[3] = {v / 9, (v / 3) % 3, v % 3};
       int real[3];
       bool ok = true;
       for (int a = 0; a < 3; ++a) {
         const int pad = ks[a] / 2;
-        real[a] = par[a] + pad - ss[a] * (vv[a] - pad);
+        real[a] = par.p[a] + pad - ss[a] * (vv[a] - pad);
         ok = ok && real[a] >= 0 && real[a] < ks[a];
       }
       if (ok) cs.taps[c].wt[v] = (signed char)(real[0] * 9 + real[1] * 3 + real[2]);

@@ -495,35 +495,35 @@ int64_t conv3_mfma_max_tiles(int Do, int Ho, int Wo) {
 }
 
 // w_kmajor: the forward or the backward weight image (27 real taps); mirror: virtual tap t uses weight tap 26 - t
-int conv3_fwd_mfma(const void *x, int ldx, const void *w_kmajor, int mirror, const float *bias, void *y, int ldy, int B,
-                   int Cin, int Cout, int CinP, int CoutP, int Di, int Hi, int Wi, int stride, int dtype,
-                   hipStream_t st, double *stats, RowsGstCtx *gst, long long xkh, bool dry) {
-  if ((xkh || dry) && (stride != 1 || dtype == DGTTA_F32)) return DGTTA_ERR_UNSUPPORTED;
-  const int Do = (Di - 1) / stride + 1, Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-  const ConvLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), w_kmajor, bias, y, dense_view(B, Do, Ho, Wo, ldy), B, Cin, Cout, CinP, CoutP,
-                     stats, 27, st, gst, xkh, dry};
+int conv3_fwd_mfma(const ConvProblem &P, Src x, const void *w_kmajor, int mirror, const float *bias, Dst y, double *stats,
+                   RowsGstCtx *gst) {
+  const int stride = P.sd, dtype = P.dtype;
+  if ((x.kh || P.dry) && (stride != 1 || dtype == DGTTA_F32)) return DGTTA_ERR_UNSUPPORTED;
+  const int Do = P.Do(), Ho = P.Ho(), Wo = P.Wo();      // (odd extents under stride 2 included)
+  const ConvLaunch L{x.p, dense_view(P.B, P.Di, P.Hi, P.Wi, x.ld), w_kmajor, bias, y.p, dense_view(P.B, Do, Ho, Wo, y.ld), P.B, P.Cin,
+                     P.Cout, P.CinP, P.CoutP, stats, 27, P.st, gst, x.kh, P.dry};
   if (stride == 2 && !mirror && dtype != DGTTA_F32 && dgtta_switches().conv_s2 != '1' && dgtta_switches().conv_s2 != '4') {
     // the two large encoder transitions: register-operand kernel (conv_s2.hip)
     const int rc = conv3_s2_regs(L, conv3_mfma_max_tiles(Do, Ho, Wo), dtype);
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
   }
-  if (!dtype_ok(dtype) || !operand_ok(epv_of(dtype), x, xkh ? 2 * ldx : ldx, Cin, CinP)) return DGTTA_ERR_UNSUPPORTED;
+  if (!dtype_ok(dtype) || !operand_ok(epv_of(dtype), x.p, x.kh ? 2 * x.ld : x.ld, P.Cin, P.CinP)) return DGTTA_ERR_UNSUPPORTED;
   DISPATCH_T(dtype, return dispatch_conv<T>(L, identity_taps(mirror), stride, 0));
 }
 
 // Data gradient of a stride-2 conv: 8 parity classes of the input lattice, each a stride-1 gather of dy with the
 // 1/2/4/8 taps that reach that class (even extents: one shape for all classes -> ONE launch, class = blockIdx.z).
 // w_kmajor: the backward weight image (N = ci, K = co), real taps.
-int conv3_dgrad_s2_mfma(const void *dy, int lddy, const void *w_kmajor, void *dx, int lddx, int B, int Cin, int Cout,
-                        int CinP, int CoutP, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st) {
-  if (!dtype_ok(dtype) || !operand_ok(epv_of(dtype), dy, lddy, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
-  const int Do = (Di - 1) / 2 + 1, Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
+int conv3_dgrad_s2_mfma(const ConvProblem &P, Src dy, const void *w_kmajor, Dst dx, int accumulate) {
+  if (!dtype_ok(P.dtype) || !operand_ok(epv_of(P.dtype), dy.p, dy.ld, P.Cout, P.CoutP)) return DGTTA_ERR_UNSUPPORTED;
   View yv;
-  const ConvClasses cs = dgrad_parity_classes(3, 2, 2, 2, Di, Hi, Wi, lddx, accumulate, &yv);
-  const ConvLaunch L{dy, dense_view(B, Do, Ho, Wo, lddy), w_kmajor, nullptr, dx, yv, B, Cout, Cin, CoutP, CinP, nullptr, 27, st};
+  const ConvClasses cs = dgrad_parity_classes(P, dx.ld, accumulate, &yv);
+  const ConvProblem G = dgrad_as_fwd(P);
+  const ConvLaunch L{dy.p, dense_view(P.B, P.Do(), P.Ho(), P.Wo(), dy.ld), w_kmajor, nullptr, dx.p, yv, G.B, G.Cin, G.Cout, G.CinP, G.CoutP,
+                     nullptr, 27, P.st};
   // DGTTA_DGRAD_S2_ALLCLS (tests): '0' = the 8-class launch
-  const bool allcls = dgtta_switches().dgrad_s2_allcls != '0' && CinP % 8 == 0;
-  DISPATCH_T(dtype, return allcls ? dgrad_s2_allcls<T>(L, cs) : dispatch_conv_classes<T>(L, cs, 1));
+  const bool allcls = dgtta_switches().dgrad_s2_allcls != '0' && P.CinP % 8 == 0;
+  DISPATCH_T(P.dtype, return allcls ? dgrad_s2_allcls<T>(L, cs) : dispatch_conv_classes<T>(L, cs, 1));
 }
 
 size_t convT_packed_bytes(int CinP, int CoutP, int dtype) {
@@ -536,13 +536,13 @@ size_t conv_image_bytes(int CinP, int CoutP, int dtype) {
 size_t conv_imgB_offset_bytes(int CinP, int CoutP, int dtype) {
   return (size_t)27 * CinP * n32(CoutP) * esize(dtype);
 }
-int conv_pack_images(const float *w_t, void *img, int ntaps, int Cin, int Cout, int CinP, int CoutP, int dtype, hipStream_t st) {
-  const int cmax = CinP > CoutP ? CinP : CoutP;
+int conv_pack_images(const ConvProblem &P, const float *w_t, void *img) {
+  const int ntaps = P.ntaps(), cmax = P.CinP > P.CoutP ? P.CinP : P.CoutP;
   const int64_t n = (int64_t)ntaps * cmax * n32(cmax);
   const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-  void *imgB = (char *)img + (size_t)ntaps * CinP * n32(CoutP) * esize(dtype);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((conva_pack_kernel<T>), dim3(blocks), dim3(256), 0, st, w_t, (T *)img, (T *)imgB, Cin, Cout,
-                                       CinP, CoutP, ntaps));
+  void *imgB = (char *)img + (size_t)ntaps * P.CinP * n32(P.CoutP) * esize(P.dtype);
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((conva_pack_kernel<T>), dim3(blocks), dim3(256), 0, P.st, w_t, (T *)img, (T *)imgB, P.Cin, P.Cout,
+                                         P.CinP, P.CoutP, ntaps));
   DG_CHECK_LAUNCH("conva_pack_kernel");
   return DGTTA_OK;
 }
@@ -573,18 +573,19 @@ __global__ void convTa_pack_kernel(const float *__restrict__ w, T *__restrict__ 
 }
 
 template <typename T>
-int convTa_run_t(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
-                 int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, hipStream_t st) {
+int convTa_run_t(const ConvProblem &P, int mode, Src in, const float *w_t, const float *bias, Dst out, void *ws) {
   constexpr int EPV = Elem<T>::EPV;
+  const int Cin = P.Cin, Cout = P.Cout, sd = P.sd, sh = P.sh, sw = P.sw, no = P.noff();
   const int CinP = (Cin + 2 * EPV - 1) / (2 * EPV) * (2 * EPV), CoutP = (Cout + 2 * EPV - 1) / (2 * EPV) * (2 * EPV);
-  const int no = sd * sh * sw;
-  if (mode == 0 ? !operand_ok(EPV, in, ldin, Cin, CinP) : !operand_ok(EPV, in, ldin, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
+  if (mode == 0 ? !operand_ok(EPV, in.p, in.ld, Cin, CinP) : !operand_ok(EPV, in.p, in.ld, Cout, CoutP)) return DGTTA_ERR_UNSUPPORTED;
   T *wf = (T *)ws, *wb = wf + (size_t)no * CinP * n32(CoutP);
   const int64_t n = (int64_t)no * (CinP > CoutP ? CinP : CoutP) * n32(CinP > CoutP ? CinP : CoutP);
-  hipLaunchKernelGGL((convTa_pack_kernel<T>), dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, st,
+  hipLaunchKernelGGL((convTa_pack_kernel<T>), dim3((unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, P.st,
                      w_t, wf, wb, Cin, Cout, CinP, CoutP, no);
   DG_CHECK_LAUNCH("convTa_pack_kernel");
-  const int Do = sd * Di, Ho = sh * Hi, Wo = sw * Wi;
+  // the fine lattice (the forward's output, the data gradient's input) and the coarse one
+  const View coarse = dense_view(P.B, P.Di, P.Hi, P.Wi, mode == 0 ? in.ld : out.ld);
+  const View fine = dense_view(P.B, P.Dt(), P.Ht(), P.Wt(), mode == 0 ? out.ld : in.ld);
   Taps taps;
   for (int t = 0; t < 27; ++t) taps.wt[t] = -1;
   taps.wt[13] = 0;
@@ -594,42 +595,34 @@ int convTa_run_t(int mode, const void *in, int ldin, const float *w_t, const flo
     cs.n = no;
     View yv{};
     for (int o = 0; o < no; ++o) {
-      yv = lattice_view(Do, Ho, Wo, ldout, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
-                        sw == 2 ? o % 2 : 0, &cs.yoff[o]);
+      yv = lattice_view(fine, sd, sh, sw, o, &cs.yoff[o]);
       cs.taps[o] = taps;
       cs.taps[o].wt[13] = (signed char)o;
     }
-    const ConvLaunch L{in, dense_view(B, Di, Hi, Wi, ldin), wf, bias, out, yv, B, Cin, Cout, CinP, CoutP, nullptr, no, st};
+    const ConvLaunch L{in.p, coarse, wf, bias, out.p, yv, P.B, Cin, Cout, CinP, CoutP, nullptr, no, P.st};
     return dispatch_conv_classes<T>(L, cs, 0);
   }
   // data gradient: ONE pointwise GEMM with K = no x Cout, the output lattices of dout concatenated along K
   ConvClasses cs = single_class(taps, 0);
   cs.kseg = CoutP;
   View xv{};
-  for (int o = 0; o < no; ++o)
-    xv = lattice_view(Do, Ho, Wo, ldin, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0, sw == 2 ? o % 2 : 0,
-                      &cs.segoff[o]);
-  const ConvLaunch L{in, xv, wb, nullptr, out, dense_view(B, Di, Hi, Wi, ldout), B, Cout, Cin, no * CoutP, CinP, nullptr, 1, st};
+  for (int o = 0; o < no; ++o) xv = lattice_view(fine, sd, sh, sw, o, &cs.segoff[o]);
+  const ConvLaunch L{in.p, xv, wb, nullptr, out.p, coarse, P.B, Cout, Cin, no * CoutP, CinP, nullptr, 1, P.st};
   return dispatch_conv_classes<T>(L, cs, 0);
 }
 }  // namespace
 
-int convTa_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B, int Cin,
-               int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int dtype, hipStream_t st) {
-  if (!dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;
-  DISPATCH_T(dtype, return convTa_run_t<T>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, sd, sh, sw, st));
+int convTa_run(const ConvProblem &P, int mode, Src in, const float *w_t, const float *bias, Dst out, void *ws) {
+  if (!dtype_ok(P.dtype)) return DGTTA_ERR_UNSUPPORTED;
+  DISPATCH_T(P.dtype, return convTa_run_t<T>(P, mode, in, w_t, bias, out, ws));
 }
 
 // ConvTranspose3d(k2,s2) forward / data gradient: the register-operand GEMM where it applies, else the 8-offset case of the above
-int convT_fwd_mfma(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, void *ws, int B, int Cin,
-                   int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st) {
-  if (ldx >= Cin && ldo >= Cout && convT_gemm_eligible(0, x, ldx, out, ldo, Cin, Cout, Wi, dtype))
-    return convT_gemm_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, dtype, st);
-  return convTa_run(0, x, ldx, w_t, bias, out, ldo, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, dtype, st);
+int convT_fwd_mfma(const ConvProblem &P, Src x, const float *w_t, const float *bias, Dst out, void *ws) {
+  if (x.ld >= P.Cin && out.ld >= P.Cout && convT_gemm_eligible(P, x, out)) return convT_gemm_run(P, 0, x, w_t, bias, out, ws);
+  return convTa_run(P, 0, x, w_t, bias, out, ws);
 }
-int convT_dgrad_mfma(const void *dout, int lddo, const float *w_t, void *dx, int lddx, void *ws, int B, int Cin, int Cout,
-                     int Di, int Hi, int Wi, int dtype, hipStream_t st) {
-  if (lddo >= Cout && lddx >= Cin && convT_gemm_eligible(1, dout, lddo, dx, lddx, Cin, Cout, Wi, dtype))
-    return convT_gemm_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, dtype, st);
-  return convTa_run(1, dout, lddo, w_t, nullptr, dx, lddx, ws, B, Cin, Cout, Di, Hi, Wi, 2, 2, 2, dtype, st);
+int convT_dgrad_mfma(const ConvProblem &P, Src dout, const float *w_t, Dst dx, void *ws) {
+  if (dout.ld >= P.Cout && dx.ld >= P.Cin && convT_gemm_eligible(P, dout, dx)) return convT_gemm_run(P, 1, dout, w_t, nullptr, dx, ws);
+  return convTa_run(P, 1, dout, w_t, nullptr, dx, ws);
 }

@@ -193,33 +193,28 @@ __global__ void convT_wgrad_ref_kernel(const T *__restrict__ x, int ldx, const T
 }  // namespace
 
 // ============================================================================ host launchers (conv_api.h)
-int conv3_pack_weights_ref(const float *w_t, void *wf, void *wb, int Cin, int Cout, int CinP, int CoutP, int dtype,
-                           hipStream_t st) {
-  const int64_t n = (int64_t)27 * CinP * CoutP;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((pack_weights_kernel<T>), dim3(gs_blocks(n)), dim3(256), 0, st,
-                                       w_t, (T *)wf, (T *)wb, Cin, Cout, CinP, CoutP));
+int conv3_pack_weights_ref(const ConvProblem &P, const float *w_t, void *wf, void *wb) {
+  const int64_t n = (int64_t)27 * P.CinP * P.CoutP;
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((pack_weights_kernel<T>), dim3(gs_blocks(n)), dim3(256), 0, P.st,
+                                         w_t, (T *)wf, (T *)wb, P.Cin, P.Cout, P.CinP, P.CoutP));
   DG_CHECK_LAUNCH("pack_weights_kernel");
   return DGTTA_OK;
 }
 
-int conv3_fwd_ref(const void *x, int ldx, const void *wf, const float *bias, void *y, int ldy, int B, int Cin, int Cout,
-                  int CinP, int CoutP, int Di, int Hi, int Wi, int stride, int dtype, hipStream_t st) {
-  const int Do = out_dim(Di, stride), Ho = out_dim(Hi, stride), Wo = out_dim(Wi, stride);
-  const int64_t total = (int64_t)B * Do * Ho * Wo * Cout;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((conv3_fwd_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st,
-                                       (const T *)x, ldx, (const T *)wf, bias, (T *)y, ldy, Cin, Cout, CinP, CoutP, Di,
-                                       Hi, Wi, Do, Ho, Wo, stride, total));
+int conv3_fwd_ref(const ConvProblem &P, Src x, const void *wf, const float *bias, Dst y) {
+  const int64_t total = P.B * P.out_vox() * P.Cout;
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((conv3_fwd_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, P.st,
+                                         (const T *)x.p, x.ld, (const T *)wf, bias, (T *)y.p, y.ld, P.Cin, P.Cout, P.CinP, P.CoutP, P.Di,
+                                         P.Hi, P.Wi, P.Do(), P.Ho(), P.Wo(), P.sd, total));
   DG_CHECK_LAUNCH("conv3_fwd_ref_kernel");
   return DGTTA_OK;
 }
 
-int conv3_dgrad_ref(const void *dy, int lddy, const void *wb, void *dx, int lddx, int B, int Cin, int Cout, int CinP,
-                    int CoutP, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st) {
-  const int Do = out_dim(Di, stride), Ho = out_dim(Hi, stride), Wo = out_dim(Wi, stride);
-  const int64_t total = (int64_t)B * Di * Hi * Wi * Cin;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((conv3_dgrad_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st,
-                                       (const T *)dy, lddy, (const T *)wb, (T *)dx, lddx, Cin, Cout, CinP, CoutP, Di, Hi,
-                                       Wi, Do, Ho, Wo, stride, accumulate, total));
+int conv3_dgrad_ref(const ConvProblem &P, Src dy, const void *wb, Dst dx, int accumulate) {
+  const int64_t total = P.B * P.in_vox() * P.Cin;
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((conv3_dgrad_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, P.st,
+                                         (const T *)dy.p, dy.ld, (const T *)wb, (T *)dx.p, dx.ld, P.Cin, P.Cout, P.CinP, P.CoutP, P.Di, P.Hi,
+                                         P.Wi, P.Do(), P.Ho(), P.Wo(), P.sd, accumulate, total));
   DG_CHECK_LAUNCH("conv3_dgrad_ref_kernel");
   return DGTTA_OK;
 }
@@ -230,38 +225,33 @@ int reduce_splits(const float *part, float *out, int64_t n, int nsplit, int accu
   return DGTTA_OK;
 }
 
-int conv3_wgrad_ref(const void *x, int ldx, const void *dy, int lddy, float *part, int nsplit, float *dw_t, int B, int Cin,
-                    int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st) {
-  const int Do = out_dim(Di, stride), Ho = out_dim(Hi, stride), Wo = out_dim(Wi, stride);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((conv3_wgrad_ref_kernel<T>), dim3(cdiv(Cin * Cout, 256), 27, nsplit), dim3(256),
-                                       0, st, (const T *)x, ldx, (const T *)dy, lddy, part, Cin, Cout, B, Di, Hi, Wi,
-                                       Do, Ho, Wo, stride));
+int conv3_wgrad_ref(const ConvProblem &P, Src x, Src dy, float *part, int nsplit, float *dw_t, int accumulate) {
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((conv3_wgrad_ref_kernel<T>), dim3(cdiv(P.Cin * P.Cout, 256), 27, nsplit), dim3(256),
+                                         0, P.st, (const T *)x.p, x.ld, (const T *)dy.p, dy.ld, part, P.Cin, P.Cout, P.B, P.Di, P.Hi, P.Wi,
+                                         P.Do(), P.Ho(), P.Wo(), P.sd));
   DG_CHECK_LAUNCH("conv3_wgrad_ref_kernel");
-  return reduce_splits(part, dw_t, (int64_t)Cout * Cin * 27, nsplit, accumulate, st);
+  return reduce_splits(part, dw_t, (int64_t)P.Cout * P.Cin * 27, nsplit, accumulate, P.st);
 }
 
-int convT_fwd_ref(const void *x, int ldx, const float *w_t, const float *bias, void *out, int ldo, int B, int Cin, int Cout,
-                  int Di, int Hi, int Wi, int dtype, hipStream_t st) {
-  const int64_t total = (int64_t)B * Di * Hi * Wi * 8 * Cout;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((convT_fwd_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st,
-                                       (const T *)x, ldx, w_t, bias, (T *)out, ldo, Cin, Cout, Di, Hi, Wi, total));
+int convT_fwd_ref(const ConvProblem &P, Src x, const float *w_t, const float *bias, Dst out) {
+  const int64_t total = P.B * P.in_vox() * 8 * P.Cout;
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((convT_fwd_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, P.st,
+                                         (const T *)x.p, x.ld, w_t, bias, (T *)out.p, out.ld, P.Cin, P.Cout, P.Di, P.Hi, P.Wi, total));
   DG_CHECK_LAUNCH("convT_fwd_ref_kernel");
   return DGTTA_OK;
 }
 
-int convT_dgrad_ref(const void *dout, int lddo, const float *w_t, void *dx, int lddx, int B, int Cin, int Cout, int Di,
-                    int Hi, int Wi, int dtype, hipStream_t st) {
-  const int64_t total = (int64_t)B * Di * Hi * Wi * Cin;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((convT_dgrad_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, st,
-                                       (const T *)dout, lddo, w_t, (T *)dx, lddx, Cin, Cout, Di, Hi, Wi, total));
+int convT_dgrad_ref(const ConvProblem &P, Src dout, const float *w_t, Dst dx) {
+  const int64_t total = P.B * P.in_vox() * P.Cin;
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((convT_dgrad_ref_kernel<T>), dim3(gs_blocks(total, 1 << 20)), dim3(256), 0, P.st,
+                                         (const T *)dout.p, dout.ld, w_t, (T *)dx.p, dx.ld, P.Cin, P.Cout, P.Di, P.Hi, P.Wi, total));
   DG_CHECK_LAUNCH("convT_dgrad_ref_kernel");
   return DGTTA_OK;
 }
 
-int convT_wgrad_ref(const void *x, int ldx, const void *dout, int lddo, float *part, int nsplit, float *dw_t, int B, int Cin,
-                    int Cout, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL((convT_wgrad_ref_kernel<T>), dim3(cdiv(Cin * Cout, 256), 8, nsplit), dim3(256),
-                                       0, st, (const T *)x, ldx, (const T *)dout, lddo, part, Cin, Cout, B, Di, Hi, Wi));
+int convT_wgrad_ref(const ConvProblem &P, Src x, Src dout, float *part, int nsplit, float *dw_t, int accumulate) {
+  DISPATCH_T(P.dtype, hipLaunchKernelGGL((convT_wgrad_ref_kernel<T>), dim3(cdiv(P.Cin * P.Cout, 256), 8, nsplit), dim3(256),
+                                         0, P.st, (const T *)x.p, x.ld, (const T *)dout.p, dout.ld, part, P.Cin, P.Cout, P.B, P.Di, P.Hi, P.Wi));
   DG_CHECK_LAUNCH("convT_wgrad_ref_kernel");
-  return reduce_splits(part, dw_t, (int64_t)Cin * Cout * 8, nsplit, accumulate, st);
+  return reduce_splits(part, dw_t, (int64_t)P.Cin * P.Cout * 8, nsplit, accumulate, P.st);
 }

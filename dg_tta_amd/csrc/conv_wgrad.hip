@@ -43,7 +43,7 @@ static int units_per_workgroup(int64_t units, int64_t gy, int slots) {
 }
 
 int wgrad_launch_classes(const WgradLaunch &L, const WgradOut &out, const WgradClasses &wc, const RealTaps &reals) {
-  if (!wgrad_dtype_ok(L.dtype)) return DGTTA_ERR_UNSUPPORTED;      // (esize() below takes every other dtype for 16-bit)
+  if (!dtype_ok(L.dtype)) return DGTTA_ERR_UNSUPPORTED;      // (esize() below takes every other dtype for 16-bit)
   const int esz = (int)esize(L.dtype), EPV = 16 / esz;
   const View &xv = L.xv, &yv = L.yv;
   // Cin may be ragged (first layer: 12 channels in rows of 16): the pad channels only feed gradient rows ci >= Cin,
@@ -95,10 +95,10 @@ int wgrad_launch_classes(const WgradLaunch &L, const WgradOut &out, const WgradC
   return wgrad_reduce_launch(L, out, p, wc.n, nslab, reals);
 }
 
-// 3x3x3 conv, stride 1 or 2 (even extents).  L.xv: x at full resolution, L.yv: dy
-static int wgrad_conv(const WgradLaunch &L, const WgradOut &out, int stride) {
+// 3x3x3 conv P, stride 1 or 2 (even extents).  L.xv: x at full resolution, L.yv: dy
+static int wgrad_conv(const ConvProblem &P, const WgradLaunch &L, const WgradOut &out) {
   RealTaps reals;
-  if (stride == 1) return wgrad_launch_classes(L, out, wgrad_single_class(0x7ffffffu, identity_taps(0), &reals), reals);
+  if (P.sd == 1) return wgrad_launch_classes(L, out, wgrad_single_class(0x7ffffffu, identity_taps(0), &reals), reals);
   if (L.xkh) return DGTTA_ERR_UNSUPPORTED;
   if (L.dtype != DGTTA_F32) {
     // one pass over x (full resolution tile) and dy with all 27 taps: conv3_wgrad_tr_s2_kernel
@@ -114,7 +114,7 @@ static int wgrad_conv(const WgradLaunch &L, const WgradOut &out, int stride) {
   }
   // x[2*vo + tap - 1] lives on the parity sub-lattices of x: 8 classes of a stride-1 problem
   WgradLaunch C = L;
-  const WgradClasses wc = wgrad_parity_classes(3, 2, 2, 2, L.xv.D, L.xv.H, L.xv.W, (int)L.xv.sw, &reals, &C.xv);
+  const WgradClasses wc = wgrad_parity_classes(P, (int)L.xv.sw, &reals, &C.xv);
   return wgrad_launch_classes(C, out, wc, reals);
 }
 
@@ -210,42 +210,42 @@ int wgrad_f32_split(const SplitOperand &x, const SplitOperand &dy, void *ws, siz
   return DGTTA_OK;
 }
 
-int conv3_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                     int Cout, int Di, int Hi, int Wi, int stride, int accumulate, int dtype, hipStream_t st, long long xkh) {
-  if (stride != 1 && stride != 2) return DGTTA_ERR_UNSUPPORTED;
-  if (stride == 2 && ((Di | Hi | Wi) & 1)) return DGTTA_ERR_UNSUPPORTED;   // odd extents: leave to the general kernel
-  const int Do = Di / stride, Ho = Hi / stride, Wo = Wi / stride;
-  WgradLaunch L{x, dense_view(B, Di, Hi, Wi, ldx), dy, dense_view(B, Do, Ho, Wo, lddy), B, Cin, Cout, dtype, ws, ws_bytes, st};
-  L.xkh = xkh;
-  const WgradOut out{dw_t, (long long)Cin * 27, 27, 1, accumulate};
-  if (dtype == DGTTA_F32) {
-    if (xkh) return DGTTA_ERR_UNSUPPORTED;      // (x as 32-channel planes: 16-bit storage only)
+int conv3_wgrad_mfma(const ConvProblem &P, Src x, Src dy, float *dw_t, Region ws, int accumulate) {
+  const int B = P.B, Di = P.Di, Hi = P.Hi, Wi = P.Wi;
+  if (!stride_ok(P.sd)) return DGTTA_ERR_UNSUPPORTED;
+  if (P.sd == 2 && ((Di | Hi | Wi) & 1)) return DGTTA_ERR_UNSUPPORTED;   // odd extents: leave to the general kernel
+  const int Do = P.Do(), Ho = P.Ho(), Wo = P.Wo();
+  WgradLaunch L{x.p, dense_view(B, Di, Hi, Wi, x.ld), dy.p, dense_view(B, Do, Ho, Wo, dy.ld), B, P.Cin, P.Cout, P.dtype, ws.p, ws.bytes, P.st};
+  L.xkh = x.kh;
+  const WgradOut out{dw_t, (long long)P.Cin * 27, 27, 1, accumulate};
+  if (P.dtype == DGTTA_F32) {
+    if (x.kh) return DGTTA_ERR_UNSUPPORTED;      // (x as 32-channel planes: 16-bit storage only)
     // the caller offered the split workspace (dgtta_conv3d_wgrad_split_ws_bytes) behind the plain one: six 16-bit launches
     // (DGTTA_WGRAD_F32_SPLIT=0: the fp32 MFMA kernel, its predecessor)
-    const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, Do, Ho, Wo), 256);
-    const SplitOperand sx{(const float *)x, ldx, Cin, B, Di, Hi, Wi}, sy{(const float *)dy, lddy, Cout, B, Do, Ho, Wo};
-    const int rc = wgrad_f32_split(sx, sy, ws, ws_bytes, slab, accumulate, st,
+    const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, P.Cin, P.Cout, Do, Ho, Wo), 256);
+    const SplitOperand sx{(const float *)x.p, x.ld, P.Cin, B, Di, Hi, Wi}, sy{(const float *)dy.p, dy.ld, P.Cout, B, Do, Ho, Wo};
+    const int rc = wgrad_f32_split(sx, sy, ws.p, ws.bytes, slab, accumulate, P.st,
                                    [&](const bf16_t *xs, int ldxs, const bf16_t *gs, int ldys, int acc) {
       WgradLaunch leg = L;
       leg.x = xs, leg.xv = dense_view(B, Di, Hi, Wi, ldxs), leg.dy = gs, leg.yv = dense_view(B, Do, Ho, Wo, ldys);
       leg.dtype = DGTTA_BF16, leg.ws_bytes = slab, leg.split_leg = true;
-      return wgrad_conv(leg, WgradOut{dw_t, out.s_co, out.s_ci, out.s_tap, acc}, stride);
+      return wgrad_conv(P, leg, WgradOut{dw_t, out.s_co, out.s_ci, out.s_tap, acc});
     });
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
-  } else if (!wgrad_dtype_ok(dtype)) {
+  } else if (!dtype_ok(P.dtype)) {
     return DGTTA_ERR_UNSUPPORTED;
   }
-  return wgrad_conv(L, out, stride);
+  return wgrad_conv(P, L, out);
 }
-// would the weight gradient of a stride-1 conv on these dims take x as 32-channel planes (only the ring sweep does)?
-bool conv3_wgrad_blocked_ok(int B, int Cin, int Cout, int D, int H, int W, int dtype) {
-  if ((dtype != DGTTA_BF16 && dtype != DGTTA_F16) || Cin % 32 || Cout % 8) return false;
+// would the weight gradient of the stride-1 conv P take x as 32-channel planes (only the ring sweep does)?
+bool conv3_wgrad_blocked_ok(const ConvProblem &P) {
+  if ((P.dtype != DGTTA_BF16 && P.dtype != DGTTA_F16) || P.Cin % 32 || P.Cout % 8) return false;
   if (dgtta_switches().wgrad_tr == '0' || dgtta_switches().wgrad_ring == '0') return false;
-  const View xv = dense_view(B, D, H, W, 32), yv = dense_view(B, D, H, W, Cout);
+  const View xv = dense_view(P.B, P.Di, P.Hi, P.Wi, 32), yv = dense_view(P.B, P.Di, P.Hi, P.Wi, P.Cout);
   int rc = DGTTA_OK;
-  const size_t ws_bytes = conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, D, H, W);
-  WgradLaunch L{(const void *)16, xv, (const void *)16, yv, B, Cin, Cout, dtype, nullptr, ws_bytes, nullptr};
-  L.xkh = (long long)B * D * H * W * 32, L.dry = true;
+  const size_t ws_bytes = conv3_wgrad_mfma_ws_bytes(P.B, P.Cin, P.Cout, P.Di, P.Hi, P.Wi);
+  WgradLaunch L{(const void *)16, xv, (const void *)16, yv, P.B, P.Cin, P.Cout, P.dtype, nullptr, ws_bytes, nullptr};
+  L.xkh = P.B * P.in_vox() * 32, L.dry = true;
   const int g = conv3_wgrad_ring_launch(L, &rc);
   return rc == DGTTA_OK && g > 0;
 }
@@ -269,12 +269,11 @@ size_t conva_wgrad_ws_bytes(int B, int Cin, int Cout, int D, int H, int W) {
   return best;
 }
 
-int conva_wgrad_mfma(const void *x, int ldx, const void *dy, int lddy, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                     int Cout, int Di, int Hi, int Wi, int kd, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
-  const int Do = (Di + 2 * (kd / 2) - kd) / sd + 1, Ho = (Hi - 1) / sh + 1, Wo = (Wi - 1) / sw + 1;
-  WgradLaunch L{x, View{}, dy, dense_view(B, Do, Ho, Wo, lddy), B, Cin, Cout, dtype, ws, ws_bytes, st};
+int conva_wgrad_mfma(const ConvProblem &P, Src x, Src dy, float *dw_t, Region ws, int accumulate) {
+  const int Do = P.Do(), Ho = P.Ho(), Wo = P.Wo();
+  WgradLaunch L{x.p, View{}, dy.p, dense_view(P.B, Do, Ho, Wo, dy.ld), P.B, P.Cin, P.Cout, P.dtype, ws.p, ws.bytes, P.st};
   RealTaps reals;
-  const WgradClasses wc = wgrad_parity_classes(kd, sd, sh, sw, Di, Hi, Wi, ldx, &reals, &L.xv);
-  if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Do, Ho, Wo, wc.n)) return DGTTA_ERR_WORKSPACE;
-  return wgrad_launch_classes(L, WgradOut{dw_t, (long long)Cin * kd * 9, kd * 9, 1, accumulate}, wc, reals);
+  const WgradClasses wc = wgrad_parity_classes(P, x.ld, &reals, &L.xv);
+  if (ws.bytes < wgrad_classes_bytes(P.B, P.Cin, P.Cout, Do, Ho, Wo, wc.n)) return DGTTA_ERR_WORKSPACE;
+  return wgrad_launch_classes(L, WgradOut{dw_t, (long long)P.Cin * P.ntaps(), P.ntaps(), 1, accumulate}, wc, reals);
 }

@@ -58,8 +58,6 @@ struct SplitOperand {
 };
 }  // namespace dgconv
 
-// the storage types the weight-gradient entry points take; anything else is DGTTA_ERR_UNSUPPORTED (no error text)
-static inline bool wgrad_dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
 // slab region of a launch of plan p with ncls classes
 static inline size_t wgrad_slab_bytes(const WgradPlan &p, int ncls) {
   return (size_t)ncls * p.units * p.cibs * p.cobs * 27 * 1024 * sizeof(float);
@@ -128,11 +126,12 @@ inline WgradClasses wgrad_single_class(unsigned tapmask, const Taps &real, RealT
 // combination that carries a tap (1 to 8, parities flattened in D, H, W order), its mask exactly the virtual taps with a real tap
 // (*reals) - each real tap belongs to one class.  *xv: the lattices' common view (steps s, extent of dy, batch stride of the dense
 // volume); strided axes need even input extents.
-inline WgradClasses wgrad_parity_classes(int kd, int sd, int sh, int sw, int Di, int Hi, int Wi, int ldx, RealTaps *reals, View *xv) {
-  const int ks[3] = {kd, 3, 3}, ss[3] = {sd, sh, sw};
+inline WgradClasses wgrad_parity_classes(const ConvProblem &P, int ldx, RealTaps *reals, View *xv) {
+  const int ks[3] = {P.kd, 3, 3}, ss[3] = {P.sd, P.sh, P.sw};
   WgradClasses wc{};
-  for (int c = 0; c < sd * sh * sw; ++c) {
-    const int par[3] = {sd == 2 ? (c / (sh * sw)) % 2 : 0, sh == 2 ? (c / sw) % 2 : 0, sw == 2 ? c % 2 : 0};
+  *xv = dense_view(1, P.Di, P.Hi, P.Wi, ldx);
+  for (int c = 0; c < P.noff(); ++c) {
+    const Parity par = class_parity(c, P.sd, P.sh, P.sw);
     unsigned mask = 0;
     Taps rt;
     for (int t = 0; t < 27; ++t) {
@@ -140,25 +139,20 @@ inline WgradClasses wgrad_parity_classes(int kd, int sd, int sh, int sw, int Di,
       int real[3];
       bool ok = true;
       for (int a = 0; a < 3; ++a) {
-        real[a] = ss[a] * u[a] + par[a] + ks[a] / 2;
+        real[a] = ss[a] * u[a] + par.p[a] + ks[a] / 2;
         ok = ok && real[a] >= 0 && real[a] < ks[a];
       }
       rt.wt[t] = ok ? (signed char)(real[0] * 9 + real[1] * 3 + real[2]) : (signed char)-1;
       if (ok) mask |= 1u << t;
     }
     if (!mask) continue;            // kd = 1 along a strided D: the odd planes carry no tap
-    wc.xoff[wc.n] = ((long long)par[0] * Hi * Wi + (long long)par[1] * Wi + par[2]) * ldx;
+    wc.xoff[wc.n] = par.p[0] * xv->sd + par.p[1] * xv->sh + par.p[2] * xv->sw;
     wc.mask[wc.n] = mask;
     reals->t[wc.n] = rt;
     ++wc.n;
   }
-  *xv = dense_view(1, Di, Hi, Wi, ldx);
-  xv->sd *= sd;
-  xv->sh *= sh;
-  xv->sw *= sw;
-  xv->D = Di / sd;
-  xv->H = Hi / sh;
-  xv->W = Wi / sw;
+  xv->sd *= P.sd, xv->sh *= P.sh, xv->sw *= P.sw;
+  xv->D = P.Do(), xv->H = P.Ho(), xv->W = P.Wo();
   return wc;
 }
 

@@ -133,35 +133,33 @@ __global__ __launch_bounds__(512) void convT_gemm_kernel(const T *__restrict__ i
 }
 
 template <typename T, int MODE, int KSP, int NBR>
-int launch_gemm(const void *in, int ldin, const T *blob, const float *bias, void *out, int ldout, int B, int Di, int Hi, int Wi,
-                int Cout, hipStream_t st) {
+int launch_gemm(const ConvProblem &P, Src in, const T *blob, const float *bias, Dst out) {
   constexpr int R = MODE == 0 ? 4 : 1, S = MODE == 0 ? 1 : 4, LDS = R * NBR * S * KSP * 1024 + NBR * 32 * 4 + 8 * 32 * 72;
   auto kern = convT_gemm_kernel<T, MODE, KSP, NBR>;
   static DynLdsOnce once;
   DG_REQUIRE(ensure_dyn_lds(once, reinterpret_cast<const void *>(kern), LDS) == hipSuccess, DGTTA_ERR_LAUNCH,
              "convT_gemm: cannot raise the dynamic LDS limit to %d", LDS);
-  const int nWB = cdiv(Wi, 32);
-  const long long nMB = (long long)B * Di * Hi * nWB;
+  const int nWB = cdiv(P.Wi, 32);
+  const long long nMB = (long long)P.B * P.Di * P.Hi * nWB;
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   const long long want = cdiv64(nMB, 8), cap = (long long)cus * (LDS <= 64 * 1024 ? 2 : 1);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(512), LDS, st, (const T *)in, ldin, blob, bias,
-                     (T *)out, ldout, Di, Hi, Wi, Cout, nWB, nMB);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(512), LDS, P.st, (const T *)in.p, in.ld, blob, bias,
+                     (T *)out.p, out.ld, P.Di, P.Hi, P.Wi, P.Cout, nWB, nMB);
   DG_CHECK_LAUNCH("convT_gemm_kernel");
   return DGTTA_OK;
 }
 
 template <typename T>
-int run_gemm(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B,
-             int Cin, int Cout, int Di, int Hi, int Wi, hipStream_t st) {
+int run_gemm(const ConvProblem &P, int mode, Src in, const float *w_t, const float *bias, Dst out, void *ws) {
   T *blob = (T *)ws;
-  const int64_t total = (int64_t)8 * Cin * Cout;
-  hipLaunchKernelGGL((convT_frag_pack_kernel<T>), dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, w_t, blob, Cin, Cout,
+  const int64_t total = (int64_t)8 * P.Cin * P.Cout;
+  hipLaunchKernelGGL((convT_frag_pack_kernel<T>), dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, P.st, w_t, blob, P.Cin, P.Cout,
                      mode);
   DG_CHECK_LAUNCH("convT_frag_pack_kernel");
-  const int KSP = (mode == 0 ? Cin : 2 * Cout) / 16;
-#define GO(M, K, N) return launch_gemm<T, M, K, N>(in, ldin, blob, bias, out, ldout, B, Di, Hi, Wi, Cout, st)
+  const int KSP = (mode == 0 ? P.Cin : 2 * P.Cout) / 16;
+#define GO(M, K, N) return launch_gemm<T, M, K, N>(P, in, blob, bias, out)
   if (mode == 0) {
     if (KSP == 4) GO(0, 4, 2);
     GO(0, 8, 4);
@@ -175,16 +173,15 @@ int run_gemm(int mode, const void *in, int ldin, const float *w_t, const float *
 
 // shapes the register-operand kernel serves: 16-bit storage, Cin = 2 * Cout in {64, 128} (the weights fit in LDS and the
 // per-wave K fits in registers), whole 32-voxel blocks worth having (Wi >= 32), vector-aligned operands
-bool convT_gemm_eligible(int mode, const void *in, int ldin, const void *out, int ldout, int Cin, int Cout, int Wi, int dtype) {
+bool convT_gemm_eligible(const ConvProblem &P, Src in, Dst out) {
   if (dgtta_switches().convt_gemm == '0') return false;
-  if (dtype != DGTTA_BF16 && dtype != DGTTA_F16) return false;
-  if (!((Cin == 64 && Cout == 32) || (Cin == 128 && Cout == 64))) return false;
-  if (Wi < 32) return false;
-  return ldin % 8 == 0 && ((uintptr_t)in & 15) == 0 && ldout % 8 == 0 && ((uintptr_t)out & 15) == 0;
+  if (P.dtype != DGTTA_BF16 && P.dtype != DGTTA_F16) return false;
+  if (!((P.Cin == 64 && P.Cout == 32) || (P.Cin == 128 && P.Cout == 64))) return false;
+  if (P.Wi < 32) return false;
+  return in.ld % 8 == 0 && ((uintptr_t)in.p & 15) == 0 && out.ld % 8 == 0 && ((uintptr_t)out.p & 15) == 0;
 }
 
-int convT_gemm_run(int mode, const void *in, int ldin, const float *w_t, const float *bias, void *out, int ldout, void *ws, int B,
-                   int Cin, int Cout, int Di, int Hi, int Wi, int dtype, hipStream_t st) {
-  if (dtype == DGTTA_BF16) return run_gemm<bf16_t>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, st);
-  return run_gemm<f16_t>(mode, in, ldin, w_t, bias, out, ldout, ws, B, Cin, Cout, Di, Hi, Wi, st);
+int convT_gemm_run(const ConvProblem &P, int mode, Src in, const float *w_t, const float *bias, Dst out, void *ws) {
+  if (P.dtype == DGTTA_BF16) return run_gemm<bf16_t>(P, mode, in, w_t, bias, out, ws);
+  return run_gemm<f16_t>(P, mode, in, w_t, bias, out, ws);
 }

@@ -198,8 +198,7 @@ static int convT_wgrad_classes(const WgradLaunch &L, float *dw_t, int sd, int sh
   RealTaps reals;
   wc.n = no;
   for (int o = 0; o < no; ++o) {
-    C.yv = lattice_view(L.yv.D, L.yv.H, L.yv.W, (int)L.yv.sw, sd, sh, sw, sd == 2 ? (o / (sh * sw)) % 2 : 0, sh == 2 ? (o / sw) % 2 : 0,
-                        sw == 2 ? o % 2 : 0, &wc.yoff[o]);
+    C.yv = lattice_view(L.yv, sd, sh, sw, o, &wc.yoff[o]);
     wc.mask[o] = 1u << 13;
     for (int t = 0; t < 27; ++t) reals.t[o].wt[t] = -1;
     reals.t[o].wt[13] = (signed char)o;
@@ -222,14 +221,14 @@ static int convT_tr_launch(const WgradLaunch &L, const WgradPlan &p, float *bp) 
 
 // ConvTranspose3d k2 s2 weight gradient: dw_t[ci][co][o] (+)= sum_v x[v][ci] * dout[2v+o][co]  (one pass, or 8 single-tap launches).
 // L.xv: the input lattice, L.yv: dout at full resolution
-static int convT_wgrad(const WgradLaunch &L, float *dw_t, int accumulate, float *bias_part, size_t bias_part_bytes, int *bias_units) {
+static int convT_wgrad(const WgradLaunch &L, float *dw_t, int accumulate, Region bias_part, int *bias_units) {
   if (bias_units) *bias_units = 0;
   if (L.dtype != DGTTA_F32) {
     const int one = dgtta_switches().convt_wgrad_onepass;      // DGTTA_CONVT_WGRAD_ONEPASS=0 (tests): the 8-class launch
     WgradPlan p = wgrad_plan(L.B, L.Cin, L.Cout, L.xv.D, L.xv.H, L.xv.W, 1, WT2::TWO, WT2::TH);      // same tile shape (2 rows x 16 voxels) on the input lattice
     if (wgrad_onepass_ok(L, p) && one != '0') {
       // bias partials [unit][32 cobs] ride along when the caller offers room for them
-      float *bp = (bias_part && bias_units && bias_part_bytes >= (size_t)p.units * p.cobs * 32 * sizeof(float)) ? bias_part : nullptr;
+      float *bp = (bias_part.p && bias_units && bias_part.bytes >= (size_t)p.units * p.cobs * 32 * sizeof(float)) ? (float *)bias_part.p : nullptr;
       if (bp) *bias_units = (int)p.units;
       const bool f16 = L.dtype == DGTTA_F16;
       int rc;
@@ -255,28 +254,27 @@ size_t convT_wgrad_split_extra_bytes(int B, int Cin, int Cout, int Di, int Hi, i
 
 // bias_part / bias_units (optional): room for [units][ceil(Cout / 32) * 32] floats; *bias_units > 0 on return means the launch left
 // the per-unit sums of dout there (convT_bias_finalize adds them up), 0 means the caller runs its own pass over dout
-int convT_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B,
-                     int Cin, int Cout, int Di, int Hi, int Wi, int accumulate, int dtype, hipStream_t st, float *bias_part,
-                     size_t bias_part_bytes, int *bias_units) {
+int convT_wgrad_mfma(const ConvProblem &P, Src x, Src dout, float *dw_t, Region ws, int accumulate, Region bias_part, int *bias_units) {
   if (bias_units) *bias_units = 0;
-  const View xv = dense_view(B, Di, Hi, Wi, ldx), yfull = dense_view(B, 2 * Di, 2 * Hi, 2 * Wi, lddo);
-  const WgradLaunch L{x, xv, dout, yfull, B, Cin, Cout, dtype, ws, ws_bytes, st};
-  if (dtype == DGTTA_F32) {
+  const int B = P.B, Di = P.Di, Hi = P.Hi, Wi = P.Wi;
+  const View xv = dense_view(B, Di, Hi, Wi, x.ld), yfull = dense_view(B, P.Dt(), P.Ht(), P.Wt(), dout.ld);
+  const WgradLaunch L{x.p, xv, dout.p, yfull, B, P.Cin, P.Cout, P.dtype, ws.p, ws.bytes, P.st};
+  if (P.dtype == DGTTA_F32) {
     // the caller offered the split workspace (dgtta_convT3d_bwd_split_ws_bytes): six 16-bit launches (DGTTA_WGRAD_F32_SPLIT=0: never)
-    const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, Cin, Cout, Di, Hi, Wi), 256);
-    const SplitOperand sx{(const float *)x, ldx, Cin, B, Di, Hi, Wi}, sy{(const float *)dout, lddo, Cout, B, 2 * Di, 2 * Hi, 2 * Wi};
-    const int rc = wgrad_f32_split(sx, sy, ws, ws_bytes, slab, accumulate, st,
+    const size_t slab = align_up(conv3_wgrad_mfma_ws_bytes(B, P.Cin, P.Cout, Di, Hi, Wi), 256);
+    const SplitOperand sx{(const float *)x.p, x.ld, P.Cin, B, Di, Hi, Wi}, sy{(const float *)dout.p, dout.ld, P.Cout, B, P.Dt(), P.Ht(), P.Wt()};
+    const int rc = wgrad_f32_split(sx, sy, ws.p, ws.bytes, slab, accumulate, P.st,
                                    [&](const bf16_t *xs, int ldxs, const bf16_t *gs, int ldys, int acc) {
       WgradLaunch leg = L;
-      leg.x = xs, leg.xv = dense_view(B, Di, Hi, Wi, ldxs), leg.dy = gs, leg.yv = dense_view(B, 2 * Di, 2 * Hi, 2 * Wi, ldys);
+      leg.x = xs, leg.xv = dense_view(B, Di, Hi, Wi, ldxs), leg.dy = gs, leg.yv = dense_view(B, P.Dt(), P.Ht(), P.Wt(), ldys);
       leg.dtype = DGTTA_BF16, leg.ws_bytes = slab;
-      return convT_wgrad(leg, dw_t, acc, nullptr, 0, nullptr);
+      return convT_wgrad(leg, dw_t, acc, Region{}, nullptr);
     });
     if (rc != DGTTA_ERR_UNSUPPORTED) return rc;
-    return convT_wgrad(L, dw_t, accumulate, nullptr, 0, nullptr);
+    return convT_wgrad(L, dw_t, accumulate, Region{}, nullptr);
   }
-  if (!wgrad_dtype_ok(dtype)) return DGTTA_ERR_UNSUPPORTED;
-  return convT_wgrad(L, dw_t, accumulate, bias_part, bias_part_bytes, bias_units);
+  if (!dtype_ok(P.dtype)) return DGTTA_ERR_UNSUPPORTED;
+  return convT_wgrad(L, dw_t, accumulate, bias_part, bias_units);
 }
 
 int convT_bias_finalize(const float *part, int units, int Cout, float *db, int accumulate, hipStream_t st) {
@@ -286,10 +284,9 @@ int convT_bias_finalize(const float *part, int units, int Cout, float *db, int a
 }
 
 // (the anisotropic plans' transposed convs: convT_wgrad_classes with any kernel = stride)
-int convTa_wgrad_mfma(const void *x, int ldx, const void *dout, int lddo, float *dw_t, void *ws, size_t ws_bytes, int B, int Cin,
-                      int Cout, int Di, int Hi, int Wi, int sd, int sh, int sw, int accumulate, int dtype, hipStream_t st) {
-  if (ws_bytes < wgrad_classes_bytes(B, Cin, Cout, Di, Hi, Wi, sd * sh * sw)) return DGTTA_ERR_WORKSPACE;
-  const View xv = dense_view(B, Di, Hi, Wi, ldx), yfull = dense_view(B, sd * Di, sh * Hi, sw * Wi, lddo);
-  const WgradLaunch L{x, xv, dout, yfull, B, Cin, Cout, dtype, ws, ws_bytes, st};
-  return convT_wgrad_classes(L, dw_t, sd, sh, sw, accumulate);
+int convTa_wgrad_mfma(const ConvProblem &P, Src x, Src dout, float *dw_t, Region ws, int accumulate) {
+  if (ws.bytes < wgrad_classes_bytes(P.B, P.Cin, P.Cout, P.Di, P.Hi, P.Wi, P.noff())) return DGTTA_ERR_WORKSPACE;
+  const View xv = dense_view(P.B, P.Di, P.Hi, P.Wi, x.ld), yfull = dense_view(P.B, P.Dt(), P.Ht(), P.Wt(), dout.ld);
+  const WgradLaunch L{x.p, xv, dout.p, yfull, P.B, P.Cin, P.Cout, P.dtype, ws.p, ws.bytes, P.st};
+  return convT_wgrad_classes(L, dw_t, P.sd, P.sh, P.sw, accumulate);
 }
