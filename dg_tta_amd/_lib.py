@@ -129,8 +129,13 @@ SIGNATURES = {
     "dgtta_intensity_stats": (I, [P, I, I64, C.POINTER(I), I, P, P, SZ, P]),
     "dgtta_intensity_map": (I, [P, P, I, I64, P, I, P, P, P]),
     "dgtta_gauss_blur3": (I, [P, P, P, I, I, I, I, P, I, P]),
+    "dgtta_mirror_batch": (I, [P, P, P, P, C.POINTER(I), I, I, I, I, I, P]),
+    "dgtta_window_gather": (I, [P, P, C.POINTER(I), C.POINTER(I), I, I, I, I, I, I, I, I, P]),
+    "dgtta_feature_window_accumulate_mirror": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_feature_window_accumulate_norm_mirror": (I, [P, P, P, P, F, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_seghead_window_accumulate_mirror_t": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_window_accumulate_mirror_t": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
 }
-
 
 
 class PatchItem(C.Structure):

@@ -21,6 +21,7 @@
 // logits-space accumulator where the top-2 margin is at rounding level - tests/test_inference.py compares both forms with the
 // CPU restatement outside such ties.  nnU-Net itself is absent from /root/reference: this stage is "parity unpinned" either way.
 #include "gfx950.h"
+#include "window_mirror.h"
 
 namespace {
 
@@ -51,10 +52,12 @@ __device__ __forceinline__ void wf_load4<f16_t>(const f16_t *p, float (&f)[4]) {
 // load and store instruction of a wave covers one contiguous run (z: 512 B, facc: 1 KiB; a window row is contiguous in the
 // volume along its last axis).  A launch touches every accumulator element once - overlapping windows are separate launches
 // in stream order, as in the logits-space form.
-template <typename T>
+// MIR (a mirrored pass of nnU-Net's test-time mirroring): the thread-to-destination mapping and gauss[p] stay, the source is read at
+// the mirrored voxel wm_source(p) - a wave row's 512 B of z are the same run, reversed voxel by voxel when the last axis is flipped.
+template <typename T, bool MIR>
 __global__ __launch_bounds__(256) void feature_accumulate_kernel(const T *__restrict__ z, const float *__restrict__ gauss,
-                                                                 float *__restrict__ facc, float *__restrict__ nsum, int PH, int PW,
-                                                                 int Y, int Z, int x0, int y0, int z0, int64_t total) {
+                                                                 float *__restrict__ facc, float *__restrict__ nsum, int PD, int PH, int PW,
+                                                                 int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int q = (int)(i & 7);
@@ -63,8 +66,9 @@ __global__ __launch_bounds__(256) void feature_accumulate_kernel(const T *__rest
   const int64_t pd = p / ((int64_t)PW * PH);
   const int64_t v = ((pd + x0) * Y + (ph + y0)) * Z + (pw + z0);
   const float g = gauss[p];
+  const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) : p;
   float f[4];
-  wf_load4<T>(z + p * WF_CIN + q * 4, f);
+  wf_load4<T>(z + ps * WF_CIN + q * 4, f);
   float4 *dst = reinterpret_cast<float4 *>(facc + v * WF_CIN + q * 4);
   float4 a = *dst;
   a.x += g * f[0], a.y += g * f[1], a.z += g * f[2], a.w += g * f[3];
@@ -86,12 +90,12 @@ __device__ __forceinline__ float wf_round<f16_t>(float v) { return f16_to_f32(f3
 // raw conv output y in registers (alpha = rstd * gamma, beta' = beta - mean * alpha: the arithmetic of in_apply_vec_kernel, so the
 // SAME z values) and never written - the apply pass (read y, write z) and the read of z disappear for the layer in front of the
 // head: 64 + 256 B per voxel instead of 128 + 320.  No backward exists in inference, so nothing else needs that z.
-template <typename T>
+template <typename T, bool MIR>
 __global__ __launch_bounds__(256) void feature_accumulate_norm_kernel(const T *__restrict__ y, const float *__restrict__ mean_rstd,
                                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
                                                                       float slope, const float *__restrict__ gauss,
-                                                                      float *__restrict__ facc, float *__restrict__ nsum, int PH, int PW,
-                                                                      int Y, int Z, int x0, int y0, int z0, int64_t total) {
+                                                                      float *__restrict__ facc, float *__restrict__ nsum, int PD, int PH, int PW,
+                                                                      int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
   __shared__ float sal[WF_CIN], sbe[WF_CIN];      // the window's per-channel constants, once per workgroup
   if (threadIdx.x < WF_CIN) {
     const int c = threadIdx.x;
@@ -108,8 +112,9 @@ __global__ __launch_bounds__(256) void feature_accumulate_norm_kernel(const T *_
   const int64_t pd = p / ((int64_t)PW * PH);
   const int64_t v = ((pd + x0) * Y + (ph + y0)) * Z + (pw + z0);
   const float g = gauss[p];
+  const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) : p;
   float f[4];
-  wf_load4<T>(y + p * WF_CIN + q * 4, f);
+  wf_load4<T>(y + ps * WF_CIN + q * 4, f);
   float4 *dst = reinterpret_cast<float4 *>(facc + v * WF_CIN + q * 4);
   float4 a = *dst;
   float zz[4];
@@ -446,53 +451,95 @@ __global__ void feature_logits_chunk_kernel(const float *__restrict__ facc, int6
 
 }  // namespace
 
-extern "C" int dgtta_feature_window_accumulate(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
-                                               int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, void *stream) {
-  DG_REQUIRE(z && gauss && facc, DGTTA_ERR_BADARG, "feature_window_accumulate: null pointer");
-  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate: built for %d feature channels (got %d)", WF_CIN, Cin);
-  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "feature_window_accumulate: dtype %d", dtype);
+// The unmirrored and the mirrored entries share one host body each (mirror = 0 launches the kernels the unmirrored entries always
+// launched: their bits).
+static int feature_window_accumulate_impl(const char *who, const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
+                                          int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror, int dtype, void *stream) {
+  DG_REQUIRE(z && gauss && facc, DGTTA_ERR_BADARG, "%s: null pointer", who);
+  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "%s: built for %d feature channels (got %d)", who, WF_CIN, Cin);
+  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: dtype %d", who, dtype);
+  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
   DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "feature_window_accumulate: window outside the volume");
-  DG_REQUIRE(((uintptr_t)z & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "feature_window_accumulate: unaligned buffer");
+             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
+  DG_REQUIRE(((uintptr_t)z & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned buffer", who);
   const int64_t total = (int64_t)PD * PH * PW * 8;
   const int64_t nblk = cdiv64(total, 256);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate: window too large");
+  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: window too large", who);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DGTTA_F32)
-    hipLaunchKernelGGL(feature_accumulate_kernel<float>, dim3((unsigned)nblk), dim3(256), 0, st, (const float *)z, gauss, facc, nsum, PH,
-                       PW, Y, Z, x0, y0, z0, total);
-  else if (dtype == DGTTA_BF16)
-    hipLaunchKernelGGL(feature_accumulate_kernel<bf16_t>, dim3((unsigned)nblk), dim3(256), 0, st, (const bf16_t *)z, gauss, facc, nsum,
-                       PH, PW, Y, Z, x0, y0, z0, total);
-  else
-    hipLaunchKernelGGL(feature_accumulate_kernel<f16_t>, dim3((unsigned)nblk), dim3(256), 0, st, (const f16_t *)z, gauss, facc, nsum, PH,
-                       PW, Y, Z, x0, y0, z0, total);
+#define WF_LAUNCH(T, MIR)                                                                                                            \
+  hipLaunchKernelGGL((feature_accumulate_kernel<T, MIR>), dim3((unsigned)nblk), dim3(256), 0, st, (const T *)z, gauss, facc, nsum, PD, PH, \
+                     PW, Y, Z, x0, y0, z0, mirror, total)
+#define WF_LAUNCH_T(MIR)                               \
+  do {                                                 \
+    if (dtype == DGTTA_F32) WF_LAUNCH(float, MIR);       \
+    else if (dtype == DGTTA_BF16) WF_LAUNCH(bf16_t, MIR); \
+    else WF_LAUNCH(f16_t, MIR);                          \
+  } while (0)
+  if (mirror) WF_LAUNCH_T(true);
+  else WF_LAUNCH_T(false);
+#undef WF_LAUNCH_T
+#undef WF_LAUNCH
   DG_CHECK_LAUNCH("feature_accumulate_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_feature_window_accumulate(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
+                                               int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, void *stream) {
+  return feature_window_accumulate_impl("feature_window_accumulate", z, gauss, facc, nsum, Cin, PD, PH, PW, X, Y, Z, x0, y0, z0, 0, dtype,
+                                        stream);
+}
+
+extern "C" int dgtta_feature_window_accumulate_mirror(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
+                                                      int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, int mirror,
+                                                      void *stream) {
+  return feature_window_accumulate_impl("feature_window_accumulate_mirror", z, gauss, facc, nsum, Cin, PD, PH, PW, X, Y, Z, x0, y0, z0,
+                                        mirror, dtype, stream);
+}
+
+static int feature_window_accumulate_norm_impl(const char *who, const void *y, const float *mean_rstd, const float *gamma, const float *beta,
+                                               float slope, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW,
+                                               int X, int Y, int Z, int x0, int y0, int z0, int mirror, int dtype, void *stream) {
+  DG_REQUIRE(y && mean_rstd && gamma && beta && gauss && facc, DGTTA_ERR_BADARG, "%s: null pointer", who);
+  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "%s: built for %d feature channels (got %d)", who, WF_CIN, Cin);
+  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: dtype %d", who, dtype);
+  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
+  DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
+             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
+  DG_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned buffer", who);
+  const int64_t total = (int64_t)PD * PH * PW * 8;
+  const int64_t nblk = cdiv64(total, 256);
+  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: window too large", who);
+  hipStream_t st = (hipStream_t)stream;
+#define WF_LAUNCH(T, MIR)                                                                                                                   \
+  hipLaunchKernelGGL((feature_accumulate_norm_kernel<T, MIR>), dim3((unsigned)nblk), dim3(256), 0, st, (const T *)y, mean_rstd, gamma, beta, \
+                     slope, gauss, facc, nsum, PD, PH, PW, Y, Z, x0, y0, z0, mirror, total)
+#define WF_LAUNCH_T(MIR)                               \
+  do {                                                 \
+    if (dtype == DGTTA_F32) WF_LAUNCH(float, MIR);       \
+    else if (dtype == DGTTA_BF16) WF_LAUNCH(bf16_t, MIR); \
+    else WF_LAUNCH(f16_t, MIR);                          \
+  } while (0)
+  if (mirror) WF_LAUNCH_T(true);
+  else WF_LAUNCH_T(false);
+#undef WF_LAUNCH_T
+#undef WF_LAUNCH
+  DG_CHECK_LAUNCH("feature_accumulate_norm_kernel");
   return DGTTA_OK;
 }
 
 extern "C" int dgtta_feature_window_accumulate_norm(const void *y, const float *mean_rstd, const float *gamma, const float *beta, float slope,
                                                     const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW, int X,
                                                     int Y, int Z, int x0, int y0, int z0, int dtype, void *stream) {
-  DG_REQUIRE(y && mean_rstd && gamma && beta && gauss && facc, DGTTA_ERR_BADARG, "feature_window_accumulate_norm: null pointer");
-  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate_norm: built for %d feature channels (got %d)", WF_CIN, Cin);
-  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "feature_window_accumulate_norm: dtype %d", dtype);
-  DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "feature_window_accumulate_norm: window outside the volume");
-  DG_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "feature_window_accumulate_norm: unaligned buffer");
-  const int64_t total = (int64_t)PD * PH * PW * 8;
-  const int64_t nblk = cdiv64(total, 256);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate_norm: window too large");
-  hipStream_t st = (hipStream_t)stream;
-#define WF_LAUNCH(T)                                                                                                              \
-  hipLaunchKernelGGL(feature_accumulate_norm_kernel<T>, dim3((unsigned)nblk), dim3(256), 0, st, (const T *)y, mean_rstd, gamma, beta, \
-                     slope, gauss, facc, nsum, PH, PW, Y, Z, x0, y0, z0, total)
-  if (dtype == DGTTA_F32) WF_LAUNCH(float);
-  else if (dtype == DGTTA_BF16) WF_LAUNCH(bf16_t);
-  else WF_LAUNCH(f16_t);
-#undef WF_LAUNCH
-  DG_CHECK_LAUNCH("feature_accumulate_norm_kernel");
-  return DGTTA_OK;
+  return feature_window_accumulate_norm_impl("feature_window_accumulate_norm", y, mean_rstd, gamma, beta, slope, gauss, facc, nsum, Cin, PD,
+                                             PH, PW, X, Y, Z, x0, y0, z0, 0, dtype, stream);
+}
+
+extern "C" int dgtta_feature_window_accumulate_norm_mirror(const void *y, const float *mean_rstd, const float *gamma, const float *beta,
+                                                           float slope, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
+                                                           int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, int mirror,
+                                                           void *stream) {
+  return feature_window_accumulate_norm_impl("feature_window_accumulate_norm_mirror", y, mean_rstd, gamma, beta, slope, gauss, facc, nsum,
+                                             Cin, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, dtype, stream);
 }
 
 extern "C" int dgtta_feature_window_accumulate_multi(const void *const *h_srcs, const float *const *h_mean_rstds, const int *h_zoffs, int nsrc,

@@ -14,6 +14,7 @@
 // the accumulator - float, or f16_t (what nnU-Net's predictor keeps, 2.2.1 `predicted_logits` dtype torch.half); the sum is
 // formed in fp32 either way and rounded once per window on the way back.
 #include "gfx950.h"
+#include "window_mirror.h"
 
 namespace {
 
@@ -79,11 +80,13 @@ struct AccRun<f16_t> {
   }
 };
 
-template <typename T, typename ACC>
+// MIR (both head kernels): a mirrored pass of nnU-Net's test-time mirroring - the feature row of a destination voxel is read at the
+// mirrored voxel of the window (wm_source); the destination, its Gaussian weight and everything after the load are the unmirrored ones.
+template <typename T, typename ACC, bool MIR>
 __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
                                                               ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0) {
+                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   // the head's weights are the same for every lane of a wave (a wave = 64 voxels x one class at a time): they are read
@@ -113,7 +116,8 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
     __syncthreads();                                              // previous tile consumed
     if (vox < nv) {
       float xr[HA_CIN];
-      const uint4 *zr = reinterpret_cast<const uint4 *>(z + p * HA_CIN);
+      const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw0 + vox, PD, PH, PW) : p;
+      const uint4 *zr = reinterpret_cast<const uint4 *>(z + ps * HA_CIN);
 #pragma unroll
       for (int g = 0; g < 4; ++g) unpack16<T>(zr[g], xr + 8 * g);
       const float gq = gauss[p];
@@ -144,11 +148,11 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
 // times 16-bit terms are exact in the fp32 accumulator, so the logits differ from the FMA chain by the order of the 32-term
 // sum only (tests: <= a few 1e-7 of the row's magnitude, same labels outside float ties).
 static_assert(HA_MAXC <= 8 * 16, "a wave takes class groups wv and wv + 4: at most 8 groups of 16 classes");
-template <typename T, typename ACC>
+template <typename T, typename ACC, bool MIR>
 __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
                                                               ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0) {
+                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -193,6 +197,7 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
   struct TilePos {
     int nv, n;
     int64_t prow, vg;
+    int pd, ph, pw0;      // (read by the mirrored source index only)
   };
   auto tile_pos = [&](int blk) {
     const int row = blk / runs, pw0 = (blk % runs) * 64;
@@ -202,6 +207,7 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
     t.n = t.nv * C;
     t.prow = ((int64_t)pd * PH + ph) * PW + pw0;                  // first voxel of the run inside the window
     t.vg = ((int64_t)(x0 + pd) * Y + (y0 + ph)) * Z + (z0 + pw0); // ... and inside the volume
+    t.pd = pd, t.ph = ph, t.pw0 = pw0;
     return t;
   };
   AccRun<ACC> run, run_n;
@@ -222,7 +228,8 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
       zz[vgp] = make_uint4(0u, 0u, 0u, 0u);
       gg[vgp] = 0.f;
       if (vox < t.nv) {
-        zz[vgp] = *reinterpret_cast<const uint4 *>(z + (t.prow + vox) * HA_CIN + lq * 8);
+        const int64_t ps = MIR ? wm_source(mirror, t.pd, t.ph, t.pw0 + vox, PD, PH, PW) : t.prow + vox;
+        zz[vgp] = *reinterpret_cast<const uint4 *>(z + ps * HA_CIN + lq * 8);
         gg[vgp] = gauss[t.prow + vox];
       }
     }
@@ -273,43 +280,69 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
 
 }  // namespace
 
-extern "C" int dgtta_seghead_window_accumulate_t(const void *z, const float *w, const float *bias, const float *gauss, void *acc,
-                                                 float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0,
-                                                 int y0, int z0, int dtype, int acc_dtype, void *stream) {
-  DG_REQUIRE(z && w && bias && gauss && acc, DGTTA_ERR_BADARG, "seghead_window_accumulate: null pointer");
+static int seghead_window_accumulate_impl(const char *who, const void *z, const float *w, const float *bias, const float *gauss, void *acc,
+                                          float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0,
+                                          int mirror, int dtype, int acc_dtype, void *stream) {
+  DG_REQUIRE(z && w && bias && gauss && acc, DGTTA_ERR_BADARG, "%s: null pointer", who);
   DG_REQUIRE(Cin == HA_CIN && C > 0 && C <= HA_MAXC && (dtype == DGTTA_BF16 || dtype == DGTTA_F16), DGTTA_ERR_UNSUPPORTED,
-             "seghead_window_accumulate: built for 32 input channels, up to %d classes, 16-bit storage", HA_MAXC);
-  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED,
-             "seghead_window_accumulate: the accumulator is fp32 or fp16 (acc_dtype %d)", acc_dtype);
+             "%s: built for 32 input channels, up to %d classes, 16-bit storage", who, HA_MAXC);
+  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED, "%s: the accumulator is fp32 or fp16 (acc_dtype %d)",
+             who, acc_dtype);
+  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
+  DG_REQUIRE(!mirror || acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "%s: a mirrored pass needs the fp32 accumulator", who);
   DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "seghead_window_accumulate: window outside the volume");
-  DG_REQUIRE(((uintptr_t)z & 15) == 0, DGTTA_ERR_BADARG, "seghead_window_accumulate: unaligned feature map");
+             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
+  DG_REQUIRE(((uintptr_t)z & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned feature map", who);
   const int64_t nblk = (int64_t)PD * PH * cdiv(PW, 64);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "seghead_window_accumulate: too many rows");
+  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: too many rows", who);
   const size_t lds = (size_t)64 * C * sizeof(float);
-  static DynLdsOnce once[8];
+  static DynLdsOnce once[16];
   const dim3 grid((unsigned)(nblk < 2048 ? nblk : 2048));
   hipStream_t st = (hipStream_t)stream;
   const bool fma = dgtta_switches().ha_mfma == '0';
-#define HA_LAUNCH(IDX, T, ACC)                                                                                               \
-  do {                                                                                                                       \
-    const void *fn = fma ? (const void *)head_accumulate_fma_kernel<T, ACC> : (const void *)head_accumulate_kernel<T, ACC>;  \
-    DG_REQUIRE(ensure_dyn_lds(once[IDX + (fma ? 4 : 0)], fn, (int)lds) == hipSuccess, DGTTA_ERR_LAUNCH,                      \
-               "seghead_window_accumulate: cannot raise the dynamic LDS limit");                                             \
-    if (fma)                                                                                                                 \
-      hipLaunchKernelGGL((head_accumulate_fma_kernel<T, ACC>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,       \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0);                                              \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((head_accumulate_kernel<T, ACC>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,           \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0);                                              \
+#define HA_LAUNCH_M(IDX, T, ACC, MIR)                                                                                                  \
+  do {                                                                                                                                 \
+    const void *fn = fma ? (const void *)head_accumulate_fma_kernel<T, ACC, MIR> : (const void *)head_accumulate_kernel<T, ACC, MIR>;  \
+    DG_REQUIRE(ensure_dyn_lds(once[IDX + (fma ? 4 : 0) + (MIR ? 8 : 0)], fn, (int)lds) == hipSuccess, DGTTA_ERR_LAUNCH,                \
+               "%s: cannot raise the dynamic LDS limit", who);                                                                         \
+    if (fma)                                                                                                                           \
+      hipLaunchKernelGGL((head_accumulate_fma_kernel<T, ACC, MIR>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,            \
+                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror);                                                \
+    else                                                                                                                               \
+      hipLaunchKernelGGL((head_accumulate_kernel<T, ACC, MIR>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,                \
+                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror);                                                \
+  } while (0)
+#define HA_LAUNCH(IDX, T, ACC)                   \
+  do {                                           \
+    if (mirror) HA_LAUNCH_M(IDX, T, ACC, true);  \
+    else HA_LAUNCH_M(IDX, T, ACC, false);        \
   } while (0)
   if (dtype == DGTTA_BF16 && acc_dtype == DGTTA_F32) HA_LAUNCH(0, bf16_t, float);
-  else if (dtype == DGTTA_BF16) HA_LAUNCH(1, bf16_t, f16_t);
+  else if (dtype == DGTTA_BF16) HA_LAUNCH_M(1, bf16_t, f16_t, false);      // (a mirrored pass never meets a fp16 accumulator: checked above)
   else if (acc_dtype == DGTTA_F32) HA_LAUNCH(2, f16_t, float);
-  else HA_LAUNCH(3, f16_t, f16_t);
+  else HA_LAUNCH_M(3, f16_t, f16_t, false);
 #undef HA_LAUNCH
+#undef HA_LAUNCH_M
   DG_CHECK_LAUNCH("head_accumulate_kernel");
   return DGTTA_OK;
+}
+
+extern "C" int dgtta_seghead_window_accumulate_t(const void *z, const float *w, const float *bias, const float *gauss, void *acc,
+                                                 float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0,
+                                                 int y0, int z0, int dtype, int acc_dtype, void *stream) {
+  return seghead_window_accumulate_impl("seghead_window_accumulate", z, w, bias, gauss, acc, nsum, Cin, C, PD, PH, PW, X, Y, Z, x0, y0, z0, 0,
+                                        dtype, acc_dtype, stream);
+}
+
+// The logits-space forms of a mirrored pass: fp32 accumulators only (eight passes per window at Gaussian weight 10 leave no headroom
+// in half).
+extern "C" int dgtta_seghead_window_accumulate_mirror_t(const void *z, const float *w, const float *bias, const float *gauss, void *acc,
+                                                        float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0,
+                                                        int y0, int z0, int dtype, int acc_dtype, int mirror, void *stream) {
+  DG_REQUIRE(acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "seghead_window_accumulate_mirror: the accumulator is fp32 (acc_dtype %d)",
+             acc_dtype);
+  return seghead_window_accumulate_impl("seghead_window_accumulate_mirror", z, w, bias, gauss, acc, nsum, Cin, C, PD, PH, PW, X, Y, Z, x0,
+                                        y0, z0, mirror, dtype, acc_dtype, stream);
 }
 
 extern "C" int dgtta_seghead_window_accumulate(const void *z, const float *w, const float *bias, const float *gauss, float *acc,
@@ -325,39 +358,56 @@ extern "C" int dgtta_seghead_window_accumulate(const void *z, const float *w, co
 //   acc[v0 + p][c] += patch[p][c] * gauss[p];   nsum[v0 + p] += gauss[p]        (voxel-major fp32 accumulators)
 // One lane per (patch voxel, channel): rows of C floats are contiguous, windows overlap only between launches.
 namespace {
-template <typename ACC>
+template <typename ACC, bool MIR>
 __global__ void window_accumulate_kernel(const float *__restrict__ patch, const float *__restrict__ gauss,
                                          ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD, int PH, int PW,
-                                         int X, int Y, int Z, int x0, int y0, int z0, int64_t total) {
+                                         int X, int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const int64_t p = i / C;
     const int pw = (int)(p % PW), ph = (int)((p / PW) % PH), pd = (int)(p / ((int64_t)PW * PH));
     const int64_t v = ((int64_t)(x0 + pd) * Y + (y0 + ph)) * Z + (z0 + pw);
     const float g = gauss[p];
-    st_f<ACC>(acc + v * C + c, ld_f<ACC>(acc + v * C + c) + patch[i] * g);
+    const int64_t is = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) * C + c : i;      // the mirrored voxel's row of C logits
+    st_f<ACC>(acc + v * C + c, ld_f<ACC>(acc + v * C + c) + patch[is] * g);
     if (c == 0 && nsum) nsum[v] += g;
   }
 }
 }  // namespace
 
-extern "C" int dgtta_window_accumulate_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
-                                         int PW, int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, void *stream) {
-  DG_REQUIRE(patch && gauss && acc, DGTTA_ERR_BADARG, "window_accumulate: null pointer");
+static int window_accumulate_impl(const char *who, const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
+                                  int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror, int acc_dtype, void *stream) {
+  DG_REQUIRE(patch && gauss && acc, DGTTA_ERR_BADARG, "%s: null pointer", who);
+  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
   DG_REQUIRE(C > 0 && PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y &&
                  z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "window_accumulate: window outside the volume");
-  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED,
-             "window_accumulate: the accumulator is fp32 or fp16 (acc_dtype %d)", acc_dtype);
+             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
+  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED, "%s: the accumulator is fp32 or fp16 (acc_dtype %d)",
+             who, acc_dtype);
+  DG_REQUIRE(!mirror || acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "%s: a mirrored pass needs the fp32 accumulator", who);
   const int64_t total = (int64_t)PD * PH * PW * C;
-  if (acc_dtype == DGTTA_F32)
-    hipLaunchKernelGGL(window_accumulate_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, patch, gauss,
-                       (float *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, total);
-  else
-    hipLaunchKernelGGL(window_accumulate_kernel<f16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, patch, gauss,
-                       (f16_t *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, total);
+#define WA_LAUNCH(ACC, MIR)                                                                                                            \
+  hipLaunchKernelGGL((window_accumulate_kernel<ACC, MIR>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, patch, gauss,       \
+                     (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, total)
+  if (acc_dtype == DGTTA_F32 && mirror) WA_LAUNCH(float, true);
+  else if (acc_dtype == DGTTA_F32) WA_LAUNCH(float, false);
+  else WA_LAUNCH(f16_t, false);
+#undef WA_LAUNCH
   DG_CHECK_LAUNCH("window_accumulate_kernel");
   return DGTTA_OK;
+}
+
+extern "C" int dgtta_window_accumulate_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
+                                         int PW, int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, void *stream) {
+  return window_accumulate_impl("window_accumulate", patch, gauss, acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, 0, acc_dtype, stream);
+}
+
+extern "C" int dgtta_window_accumulate_mirror_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
+                                                int PW, int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, int mirror,
+                                                void *stream) {
+  DG_REQUIRE(acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "window_accumulate_mirror: the accumulator is fp32 (acc_dtype %d)", acc_dtype);
+  return window_accumulate_impl("window_accumulate_mirror", patch, gauss, acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, acc_dtype,
+                                stream);
 }
 
 extern "C" int dgtta_window_accumulate(const float *patch, const float *gauss, float *acc, float *nsum, int C, int PD, int PH,

@@ -1047,6 +1047,68 @@ def sample_patches_aug(coefs, label_maps, maps, patch_size, order=3):
     return image, labels
 
 
+# ------------------------------------------------------------------------------------------------ mirroring
+MIRROR_SUBSET_ORDER = ((), (0,), (1,), (2,), (0, 1), (0, 2), (1, 2), (0, 1, 2))
+
+
+def check_mirror_axes(axes):
+    """None, or the sorted tuple of a subset of (0, 1, 2) (an empty subset is None: nothing to mirror)."""
+    if axes is None:
+        return None
+    axes = tuple(sorted(int(a) for a in axes))
+    if len(set(axes)) != len(axes) or any(a not in (0, 1, 2) for a in axes):
+        raise ValueError(f"mirror axes {axes}: None or a subset of (0, 1, 2) expected")
+    return axes or None
+
+
+def mirror_masks(axes):
+    """The mirror masks (bit a = axis a flipped) of every subset of the allowed axes, in the order nnU-Net's predictor runs its
+    passes: (), (0), (1), (2), (0,1), (0,2), (1,2), (0,1,2) restricted to `axes`.  None -> [0]."""
+    axes = check_mirror_axes(axes)
+    if axes is None:
+        return [0]
+    return [sum(1 << a for a in s) for s in MIRROR_SUBSET_ORDER if all(a in axes for a in s)]
+
+
+def mirror_batch(images, labels, masks):
+    """nnU-Net's MirrorTransform on a batch in one launch (csrc/mirror.hip): images float32 [B, C, D, H, W] and labels int64
+    [B, D, H, W] on the GPU, masks: B host integers 0..7 (bit 0 = D, bit 1 = H, bit 2 = W flipped; 0 = copied).  Returns new
+    (images, labels)."""
+    import ctypes
+    require_cuda(images, labels)
+    B = images.shape[0] if images.dim() == 5 else -1
+    if (images.dim() != 5 or images.dtype != torch.float32 or labels.dtype != torch.int64 or
+            tuple(labels.shape) != (B, *images.shape[2:]) or labels.device != images.device):
+        raise ValueError(f"mirror_batch: float32 images [B, C, D, H, W] and int64 labels [B, D, H, W] on one device expected "
+                         f"(got {tuple(images.shape)} {images.dtype}, {tuple(labels.shape)} {labels.dtype})")
+    masks = [int(m) for m in masks]
+    if len(masks) != B or any(not 0 <= m <= 7 for m in masks):
+        raise ValueError(f"mirror_batch: {B} masks in 0..7 expected (got {masks})")
+    images, labels = images.contiguous(), labels.contiguous()
+    out_i, out_l = torch.empty_like(images), torch.empty_like(labels)
+    check(_lib.load().dgtta_mirror_batch(ptr(images), ptr(labels), ptr(out_i), ptr(out_l), (ctypes.c_int * B)(*masks), B,
+                                         *(int(s) for s in images.shape[1:]), stream_of(images.device)), "dgtta_mirror_batch")
+    return out_i, out_l
+
+
+def window_gather(volume, origins, masks, patch_size):
+    """The window batch [n, C, *patch_size] (float32) of sliding-window inference with mirroring, in one launch per 16 windows
+    (csrc/mirror.hip): window k is the block of `volume` [C, X, Y, Z] (float32, GPU) at origins[k], flipped along the axes of
+    masks[k]."""
+    import ctypes
+    require_cuda(volume)
+    n = len(origins)
+    if volume.dim() != 4 or volume.dtype != torch.float32 or len(masks) != n or n < 1:
+        raise ValueError("window_gather: a float32 volume [C, X, Y, Z], n >= 1 origins and n masks expected")
+    volume = volume.contiguous()
+    flat = [int(v) for o in origins for v in o]
+    out = torch.empty((n, volume.shape[0], *(int(p) for p in patch_size)), dtype=torch.float32, device=volume.device)
+    check(_lib.load().dgtta_window_gather(ptr(volume), ptr(out), (ctypes.c_int * (3 * n))(*flat), (ctypes.c_int * n)(*[int(m) for m in masks]),
+                                          n, volume.shape[0], *(int(p) for p in patch_size), *(int(s) for s in volume.shape[1:]),
+                                          stream_of(volume.device)), "dgtta_window_gather")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ intensity augmentation
 IMAP_MODES = {"linear": _lib.IMAP_LINEAR, "contrast": _lib.IMAP_CONTRAST, "gamma": _lib.IMAP_GAMMA, "restore": _lib.IMAP_RESTORE}
 

@@ -3,28 +3,25 @@ dg_tta/pretraining/nnUNetTrainer_GIN_MIND.py:38-59, nnUNetTrainer_GIN.py:38-58, 
 channel count of the descriptor (12 for MIND), internal augmentation switched on, and the forward pre-hooks registered
 in the reference's order (gin_hook first, then mind_hook).  The hooks run the HIP kernels (csrc/gin.hip, csrc/mind3d.hip)
 for any batch size, GIN with one random kernel chain per batch item (groups = nb, gin.py:168-230)."""
-from ..gin import gin_hook
-from ..mind import mind_hook
+from ..gin import gin_hook  # noqa: F401  (re-exported: the hooks this module registers)
+from ..mind import mind_hook  # noqa: F401
+from ..tta.nnunet_utils import trainer_hooks, trainer_mirror_axes  # noqa: F401
 from ..unet import PLANS_3D_FULLRES, HipPlainConvUNet
 from ..utils import enable_internal_augmentation
 
 
 def trainer_spec(trainer_name):
-    """(network input channels, [pre-hooks]) of a DG trainer name (with or without the _MultiRes suffix)."""
-    name = trainer_name.replace("_MultiRes", "")
-    if name.endswith("GIN_MIND"):
-        return 12, [gin_hook, mind_hook]
-    if name.endswith("MIND"):
-        return 12, [mind_hook]
-    if name.endswith("GIN"):
-        return 1, [gin_hook]
-    raise NotImplementedError(f"trainer {trainer_name}: only the DG-TTA trainers (GIN / MIND / GIN_MIND) are built")
+    """(network input channels, [pre-hooks]) of a DG trainer name (with or without the _MultiRes suffix), or of the stock
+    nnUNetTrainer: (1, [])."""
+    return trainer_hooks(trainer_name)
 
 
 def register_dg_hooks(network, trainer_name="nnUNetTrainer_GIN_MIND"):
-    """enable_internal_augmentation() + register_forward_pre_hook(gin_hook / mind_hook), as the trainers do."""
+    """enable_internal_augmentation() + register_forward_pre_hook(gin_hook / mind_hook), as the trainers do.  A trainer
+    without hooks (the stock nnUNetTrainer) has no internal augmentation to switch on."""
     _, hooks = trainer_spec(trainer_name)
-    enable_internal_augmentation()
+    if hooks:
+        enable_internal_augmentation()
     return [network.register_forward_pre_hook(h) for h in hooks]
 
 

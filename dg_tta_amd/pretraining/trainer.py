@@ -16,7 +16,15 @@ transforms are NOT applied.  `augmentation="spatial"` (`--augmentation spatial`)
 (`--augmentation full`) adds both: the rotation / scaling and nnU-Net's noise / blur / brightness / contrast / low-resolution /
 gamma chain (pretraining/intensity.py, csrc/intensity_aug.hip), with the *_MultiRes trainers' discrete low-resolution transform
 in the chain's low-resolution slot, where the reference puts it.  What `full` still lacks against nnU-Net: elastic deformation
-(nnU-Net's default switches it off too) and mirroring (the DG trainers switch it off).  Experiment planning is out of
+(nnU-Net's default switches it off too); mirroring is off for the DG trainers, as they set it.
+
+THE STOCK TRAINER: `nnUNetTrainer` (TRAINERS = DG_TRAINERS + it) is the baseline the DG trainers are compared with: one image
+channel, no hooks, no internal augmentation - and nnU-Net's MirrorTransform (from memory of nnunetv2 2.2 / batchgenerators,
+UNPINNED) as the LAST transform of every training batch, after the intensity stages, whatever `augmentation` says: for every batch
+item and every axis of trainer_mirror_axes(trainer_name) = (0, 1, 2), independently, image and label are flipped with probability
+0.5 (draw_mirror_masks states the draws; one ops.mirror_batch launch, csrc/mirror.hip).  Validation batches are never mirrored.
+Its checkpoint carries inference_allowed_mirroring_axes = [0, 1, 2], which sliding-window inference obeys (tta/inference.py); a DG
+trainer's carries None, draws nothing for mirroring and runs the code it ran before.  Multi-channel data stays out.  Experiment planning is out of
 scope: nnUNetPlans.json must exist.  Random streams are not part of a checkpoint: a continued run draws differently from
 an uninterrupted one."""
 import json
@@ -37,11 +45,12 @@ from ..tta.torch_utils import _resident, as_label_map_case, get_batch, release_r
 from ..unet import HipPlainConvUNet
 from ..utils import disable_internal_augmentation, numpy_rng
 from .discrete_downsampling import SimulateDiscreteLowResolutionTransform
-from .hooks import register_dg_hooks, trainer_spec
+from .hooks import register_dg_hooks, trainer_mirror_axes, trainer_spec
 from .intensity import IntensityAugmentation
 from .spatial import SpatialAugmentation, patch_start, sampling_map
 
 DG_TRAINERS = tuple(f"nnUNetTrainer_{n}{m}" for m in ("", "_MultiRes") for n in ("GIN", "MIND", "GIN_MIND"))
+TRAINERS = DG_TRAINERS + ("nnUNetTrainer",)
 INITIAL_LR = 1e-2
 OVERSAMPLE_FOREGROUND = 0.33
 MAX_LOCATIONS_PER_CLASS = 10000
@@ -186,7 +195,8 @@ def load_case(name, entry, plans, configuration, device):
     with np.load(npz) as z:
         data, seg = z["data"], z["seg"]
     if data.shape[0] != 1:
-        raise NotImplementedError(f"case {name}: {data.shape[0]} image channels; the DG trainers' hooks take one")
+        raise NotImplementedError(f"case {name}: {data.shape[0]} image channels; the DG trainers' hooks and the stock "
+                                  f"nnUNetTrainer as built here take one")
     return _Case(name, data, seg)
 
 
@@ -261,6 +271,29 @@ def _sample(cases, batch_size, patch, device, multires, spatial=None, *, intensi
     return torch.stack(imgs), torch.cat(labels, dim=0)[:, 0], picks
 
 
+def draw_mirror_masks(batch_size, axes, rng):
+    """nnU-Net's MirrorTransform draws for one training batch: for every item and every allowed axis, independently, a flip with
+    probability 0.5.  Draws (numpy_rng(), in this order): item-major, axis 0 first, one rng.uniform() per (item, axis) of `axes`,
+    flipped when the draw is < 0.5 - len(axes) * batch_size draws, and NONE when axes is None (a DG trainer's stream does not
+    move).  Returns one mask per item: bit a set = axis a flipped (ops.mirror_batch)."""
+    if axes is None:
+        return [0] * batch_size
+    return [sum(1 << a for a in axes if rng.uniform() < 0.5) for _ in range(batch_size)]
+
+
+def _mirror(imgs, target, axes):
+    """The last transform of the training chain (after the intensity stages): one ops.mirror_batch launch for the batch; nothing
+    is drawn or launched for a trainer without mirror axes.  The deep-supervision targets are read from the full-resolution
+    label map inside ops.deep_supervision_loss, so flipping that map is enough."""
+    if axes is None:
+        return imgs, target
+    masks = draw_mirror_masks(imgs.shape[0], axes, numpy_rng())
+    if not any(masks):
+        return imgs, target
+    with torch.no_grad():
+        return ops.mirror_batch(imgs, target, masks)
+
+
 # ------------------------------------------------------------------------------------------------ the loop
 def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iterations_per_epoch=250, val_iterations=50,
                device="cuda", act_dtype=torch.float32, continue_training=False, seed=None, augmentation="reduced"):
@@ -284,8 +317,9 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
             intensity = IntensityAugmentation()
     else:
         raise ValueError(f"augmentation {augmentation!r}: one of {', '.join(AUGMENTATIONS)} expected")
-    if trainer_name not in DG_TRAINERS:
-        raise ValueError(f"trainer {trainer_name}: one of {', '.join(DG_TRAINERS)} expected")
+    if trainer_name not in TRAINERS:
+        raise ValueError(f"trainer {trainer_name}: one of {', '.join(TRAINERS)} expected")
+    mirror_axes = trainer_mirror_axes(trainer_name)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("dg_tta_amd trains on the MI355X only (no CPU fallback)")
@@ -371,7 +405,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
         torch.save({"network_weights": {k: v.detach().cpu() for k, v in net.state_dict().items()},
                     "optimizer_state": opt.state_dict(), "current_epoch": epoch, "trainer_name": trainer_name,
                     "init_args": dict(plans=plans, configuration=configuration, fold=fold, dataset_json=dataset_json),
-                    "inference_allowed_mirroring_axes": None, "logging": log,
+                    "inference_allowed_mirroring_axes": None if mirror_axes is None else list(mirror_axes), "logging": log,
                     "grad_scaler_state": {"scale": opt.grad_scale}}, fold_dir / name)
 
     handles = register_dg_hooks(net, trainer_name)          # switches the internal augmentation on, as the trainers do
@@ -387,6 +421,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                     if opt.resolve_overflow():             # (reads a flag only on the guarded fp16 path)
                         print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
                     imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial, intensity=intensity)
+                    imgs, target = _mirror(imgs, target, mirror_axes)
                     loss, _ = ops.deep_supervision_loss(net(imgs), target)
                     torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
                                                                           device=device))

@@ -85,14 +85,18 @@ class DGTTAProgram:
                          "nothing is injected here: `dgtta pretrain` trains on this engine and no longer needs it.")
 
     @staticmethod
-    def _pretrain_parser():
+    def _pretrain_parser(trainers=None):
+        """trainers: the names `-tr` takes.  The bare parser keeps the six DG trainers it always took (callers and tests that
+        build it themselves see no change); the `pretrain` command asks for TRAINERS, which adds the stock nnUNetTrainer."""
         from .pretraining.trainer import DG_TRAINERS
+        trainers = DG_TRAINERS if trainers is None else tuple(trainers)
         parser = argparse.ArgumentParser(description="Pre-train a DG trainer's network on the source dataset (positional "
                                          "arguments, -tr and --c as in nnUNetv2_train)", usage="dgtta pretrain [-h]")
         parser.add_argument("dataset_id", help="Dataset name or numeric id of the source dataset")
         parser.add_argument("configuration", help="Configuration of nnUNetPlans.json, e.g. 3d_fullres")
         parser.add_argument("fold", help="Fold of the 5-fold split, 0..4, or 'all'")
-        parser.add_argument("-tr", dest="trainer", required=True, choices=DG_TRAINERS, help="DG trainer")
+        parser.add_argument("-tr", dest="trainer", required=True, choices=trainers,
+                            help="DG trainer, or the stock nnUNetTrainer (the baseline: no hooks, mirroring)")
         parser.add_argument("--num_epochs", type=int, default=1000)
         parser.add_argument("--iterations_per_epoch", type=int, default=250)
         parser.add_argument("--val_iterations", type=int, default=50)
@@ -107,11 +111,18 @@ class DGTTAProgram:
         return parser
 
     def pretrain(self):
-        args = self._pretrain_parser().parse_args(self.argv[2:])
+        from .pretraining.trainer import TRAINERS
+        args = self._pretrain_parser(TRAINERS).parse_args(self.argv[2:])
         if args.fold != "all" and not args.fold.isnumeric():
             raise SystemExit(f"pretrain: fold {args.fold!r} is neither a number nor 'all'")
         from .pretraining.trainer import FULL_AUGMENTATION_NOTE, REDUCED_AUGMENTATION_NOTE, SPATIAL_AUGMENTATION_NOTE, train_fold
         print({"spatial": SPATIAL_AUGMENTATION_NOTE, "full": FULL_AUGMENTATION_NOTE}.get(args.augmentation, REDUCED_AUGMENTATION_NOTE))
+        from .pretraining.hooks import trainer_mirror_axes
+        axes = trainer_mirror_axes(args.trainer)
+        if axes is not None:
+            print(f"pretrain: {args.trainer} - no GIN / MIND hooks; nnU-Net's mirroring IS applied to the training batches along axes "
+                  f"{list(axes)} (each with probability 0.5, after the other transforms) and the checkpoint allows the same axes at "
+                  f"inference (inference_allowed_mirroring_axes).")
         final = train_fold(args.dataset_id, args.configuration, args.fold, args.trainer, num_epochs=args.num_epochs,
                            iterations_per_epoch=args.iterations_per_epoch, val_iterations=args.val_iterations,
                            device=torch.device(args.device), continue_training=args.continue_training, seed=args.seed, augmentation=args.augmentation,

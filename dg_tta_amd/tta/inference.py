@@ -1,8 +1,17 @@
 """Post-TTA ensemble sliding-window inference (SURVEY.md §8f "next" #1) — what the reference does at
 dg_tta/tta/tta.py:379-416 through nnU-Net's predictor (dg_tta/tta/nnunet_utils.py:116-125, 208-230):
 Gaussian-weighted 50 %-overlap sliding window, logits averaged over the ensemble's TTA'd parameter sets, argmax over
-ALL pretrain classes, then map_label(argmaxed) to the target label ids.  Mirroring is off (the DG trainers set
-inference_allowed_mirroring_axes=None, nnUNetTrainer_GIN_MIND.py:34-35).
+ALL pretrain classes, then map_label(argmaxed) to the target label ids.
+
+Mirroring follows the checkpoint, as nnU-Net's predictor does (use_mirroring=True is its default): the DG trainers set
+inference_allowed_mirroring_axes=None (nnUNetTrainer_GIN_MIND.py:34-35) and run exactly the passes they ran before; a stock
+nnUNetTrainer checkpoint says (0, 1, 2), and `mirror_axes` then predicts every window under all 2^|A| flips - the window's
+prediction is the mean over the subsets S of flip_S(net(flip_S(x))), subsets in the order (), (0), (1), (2), (0,1), (0,2), (1,2),
+(0,1,2) (nnunetv2 2.2.1 _internal_maybe_mirror_and_predict, from memory: UNPINNED like the window logic).  Here every mirrored pass
+is one more window of a batch (_mirror_work): ops.window_gather builds the flipped inputs in one launch and the mirrored accumulate
+kernels add gauss[p] * out[flip_S(p)] at origin + p and gauss[p] into nsum, so acc / nsum is the mean over the mirrors and
+everything downstream of the accumulators is untouched.  The Gaussian is NOT flipped: it is centred at i // 2 and at even tile
+sizes its flip is a different array.  A fp16 logits accumulator is refused with mirroring (no headroom for eight passes).
 
 The window logic is a restatement of nnunetv2==2.2.1 (`compute_gaussian`, `compute_steps_for_sliding_window`,
 `predict_sliding_window_return_logits`) from its published behaviour: that package is not vendored with the reference, so
@@ -202,54 +211,74 @@ def _mind_ahead_ok(model, dev):
     return all(h is mind_hook or leaves_input_alone(h) for h in hooks) and sum(h is mind_hook for h in hooks) == 1
 
 
-def _window_batches(model, data, origins, patch_size, dev):
-    """Yields (group, work) per batch of WINDOW_BATCH windows.  Where _mind_ahead_ok, the window stack and its MIND descriptor
-    (noise draw included: the draws keep their order, one batch after the other) are produced on a side stream one batch ahead
-    and handed to the model's mind_hook (mind.push_features): same kernels, same draws, same result."""
+def _mirror_work(origins, mirror_axes):
+    """The work list of a sliding-window pass: (origins, masks) with every window repeated once per mirror mask, in window order
+    and, per window, in the order nnU-Net's predictor runs its mirrored passes (ops.mirror_masks).  Every mirrored pass is one
+    more "window" of a batch: it adds gauss[p] * out[flip(p)] at origin + p and gauss[p] into nsum, so acc / nsum is the mean over
+    the mirrors of the window-normalised logits and nothing downstream of the accumulators changes."""
+    masks = ops.mirror_masks(mirror_axes)
+    return [o for o in origins for _ in masks], [m for _ in origins for m in masks]
+
+
+def _window_batches(model, data, origins, patch_size, dev, masks=None):
+    """Yields (group, group_masks, work) per batch of WINDOW_BATCH windows.  masks: one mirror mask per origin (_mirror_work) -
+    the batch is then built by ops.window_gather (one launch: slices and flips) instead of torch.stack.  Where _mind_ahead_ok,
+    the window stack and its MIND descriptor (noise draw included: the draws keep their order, one batch after the other) are
+    produced on a side stream one batch ahead and handed to the model's mind_hook (mind.push_features): same kernels, same draws,
+    same result - the descriptor of a mirrored pass is that of the flipped window, as nnU-Net's hook order gives it."""
     from .._state import state_of
     from ..mind import MIND3D, hook_owner, push_features
 
-    def stack(group):
+    mirrored = masks is not None and any(masks)
+    masks = [0] * len(origins) if masks is None else masks
+
+    def stack(item):
+        group, gmasks = item
+        if mirrored:
+            return ops.window_gather(data, group, gmasks, patch_size)
         return torch.stack([data[:, sx:sx + patch_size[0], sy:sy + patch_size[1], sz:sz + patch_size[2]]
                             for sx, sy, sz in group]).contiguous()
 
-    groups = [origins[g0:g0 + WINDOW_BATCH] for g0 in range(0, len(origins), WINDOW_BATCH)]
+    groups = [(origins[g0:g0 + WINDOW_BATCH], masks[g0:g0 + WINDOW_BATCH]) for g0 in range(0, len(origins), WINDOW_BATCH)]
     if not groups:
         return
     if not _mind_ahead_ok(model, dev):
-        for group in groups:
-            yield group, stack(group)
+        for item in groups:
+            yield item[0], item[1], stack(item)
         return
     main = torch.cuda.current_stream(dev)
     side = state_of(hook_owner(model)).stream("prep_stream", dev)
     adt = getattr(_inner(model), "act_dtype", torch.float32)
     side.wait_stream(main)          # once: the volume (uploaded on the main stream) is visible to the side stream
 
-    def prepare(group):
+    def prepare(item):
         with torch.cuda.stream(side):
-            work = stack(group)
-            feat = MIND3D().forward(work, out_dtype=adt, groups=len(group))
+            work = stack(item)
+            feat = MIND3D().forward(work, out_dtype=adt, groups=len(item[0]))
         for t in (work, feat):
             t.record_stream(main)
         return work, feat
 
     nxt = prepare(groups[0])
     try:
-        for i, group in enumerate(groups):
+        for i, item in enumerate(groups):
             work, feat = nxt
             main.wait_stream(side)
             nxt = prepare(groups[i + 1]) if i + 1 < len(groups) else None      # runs beside this batch's network pass
             push_features(model, feat)
-            yield group, work
+            yield item[0], item[1], work
     finally:
         state_of(hook_owner(model)).features.clear()      # (a descriptor no mind_hook call took must not meet a later input)
 
 
 @torch.no_grad()
-def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile_step_size=0.5, acc_dtype=None):
+def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile_step_size=0.5, acc_dtype=None, mirror_axes=None):
     """data [C,X,Y,Z] (CPU or GPU) -> accumulates gauss-weighted logits of `model` into acc [X,Y,Z,ncls] (GPU; fp32 or
     fp16: the dtype of a given `acc`, else `acc_dtype`, else window_acc_dtype()).
-    Returns (acc, nsum, crop) ; logits = acc / nsum[..., None] cropped by `crop`."""
+    Returns (acc, nsum, crop) ; logits = acc / nsum[..., None] cropped by `crop`.
+    mirror_axes: None, or the subset of (0, 1, 2) nnU-Net's predictor mirrors along (module docstring): every window is then
+    predicted under all 2^n flips, each un-flipped on its way into the accumulator; fp32 accumulator only."""
+    mirror_axes = ops.check_mirror_axes(mirror_axes)
     if acc_dtype is None:
         acc_dtype = acc.dtype if acc is not None else window_acc_dtype()
     if acc_dtype not in (torch.float32, torch.float16):
@@ -258,6 +287,10 @@ def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile
         raise ValueError(f"acc is {acc.dtype} but acc_dtype = {acc_dtype}")
     if acc is not None and not (acc.is_cuda and acc.is_contiguous()):
         raise ValueError("acc must be a contiguous GPU tensor [X,Y,Z,classes]")
+    if mirror_axes is not None and acc_dtype == torch.float16:
+        raise ValueError(f"mirroring along {mirror_axes} with a fp16 window accumulator: {2 ** len(mirror_axes)} passes per window at "
+                         "Gaussian weight 10 leave no headroom in half - use the fp32 logits accumulator (DGTTA_WINDOW_ACC=fp32) or "
+                         "the feature-space accumulator (DGTTA_WINDOW_ACC=features)")
     lib = _lib.load()
     dev = next(model.parameters()).device
     data, crop = pad_to_patch(data.float(), patch_size)
@@ -272,14 +305,16 @@ def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile
     # batch 1 (same observation as in the TTA loop); per-sample InstanceNorm and per-window MIND statistics (below) make
     # the result independent of the grouping
     origins = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
-    for group, work in _window_batches(model, data, origins, patch_size, dev):
+    origins, masks = _mirror_work(origins, mirror_axes)
+    for group, gmasks, work in _window_batches(model, data, origins, patch_size, dev, masks):
+        mirrors = {"mirrors": gmasks} if any(gmasks) else {}
         # MIND's variance clamp uses the mean over the whole CALL's batch (mind.py:159-161) and nnU-Net predicts one
         # window per call: the batched pass keeps per-window statistics (groups = windows in the batch)
         if _can_fuse_head_accumulate(model):
             # the head evaluates straight into the accumulator (the windows' logits - 880 MB each at 128^3 x 105 - are not written)
             if acc is None:
                 acc = torch.zeros((X, Y, Z, _num_classes(model)), dtype=acc_dtype, device=dev)
-            with mind_groups(model, len(group)), _inner(model).fuse_window_accumulate(acc, nsum, gauss, group):
+            with mind_groups(model, len(group)), _inner(model).fuse_window_accumulate(acc, nsum, gauss, group, **mirrors):
                 model(work)
             continue
         with mind_groups(model, len(group)):
@@ -291,6 +326,11 @@ def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile
         if acc is None:
             acc = torch.zeros((X, Y, Z, ncls), dtype=acc_dtype, device=dev)
         for k, (sx, sy, sz) in enumerate(group):       # overlapping windows: accumulated one after the other
+            if gmasks[k]:      # a mirrored pass: un-flipped on its way into the accumulator
+                check(lib.dgtta_window_accumulate_mirror_t(ptr(out[k]), ptr(gauss), ptr(acc), ptr(nsum), ncls, *patch_size, X, Y, Z,
+                                                           sx, sy, sz, _acc_code(acc), gmasks[k], stream_of(dev)),
+                      "dgtta_window_accumulate_mirror_t")
+                continue
             check(lib.dgtta_window_accumulate_t(ptr(out[k]), ptr(gauss), ptr(acc), ptr(nsum), ncls, *patch_size, X, Y, Z, sx,
                                                 sy, sz, _acc_code(acc), stream_of(dev)), "dgtta_window_accumulate_t")
     model.train(was_training)
@@ -298,9 +338,11 @@ def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile
 
 
 @torch.no_grad()
-def accumulate_window_features(model, data, patch_size, facc=None, tile_step_size=0.5):
+def accumulate_window_features(model, data, patch_size, facc=None, tile_step_size=0.5, mirror_axes=None):
     """The feature-space form of predict_sliding_window_return_logits for one member: data [C,X,Y,Z] -> adds gauss * (the head's
-    input of every window) into facc [X,Y,Z,32] (fp32, GPU; allocated when None).  Returns (facc, nsum, crop)."""
+    input of every window, under every flip of mirror_axes) into facc [X,Y,Z,32] (fp32, GPU; allocated when None).  Returns
+    (facc, nsum, crop)."""
+    mirror_axes = ops.check_mirror_axes(mirror_axes)
     m = _inner(model)
     if not _can_accumulate_features(model):
         raise RuntimeError("accumulate_window_features: the network does not offer the feature-space accumulation here")
@@ -318,15 +360,17 @@ def accumulate_window_features(model, data, patch_size, facc=None, tile_step_siz
     was_training = model.training
     model.eval()
     origins = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
-    for group, work in _window_batches(model, data, origins, patch_size, dev):
-        with mind_groups(model, len(group)), m.fuse_window_feature_accumulate(facc, nsum, gauss, group):
+    origins, masks = _mirror_work(origins, mirror_axes)
+    for group, gmasks, work in _window_batches(model, data, origins, patch_size, dev, masks):
+        mirrors = {"mirrors": gmasks} if any(gmasks) else {}
+        with mind_groups(model, len(group)), m.fuse_window_feature_accumulate(facc, nsum, gauss, group, **mirrors):
             model(work)
     model.train(was_training)
     return facc, nsum, crop
 
 
 @torch.no_grad()
-def predict_ensemble_features(data, model, parameter_sets, patch_size):
+def predict_ensemble_features(data, model, parameter_sets, patch_size, mirror_axes=None):
     """Feature-space accumulators of the whole ensemble for one preprocessed case (see WindowFeatures); one [X,Y,Z,32] fp32
     volume per member, because the members' heads differ."""
     if hasattr(model, "set_selected_classes"):
@@ -342,22 +386,23 @@ def predict_ensemble_features(data, model, parameter_sets, patch_size):
         head = _inner(model).decoder.seg_layers[-1]
         ws.append(head.weight.detach().reshape(head.out_channels, -1).float().clone())
         bs.append(head.bias.detach().float().clone())
-        _, nsum, crop = accumulate_window_features(model, data, patch_size, facc[k])
+        _, nsum, crop = accumulate_window_features(model, data, patch_size, facc[k], mirror_axes=mirror_axes)
     return WindowFeatures(facc, nsum, crop, torch.stack(ws), torch.stack(bs))
 
 
 @torch.no_grad()
-def predict_ensemble(data, model, parameter_sets, patch_size):
+def predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes=None):
     """What run_inference / dgtta run_tta predict with: (acc, nsum, crop) for export_segmentation - acc a WindowFeatures when
-    DGTTA_WINDOW_ACC=features (default) and the network offers it, else the logits-space accumulator of predict_ensemble_logits."""
+    DGTTA_WINDOW_ACC=features (default) and the network offers it, else the logits-space accumulator of predict_ensemble_logits.
+    mirror_axes: the checkpoint's inference_allowed_mirroring_axes (None for the DG trainers)."""
     if window_acc_mode() == "features" and _can_accumulate_features(model, len(parameter_sets)):
-        feats = predict_ensemble_features(data, model, parameter_sets, patch_size)
+        feats = predict_ensemble_features(data, model, parameter_sets, patch_size, mirror_axes)
         return feats, feats.nsum, feats.crop
-    return predict_ensemble_logits(data, model, parameter_sets, patch_size)
+    return predict_ensemble_logits(data, model, parameter_sets, patch_size, mirror_axes)
 
 
 @torch.no_grad()
-def predict_ensemble_logits(data, model, parameter_sets, patch_size):
+def predict_ensemble_logits(data, model, parameter_sets, patch_size, mirror_axes=None):
     """Window-accumulated logits of the whole ensemble for one preprocessed case: data [C,X,Y,Z] (image channel(s) only),
     parameter_sets: list of state dicts (the `*_tta_parameters.pt` contents).  Returns (acc [X,Y,Z,ncls] fp32 on the GPU =
     sum over members and windows of gauss * logits, nsum [X,Y,Z], crop): the ensemble-mean logits nnU-Net's predictor hands
@@ -368,16 +413,16 @@ def predict_ensemble_logits(data, model, parameter_sets, patch_size):
     data = data.float().to(next(model.parameters()).device)      # one upload for all ensemble members
     for params in parameter_sets:
         model.load_state_dict(params)
-        acc, nsum, crop = predict_sliding_window_return_logits(model, data, patch_size, acc)
+        acc, nsum, crop = predict_sliding_window_return_logits(model, data, patch_size, acc, mirror_axes=mirror_axes)
     return acc, nsum, crop
 
 
 @torch.no_grad()
-def run_inference(data, model, parameter_sets, patch_size, label_mapping=None, optimized_labels=None):
+def run_inference(data, model, parameter_sets, patch_size, label_mapping=None, optimized_labels=None, mirror_axes=None):
     """Ensemble prediction of one preprocessed case in the PREPROCESSED geometry.  Returns the label map [X,Y,Z] (int64,
     CPU), mapped to the target ids when label_mapping/optimized_labels are given (tta.py:407-411)."""
     from .torch_utils import get_map_idxs
-    acc, nsum, crop = predict_ensemble(data, model, parameter_sets, patch_size)
+    acc, nsum, crop = predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes)
     seg = torch.as_tensor(export_segmentation(acc, nsum, crop, None, None, None).astype(np.int64))
     if label_mapping is not None:
         seg = map_label(seg[None], get_map_idxs(label_mapping, optimized_labels, "pretrain_labels"), "argmaxed")[0]

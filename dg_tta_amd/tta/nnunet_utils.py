@@ -3,7 +3,8 @@ reference's dg_tta/tta/nnunet_utils.py (load_network :88-113, load_tta_data :63-
 
 * `load_network` reads `<model_folder>/{plans.json,dataset.json}` + `fold_k/checkpoint_final.pth` (nnU-Net layout),
   builds a HipPlainConvUNet with the plans' topology and registers the trainer's forward pre-hooks in the reference's
-  order (gin_hook, then mind_hook: dg_tta/pretraining/nnUNetTrainer_GIN_MIND.py:55-57).
+  order (gin_hook, then mind_hook: dg_tta/pretraining/nnUNetTrainer_GIN_MIND.py:55-57); the stock nnUNetTrainer has none.  The
+  checkpoint's `inference_allowed_mirroring_axes` goes onto the predictor as `allowed_mirroring_axes` (nnU-Net's attribute name).
 * `load_tta_data` yields `{"data": FloatTensor[1+K,D,H,W], "data_properties", "ofile"}` items like
   preprocess_fromfile.  Raw NIfTI cases are cropped, normalised and resampled as nnU-Net's DefaultPreprocessor does
   (tta/preprocessing.py); `.npy`, `.npz` (key `data`) and `.pt` files are taken as already preprocessed arrays.
@@ -63,16 +64,35 @@ def anisotropic_stages(pools, kernels):
     return tuple(tuple(int(a) for a in p) for p in pools), tuple(tuple(int(a) for a in k) for k in kernels)
 
 
-def trainer_hooks(trainer_name):
-    """(input channels, [pre-hooks]) for the DG trainers (nnUNetTrainer_{GIN,MIND,GIN_MIND}[_MultiRes].py:38-59)."""
+STOCK_TRAINER = "nnUNetTrainer"
+
+
+def _trainer_entry(trainer_name):
+    """(input channels, [pre-hooks], mirror axes) - the one table behind trainer_hooks, trainer_mirror_axes and
+    pretraining.hooks.trainer_spec.  The stock trainer is matched exactly, the DG names by their endings."""
+    if trainer_name == STOCK_TRAINER:
+        return 1, [], (0, 1, 2)
     name = trainer_name.replace("_MultiRes", "")
     if name.endswith("GIN_MIND"):
-        return 12, [gin_hook, mind_hook]
+        return 12, [gin_hook, mind_hook], None
     if name.endswith("MIND"):
-        return 12, [mind_hook]
+        return 12, [mind_hook], None
     if name.endswith("GIN"):
-        return 1, [gin_hook]
-    raise NotImplementedError(f"trainer {trainer_name}: only the DG-TTA trainers (GIN / MIND / GIN_MIND) are built")
+        return 1, [gin_hook], None
+    raise NotImplementedError(f"trainer {trainer_name}: only the DG-TTA trainers (GIN / MIND / GIN_MIND) and the stock "
+                              f"{STOCK_TRAINER} (one image channel) are built")
+
+
+def trainer_hooks(trainer_name):
+    """(input channels, [pre-hooks]) for the DG trainers (nnUNetTrainer_{GIN,MIND,GIN_MIND}[_MultiRes].py:38-59) and the stock
+    nnUNetTrainer (one image channel, no hooks)."""
+    return _trainer_entry(trainer_name)[:2]
+
+
+def trainer_mirror_axes(trainer_name):
+    """The trainer's inference_allowed_mirroring_axes, which are also the axes its training batches are mirrored along: (0, 1, 2)
+    for the stock nnUNetTrainer, None for the DG trainers (nnUNetTrainer_GIN_MIND.py:34-35)."""
+    return _trainer_entry(trainer_name)[2]
 
 
 def _load_checked(network, state, weights_file, trainer_name, configuration):
@@ -110,22 +130,30 @@ def load_network(weights_file, device, act_dtype=torch.float32, conv_impl=0):
     with open(model_folder / "dataset.json") as f:
         dataset_json = json.load(f)
     checkpoint = torch.load(weights_file, map_location="cpu", weights_only=False)
+    mirror_axes = None      # a bare state dict says nothing about mirroring
     if isinstance(checkpoint, dict) and "network_weights" in checkpoint:
         trainer_name = checkpoint.get("trainer_name", trainer_name)
         state = checkpoint["network_weights"]
+        mirror_axes = checkpoint.get("inference_allowed_mirroring_axes")
     else:
         state = checkpoint
+    mirror_axes = None if mirror_axes is None else tuple(int(a) for a in mirror_axes)
     in_ch, hooks = trainer_hooks(trainer_name)
+    n_channels = len(dataset_json.get("channel_names", dataset_json.get("modality", {})))
+    if trainer_name == STOCK_TRAINER and n_channels > 1:
+        raise NotImplementedError(f"{weights_file}: dataset.json lists {n_channels} image channels; {STOCK_TRAINER} is built for "
+                                  f"one (the TTA sampler and the preprocessing take one image channel)")
     cfg, patch_size = unet_cfg_from_plans(plans, dataset_json, configuration, in_ch)
     network = HipPlainConvUNet(cfg, act_dtype=act_dtype, conv_impl=conv_impl)
     state = {k.replace("_orig_mod.", ""): v for k, v in state.items()}
     _load_checked(network, state, weights_file, trainer_name, configuration)
-    enable_internal_augmentation()          # as build_network_architecture does; tta_main switches it off again
+    if hooks:                               # (the stock trainer has no internal augmentation to switch on)
+        enable_internal_augmentation()      # as build_network_architecture does; tta_main switches it off again
     for h in hooks:
         network.register_forward_pre_hook(h)
     predictor = SimpleNamespace(plans=plans, dataset_json=dataset_json, configuration=configuration,
                                 trainer_name=trainer_name, device=torch.device(device), network=network,
-                                list_of_parameters=[state], patch_size=patch_size)
+                                list_of_parameters=[state], patch_size=patch_size, allowed_mirroring_axes=mirror_axes)
     return predictor, patch_size, network, [state]
 
 

@@ -627,8 +627,11 @@ def _predict_case(case, config, network, predictor, patch_size, label_mapping, m
     image = get_imgs(sample["data"].unsqueeze(0)).squeeze(0)
     props = sample.get("data_properties") or {}
     nii = props.get("nifti_header")
+    # mirroring follows the checkpoint as in nnU-Net's predictor (use_mirroring=True is its default; None for the DG trainers);
+    # the plan key "inference_use_mirroring": false skips the mirrored passes
+    mirror_axes = getattr(predictor, "allowed_mirroring_axes", None) if config.get("inference_use_mirroring", True) else None
     with _inference_noise(config, smp_idx):
-        acc, nsum, crop = predict_ensemble(image, model, params, patch_size)
+        acc, nsum, crop = predict_ensemble(image, model, params, patch_size, mirror_axes=mirror_axes)
     plans = getattr(predictor, "plans", None)
     original = nii is not None and plans is not None and "shape_before_cropping" in props
     save_probs = bool(config.get("inference_save_probabilities", False))

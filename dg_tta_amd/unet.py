@@ -219,15 +219,28 @@ class HipPlainConvUNet(nn.Module):
                 self.act_dtype in (torch.float16, torch.bfloat16) and self.decoder.seg_layers[-1].in_channels == 32 and
                 self.decoder.seg_layers[-1].out_channels <= 112 and not torch.is_grad_enabled())
 
-    def fuse_window_accumulate(self, acc, nsum, gauss, origins):
+    def fuse_window_accumulate(self, acc, nsum, gauss, origins, *, mirrors=None):
         """Context (inference, no grad): the next forward adds gauss * logits of window k of the batch into
-        acc [X,Y,Z,ncls] / nsum [X,Y,Z] at origins[k] instead of returning the logits (it returns an empty placeholder)."""
+        acc [X,Y,Z,ncls] / nsum [X,Y,Z] at origins[k] instead of returning the logits (it returns an empty placeholder).
+        mirrors: one mirror mask per origin (bit a = the window was fed flipped along axis a: its logits are un-flipped on the
+        way into the accumulator, the Gaussian is not); fp32 accumulators only."""
+        mirrors = self._window_mirrors(mirrors, origins, "fuse_window_accumulate")
+        if any(mirrors) and acc.dtype != torch.float32:
+            raise ValueError("fuse_window_accumulate: mirrored windows need the fp32 accumulator (eight passes per window at "
+                             "Gaussian weight 10 leave no headroom in half)")
         if acc.dtype not in (torch.float32, torch.float16):      # the kernel knows these two accumulator storage types
             raise ValueError(f"fuse_window_accumulate: the accumulator is fp32 or fp16, not {acc.dtype}")
         if not (acc.is_contiguous() and nsum.dtype == torch.float32 and gauss.dtype == torch.float32):
             raise ValueError("fuse_window_accumulate: contiguous accumulator, fp32 weight sum and fp32 Gaussian expected")
         self._no_deep_supervision("fuse_window_accumulate")
-        return self._during("_window_acc", lambda: (acc, nsum, gauss, list(origins)))
+        return self._during("_window_acc", lambda: (acc, nsum, gauss, list(origins), mirrors))
+
+    @staticmethod
+    def _window_mirrors(mirrors, origins, what):
+        mirrors = [0] * len(origins) if mirrors is None else [int(m) for m in mirrors]
+        if len(mirrors) != len(origins) or any(not 0 <= m <= 7 for m in mirrors):
+            raise ValueError(f"{what}: one mirror mask in 0..7 per origin expected")
+        return mirrors
 
     # -- the same in FEATURE space (csrc/window_features.hip): the head is linear and last, so the window accumulator
     #    holds the Gaussian-weighted input of the head and the head runs once per voxel at the end
@@ -235,15 +248,17 @@ class HipPlainConvUNet(nn.Module):
         return (os.environ.get("DGTTA_FUSE_HEAD_ACCUMULATE", "1") != "0" and self.selected_classes is None and
                 self.decoder.seg_layers[-1].in_channels == 32 and not torch.is_grad_enabled())
 
-    def fuse_window_feature_accumulate(self, facc, nsum, gauss, origins):
+    def fuse_window_feature_accumulate(self, facc, nsum, gauss, origins, *, mirrors=None):
         """Context (inference, no grad): the next forward adds gauss * z of window k of the batch - z = the 32 feature channels the
         segmentation head reads - into facc [X,Y,Z,32] (fp32) / nsum [X,Y,Z] at origins[k]; the head is NOT evaluated (the forward
-        returns an empty placeholder).  Label map: ops.feature_head_argmax with the members' head weights."""
+        returns an empty placeholder).  Label map: ops.feature_head_argmax with the members' head weights.  mirrors: as in
+        fuse_window_accumulate."""
+        mirrors = self._window_mirrors(mirrors, origins, "fuse_window_feature_accumulate")
         if not (facc.dtype == torch.float32 and facc.is_contiguous() and facc.shape[-1] == 32 and nsum.dtype == torch.float32 and
                 gauss.dtype == torch.float32):
             raise ValueError("fuse_window_feature_accumulate: contiguous fp32 accumulator [X,Y,Z,32], fp32 weight sum and Gaussian expected")
         self._no_deep_supervision("fuse_window_feature_accumulate")
-        return self._during("_window_acc", lambda: (facc, nsum, gauss, list(origins), "features"))
+        return self._during("_window_acc", lambda: (facc, nsum, gauss, list(origins), mirrors, "features"))
 
     def forward(self, x):
         sel = self.selected_classes

@@ -463,9 +463,22 @@ def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
     wbytes = D * H * W * 32 * p.esz            # one window of the source
     mrbytes = 32 * 2 * 4                       # one window of mean / rstd
     segments = os.environ.get("DGTTA_FEATURE_SEGMENTS", "1") != "0"
-    for launch in window_segments(origins, W) if segments else range(len(origins)):
+    mirrors = wa[4]
+    for k in (k for k in range(len(origins)) if mirrors[k]):      # mirrored passes: one window per launch, un-flipped by the kernel
+        sx, sy, sz = origins[k]
+        if feat_fold:
+            check(lib.dgtta_feature_window_accumulate_norm_mirror(src0 + k * wbytes, last.mr.data_ptr() + k * mrbytes, ptr(nrm.weight),
+                                                                  ptr(nrm.bias), SLOPE, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W,
+                                                                  X, Y, Z, sx, sy, sz, dt, mirrors[k], st),
+                  "dgtta_feature_window_accumulate_norm_mirror")
+        else:
+            check(lib.dgtta_feature_window_accumulate_mirror(src0 + k * wbytes, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W, X, Y, Z,
+                                                             sx, sy, sz, dt, mirrors[k], st), "dgtta_feature_window_accumulate_mirror")
+    plain = [k for k in range(len(origins)) if not mirrors[k]]      # the unmirrored windows keep the segment merging
+    plain_origins = [origins[k] for k in plain]
+    for launch in window_segments(plain_origins, W) if segments else range(len(plain)):
         if isinstance(launch, int):
-            k = launch
+            k = plain[launch]
             sx, sy, sz = origins[k]
             if feat_fold:
                 check(lib.dgtta_feature_window_accumulate_norm(src0 + k * wbytes, last.mr.data_ptr() + k * mrbytes, ptr(nrm.weight),
@@ -476,6 +489,7 @@ def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
                                                           sx, sy, sz, dt, st), "dgtta_feature_window_accumulate")
             continue
         sx, sy, a, b, part = launch
+        part = [plain[i] for i in part]
         n = len(part)
         srcs = (C.c_void_p * n)(*[src0 + i * wbytes for i in part])
         mrs = (C.c_void_p * n)(*[last.mr.data_ptr() + i * mrbytes for i in part]) if feat_fold else None
@@ -487,11 +501,18 @@ def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
 
 def _accumulate_logit_windows(p, wa, head, z, dims):
     """Head fused with the Gaussian window accumulation: overlapping windows are accumulated one after the other."""
-    acc, nsum, gauss, origins = wa[:4]
+    acc, nsum, gauss, origins, mirrors = wa[:5]
     X, Y, Z = acc.shape[:3]
     D, H, W = dims
     for k, (sx, sy, sz) in enumerate(origins):
-        check(p.lib.dgtta_seghead_window_accumulate_t(z.ptr + k * D * H * W * z.ld * p.esz, ptr(head.weight), ptr(head.bias),
+        src = z.ptr + k * D * H * W * z.ld * p.esz
+        if mirrors[k]:      # a mirrored pass: its logits are un-flipped on the way into the accumulator
+            check(p.lib.dgtta_seghead_window_accumulate_mirror_t(src, ptr(head.weight), ptr(head.bias), ptr(gauss), ptr(acc), ptr(nsum),
+                                                                 head.in_channels, head.out_channels, D, H, W, X, Y, Z, sx, sy, sz, p.dt,
+                                                                 F32 if acc.dtype == torch.float32 else F16, mirrors[k], p.st),
+                  "dgtta_seghead_window_accumulate_mirror_t")
+            continue
+        check(p.lib.dgtta_seghead_window_accumulate_t(src, ptr(head.weight), ptr(head.bias),
                                                       ptr(gauss), ptr(acc), ptr(nsum), head.in_channels, head.out_channels, D, H,
                                                       W, X, Y, Z, sx, sy, sz, p.dt, F32 if acc.dtype == torch.float32 else F16,
                                                       p.st), "dgtta_seghead_window_accumulate_t")
@@ -674,7 +695,7 @@ class _UNetFn(torch.autograd.Function):
         _check_patch_divisible(cfg["strides"], dims)
         head = net.decoder.seg_layers[-1]
         wa = net._window_acc
-        feat_fold = (wa is not None and len(wa) > 4 and not need_grad and os.environ.get("DGTTA_FEATURE_FOLD", "1") != "0" and
+        feat_fold = (wa is not None and wa[-1] == "features" and not need_grad and os.environ.get("DGTTA_FEATURE_FOLD", "1") != "0" and
                      head.in_channels == cfg["features"][0] == 32)
         enc, ups, dec = _plan(p, cin0, dims)
         z, cats = _encoder_forward(p, enc, ups, dec, _input_rows(p, x))
@@ -682,7 +703,7 @@ class _UNetFn(torch.autograd.Function):
         z = stage_rows[-1]
         if wa is not None:
             assert not need_grad and sel is None and z.ld == head.in_channels and len(wa[3]) == B, "fuse_window_accumulate: misuse"
-            if len(wa) > 4:      # feature space: no head here
+            if wa[-1] == "features":      # feature space: no head here
                 _accumulate_feature_windows(p, wa, dec[-1][-1], z, feat_fold, dims)
             else:
                 _accumulate_logit_windows(p, wa, head, z, dims)

@@ -768,6 +768,39 @@ int dgtta_intensity_map(const float *src, float *dst, int B, int64_t V, const Dg
 int dgtta_gauss_blur3(const float *src, float *dst, float *scratch, int B, int D, int H, int W, const DgttaBlurItem *h_items,
                       int n_items, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mirroring for the stock nnUNetTrainer (csrc/mirror.hip, csrc/window_mirror.h): nnU-Net's MirrorTransform in pre-training and the
+ * mirrored passes of its sliding-window predictor (nnunetv2 2.2.1 _internal_maybe_mirror_and_predict), both restated from memory,
+ * UNPINNED.  A mirror mask selects the flipped axes of a [D][H][W] block: bit 0 = axis 0 (D), bit 1 = axis 1 (H), bit 2 = axis 2
+ * (W); masks outside 0..7 are DGTTA_ERR_BADARG.  Masks and origins are HOST arrays copied into the kernel arguments (one launch per
+ * DGTTA_MIRROR_MAX_ITEMS items); the library allocates nothing and does not wait for the stream.
+ *
+ * dgtta_mirror_batch: image_out[b][c][p] = image[b][c][flip(p)], labels_out[b][p] = labels[b][flip(p)] with item b's mask (mask 0:
+ *   a copy); image [B][C][D][H][W] fp32, labels [B][D][H][W] int64, source and destination distinct buffers.
+ * dgtta_window_gather: out[k][c][p] = volume[c][origin_k + flip_k(p)] for n windows [PD][PH][PW] of the volume [C][X][Y][Z];
+ *   h_origins holds n (x0, y0, z0) triples; a window outside the volume is DGTTA_ERR_BADARG.
+ * dgtta_*_window_accumulate_mirror*: the window accumulations above for a mirrored pass - the arguments of the unmirrored entry plus
+ *   `mirror`: the destination voxel origin + p receives gauss[p] * (source value at flip(p)), nsum receives gauss[p].  The Gaussian is
+ *   NOT flipped (at even tile sizes the flipped map is a different array).  mirror = 0 produces the bits of the unmirrored entry.  The
+ *   two logits-space forms take fp32 accumulators only (acc_dtype DGTTA_F32, else DGTTA_ERR_UNSUPPORTED): eight passes per window at
+ *   Gaussian weight 10 leave no headroom in half.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_MIRROR_MAX_ITEMS 16
+int dgtta_mirror_batch(const float *image, const int64_t *labels, float *image_out, int64_t *labels_out, const int *h_masks, int B,
+                       int C, int D, int H, int W, void *stream);
+int dgtta_window_gather(const float *volume, float *out, const int *h_origins, const int *h_masks, int n, int C, int PD, int PH, int PW,
+                        int X, int Y, int Z, void *stream);
+int dgtta_feature_window_accumulate_mirror(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW,
+                                           int X, int Y, int Z, int x0, int y0, int z0, int dtype, int mirror, void *stream);
+int dgtta_feature_window_accumulate_norm_mirror(const void *y, const float *mean_rstd, const float *gamma, const float *beta, float slope,
+                                                const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW, int X,
+                                                int Y, int Z, int x0, int y0, int z0, int dtype, int mirror, void *stream);
+int dgtta_seghead_window_accumulate_mirror_t(const void *z, const float *w, const float *bias, const float *gauss, void *acc,
+                                             float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0, int y0,
+                                             int z0, int dtype, int acc_dtype, int mirror, void *stream);
+int dgtta_window_accumulate_mirror_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH, int PW,
+                                     int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, int mirror, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
