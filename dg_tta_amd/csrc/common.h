@@ -69,6 +69,24 @@ struct RowsGstCtx {
     }                                                                             \
   } while (0)
 
+// runs CALL with T = the storage type of `dtype`; an unknown dtype returns DGTTA_ERR_BADARG from the enclosing function
+#define DISPATCH_T(dtype, CALL)                                                        \
+  do {                                                                                 \
+    if ((dtype) == DGTTA_F32) {                                                        \
+      typedef float T;                                                                 \
+      CALL;                                                                            \
+    } else if ((dtype) == DGTTA_BF16) {                                                \
+      typedef bf16_t T;                                                                \
+      CALL;                                                                            \
+    } else if ((dtype) == DGTTA_F16) {                                                 \
+      typedef f16_t T;                                                                 \
+      CALL;                                                                            \
+    } else {                                                                           \
+      dgtta_set_error("bad dtype %d", (int)(dtype));                                   \
+      return DGTTA_ERR_BADARG;                                                         \
+    }                                                                                  \
+  } while (0)
+
 __host__ __device__ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

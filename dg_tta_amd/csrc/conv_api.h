@@ -3,30 +3,12 @@
 // together.  (The View / Taps-level launchers of the MFMA units and their launch descriptor are in conv_common.h.)
 // The convolution functions take one problem descriptor (ConvProblem, which the extern "C" entry points fill once) plus their
 // operands (Src / Dst / Region).  Also what those entry points share: the argument checks (CONV_REQUIRE_*), the workspace layouts
-// (one function each for the size query and the launcher that carves the workspace), and the small host helpers: the dtype
-// fan-out, element / granule / output sizes.  Needs only common.h.
+// (one function each for the size query and the launcher that carves the workspace), and the small host helpers: element /
+// granule / output sizes (the dtype fan-out, DISPATCH_T, is in common.h).  Needs only common.h.
 #pragma once
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------------- host helpers
-// runs CALL with T = the storage type of `dtype`; an unknown dtype returns DGTTA_ERR_BADARG from the enclosing function
-#define DISPATCH_T(dtype, CALL)                                                        \
-  do {                                                                                 \
-    if ((dtype) == DGTTA_F32) {                                                        \
-      typedef float T;                                                                 \
-      CALL;                                                                            \
-    } else if ((dtype) == DGTTA_BF16) {                                                \
-      typedef bf16_t T;                                                                \
-      CALL;                                                                            \
-    } else if ((dtype) == DGTTA_F16) {                                                 \
-      typedef f16_t T;                                                                 \
-      CALL;                                                                            \
-    } else {                                                                           \
-      dgtta_set_error("bad dtype %d", (int)(dtype));                                   \
-      return DGTTA_ERR_BADARG;                                                         \
-    }                                                                                  \
-  } while (0)
-
 static inline bool dtype_ok(int dtype) { return dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16; }
 static inline size_t esize(int dtype) { return dtype == DGTTA_F32 ? 4 : 2; }      // bytes per stored element
 

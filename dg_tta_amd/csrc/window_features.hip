@@ -20,8 +20,13 @@
 // fp32 features with the fp32 weights instead of on 16-bit features window by window), so labels can differ from the
 // logits-space accumulator where the top-2 margin is at rounding level - tests/test_inference.py compares both forms with the
 // CPU restatement outside such ties.  nnU-Net itself is absent from /root/reference: this stage is "parity unpinned" either way.
+//
+// Layout: ONE accumulate kernel template (feature_accumulate_kernel<T, NS, NORM, MIR>: storage type, windows per launch, folded
+// InstanceNorm apply, mirrored source) behind one host launcher that the five dgtta_feature_window_accumulate* entries forward to;
+// the window's place in the volume, its checks and the index arithmetic are window_api.h's, shared with window_logits.hip.  Then the
+// head kernels that read the accumulator (argmax, softmax, export chunk).
 #include "gfx950.h"
-#include "window_mirror.h"
+#include "window_api.h"
 
 namespace {
 
@@ -48,34 +53,6 @@ __device__ __forceinline__ void wf_load4<f16_t>(const f16_t *p, float (&f)[4]) {
   f[2] = f16_to_f32((unsigned short)(v.y & 0xffffu)), f[3] = f16_to_f32((unsigned short)(v.y >> 16));
 }
 
-// facc[(x0 + pd, y0 + ph, z0 + pw)][c] += gauss[p] * z[p][c], nsum[..] += gauss[p]; 8 threads per voxel, 4 channels each: every
-// load and store instruction of a wave covers one contiguous run (z: 512 B, facc: 1 KiB; a window row is contiguous in the
-// volume along its last axis).  A launch touches every accumulator element once - overlapping windows are separate launches
-// in stream order, as in the logits-space form.
-// MIR (a mirrored pass of nnU-Net's test-time mirroring): the thread-to-destination mapping and gauss[p] stay, the source is read at
-// the mirrored voxel wm_source(p) - a wave row's 512 B of z are the same run, reversed voxel by voxel when the last axis is flipped.
-template <typename T, bool MIR>
-__global__ __launch_bounds__(256) void feature_accumulate_kernel(const T *__restrict__ z, const float *__restrict__ gauss,
-                                                                 float *__restrict__ facc, float *__restrict__ nsum, int PD, int PH, int PW,
-                                                                 int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int q = (int)(i & 7);
-  const int64_t p = i >> 3;
-  const int pw = (int)(p % PW), ph = (int)((p / PW) % PH);
-  const int64_t pd = p / ((int64_t)PW * PH);
-  const int64_t v = ((pd + x0) * Y + (ph + y0)) * Z + (pw + z0);
-  const float g = gauss[p];
-  const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) : p;
-  float f[4];
-  wf_load4<T>(z + ps * WF_CIN + q * 4, f);
-  float4 *dst = reinterpret_cast<float4 *>(facc + v * WF_CIN + q * 4);
-  float4 a = *dst;
-  a.x += g * f[0], a.y += g * f[1], a.z += g * f[2], a.w += g * f[3];
-  *dst = a;
-  if (q == 0 && nsum) nsum[v] += g;
-}
-
 // value -> storage type T and back (what the network's apply pass writes and the head would read)
 template <typename T>
 __device__ __forceinline__ float wf_round(float v);
@@ -86,63 +63,35 @@ __device__ __forceinline__ float wf_round<bf16_t>(float v) { return bf16_to_f32(
 template <>
 __device__ __forceinline__ float wf_round<f16_t>(float v) { return f16_to_f32(f32_to_f16(v)); }
 
-// The same with the last block's InstanceNorm + LeakyReLU apply folded in: z = round_T(lrelu(y * alpha + beta')) is formed from the
-// raw conv output y in registers (alpha = rstd * gamma, beta' = beta - mean * alpha: the arithmetic of in_apply_vec_kernel, so the
-// SAME z values) and never written - the apply pass (read y, write z) and the read of z disappear for the layer in front of the
-// head: 64 + 256 B per voxel instead of 128 + 320.  No backward exists in inference, so nothing else needs that z.
-template <typename T, bool MIR>
-__global__ __launch_bounds__(256) void feature_accumulate_norm_kernel(const T *__restrict__ y, const float *__restrict__ mean_rstd,
-                                                                      const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                                      float slope, const float *__restrict__ gauss,
-                                                                      float *__restrict__ facc, float *__restrict__ nsum, int PD, int PH, int PW,
-                                                                      int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
-  __shared__ float sal[WF_CIN], sbe[WF_CIN];      // the window's per-channel constants, once per workgroup
-  if (threadIdx.x < WF_CIN) {
-    const int c = threadIdx.x;
-    const float al = mean_rstd[c * 2 + 1] * gamma[c];
-    sal[c] = al;
-    sbe[c] = beta[c] - mean_rstd[c * 2] * al;
-  }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int q = (int)(i & 7);
-  const int64_t p = i >> 3;
-  const int pw = (int)(p % PW), ph = (int)((p / PW) % PH);
-  const int64_t pd = p / ((int64_t)PW * PH);
-  const int64_t v = ((pd + x0) * Y + (ph + y0)) * Z + (pw + z0);
-  const float g = gauss[p];
-  const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) : p;
-  float f[4];
-  wf_load4<T>(y + ps * WF_CIN + q * 4, f);
-  float4 *dst = reinterpret_cast<float4 *>(facc + v * WF_CIN + q * 4);
-  float4 a = *dst;
-  float zz[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) zz[e] = wf_round<T>(lrelu(f[e] * sal[q * 4 + e] + sbe[q * 4 + e], slope));
-  a.x += g * zz[0], a.y += g * zz[1], a.z += g * zz[2], a.w += g * zz[3];
-  *dst = a;
-  if (q == 0 && nsum) nsum[v] += g;
-}
-
-// Several windows of one network pass that overlap along the last axis (consecutive origins of a sliding-window row), one SEGMENT of
-// that axis per launch: every voxel of the segment receives the contributions of all NS windows that cover it, added in window order
-// in registers - (acc + t_0) + t_1: the bits the one-window launches produce - and the accumulator is read and written ONCE instead
-// of NS times.  With 50 % overlap a row of 7 windows is 8 half-window segments: 57 % of the read-modify-write traffic.
-// NORM: the sources are raw conv outputs and the InstanceNorm + LeakyReLU apply runs here (feature_accumulate_norm_kernel).
+// The NS windows of a launch: a whole window (NS = 1, zoff 0), or the windows of one network pass that cover a SEGMENT of the last axis
 struct WfSources {
   const void *src[4];            // window k: [PD][PH][PW][32]
   const float *mean_rstd[4];     // NORM: the window's statistics [32][2]
   int zoff[4];                   // the segment's first voxel along the last axis, in window k's coordinates
 };
 
-template <typename T, int NS, bool NORM>
-__global__ __launch_bounds__(256) void feature_accumulate_multi_kernel(WfSources ws, const float *__restrict__ gamma,
-                                                                       const float *__restrict__ beta, float slope,
-                                                                       const float *__restrict__ gauss, float *__restrict__ facc,
-                                                                       float *__restrict__ nsum, int PH, int PW, int SL, int Y, int Z, int x0,
-                                                                       int y0, int z0, int64_t total) {
-  __shared__ float sal[NS][WF_CIN], sbe[NS][WF_CIN];
+// facc[(x0 + pd, y0 + ph, z0 + zz)][c] += gauss[p_k] * z_k[p_k][c], nsum[..] += gauss[p_k] over the [PD][PH][SL] voxels of a segment
+// of the last axis that starts at z0 in the volume and at zoff[k] in window k (p_k = (pd, ph, zoff[k] + zz)); a whole window is the
+// segment SL = PW, zoff = 0.  8 threads per voxel, 4 channels each: every load and store instruction of a wave covers one contiguous
+// run (z: 512 B, facc: 1 KiB; a row is contiguous in the volume along its last axis).  A launch touches every accumulator element
+// once - overlapping windows are separate launches in stream order, as in the logits-space form - unless they overlap along the
+// last axis only (consecutive origins of a sliding-window row): then NS > 1 windows share a launch per segment, every voxel receives
+// the contributions of all NS windows that cover it, added in window order in registers - (acc + t_0) + t_1: the bits the one-window
+// launches produce - and the accumulator is read and written ONCE instead of NS times.  With 50 % overlap a row of 7 windows is 8
+// half-window segments: 57 % of the read-modify-write traffic.
+// NORM: the sources are raw conv outputs y of the last block and its InstanceNorm + LeakyReLU apply is folded in: z = round_T(lrelu(y *
+// alpha + beta')) is formed in registers (alpha = rstd * gamma, beta' = beta - mean * alpha: the arithmetic of in_apply_vec_kernel, so
+// the SAME z values) and never written - the apply pass (read y, write z) and the read of z disappear for the layer in front of the
+// head: 64 + 256 B per voxel instead of 128 + 320.  No backward exists in inference, so nothing else needs that z.
+// MIR (a mirrored pass of nnU-Net's test-time mirroring, NS = 1 only): the thread-to-destination mapping and gauss[p] stay, the source
+// is read at the mirrored voxel - a wave row's 512 B of z are the same run, reversed voxel by voxel when the last axis is flipped.
+template <typename T, int NS, bool NORM, bool MIR>
+__global__ __launch_bounds__(256) void feature_accumulate_kernel(WfSources ws, const float *__restrict__ gamma,
+                                                                 const float *__restrict__ beta, float slope,
+                                                                 const float *__restrict__ gauss, float *__restrict__ facc,
+                                                                 float *__restrict__ nsum, WindowPlace wp, int SL, int64_t total) {
+  static_assert(!MIR || NS == 1, "mirrored passes go one window per launch");
+  __shared__ float sal[NS][WF_CIN], sbe[NS][WF_CIN];      // the windows' per-channel constants, once per workgroup
   if (NORM) {
     if (threadIdx.x < NS * WF_CIN) {
       const int k = threadIdx.x / WF_CIN, c = threadIdx.x % WF_CIN;
@@ -155,19 +104,17 @@ __global__ __launch_bounds__(256) void feature_accumulate_multi_kernel(WfSources
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int q = (int)(i & 7);
-  const int64_t p = i >> 3;                  // voxel of the segment [PD][PH][SL]
-  const int zz = (int)(p % SL), ph = (int)((p / SL) % PH);
-  const int64_t pd = p / ((int64_t)SL * PH);
-  const int64_t v = ((pd + x0) * Y + (ph + y0)) * Z + (zz + z0);
+  const WindowVoxel s = wp_voxel(i >> 3, wp.PH, SL);      // voxel of the segment [PD][PH][SL]
+  const int64_t v = wp_volume(wp, s.pd, s.ph, s.pw);
   float4 *dst = reinterpret_cast<float4 *>(facc + v * WF_CIN + q * 4);
   float4 a = *dst;
   float n = (q == 0 && nsum) ? nsum[v] : 0.f;
   float f[NS][4], g[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) {             // all loads first
-    const int64_t pk = (pd * PH + ph) * PW + ws.zoff[k] + zz;
-    g[k] = gauss[pk];
-    wf_load4<T>(reinterpret_cast<const T *>(ws.src[k]) + pk * WF_CIN + q * 4, f[k]);
+    const int pw = ws.zoff[k] + s.pw;
+    g[k] = gauss[wp_window(wp, s.pd, s.ph, pw)];
+    wf_load4<T>(reinterpret_cast<const T *>(ws.src[k]) + wp_source<MIR>(wp, s.pd, s.ph, pw) * WF_CIN + q * 4, f[k]);
   }
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
@@ -451,145 +398,102 @@ __global__ void feature_logits_chunk_kernel(const float *__restrict__ facc, int6
 
 }  // namespace
 
-// The unmirrored and the mirrored entries share one host body each (mirror = 0 launches the kernels the unmirrored entries always
-// launched: their bits).
-static int feature_window_accumulate_impl(const char *who, const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
-                                          int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror, int dtype, void *stream) {
-  DG_REQUIRE(z && gauss && facc, DGTTA_ERR_BADARG, "%s: null pointer", who);
-  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "%s: built for %d feature channels (got %d)", who, WF_CIN, Cin);
-  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: dtype %d", who, dtype);
-  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
-  DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
-  DG_REQUIRE(((uintptr_t)z & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned buffer", who);
-  const int64_t total = (int64_t)PD * PH * PW * 8;
-  const int64_t nblk = cdiv64(total, 256);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: window too large", who);
-  hipStream_t st = (hipStream_t)stream;
-#define WF_LAUNCH(T, MIR)                                                                                                            \
-  hipLaunchKernelGGL((feature_accumulate_kernel<T, MIR>), dim3((unsigned)nblk), dim3(256), 0, st, (const T *)z, gauss, facc, nsum, PD, PH, \
-                     PW, Y, Z, x0, y0, z0, mirror, total)
-#define WF_LAUNCH_T(MIR)                               \
-  do {                                                 \
-    if (dtype == DGTTA_F32) WF_LAUNCH(float, MIR);       \
-    else if (dtype == DGTTA_BF16) WF_LAUNCH(bf16_t, MIR); \
-    else WF_LAUNCH(f16_t, MIR);                          \
-  } while (0)
-  if (mirror) WF_LAUNCH_T(true);
-  else WF_LAUNCH_T(false);
-#undef WF_LAUNCH_T
-#undef WF_LAUNCH
+// The one launcher of feature_accumulate_kernel: nsrc windows on a segment of seg_len voxels of the last axis (a whole window: nsrc = 1,
+// seg_len = PW); `what` names that block in the message.  mirror = 0 launches the kernel the unmirrored entries launch: their bits.
+template <typename T, bool NORM>
+static void feature_accumulate_launch_t(const WfSources &ws, int nsrc, const float *gamma, const float *beta, float slope, const float *gauss,
+                                        float *facc, float *nsum, const WindowPlace &wp, int seg_len, int64_t total, hipStream_t st) {
+  const auto kernel = wp.mirror   ? feature_accumulate_kernel<T, 1, NORM, true>
+                      : nsrc == 1 ? feature_accumulate_kernel<T, 1, NORM, false>
+                      : nsrc == 2 ? feature_accumulate_kernel<T, 2, NORM, false>
+                      : nsrc == 3 ? feature_accumulate_kernel<T, 3, NORM, false>
+                                  : feature_accumulate_kernel<T, 4, NORM, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, ws, gamma, beta, slope, gauss, facc, nsum, wp, seg_len,
+                     total);
+}
+
+static int feature_accumulate_launch(const char *who, const char *what, const WfSources &ws, int nsrc, bool norm, const float *gamma,
+                                     const float *beta, float slope, const float *gauss, float *facc, float *nsum, const WindowPlace &wp,
+                                     int seg_len, int dtype, void *stream) {
+  const int64_t total = (int64_t)wp.PD * wp.PH * seg_len * 8;
+  DG_REQUIRE(cdiv64(total, 256) < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: %s too large", who, what);
+  DISPATCH_T(dtype, (norm ? feature_accumulate_launch_t<T, true> : feature_accumulate_launch_t<T, false>)(
+                        ws, nsrc, gamma, beta, slope, gauss, facc, nsum, wp, seg_len, total, (hipStream_t)stream));
   DG_CHECK_LAUNCH("feature_accumulate_kernel");
   return DGTTA_OK;
 }
 
+static int feature_storage_check(const char *who, int Cin, int dtype) {
+  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "%s: built for %d feature channels (got %d)", who, WF_CIN, Cin);
+  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: dtype %d", who, dtype);
+  return DGTTA_OK;
+}
+
+// The four one-window entries: src = the window's features, or (norm) its raw conv output with the statistics mean_rstd
+static int feature_window_accumulate_one(const char *who, const void *src, bool norm, const float *mean_rstd, const float *gamma,
+                                         const float *beta, float slope, const float *gauss, float *facc, float *nsum, int Cin,
+                                         const WindowPlace &wp, int dtype, void *stream) {
+  DG_REQUIRE(src && gauss && facc && (!norm || (mean_rstd && gamma && beta)), DGTTA_ERR_BADARG, "%s: null pointer", who);
+  if (const int rc = feature_storage_check(who, Cin, dtype)) return rc;
+  if (const int rc = window_place_check(who, wp)) return rc;
+  DG_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned buffer", who);
+  WfSources ws{};
+  ws.src[0] = src;
+  ws.mean_rstd[0] = mean_rstd;
+  return feature_accumulate_launch(who, "window", ws, 1, norm, gamma, beta, slope, gauss, facc, nsum, wp, wp.PW, dtype, stream);
+}
+
 extern "C" int dgtta_feature_window_accumulate(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
                                                int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, void *stream) {
-  return feature_window_accumulate_impl("feature_window_accumulate", z, gauss, facc, nsum, Cin, PD, PH, PW, X, Y, Z, x0, y0, z0, 0, dtype,
-                                        stream);
+  return feature_window_accumulate_one("feature_window_accumulate", z, false, nullptr, nullptr, nullptr, 0.f, gauss, facc, nsum, Cin,
+                                       {PD, PH, PW, X, Y, Z, x0, y0, z0, 0}, dtype, stream);
 }
 
 extern "C" int dgtta_feature_window_accumulate_mirror(const void *z, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
                                                       int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, int mirror,
                                                       void *stream) {
-  return feature_window_accumulate_impl("feature_window_accumulate_mirror", z, gauss, facc, nsum, Cin, PD, PH, PW, X, Y, Z, x0, y0, z0,
-                                        mirror, dtype, stream);
-}
-
-static int feature_window_accumulate_norm_impl(const char *who, const void *y, const float *mean_rstd, const float *gamma, const float *beta,
-                                               float slope, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW,
-                                               int X, int Y, int Z, int x0, int y0, int z0, int mirror, int dtype, void *stream) {
-  DG_REQUIRE(y && mean_rstd && gamma && beta && gauss && facc, DGTTA_ERR_BADARG, "%s: null pointer", who);
-  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "%s: built for %d feature channels (got %d)", who, WF_CIN, Cin);
-  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "%s: dtype %d", who, dtype);
-  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
-  DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
-  DG_REQUIRE(((uintptr_t)y & 15) == 0 && ((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned buffer", who);
-  const int64_t total = (int64_t)PD * PH * PW * 8;
-  const int64_t nblk = cdiv64(total, 256);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: window too large", who);
-  hipStream_t st = (hipStream_t)stream;
-#define WF_LAUNCH(T, MIR)                                                                                                                   \
-  hipLaunchKernelGGL((feature_accumulate_norm_kernel<T, MIR>), dim3((unsigned)nblk), dim3(256), 0, st, (const T *)y, mean_rstd, gamma, beta, \
-                     slope, gauss, facc, nsum, PD, PH, PW, Y, Z, x0, y0, z0, mirror, total)
-#define WF_LAUNCH_T(MIR)                               \
-  do {                                                 \
-    if (dtype == DGTTA_F32) WF_LAUNCH(float, MIR);       \
-    else if (dtype == DGTTA_BF16) WF_LAUNCH(bf16_t, MIR); \
-    else WF_LAUNCH(f16_t, MIR);                          \
-  } while (0)
-  if (mirror) WF_LAUNCH_T(true);
-  else WF_LAUNCH_T(false);
-#undef WF_LAUNCH_T
-#undef WF_LAUNCH
-  DG_CHECK_LAUNCH("feature_accumulate_norm_kernel");
-  return DGTTA_OK;
+  return feature_window_accumulate_one("feature_window_accumulate_mirror", z, false, nullptr, nullptr, nullptr, 0.f, gauss, facc, nsum, Cin,
+                                       {PD, PH, PW, X, Y, Z, x0, y0, z0, mirror}, dtype, stream);
 }
 
 extern "C" int dgtta_feature_window_accumulate_norm(const void *y, const float *mean_rstd, const float *gamma, const float *beta, float slope,
                                                     const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH, int PW, int X,
                                                     int Y, int Z, int x0, int y0, int z0, int dtype, void *stream) {
-  return feature_window_accumulate_norm_impl("feature_window_accumulate_norm", y, mean_rstd, gamma, beta, slope, gauss, facc, nsum, Cin, PD,
-                                             PH, PW, X, Y, Z, x0, y0, z0, 0, dtype, stream);
+  return feature_window_accumulate_one("feature_window_accumulate_norm", y, true, mean_rstd, gamma, beta, slope, gauss, facc, nsum, Cin,
+                                       {PD, PH, PW, X, Y, Z, x0, y0, z0, 0}, dtype, stream);
 }
 
 extern "C" int dgtta_feature_window_accumulate_norm_mirror(const void *y, const float *mean_rstd, const float *gamma, const float *beta,
                                                            float slope, const float *gauss, float *facc, float *nsum, int Cin, int PD, int PH,
                                                            int PW, int X, int Y, int Z, int x0, int y0, int z0, int dtype, int mirror,
                                                            void *stream) {
-  return feature_window_accumulate_norm_impl("feature_window_accumulate_norm_mirror", y, mean_rstd, gamma, beta, slope, gauss, facc, nsum,
-                                             Cin, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, dtype, stream);
+  return feature_window_accumulate_one("feature_window_accumulate_norm_mirror", y, true, mean_rstd, gamma, beta, slope, gauss, facc, nsum, Cin,
+                                       {PD, PH, PW, X, Y, Z, x0, y0, z0, mirror}, dtype, stream);
 }
 
 extern "C" int dgtta_feature_window_accumulate_multi(const void *const *h_srcs, const float *const *h_mean_rstds, const int *h_zoffs, int nsrc,
                                                      const float *gamma, const float *beta, float slope, const float *gauss, float *facc,
                                                      float *nsum, int Cin, int PD, int PH, int PW, int seg_len, int X, int Y, int Z, int x0,
                                                      int y0, int z0, int dtype, void *stream) {
-  DG_REQUIRE(h_srcs && h_zoffs && gauss && facc, DGTTA_ERR_BADARG, "feature_window_accumulate_multi: null pointer");
-  DG_REQUIRE(nsrc >= 1 && nsrc <= 4, DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate_multi: 1..4 windows per segment (got %d)", nsrc);
-  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate_multi: built for %d feature channels (got %d)", WF_CIN, Cin);
-  DG_REQUIRE(dtype == DGTTA_F32 || dtype == DGTTA_BF16 || dtype == DGTTA_F16, DGTTA_ERR_BADARG, "feature_window_accumulate_multi: dtype %d", dtype);
+  const char *who = "feature_window_accumulate_multi";
+  DG_REQUIRE(h_srcs && h_zoffs && gauss && facc, DGTTA_ERR_BADARG, "%s: null pointer", who);
+  DG_REQUIRE(nsrc >= 1 && nsrc <= 4, DGTTA_ERR_UNSUPPORTED, "%s: 1..4 windows per segment (got %d)", who, nsrc);
+  if (const int rc = feature_storage_check(who, Cin, dtype)) return rc;
   const bool norm = h_mean_rstds != nullptr;
-  DG_REQUIRE(!norm || (gamma && beta), DGTTA_ERR_BADARG, "feature_window_accumulate_multi: statistics without gamma / beta");
+  DG_REQUIRE(!norm || (gamma && beta), DGTTA_ERR_BADARG, "%s: statistics without gamma / beta", who);
   DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && seg_len > 0 && seg_len <= PW && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y &&
-                 z0 + seg_len <= Z, DGTTA_ERR_BADARG, "feature_window_accumulate_multi: segment outside the volume");
+                 z0 + seg_len <= Z, DGTTA_ERR_BADARG, "%s: segment outside the volume", who);
   WfSources ws{};
   for (int k = 0; k < nsrc; ++k) {
     DG_REQUIRE(h_srcs[k] && ((uintptr_t)h_srcs[k] & 15) == 0 && h_zoffs[k] >= 0 && h_zoffs[k] + seg_len <= PW && (!norm || h_mean_rstds[k]),
-               DGTTA_ERR_BADARG, "feature_window_accumulate_multi: window %d (null / unaligned source or segment outside the window)", k);
+               DGTTA_ERR_BADARG, "%s: window %d (null / unaligned source or segment outside the window)", who, k);
     ws.src[k] = h_srcs[k];
     ws.mean_rstd[k] = norm ? h_mean_rstds[k] : nullptr;
     ws.zoff[k] = h_zoffs[k];
   }
-  DG_REQUIRE(((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "feature_window_accumulate_multi: unaligned accumulator");
-  const int64_t total = (int64_t)PD * PH * seg_len * 8;
-  const int64_t nblk = cdiv64(total, 256);
-  DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "feature_window_accumulate_multi: segment too large");
-  hipStream_t st = (hipStream_t)stream;
-#define WFM(T, NS, NRM)                                                                                                                \
-  hipLaunchKernelGGL((feature_accumulate_multi_kernel<T, NS, NRM>), dim3((unsigned)nblk), dim3(256), 0, st, ws, gamma, beta, slope, gauss, \
-                     facc, nsum, PH, PW, seg_len, Y, Z, x0, y0, z0, total)
-#define WFM_NS(T, NRM)                  \
-  do {                                  \
-    if (nsrc == 1) WFM(T, 1, NRM);      \
-    else if (nsrc == 2) WFM(T, 2, NRM); \
-    else if (nsrc == 3) WFM(T, 3, NRM); \
-    else WFM(T, 4, NRM);                \
-  } while (0)
-#define WFM_T(NRM)                                   \
-  do {                                               \
-    if (dtype == DGTTA_F32) WFM_NS(float, NRM);      \
-    else if (dtype == DGTTA_BF16) WFM_NS(bf16_t, NRM); \
-    else WFM_NS(f16_t, NRM);                         \
-  } while (0)
-  if (norm) WFM_T(true);
-  else WFM_T(false);
-#undef WFM_T
-#undef WFM_NS
-#undef WFM
-  DG_CHECK_LAUNCH("feature_accumulate_multi_kernel");
-  return DGTTA_OK;
+  DG_REQUIRE(((uintptr_t)facc & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned accumulator", who);
+  return feature_accumulate_launch(who, "segment", ws, nsrc, norm, gamma, beta, slope, gauss, facc, nsum, {PD, PH, PW, X, Y, Z, x0, y0, z0, 0},
+                                   seg_len, dtype, stream);
 }
 
 extern "C" int dgtta_feature_head_argmax(const float *facc, int64_t member_stride, const float *nsum, const float *w, const float *bsum,

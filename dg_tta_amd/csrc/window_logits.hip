@@ -1,6 +1,8 @@
 // Sliding-window inference in LOGIT space: the Gaussian-weighted accumulation of a window's logits into the volume, plain
 // (window_accumulate_kernel, at the end of the file) and fused with the segmentation head (head_accumulate*_kernel).
 // window_features.hip is the same stage in FEATURE space (the head runs once per voxel at the end, fused with the argmax).
+// Every kernel takes the window's place in the volume as one WindowPlace (window_api.h: the descriptor, its host checks and the
+// index helpers, shared with window_features.hip); the head kernels are launched through head_accumulate_launch<T, ACC, MIR, FMA>.
 //
 // Segmentation head fused with the Gaussian window accumulation (round 3, BASELINE config 3): a window's logits over ALL
 // classes ([3P] nnU-Net predict_sliding_window_return_logits via dg_tta/tta/nnunet_utils.py:116-125) are 880 MB at
@@ -14,7 +16,7 @@
 // the accumulator - float, or f16_t (what nnU-Net's predictor keeps, 2.2.1 `predicted_logits` dtype torch.half); the sum is
 // formed in fp32 either way and rounded once per window on the way back.
 #include "gfx950.h"
-#include "window_mirror.h"
+#include "window_api.h"
 
 namespace {
 
@@ -85,8 +87,7 @@ struct AccRun<f16_t> {
 template <typename T, typename ACC, bool MIR>
 __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
-                                                              ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror) {
+                                                              ACC *__restrict__ acc, float *__restrict__ nsum, int C, WindowPlace wp) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   // the head's weights are the same for every lane of a wave (a wave = 64 voxels x one class at a time): they are read
@@ -95,15 +96,16 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
   // them per tile and wave kept the LDS pipe busier than HBM (0.42 of the 0.79 ms per window)
   typedef const __attribute__((address_space(4))) float *cptr_t;
   const cptr_t wc = (cptr_t)w, bc = (cptr_t)bias;
-  const int runs = (PW + 63) >> 6, nblk = PD * PH * runs;
+  const int PH = wp.PH, PW = wp.PW;
+  const int runs = (PW + 63) >> 6, nblk = wp.PD * PH * runs;
   const int vox = threadIdx.x & 63;
   const int grp = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));       // 4 class groups per voxel
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int row = blk / runs, pw0 = (blk % runs) * 64;
     const int pd = row / PH, ph = row % PH;
     const int nv = PW - pw0 < 64 ? PW - pw0 : 64;
-    const int64_t p = ((int64_t)pd * PH + ph) * PW + pw0 + vox;   // voxel inside the window
-    const int64_t vg = ((int64_t)(x0 + pd) * Y + (y0 + ph)) * Z + (z0 + pw0);
+    const int64_t p = wp_window(wp, pd, ph, pw0 + vox);           // voxel inside the window
+    const int64_t vg = wp_volume(wp, pd, ph, pw0);
     ACC *ap = acc + vg * C;
     const int n = nv * C;
     AccRun<ACC> run;
@@ -111,12 +113,12 @@ __global__ __launch_bounds__(256) void head_accumulate_fma_kernel(const T *__res
     float ns = 0.f, gs = 0.f;
     if (nsum && (int)threadIdx.x < nv) {
       ns = nsum[vg + threadIdx.x];
-      gs = gauss[((int64_t)pd * PH + ph) * PW + pw0 + threadIdx.x];
+      gs = gauss[wp_window(wp, pd, ph, pw0 + (int)threadIdx.x)];
     }
     __syncthreads();                                              // previous tile consumed
     if (vox < nv) {
       float xr[HA_CIN];
-      const int64_t ps = MIR ? wm_source(mirror, pd, ph, pw0 + vox, PD, PH, PW) : p;
+      const int64_t ps = wp_source<MIR>(wp, pd, ph, pw0 + vox);
       const uint4 *zr = reinterpret_cast<const uint4 *>(z + ps * HA_CIN);
 #pragma unroll
       for (int g = 0; g < 4; ++g) unpack16<T>(zr[g], xr + 8 * g);
@@ -151,8 +153,7 @@ static_assert(HA_MAXC <= 8 * 16, "a wave takes class groups wv and wv + 4: at mo
 template <typename T, typename ACC, bool MIR>
 __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restrict__ z, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gauss,
-                                                              ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD,
-                                                              int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror) {
+                                                              ACC *__restrict__ acc, float *__restrict__ nsum, int C, WindowPlace wp) {
   extern __shared__ float hsm[];
   float *tile = hsm;                        // [64][C]
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -188,7 +189,8 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
       bq[j][r] = k < C ? bias[k] : 0.f;
     }
   }
-  const int runs = (PW + 63) >> 6, nblk = PD * PH * runs;
+  const int PH = wp.PH, PW = wp.PW;
+  const int runs = (PW + 63) >> 6, nblk = wp.PD * PH * runs;
   // Software pipeline over the workgroup's tiles: the accumulator run and the feature rows of tile t + 1 are requested
   // before tile t is evaluated, so that every workgroup keeps loads in flight while its waves are in the MFMA / LDS phase
   // (loads return in order: a wave that asked for its 27 accumulator values first and its feature rows second cannot start
@@ -205,8 +207,8 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
     TilePos t;
     t.nv = PW - pw0 < 64 ? PW - pw0 : 64;
     t.n = t.nv * C;
-    t.prow = ((int64_t)pd * PH + ph) * PW + pw0;                  // first voxel of the run inside the window
-    t.vg = ((int64_t)(x0 + pd) * Y + (y0 + ph)) * Z + (z0 + pw0); // ... and inside the volume
+    t.prow = wp_window(wp, pd, ph, pw0);                          // first voxel of the run inside the window
+    t.vg = wp_volume(wp, pd, ph, pw0);                            // ... and inside the volume
     t.pd = pd, t.ph = ph, t.pw0 = pw0;
     return t;
   };
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
       zz[vgp] = make_uint4(0u, 0u, 0u, 0u);
       gg[vgp] = 0.f;
       if (vox < t.nv) {
-        const int64_t ps = MIR ? wm_source(mirror, t.pd, t.ph, t.pw0 + vox, PD, PH, PW) : t.prow + vox;
+        const int64_t ps = MIR ? wp_source<true>(wp, t.pd, t.ph, t.pw0 + vox) : t.prow + vox;
         zz[vgp] = *reinterpret_cast<const uint4 *>(z + ps * HA_CIN + lq * 8);
         gg[vgp] = gauss[t.prow + vox];
       }
@@ -280,49 +282,55 @@ __global__ __launch_bounds__(256) void head_accumulate_kernel(const T *__restric
 
 }  // namespace
 
+// One launch of a head kernel as the entry points hand it down; the templates below pick the instantiation from the storage
+// types, the mirror mask and DGTTA_HA_MFMA
+struct HeadCall {
+  const void *z;
+  const float *w, *bias, *gauss;
+  void *acc;
+  float *nsum;
+  int C;
+  WindowPlace wp;
+  int acc_dtype;
+  bool fma;
+  dim3 grid;
+  size_t lds;
+  hipStream_t st;
+};
+
+template <typename T, typename ACC, bool MIR, bool FMA>
+static hipError_t head_accumulate_launch(const HeadCall &c) {
+  static DynLdsOnce once;      // one per instantiation: one per kernel
+  const auto kernel = FMA ? head_accumulate_fma_kernel<T, ACC, MIR> : head_accumulate_kernel<T, ACC, MIR>;
+  const hipError_t e = ensure_dyn_lds(once, (const void *)kernel, (int)c.lds);
+  if (e == hipSuccess)
+    hipLaunchKernelGGL(kernel, c.grid, dim3(256), c.lds, c.st, (const T *)c.z, c.w, c.bias, c.gauss, (ACC *)c.acc, c.nsum, c.C, c.wp);
+  return e;
+}
+template <typename T, typename ACC, bool MIR>
+static hipError_t head_accumulate_launch_k(const HeadCall &c) {
+  return c.fma ? head_accumulate_launch<T, ACC, MIR, true>(c) : head_accumulate_launch<T, ACC, MIR, false>(c);
+}
+template <typename T>
+static hipError_t head_accumulate_launch_t(const HeadCall &c) {
+  if (c.acc_dtype == DGTTA_F16) return head_accumulate_launch_k<T, f16_t, false>(c);      // (never mirrored: window_acc_check)
+  return c.wp.mirror ? head_accumulate_launch_k<T, float, true>(c) : head_accumulate_launch_k<T, float, false>(c);
+}
+
 static int seghead_window_accumulate_impl(const char *who, const void *z, const float *w, const float *bias, const float *gauss, void *acc,
-                                          float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0, int y0, int z0,
-                                          int mirror, int dtype, int acc_dtype, void *stream) {
+                                          float *nsum, int Cin, int C, const WindowPlace &wp, int dtype, int acc_dtype, void *stream) {
   DG_REQUIRE(z && w && bias && gauss && acc, DGTTA_ERR_BADARG, "%s: null pointer", who);
   DG_REQUIRE(Cin == HA_CIN && C > 0 && C <= HA_MAXC && (dtype == DGTTA_BF16 || dtype == DGTTA_F16), DGTTA_ERR_UNSUPPORTED,
              "%s: built for 32 input channels, up to %d classes, 16-bit storage", who, HA_MAXC);
-  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED, "%s: the accumulator is fp32 or fp16 (acc_dtype %d)",
-             who, acc_dtype);
-  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
-  DG_REQUIRE(!mirror || acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "%s: a mirrored pass needs the fp32 accumulator", who);
-  DG_REQUIRE(PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y && z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
+  if (const int rc = window_acc_check(who, acc_dtype, wp.mirror)) return rc;
+  if (const int rc = window_place_check(who, wp)) return rc;
   DG_REQUIRE(((uintptr_t)z & 15) == 0, DGTTA_ERR_BADARG, "%s: unaligned feature map", who);
-  const int64_t nblk = (int64_t)PD * PH * cdiv(PW, 64);
+  const int64_t nblk = (int64_t)wp.PD * wp.PH * cdiv(wp.PW, 64);
   DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "%s: too many rows", who);
-  const size_t lds = (size_t)64 * C * sizeof(float);
-  static DynLdsOnce once[16];
-  const dim3 grid((unsigned)(nblk < 2048 ? nblk : 2048));
-  hipStream_t st = (hipStream_t)stream;
-  const bool fma = dgtta_switches().ha_mfma == '0';
-#define HA_LAUNCH_M(IDX, T, ACC, MIR)                                                                                                  \
-  do {                                                                                                                                 \
-    const void *fn = fma ? (const void *)head_accumulate_fma_kernel<T, ACC, MIR> : (const void *)head_accumulate_kernel<T, ACC, MIR>;  \
-    DG_REQUIRE(ensure_dyn_lds(once[IDX + (fma ? 4 : 0) + (MIR ? 8 : 0)], fn, (int)lds) == hipSuccess, DGTTA_ERR_LAUNCH,                \
-               "%s: cannot raise the dynamic LDS limit", who);                                                                         \
-    if (fma)                                                                                                                           \
-      hipLaunchKernelGGL((head_accumulate_fma_kernel<T, ACC, MIR>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,            \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror);                                                \
-    else                                                                                                                               \
-      hipLaunchKernelGGL((head_accumulate_kernel<T, ACC, MIR>), grid, dim3(256), lds, st, (const T *)z, w, bias, gauss,                \
-                         (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror);                                                \
-  } while (0)
-#define HA_LAUNCH(IDX, T, ACC)                   \
-  do {                                           \
-    if (mirror) HA_LAUNCH_M(IDX, T, ACC, true);  \
-    else HA_LAUNCH_M(IDX, T, ACC, false);        \
-  } while (0)
-  if (dtype == DGTTA_BF16 && acc_dtype == DGTTA_F32) HA_LAUNCH(0, bf16_t, float);
-  else if (dtype == DGTTA_BF16) HA_LAUNCH_M(1, bf16_t, f16_t, false);      // (a mirrored pass never meets a fp16 accumulator: checked above)
-  else if (acc_dtype == DGTTA_F32) HA_LAUNCH(2, f16_t, float);
-  else HA_LAUNCH_M(3, f16_t, f16_t, false);
-#undef HA_LAUNCH
-#undef HA_LAUNCH_M
+  const HeadCall c = {z, w, bias, gauss, acc, nsum, C, wp, acc_dtype, dgtta_switches().ha_mfma == '0',
+                      dim3((unsigned)(nblk < 2048 ? nblk : 2048)), (size_t)64 * C * sizeof(float), (hipStream_t)stream};
+  DG_REQUIRE((dtype == DGTTA_BF16 ? head_accumulate_launch_t<bf16_t>(c) : head_accumulate_launch_t<f16_t>(c)) == hipSuccess,
+             DGTTA_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit", who);
   DG_CHECK_LAUNCH("head_accumulate_kernel");
   return DGTTA_OK;
 }
@@ -330,8 +338,8 @@ static int seghead_window_accumulate_impl(const char *who, const void *z, const 
 extern "C" int dgtta_seghead_window_accumulate_t(const void *z, const float *w, const float *bias, const float *gauss, void *acc,
                                                  float *nsum, int Cin, int C, int PD, int PH, int PW, int X, int Y, int Z, int x0,
                                                  int y0, int z0, int dtype, int acc_dtype, void *stream) {
-  return seghead_window_accumulate_impl("seghead_window_accumulate", z, w, bias, gauss, acc, nsum, Cin, C, PD, PH, PW, X, Y, Z, x0, y0, z0, 0,
-                                        dtype, acc_dtype, stream);
+  return seghead_window_accumulate_impl("seghead_window_accumulate", z, w, bias, gauss, acc, nsum, Cin, C,
+                                        {PD, PH, PW, X, Y, Z, x0, y0, z0, 0}, dtype, acc_dtype, stream);
 }
 
 // The logits-space forms of a mirrored pass: fp32 accumulators only (eight passes per window at Gaussian weight 10 leave no headroom
@@ -341,8 +349,8 @@ extern "C" int dgtta_seghead_window_accumulate_mirror_t(const void *z, const flo
                                                         int y0, int z0, int dtype, int acc_dtype, int mirror, void *stream) {
   DG_REQUIRE(acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "seghead_window_accumulate_mirror: the accumulator is fp32 (acc_dtype %d)",
              acc_dtype);
-  return seghead_window_accumulate_impl("seghead_window_accumulate_mirror", z, w, bias, gauss, acc, nsum, Cin, C, PD, PH, PW, X, Y, Z, x0,
-                                        y0, z0, mirror, dtype, acc_dtype, stream);
+  return seghead_window_accumulate_impl("seghead_window_accumulate_mirror", z, w, bias, gauss, acc, nsum, Cin, C,
+                                        {PD, PH, PW, X, Y, Z, x0, y0, z0, mirror}, dtype, acc_dtype, stream);
 }
 
 extern "C" int dgtta_seghead_window_accumulate(const void *z, const float *w, const float *bias, const float *gauss, float *acc,
@@ -360,53 +368,46 @@ extern "C" int dgtta_seghead_window_accumulate(const void *z, const float *w, co
 namespace {
 template <typename ACC, bool MIR>
 __global__ void window_accumulate_kernel(const float *__restrict__ patch, const float *__restrict__ gauss,
-                                         ACC *__restrict__ acc, float *__restrict__ nsum, int C, int PD, int PH, int PW,
-                                         int X, int Y, int Z, int x0, int y0, int z0, int mirror, int64_t total) {
+                                         ACC *__restrict__ acc, float *__restrict__ nsum, int C, WindowPlace wp, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const int64_t p = i / C;
-    const int pw = (int)(p % PW), ph = (int)((p / PW) % PH), pd = (int)(p / ((int64_t)PW * PH));
-    const int64_t v = ((int64_t)(x0 + pd) * Y + (y0 + ph)) * Z + (z0 + pw);
+    const WindowVoxel s = wp_voxel(p, wp.PH, wp.PW);
+    const int64_t v = wp_volume(wp, s.pd, s.ph, s.pw);
     const float g = gauss[p];
-    const int64_t is = MIR ? wm_source(mirror, pd, ph, pw, PD, PH, PW) * C + c : i;      // the mirrored voxel's row of C logits
+    const int64_t is = MIR ? wp_source<true>(wp, s.pd, s.ph, s.pw) * C + c : i;      // the mirrored voxel's row of C logits
     st_f<ACC>(acc + v * C + c, ld_f<ACC>(acc + v * C + c) + patch[is] * g);
     if (c == 0 && nsum) nsum[v] += g;
   }
 }
 }  // namespace
 
-static int window_accumulate_impl(const char *who, const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
-                                  int PW, int X, int Y, int Z, int x0, int y0, int z0, int mirror, int acc_dtype, void *stream) {
+static int window_accumulate_impl(const char *who, const float *patch, const float *gauss, void *acc, float *nsum, int C, const WindowPlace &wp,
+                                  int acc_dtype, void *stream) {
   DG_REQUIRE(patch && gauss && acc, DGTTA_ERR_BADARG, "%s: null pointer", who);
-  DG_REQUIRE(mirror >= 0 && mirror <= 7, DGTTA_ERR_BADARG, "%s: mirror mask %d outside 0..7", who, mirror);
-  DG_REQUIRE(C > 0 && PD > 0 && PH > 0 && PW > 0 && x0 >= 0 && y0 >= 0 && z0 >= 0 && x0 + PD <= X && y0 + PH <= Y &&
-                 z0 + PW <= Z,
-             DGTTA_ERR_BADARG, "%s: window outside the volume", who);
-  DG_REQUIRE(acc_dtype == DGTTA_F32 || acc_dtype == DGTTA_F16, DGTTA_ERR_UNSUPPORTED, "%s: the accumulator is fp32 or fp16 (acc_dtype %d)",
-             who, acc_dtype);
-  DG_REQUIRE(!mirror || acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "%s: a mirrored pass needs the fp32 accumulator", who);
-  const int64_t total = (int64_t)PD * PH * PW * C;
-#define WA_LAUNCH(ACC, MIR)                                                                                                            \
-  hipLaunchKernelGGL((window_accumulate_kernel<ACC, MIR>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, patch, gauss,       \
-                     (ACC *)acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, total)
-  if (acc_dtype == DGTTA_F32 && mirror) WA_LAUNCH(float, true);
-  else if (acc_dtype == DGTTA_F32) WA_LAUNCH(float, false);
-  else WA_LAUNCH(f16_t, false);
-#undef WA_LAUNCH
+  if (const int rc = window_place_check(who, wp, C > 0)) return rc;
+  if (const int rc = window_acc_check(who, acc_dtype, wp.mirror)) return rc;
+  const int64_t total = (int64_t)wp.PD * wp.PH * wp.PW * C;
+  const auto launch = [&](auto kernel, auto *a) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, patch, gauss, a, nsum, C, wp, total);
+  };
+  if (acc_dtype == DGTTA_F16) launch(window_accumulate_kernel<f16_t, false>, (f16_t *)acc);
+  else if (wp.mirror) launch(window_accumulate_kernel<float, true>, (float *)acc);
+  else launch(window_accumulate_kernel<float, false>, (float *)acc);
   DG_CHECK_LAUNCH("window_accumulate_kernel");
   return DGTTA_OK;
 }
 
 extern "C" int dgtta_window_accumulate_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
                                          int PW, int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, void *stream) {
-  return window_accumulate_impl("window_accumulate", patch, gauss, acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, 0, acc_dtype, stream);
+  return window_accumulate_impl("window_accumulate", patch, gauss, acc, nsum, C, {PD, PH, PW, X, Y, Z, x0, y0, z0, 0}, acc_dtype, stream);
 }
 
 extern "C" int dgtta_window_accumulate_mirror_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH,
                                                 int PW, int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, int mirror,
                                                 void *stream) {
   DG_REQUIRE(acc_dtype == DGTTA_F32, DGTTA_ERR_UNSUPPORTED, "window_accumulate_mirror: the accumulator is fp32 (acc_dtype %d)", acc_dtype);
-  return window_accumulate_impl("window_accumulate_mirror", patch, gauss, acc, nsum, C, PD, PH, PW, X, Y, Z, x0, y0, z0, mirror, acc_dtype,
+  return window_accumulate_impl("window_accumulate_mirror", patch, gauss, acc, nsum, C, {PD, PH, PW, X, Y, Z, x0, y0, z0, mirror}, acc_dtype,
                                 stream);
 }
 

@@ -26,6 +26,8 @@ the volume holds the 32 Gaussian-weighted feature channels the head reads (fp32:
 logits, 2.8x less read-modify-write traffic per window) and the head runs once per voxel, fused with the argmax over the ensemble
 (csrc/window_features.hip).  `predict_sliding_window_return_logits` / `predict_ensemble_logits` keep nnU-Net's logits-space form.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -85,17 +87,15 @@ def pad_to_patch(data, patch_size):
     return data, crop
 
 
-import os as _os
-
 # windows per network pass.  Measured at 512^3: 2 / 4 / 8 / 16 windows per pass = 3.26 / 3.14 / 3.07 / 3.03 ms per window in round 3;
 # round 5 (feature-space accumulator): 0.541 s per member with 8, 0.537 with 12, 0.533 with 16 (~25 GB of activations in 16-bit storage)
-WINDOW_BATCH = max(1, int(_os.environ.get("DGTTA_WINDOW_BATCH", "16")))
+WINDOW_BATCH = max(1, int(os.environ.get("DGTTA_WINDOW_BATCH", "16")))
 
 
 def window_acc_mode():
     """DGTTA_WINDOW_ACC = features (default: feature-space accumulator where the network offers it, else fp32 logits) | fp32 | fp16
     (logits-space accumulator of that storage type)."""
-    v = _os.environ.get("DGTTA_WINDOW_ACC", "features").lower()
+    v = os.environ.get("DGTTA_WINDOW_ACC", "features").lower()
     if v not in ("features", "fp32", "fp16"):
         raise ValueError(f"DGTTA_WINDOW_ACC={v!r}: features, fp32 or fp16")
     return v
@@ -194,7 +194,6 @@ def _mind_ahead_ok(model, dev):
     (as tta.tta_epoch does for the next pass) when mind_hook is the last forward pre-hook and whatever stands in front of it
     leaves the input alone (gin_hook with the trainers' internal augmentation off, the plan's untouched input modifier).
     DGTTA_INFER_PREFETCH=0: in line."""
-    import os
     from ..gin import gin_hook
     from ..mind import hook_owner, mind_hook
     from ..utils import get_internal_augmentation_enabled
@@ -271,6 +270,38 @@ def _window_batches(model, data, origins, patch_size, dev, masks=None):
         state_of(hook_owner(model)).features.clear()      # (a descriptor no mind_hook call took must not meet a later input)
 
 
+def _sliding_windows(model, data, patch_size, tile_step_size, mirror_axes, batch):
+    """The sliding-window pass behind both accumulators: pads data [C,X,Y,Z] to the patch size, uploads it and sends every window,
+    under every flip of mirror_axes (_mirror_work), through batch(work, group, gmasks, nsum, gauss) with the model in eval mode -
+    work the stacked (flipped) windows of one network pass, group their origins, gmasks their mirror masks.  Returns (nsum, crop)."""
+    dev = next(model.parameters()).device
+    data, crop = pad_to_patch(data.float(), patch_size)
+    data = data.to(dev)
+    X, Y, Z = data.shape[1:]
+    gauss = compute_gaussian(tuple(patch_size)).to(dev).contiguous()
+    steps = compute_steps_for_sliding_window((X, Y, Z), patch_size, tile_step_size)
+    nsum = torch.zeros((X, Y, Z), dtype=torch.float32, device=dev)
+    was_training = model.training
+    model.eval()
+    # windows go through the network WINDOW_BATCH at a time: the 16^3-and-below layers are launch / occupancy bound at
+    # batch 1 (same observation as in the TTA loop); per-sample InstanceNorm and per-window MIND statistics (below) make
+    # the result independent of the grouping
+    origins = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
+    origins, masks = _mirror_work(origins, mirror_axes)
+    for group, gmasks, work in _window_batches(model, data, origins, patch_size, dev, masks):
+        # MIND's variance clamp uses the mean over the whole CALL's batch (mind.py:159-161) and nnU-Net predicts one
+        # window per call: the batched pass keeps per-window statistics (groups = windows in the batch)
+        with mind_groups(model, len(group)):
+            batch(work, group, gmasks, nsum, gauss)
+    model.train(was_training)
+    return nsum, crop
+
+
+def _mirrors_kw(gmasks):
+    """The `mirrors` argument of a fuse_window_* context for one batch."""
+    return {"mirrors": gmasks} if any(gmasks) else {}
+
+
 @torch.no_grad()
 def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile_step_size=0.5, acc_dtype=None, mirror_axes=None):
     """data [C,X,Y,Z] (CPU or GPU) -> accumulates gauss-weighted logits of `model` into acc [X,Y,Z,ncls] (GPU; fp32 or
@@ -292,48 +323,32 @@ def predict_sliding_window_return_logits(model, data, patch_size, acc=None, tile
                          "Gaussian weight 10 leave no headroom in half - use the fp32 logits accumulator (DGTTA_WINDOW_ACC=fp32) or "
                          "the feature-space accumulator (DGTTA_WINDOW_ACC=features)")
     lib = _lib.load()
-    dev = next(model.parameters()).device
-    data, crop = pad_to_patch(data.float(), patch_size)
-    data = data.to(dev)
-    X, Y, Z = data.shape[1:]
-    gauss = compute_gaussian(tuple(patch_size)).to(dev).contiguous()
-    steps = compute_steps_for_sliding_window((X, Y, Z), patch_size, tile_step_size)
-    nsum = torch.zeros((X, Y, Z), dtype=torch.float32, device=dev)
-    was_training = model.training
-    model.eval()
-    # windows go through the network WINDOW_BATCH at a time: the 16^3-and-below layers are launch / occupancy bound at
-    # batch 1 (same observation as in the TTA loop); per-sample InstanceNorm and per-window MIND statistics (below) make
-    # the result independent of the grouping
-    origins = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
-    origins, masks = _mirror_work(origins, mirror_axes)
-    for group, gmasks, work in _window_batches(model, data, origins, patch_size, dev, masks):
-        mirrors = {"mirrors": gmasks} if any(gmasks) else {}
-        # MIND's variance clamp uses the mean over the whole CALL's batch (mind.py:159-161) and nnU-Net predicts one
-        # window per call: the batched pass keeps per-window statistics (groups = windows in the batch)
+
+    def batch(work, group, gmasks, nsum, gauss):
+        nonlocal acc
+        dev, vol = nsum.device, tuple(nsum.shape)
         if _can_fuse_head_accumulate(model):
             # the head evaluates straight into the accumulator (the windows' logits - 880 MB each at 128^3 x 105 - are not written)
             if acc is None:
-                acc = torch.zeros((X, Y, Z, _num_classes(model)), dtype=acc_dtype, device=dev)
-            with mind_groups(model, len(group)), _inner(model).fuse_window_accumulate(acc, nsum, gauss, group, **mirrors):
+                acc = torch.zeros((*vol, _num_classes(model)), dtype=acc_dtype, device=dev)
+            with _inner(model).fuse_window_accumulate(acc, nsum, gauss, group, **_mirrors_kw(gmasks)):
                 model(work)
-            continue
-        with mind_groups(model, len(group)):
-            out = model(work)
+            return
+        out = model(work)
         if isinstance(out, tuple):
             out = out[0]
         out = out.float().contiguous(memory_format=torch.channels_last_3d)        # [n,C,P] stored voxel-major
         ncls = out.shape[1]
         if acc is None:
-            acc = torch.zeros((X, Y, Z, ncls), dtype=acc_dtype, device=dev)
-        for k, (sx, sy, sz) in enumerate(group):       # overlapping windows: accumulated one after the other
-            if gmasks[k]:      # a mirrored pass: un-flipped on its way into the accumulator
-                check(lib.dgtta_window_accumulate_mirror_t(ptr(out[k]), ptr(gauss), ptr(acc), ptr(nsum), ncls, *patch_size, X, Y, Z,
-                                                           sx, sy, sz, _acc_code(acc), gmasks[k], stream_of(dev)),
-                      "dgtta_window_accumulate_mirror_t")
-                continue
-            check(lib.dgtta_window_accumulate_t(ptr(out[k]), ptr(gauss), ptr(acc), ptr(nsum), ncls, *patch_size, X, Y, Z, sx,
-                                                sy, sz, _acc_code(acc), stream_of(dev)), "dgtta_window_accumulate_t")
-    model.train(was_training)
+            acc = torch.zeros((*vol, ncls), dtype=acc_dtype, device=dev)
+        for k, origin in enumerate(group):       # overlapping windows: accumulated one after the other
+            args = (ptr(out[k]), ptr(gauss), ptr(acc), ptr(nsum), ncls, *patch_size, *vol, *origin, _acc_code(acc))
+            if acc.dtype == torch.float32:       # a mirrored pass is un-flipped on its way into the accumulator (mask 0: no flip)
+                check(lib.dgtta_window_accumulate_mirror_t(*args, gmasks[k], stream_of(dev)), "dgtta_window_accumulate_mirror_t")
+            else:                                # (the _mirror entry takes fp32 accumulators only; fp16 is never mirrored: above)
+                check(lib.dgtta_window_accumulate_t(*args, stream_of(dev)), "dgtta_window_accumulate_t")
+
+    nsum, crop = _sliding_windows(model, data, patch_size, tile_step_size, mirror_axes, batch)
     return acc, nsum, crop
 
 
@@ -346,26 +361,17 @@ def accumulate_window_features(model, data, patch_size, facc=None, tile_step_siz
     m = _inner(model)
     if not _can_accumulate_features(model):
         raise RuntimeError("accumulate_window_features: the network does not offer the feature-space accumulation here")
-    dev = next(model.parameters()).device
-    data, crop = pad_to_patch(data.float(), patch_size)
-    data = data.to(dev)
-    X, Y, Z = data.shape[1:]
+    X, Y, Z = (max(have, want) for have, want in zip(data.shape[1:], patch_size))      # the padded volume (pad_to_patch)
     if facc is None:
-        facc = torch.zeros((X, Y, Z, 32), dtype=torch.float32, device=dev)
+        facc = torch.zeros((X, Y, Z, 32), dtype=torch.float32, device=next(model.parameters()).device)
     if tuple(facc.shape) != (X, Y, Z, 32) or facc.dtype != torch.float32 or not (facc.is_cuda and facc.is_contiguous()):
         raise ValueError(f"facc must be a contiguous fp32 GPU tensor [{X},{Y},{Z},32]")
-    gauss = compute_gaussian(tuple(patch_size)).to(dev).contiguous()
-    steps = compute_steps_for_sliding_window((X, Y, Z), patch_size, tile_step_size)
-    nsum = torch.zeros((X, Y, Z), dtype=torch.float32, device=dev)
-    was_training = model.training
-    model.eval()
-    origins = [(sx, sy, sz) for sx in steps[0] for sy in steps[1] for sz in steps[2]]
-    origins, masks = _mirror_work(origins, mirror_axes)
-    for group, gmasks, work in _window_batches(model, data, origins, patch_size, dev, masks):
-        mirrors = {"mirrors": gmasks} if any(gmasks) else {}
-        with mind_groups(model, len(group)), m.fuse_window_feature_accumulate(facc, nsum, gauss, group, **mirrors):
+
+    def batch(work, group, gmasks, nsum, gauss):
+        with m.fuse_window_feature_accumulate(facc, nsum, gauss, group, **_mirrors_kw(gmasks)):
             model(work)
-    model.train(was_training)
+
+    nsum, crop = _sliding_windows(model, data, patch_size, tile_step_size, mirror_axes, batch)
     return facc, nsum, crop
 
 

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import check, ptr, stream_of
 from ._state import state_of
 from .ops import F32, BF16, F16, dtype_code
-from .unet_exec import EPS, SLOPE, _UNetFn, _k3
+from .unet_exec import EPS, SLOPE, WindowSink, _UNetFn, _k3
 
 PLANS_3D_FULLRES = dict(features=(32, 64, 128, 256, 320), strides=(1, 2, 2, 2, 2),
                         n_conv_enc=(2, 2, 2, 2, 2), n_conv_dec=(2, 2, 2, 2),
@@ -156,7 +156,7 @@ class HipPlainConvUNet(nn.Module):
         self._packed = {}        # id(weight) -> (version, wf, wb)
         self.selected_classes = None   # optional LongTensor: evaluate only these head rows (== map_label 'logits')
         self._fused_warp = None        # (theta on the device, theta on the host) while fuse_output_warp() is active
-        self._window_acc = None        # sliding-window target while fuse_window_accumulate() is active
+        self._window_acc = None        # sliding-window target (a WindowSink) while a fuse_window_*() context is active
         self.deep_supervision = bool(deep_supervision)
 
     def __deepcopy__(self, memo):
@@ -233,7 +233,7 @@ class HipPlainConvUNet(nn.Module):
         if not (acc.is_contiguous() and nsum.dtype == torch.float32 and gauss.dtype == torch.float32):
             raise ValueError("fuse_window_accumulate: contiguous accumulator, fp32 weight sum and fp32 Gaussian expected")
         self._no_deep_supervision("fuse_window_accumulate")
-        return self._during("_window_acc", lambda: (acc, nsum, gauss, list(origins), mirrors))
+        return self._during("_window_acc", lambda: WindowSink(acc, nsum, gauss, list(origins), mirrors, "logits"))
 
     @staticmethod
     def _window_mirrors(mirrors, origins, what):
@@ -258,7 +258,7 @@ class HipPlainConvUNet(nn.Module):
                 gauss.dtype == torch.float32):
             raise ValueError("fuse_window_feature_accumulate: contiguous fp32 accumulator [X,Y,Z,32], fp32 weight sum and Gaussian expected")
         self._no_deep_supervision("fuse_window_feature_accumulate")
-        return self._during("_window_acc", lambda: (facc, nsum, gauss, list(origins), mirrors, "features"))
+        return self._during("_window_acc", lambda: WindowSink(facc, nsum, gauss, list(origins), mirrors, "features"))
 
     def forward(self, x):
         sel = self.selected_classes

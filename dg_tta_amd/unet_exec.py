@@ -7,6 +7,7 @@ Data layout in HBM: activations are channels-last [B][D][H][W][C] (fp32, or bf16
 `torch.cat((up, skip), 1)` never happens: the transposed conv writes the first channel half of a pre-allocated
 [.., 2C] buffer and the encoder's InstanceNorm+LeakyReLU writes the skip directly into the second half.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -45,7 +46,12 @@ def _check_patch_divisible(strides, dims):
         f"patch {dims[0]}x{dims[1]}x{dims[2]} must be divisible by {tot[0]}x{tot[1]}x{tot[2]} (the product of the strides per axis)"
 
 
-# ------------------------------------------------------------------------------------------------ sliding-window segments
+# ------------------------------------------------------------------------------------------------ sliding-window target
+# What HipPlainConvUNet.fuse_window_accumulate / fuse_window_feature_accumulate hand the forward: window k of the batch goes into
+# acc / nsum at origins[k], read under the mirror mask mirrors[k]; space: "logits" (the head runs here) or "features" (it does not)
+WindowSink = collections.namedtuple("WindowSink", "acc nsum gauss origins mirrors space")
+
+
 def window_segments(origins, w, max_cover=4):
     """Launches of the feature-space window accumulation for windows at origins[k] = (x, y, z), w long on the last axis: a
     window index k (that window on its own) or (x, y, a, b, [window indices]): positions a..b-1 of the last axis of a row,
@@ -451,10 +457,10 @@ def _decoder_forward(p, ups, dec, cats, x, feat_fold):
     return stage_rows
 
 
-def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
+def _accumulate_feature_windows(p, sink, last, z, feat_fold, dims):
     """Adds gauss * (the 32 channels the head reads) of window k into the accumulator at origins[k] (csrc/window_features.hip)."""
     lib, dt, st = p.lib, p.dt, p.st
-    acc, nsum, gauss, origins = wa[:4]
+    acc, nsum, gauss, origins, mirrors = sink.acc, sink.nsum, sink.gauss, sink.origins, sink.mirrors
     X, Y, Z = acc.shape[:3]
     D, H, W = dims
     nrm = last.mod.norm
@@ -462,31 +468,23 @@ def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
     assert (32 if feat_fold else z.ld) == 32
     wbytes = D * H * W * 32 * p.esz            # one window of the source
     mrbytes = 32 * 2 * 4                       # one window of mean / rstd
-    segments = os.environ.get("DGTTA_FEATURE_SEGMENTS", "1") != "0"
-    mirrors = wa[4]
-    for k in (k for k in range(len(origins)) if mirrors[k]):      # mirrored passes: one window per launch, un-flipped by the kernel
-        sx, sy, sz = origins[k]
+    fold = (ptr(nrm.weight), ptr(nrm.bias), SLOPE)
+
+    def one(k):      # one window per launch, un-flipped by the kernel (mask 0: the unmirrored kernel)
+        place = (ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W, X, Y, Z, *origins[k], dt, mirrors[k], st)
         if feat_fold:
-            check(lib.dgtta_feature_window_accumulate_norm_mirror(src0 + k * wbytes, last.mr.data_ptr() + k * mrbytes, ptr(nrm.weight),
-                                                                  ptr(nrm.bias), SLOPE, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W,
-                                                                  X, Y, Z, sx, sy, sz, dt, mirrors[k], st),
+            check(lib.dgtta_feature_window_accumulate_norm_mirror(src0 + k * wbytes, last.mr.data_ptr() + k * mrbytes, *fold, *place),
                   "dgtta_feature_window_accumulate_norm_mirror")
         else:
-            check(lib.dgtta_feature_window_accumulate_mirror(src0 + k * wbytes, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W, X, Y, Z,
-                                                             sx, sy, sz, dt, mirrors[k], st), "dgtta_feature_window_accumulate_mirror")
+            check(lib.dgtta_feature_window_accumulate_mirror(src0 + k * wbytes, *place), "dgtta_feature_window_accumulate_mirror")
+
+    for k in (k for k in range(len(origins)) if mirrors[k]):
+        one(k)
     plain = [k for k in range(len(origins)) if not mirrors[k]]      # the unmirrored windows keep the segment merging
-    plain_origins = [origins[k] for k in plain]
-    for launch in window_segments(plain_origins, W) if segments else range(len(plain)):
+    segments = os.environ.get("DGTTA_FEATURE_SEGMENTS", "1") != "0"
+    for launch in window_segments([origins[k] for k in plain], W) if segments else range(len(plain)):
         if isinstance(launch, int):
-            k = plain[launch]
-            sx, sy, sz = origins[k]
-            if feat_fold:
-                check(lib.dgtta_feature_window_accumulate_norm(src0 + k * wbytes, last.mr.data_ptr() + k * mrbytes, ptr(nrm.weight),
-                                                               ptr(nrm.bias), SLOPE, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W,
-                                                               X, Y, Z, sx, sy, sz, dt, st), "dgtta_feature_window_accumulate_norm")
-            else:
-                check(lib.dgtta_feature_window_accumulate(src0 + k * wbytes, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W, X, Y, Z,
-                                                          sx, sy, sz, dt, st), "dgtta_feature_window_accumulate")
+            one(plain[launch])
             continue
         sx, sy, a, b, part = launch
         part = [plain[i] for i in part]
@@ -494,28 +492,22 @@ def _accumulate_feature_windows(p, wa, last, z, feat_fold, dims):
         srcs = (C.c_void_p * n)(*[src0 + i * wbytes for i in part])
         mrs = (C.c_void_p * n)(*[last.mr.data_ptr() + i * mrbytes for i in part]) if feat_fold else None
         zoffs = (C.c_int * n)(*[a - origins[i][2] for i in part])
-        check(lib.dgtta_feature_window_accumulate_multi(srcs, mrs, zoffs, n, ptr(nrm.weight), ptr(nrm.bias), SLOPE, ptr(gauss),
-                                                        ptr(acc), ptr(nsum), 32, D, H, W, b - a, X, Y, Z, sx, sy, a, dt, st),
-              "dgtta_feature_window_accumulate_multi")
+        check(lib.dgtta_feature_window_accumulate_multi(srcs, mrs, zoffs, n, *fold, ptr(gauss), ptr(acc), ptr(nsum), 32, D, H, W, b - a,
+                                                        X, Y, Z, sx, sy, a, dt, st), "dgtta_feature_window_accumulate_multi")
 
 
-def _accumulate_logit_windows(p, wa, head, z, dims):
-    """Head fused with the Gaussian window accumulation: overlapping windows are accumulated one after the other."""
-    acc, nsum, gauss, origins, mirrors = wa[:5]
-    X, Y, Z = acc.shape[:3]
+def _accumulate_logit_windows(p, sink, head, z, dims):
+    """Head fused with the Gaussian window accumulation: overlapping windows are accumulated one after the other, a mirrored pass
+    un-flipped on its way into the accumulator (mask 0: the unmirrored kernel)."""
+    acc, nsum = sink.acc, sink.nsum
     D, H, W = dims
-    for k, (sx, sy, sz) in enumerate(origins):
-        src = z.ptr + k * D * H * W * z.ld * p.esz
-        if mirrors[k]:      # a mirrored pass: its logits are un-flipped on the way into the accumulator
-            check(p.lib.dgtta_seghead_window_accumulate_mirror_t(src, ptr(head.weight), ptr(head.bias), ptr(gauss), ptr(acc), ptr(nsum),
-                                                                 head.in_channels, head.out_channels, D, H, W, X, Y, Z, sx, sy, sz, p.dt,
-                                                                 F32 if acc.dtype == torch.float32 else F16, mirrors[k], p.st),
-                  "dgtta_seghead_window_accumulate_mirror_t")
-            continue
-        check(p.lib.dgtta_seghead_window_accumulate_t(src, ptr(head.weight), ptr(head.bias),
-                                                      ptr(gauss), ptr(acc), ptr(nsum), head.in_channels, head.out_channels, D, H,
-                                                      W, X, Y, Z, sx, sy, sz, p.dt, F32 if acc.dtype == torch.float32 else F16,
-                                                      p.st), "dgtta_seghead_window_accumulate_t")
+    for k, origin in enumerate(sink.origins):
+        args = (z.ptr + k * D * H * W * z.ld * p.esz, ptr(head.weight), ptr(head.bias), ptr(sink.gauss), ptr(acc), ptr(nsum),
+                head.in_channels, head.out_channels, D, H, W, *acc.shape[:3], *origin, p.dt)
+        if acc.dtype == torch.float32:
+            check(p.lib.dgtta_seghead_window_accumulate_mirror_t(*args, F32, sink.mirrors[k], p.st), "dgtta_seghead_window_accumulate_mirror_t")
+        else:      # the _mirror entry takes fp32 accumulators only; a fp16 one is never mirrored into (fuse_window_accumulate)
+            check(p.lib.dgtta_seghead_window_accumulate_t(*args, F16, p.st), "dgtta_seghead_window_accumulate_t")
 
 
 def _head_forward(p, head, z, sel, nsel, fw, dims):
@@ -694,19 +686,19 @@ class _UNetFn(torch.autograd.Function):
         assert cin0 == cfg["in_channels"], f"expected {cfg['in_channels']} input channels, got {cin0}"
         _check_patch_divisible(cfg["strides"], dims)
         head = net.decoder.seg_layers[-1]
-        wa = net._window_acc
-        feat_fold = (wa is not None and wa[-1] == "features" and not need_grad and os.environ.get("DGTTA_FEATURE_FOLD", "1") != "0" and
+        sink_w = net._window_acc      # a WindowSink or None
+        feat_fold = (sink_w is not None and sink_w.space == "features" and not need_grad and os.environ.get("DGTTA_FEATURE_FOLD", "1") != "0" and
                      head.in_channels == cfg["features"][0] == 32)
         enc, ups, dec = _plan(p, cin0, dims)
         z, cats = _encoder_forward(p, enc, ups, dec, _input_rows(p, x))
         stage_rows = _decoder_forward(p, ups, dec, cats, z, feat_fold)
         z = stage_rows[-1]
-        if wa is not None:
-            assert not need_grad and sel is None and z.ld == head.in_channels and len(wa[3]) == B, "fuse_window_accumulate: misuse"
-            if wa[-1] == "features":      # feature space: no head here
-                _accumulate_feature_windows(p, wa, dec[-1][-1], z, feat_fold, dims)
+        if sink_w is not None:
+            assert not need_grad and sel is None and z.ld == head.in_channels and len(sink_w.origins) == B, "fuse_window_accumulate: misuse"
+            if sink_w.space == "features":      # feature space: no head here
+                _accumulate_feature_windows(p, sink_w, dec[-1][-1], z, feat_fold, dims)
             else:
-                _accumulate_logit_windows(p, wa, head, z, dims)
+                _accumulate_logit_windows(p, sink_w, head, z, dims)
             return p.empty(B, 0, D, H, W, dtype=torch.float32)
         nsel = head.out_channels if sel is None else int(sel.numel())
         fw = net._fused_warp

@@ -271,8 +271,86 @@ def test_seghead_window_accumulate_mirror_t(dts, case, kernel, monkeypatch):
         reload_kernel_switches()
 
 
+# Every window entry of the C ABI: (the arguments it takes of c = Cin, a = acc_dtype, m = mirror; call(lib, t, P, origin, mask, cin,
+# acc_code)).  16-bit sources are bf16 (dtype code 1); the multi entry is given one whole window (zoff 0, seg_len = PW).
+def _multi(L, t, P, o, mask, cin, acc):
+    import ctypes as C
+    return L.dgtta_feature_window_accumulate_multi((C.c_void_p * 1)(t.z), (C.c_void_p * 1)(t.mr), (C.c_int * 1)(0), 1, t.gamma, t.beta, 0.01,
+                                                   t.g, t.acc, t.n, cin, *P, P[2], *t.V, *o, 1, None)
+
+
+WINDOW_ENTRIES = {
+    "dgtta_window_accumulate": ("", lambda L, t, P, o, mask, cin, acc:
+                                L.dgtta_window_accumulate(t.patch, t.g, t.acc, t.n, t.C, *P, *t.V, *o, None)),
+    "dgtta_window_accumulate_t": ("a", lambda L, t, P, o, mask, cin, acc:
+                                  L.dgtta_window_accumulate_t(t.patch, t.g, t.acc, t.n, t.C, *P, *t.V, *o, acc, None)),
+    "dgtta_window_accumulate_mirror_t": ("am", lambda L, t, P, o, mask, cin, acc:
+                                         L.dgtta_window_accumulate_mirror_t(t.patch, t.g, t.acc, t.n, t.C, *P, *t.V, *o, acc, mask, None)),
+    "dgtta_seghead_window_accumulate": ("c", lambda L, t, P, o, mask, cin, acc:
+                                        L.dgtta_seghead_window_accumulate(t.z, t.w, t.b, t.g, t.acc, t.n, cin, t.C, *P, *t.V, *o, 1, None)),
+    "dgtta_seghead_window_accumulate_t": ("ca", lambda L, t, P, o, mask, cin, acc:
+                                          L.dgtta_seghead_window_accumulate_t(t.z, t.w, t.b, t.g, t.acc, t.n, cin, t.C, *P, *t.V, *o, 1, acc,
+                                                                              None)),
+    "dgtta_seghead_window_accumulate_mirror_t": ("cam", lambda L, t, P, o, mask, cin, acc:
+                                                 L.dgtta_seghead_window_accumulate_mirror_t(t.z, t.w, t.b, t.g, t.acc, t.n, cin, t.C, *P, *t.V,
+                                                                                            *o, 1, acc, mask, None)),
+    "dgtta_feature_window_accumulate": ("c", lambda L, t, P, o, mask, cin, acc:
+                                        L.dgtta_feature_window_accumulate(t.z, t.g, t.acc, t.n, cin, *P, *t.V, *o, 1, None)),
+    "dgtta_feature_window_accumulate_mirror": ("cm", lambda L, t, P, o, mask, cin, acc:
+                                               L.dgtta_feature_window_accumulate_mirror(t.z, t.g, t.acc, t.n, cin, *P, *t.V, *o, 1, mask, None)),
+    "dgtta_feature_window_accumulate_norm": ("c", lambda L, t, P, o, mask, cin, acc:
+                                             L.dgtta_feature_window_accumulate_norm(t.z, t.mr, t.gamma, t.beta, 0.01, t.g, t.acc, t.n, cin, *P,
+                                                                                    *t.V, *o, 1, None)),
+    "dgtta_feature_window_accumulate_norm_mirror": ("cm", lambda L, t, P, o, mask, cin, acc:
+                                                    L.dgtta_feature_window_accumulate_norm_mirror(t.z, t.mr, t.gamma, t.beta, 0.01, t.g, t.acc,
+                                                                                                  t.n, cin, *P, *t.V, *o, 1, mask, None)),
+    "dgtta_feature_window_accumulate_multi": ("c", _multi),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", list(WINDOW_ENTRIES))
+def test_window_entries_refuse_bad_places_with_their_codes(entry):
+    """Every window entry on p568: a window outside the volume (one voxel too far on each axis, a negative origin, a zero patch extent) and
+    a mirror mask outside 0..7 are DGTTA_ERR_BADARG, Cin = 16 and a fp16 accumulator with a non-zero mask DGTTA_ERR_UNSUPPORTED - for the
+    arguments the entry takes - and a refused call launches nothing.  (The accumulators are the middle of a larger zeroed buffer:
+    a launch that slipped through would show there, not beyond the allocation.)"""
+    import types
+    lib = _lib()
+    takes, call = WINDOW_ENTRIES[entry]
+    P, V, _ = CASES["p568"]
+    torch.manual_seed(5)
+    C = 7
+    big_a, big_n = torch.zeros(V[0] + 4, V[1], V[2], 32, device=DEV), torch.zeros(V[0] + 4, V[1], V[2], device=DEV)
+    tensors = dict(patch=torch.randn(*P, C, device=DEV), z=torch.randn(*P, 32, device=DEV).to(torch.bfloat16),
+                   g=torch.rand(*P, device=DEV) + 0.1, w=torch.randn(C, 32, device=DEV), b=torch.randn(C, device=DEV),
+                   mr=torch.stack([torch.randn(32, device=DEV), torch.rand(32, device=DEV) + 0.5], -1).contiguous(),
+                   gamma=torch.randn(32, device=DEV), beta=torch.randn(32, device=DEV), acc=big_a[2:], n=big_n[2:])
+    t = types.SimpleNamespace(V=V, C=C, **{k: v.data_ptr() for k, v in tensors.items()})
+
+    def rc(P=P, o=(0, 0, 0), mask=0, cin=32, acc=0):
+        return call(lib, t, P, o, mask, cin, acc)
+
+    for axis in range(3):
+        far, neg, flat = [0, 0, 0], [0, 0, 0], list(P)
+        far[axis], neg[axis], flat[axis] = V[axis] - P[axis] + 1, -1, 0
+        assert rc(o=far) == BADARG and rc(o=neg) == BADARG and rc(P=flat) == BADARG
+    if "m" in takes:
+        assert rc(mask=8) == BADARG and rc(mask=-1) == BADARG
+    if "c" in takes:
+        assert rc(cin=16) == UNSUPPORTED
+    if "a" in takes and "m" in takes:
+        assert rc(mask=1, acc=2) == UNSUPPORTED
+    torch.cuda.synchronize()
+    assert float(big_a.abs().max()) == 0.0 and float(big_n.abs().max()) == 0.0
+    assert rc(o=(V[0] - P[0], V[1] - P[1], V[2] - P[2]), mask=7 if "m" in takes else 0) == 0      # (the call itself is well formed)
+    torch.cuda.synchronize()
+    assert float(big_a[2:].abs().max()) > 0 and float(big_n[2:].min()) >= 0 and float(big_n[2:].max()) > 0
+    assert float(big_a[:2].abs().max()) == 0.0 and float(big_a[2 + V[0]:].abs().max()) == 0.0
+
+
 # ------------------------------------------------------------------------------------------------ network level
-FEAT32_1CH = dict(features=(32, 40), strides=(1, 2), n_conv_enc=(2, 2), n_conv_dec=(2,), in_channels=1, num_classes=9)
+FEAT32_1CH =dict(features=(32, 40), strides=(1, 2), n_conv_enc=(2, 2), n_conv_dec=(2,), in_channels=1, num_classes=9)
 
 
 def _small_1ch():

@@ -396,9 +396,17 @@ def test_feature_window_accumulate_kernel(dts):
             zoffs = (C.c_int * len(cover))(*[a - zs[k] for k in cover])
             check(lib.dgtta_feature_window_accumulate_multi(srcs, mrs, zoffs, len(cover), ptr(gamma), ptr(beta), 0.01, ptr(gauss), ptr(seg_f),
                                                             ptr(seg_n), 32, *P, b - a, X, Y, Z, 2, 1, a, dt, stream_of()), "multi")
+        # the multi entry on one WHOLE window at a time (nsrc = 1, zoff = 0, seg_len = PW) is the single-window entry: the same bits
+        whole_f, whole_n = facc.clone(), nsum.clone()
+        for k, sz in enumerate(zs):
+            mrs = (C.c_void_p * 1)(mr[k].data_ptr()) if norm else None
+            check(lib.dgtta_feature_window_accumulate_multi((C.c_void_p * 1)(y[k].data_ptr()), mrs, (C.c_int * 1)(0), 1, ptr(gamma), ptr(beta),
+                                                            0.01, ptr(gauss), ptr(whole_f), ptr(whole_n), 32, *P, P[2], X, Y, Z, 2, 1, sz, dt,
+                                                            stream_of()), "multi, one window")
         torch.cuda.synchronize()
         assert max(len(cover) for _, _, _, _, cover in launches) == 3
         assert torch.equal(seg_f, one_f) and torch.equal(seg_n, one_n) and not torch.equal(seg_f, facc)
+        assert torch.equal(whole_f, one_f) and torch.equal(whole_n, one_n)
 
 
 @pytest.mark.gpu
