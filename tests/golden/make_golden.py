@@ -77,7 +77,8 @@ def gold_mind():
         noise = torch.randn(shape[0], 12, *shape[2:])
         check(omind.mind3d(img, noise), ref, f"mind3d {tag}")
         save(f"mind3d_{tag}", img=img, noise=noise, out=ref)
-    # constant image: edge == noise only; exercises the global clamp
+    # constant image: edge == noise only (no voxel reaches the variance clamp: tests/test_mind_ref.py prints the counts;
+    # tests/test_gpu_mind_exact.py brings the case that clamps on both sides)
     img = torch.full((1, 1, 8, 8, 8), 3.0)
     torch.manual_seed(5)
     ref = MIND3D()(img)
