@@ -43,6 +43,8 @@ SIGNATURES = {
     "dgtta_dice_ce_ds_ws_bytes": (SZ, [I, I, I, I, I]),
     "dgtta_dice_ce_ds_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, F, I, P]),
     "dgtta_dice_ce_ds_bwd": (I, [P, I, P, P, F, P, P, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_dice_ce_batch_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I64, F, I, I, P]),
+    "dgtta_dice_ce_ds_batch_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, F, I, I, P]),
     "dgtta_adamw_step": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I64), I, F, F, F, F, F,
                              I, F, P, P]),
     "dgtta_grads_nonfinite": (I, [C.POINTER(P), C.POINTER(I64), I, P, P]),

@@ -7,6 +7,14 @@
 //   ce   = -(1/N) sum_v log p[v][y_v]                                   N = valid voxels of the whole batch
 //   dc_bc = (2 sum_v p y + s) / (sum_v p + sum_v y + s)                  per sample b and class c, y one-hot
 //   loss = ce - mean_{b, c >= first} dc_bc                               first = 1 (do_bg = False) or 0
+// Batch Dice (the `batch_dice` argument of the dgtta_dice_ce_batch_fwd / dgtta_dice_ce_ds_batch_fwd entries; what nnU-Net's planner
+// sets for 3d_fullres whenever a 3d_lowres configuration exists): the three sums are pooled over the batch BEFORE the ratio,
+//   I_c = sum_b sum_v p y;  P_c = sum_b sum_v p;  Y_c = sum_b sum_v y;  dc_c = (2 I_c + s) / max(P_c + Y_c + s, 1e-8)
+//   loss = ce - mean_{c >= first} dc_c                                   (ce unchanged)
+// - a restatement FROM MEMORY of MemoryEfficientSoftDiceLoss(batch_dice=True, do_bg=False, smooth=1e-5) inside DC_and_CE_loss
+// [3P nnunetv2==2.2.1, not available here]: UNPINNED.  Only the finalize kernel knows the mode: it forms the per-sample sums in the
+// per-sample mode's order, adds them over b in ascending order (double, no atomics: bit-reproducible) and writes the same
+// {alpha, beta} pair - with w = 1 / (C - first) - for every b, so the backward kernel is the per-sample one.
 // Logits are voxel-major [B][V][ldc] fp32 (what the head writes); a workgroup stages 128 rows through LDS as one contiguous run,
 // one lane = one voxel inside the tile; HBM-bound and NOT on the timed path.
 // Deterministic: per-workgroup partial sums (double) in fixed slots, one finalize workgroup adds them in slot order.
@@ -156,14 +164,16 @@ __global__ __launch_bounds__(DC_THREADS) void dice_ce_fwd_kernel(const float *__
 }
 
 // one workgroup: loss[0] = total, loss[1] = ce, loss[2] = -mean dice; dice[B][C]; coef[(b * C + c) * 2 + {0, 1}] = {alpha, beta}
-// with dL/dp[v][c] = alpha * [y_v == c] + beta, coef[2 B C] = 1 / N
+// with dL/dp[v][c] = alpha * [y_v == c] + beta, coef[2 B C] = 1 / N.  batch_dice: the sums of a class are pooled over b first
+// (file header); every row of dice and every b of coef then holds the class's one value.
 __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const double *__restrict__ partial, int nblk, int B, int C,
-                                                             float smooth, int first, float *__restrict__ loss,
+                                                             float smooth, int first, int batch_dice, float *__restrict__ loss,
                                                              float *__restrict__ dice, float *__restrict__ coef) {
   __shared__ double s_dc[8 * DC_MAXC];
+  __shared__ double s_sum[3][8 * DC_MAXC];             // batch mode: the per-sample {I, P, Y} of every (b, c)
   __shared__ double s_ce, s_nv;
   const int n = B * C, W = 3 * C + 2;
-  const double w = 1.0 / (double)(B * (C - first));
+  const double w = 1.0 / (double)((batch_dice ? 1 : B) * (C - first));
   // four lanes per (b, c): lane p adds the partial slots p, p + 4, ... (three independent loads per slot), the quad combines in
   // lane order - a fixed summation order, so the loss is reproducible run to run
   const int p4 = threadIdx.x & 3;
@@ -184,7 +194,11 @@ __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const double *__
       P += __shfl_xor(P, m, 64);
       Y += __shfl_xor(Y, m, 64);
     }
-    if (on && p4 == 0) {
+    if (on && p4 == 0 && batch_dice) {
+      s_sum[0][i] = I;
+      s_sum[1][i] = P;
+      s_sum[2][i] = Y;
+    } else if (on && p4 == 0) {
       const double N = 2.0 * I + (double)smooth;
       double D = P + Y + (double)smooth;
       if (D < 1e-8) D = 1e-8;
@@ -207,9 +221,32 @@ __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const double *__
     if (threadIdx.x == 0) s_ce = ce, s_nv = nv;
   }
   __syncthreads();
+  if (batch_dice) {
+    if (threadIdx.x < C) {       // a lane per class: the samples' sums in ascending b
+      const int c = threadIdx.x;
+      double I = s_sum[0][c], P = s_sum[1][c], Y = s_sum[2][c];
+      for (int b = 1; b < B; ++b) {
+        I += s_sum[0][b * C + c];
+        P += s_sum[1][b * C + c];
+        Y += s_sum[2][b * C + c];
+      }
+      const double N = 2.0 * I + (double)smooth;
+      double D = P + Y + (double)smooth;
+      if (D < 1e-8) D = 1e-8;
+      const double dc = N / D;
+      s_dc[c] = dc;
+      const float alpha = c >= first ? (float)(-2.0 * w / D) : 0.f, beta = c >= first ? (float)(w * N / (D * D)) : 0.f;
+      for (int b = 0; b < B; ++b) {
+        dice[b * C + c] = (float)dc;
+        coef[2 * (b * C + c)] = alpha;
+        coef[2 * (b * C + c) + 1] = beta;
+      }
+    }
+    __syncthreads();
+  }
   if (threadIdx.x == 0) {
     double acc = 0.0;
-    for (int b = 0; b < B; ++b)
+    for (int b = 0; b < (batch_dice ? 1 : B); ++b)
       for (int c = first; c < C; ++c) acc += s_dc[b * C + c];
     const double nv = s_nv > 0.0 ? s_nv : 1.0;
     const double cem = s_ce / nv, dl = -acc * w;
@@ -279,8 +316,9 @@ extern "C" size_t dgtta_dice_ce_ws_bytes(int B, int C, int64_t V) {
 }
 
 static int dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws, size_t ws_bytes,
-                       int B, int C, int64_t V, float smooth, int do_bg, void *stream, const DcLabels &lm) {
+                       int B, int C, int64_t V, float smooth, int do_bg, int batch_dice, void *stream, const DcLabels &lm) {
   DG_REQUIRE(logits && labels && loss3 && dice && ws, DGTTA_ERR_BADARG, "dice_ce_fwd: null pointer");
+  DG_REQUIRE(batch_dice == 0 || batch_dice == 1, DGTTA_ERR_BADARG, "dice_ce_fwd: batch_dice is 0 or 1, not %d", batch_dice);
   DG_REQUIRE(B > 0 && B <= 8 && C >= 2 && C <= DC_MAXC && V > 0 && ldc >= C, DGTTA_ERR_BADARG,
              "dice_ce_fwd: need 1<=B<=8, 2<=C<=%d, ldc>=C (B=%d C=%d ldc=%d)", DC_MAXC, B, C, ldc);
   DG_REQUIRE(ws_bytes >= dgtta_dice_ce_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "dice_ce_fwd: workspace too small");
@@ -294,8 +332,8 @@ static int dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, floa
              DGTTA_ERR_LAUNCH, "dice_ce_fwd: cannot raise the dynamic LDS limit");
   hipLaunchKernelGGL(dice_ce_fwd_kernel, dim3(nblk, B), dim3(DC_THREADS), lds, st, logits, ldc, labels, partial, C, V, lm);
   DG_CHECK_LAUNCH("dice_ce_fwd_kernel");
-  hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, nblk, B, C, smooth, do_bg ? 0 : 1, loss3, dice,
-                     coef);
+  hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, nblk, B, C, smooth, do_bg ? 0 : 1, batch_dice, loss3,
+                     dice, coef);
   DG_CHECK_LAUNCH("dice_ce_finalize_kernel");
   return DGTTA_OK;
 }
@@ -322,7 +360,13 @@ static const DcLabels DC_DENSE = {0, 0, 1, 1, 1, 0, 0, 0};
 
 extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
                                  size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, void *stream) {
-  return dice_ce_fwd(logits, ldc, labels, loss3, dice, ws, ws_bytes, B, C, V, smooth, do_bg, stream, DC_DENSE);
+  return dice_ce_fwd(logits, ldc, labels, loss3, dice, ws, ws_bytes, B, C, V, smooth, do_bg, 0, stream, DC_DENSE);
+}
+
+extern "C" int dgtta_dice_ce_batch_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
+                                       size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, int batch_dice,
+                                       void *stream) {
+  return dice_ce_fwd(logits, ldc, labels, loss3, dice, ws, ws_bytes, B, C, V, smooth, do_bg, batch_dice, stream, DC_DENSE);
 }
 
 extern "C" int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, const void *ws, float grad_scale,
@@ -351,7 +395,16 @@ extern "C" int dgtta_dice_ce_ds_fwd(const float *logits, int ldc, const int64_t 
                                     int do_bg, void *stream) {
   DG_REQUIRE(dc_ds_dims_ok(d, h, w, sd, sh, sw), DGTTA_ERR_BADARG, "dice_ce_ds_fwd: bad dims %dx%dx%d strides %d,%d,%d", d, h, w, sd,
              sh, sw);
-  return dice_ce_fwd(logits, ldc, labels_full, loss3, dice, ws, ws_bytes, B, C, (int64_t)d * h * w, smooth, do_bg, stream,
+  return dice_ce_fwd(logits, ldc, labels_full, loss3, dice, ws, ws_bytes, B, C, (int64_t)d * h * w, smooth, do_bg, 0, stream,
+                     dc_ds_labels(d, h, w, sd, sh, sw));
+}
+
+extern "C" int dgtta_dice_ce_ds_batch_fwd(const float *logits, int ldc, const int64_t *labels_full, float *loss3, float *dice,
+                                          void *ws, size_t ws_bytes, int B, int C, int d, int h, int w, int sd, int sh, int sw,
+                                          float smooth, int do_bg, int batch_dice, void *stream) {
+  DG_REQUIRE(dc_ds_dims_ok(d, h, w, sd, sh, sw), DGTTA_ERR_BADARG, "dice_ce_ds_batch_fwd: bad dims %dx%dx%d strides %d,%d,%d", d, h, w,
+             sd, sh, sw);
+  return dice_ce_fwd(logits, ldc, labels_full, loss3, dice, ws, ws_bytes, B, C, (int64_t)d * h * w, smooth, do_bg, batch_dice, stream,
                      dc_ds_labels(d, h, w, sd, sh, sw));
 }
 

@@ -373,7 +373,7 @@ def consistency_loss(target_a, target_b, start_class=1):
 
 class _DiceCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, smooth, do_bg):
+    def forward(ctx, logits, labels, smooth, do_bg, batch_dice=False):
         lib = _lib.load()
         b, c = logits.shape[:2]
         v = logits[0, 0].numel()
@@ -383,8 +383,12 @@ class _DiceCE(torch.autograd.Function):
         dice = torch.empty((b, c), dtype=torch.float32, device=logits.device)
         nbytes = lib.dgtta_dice_ce_ws_bytes(b, c, v)
         ws = _ws(nbytes, logits.device)
-        check(lib.dgtta_dice_ce_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, v, float(smooth),
-                                    int(do_bg), stream_of(logits.device)), "dgtta_dice_ce_fwd")
+        if batch_dice:
+            check(lib.dgtta_dice_ce_batch_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, v, float(smooth),
+                                              int(do_bg), 1, stream_of(logits.device)), "dgtta_dice_ce_batch_fwd")
+        else:
+            check(lib.dgtta_dice_ce_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, v, float(smooth),
+                                        int(do_bg), stream_of(logits.device)), "dgtta_dice_ce_fwd")
         ctx.save_for_backward(logits, labels, ws)
         ctx.meta = (b, c, v)
         ctx.mark_non_differentiable(dice)
@@ -399,24 +403,26 @@ class _DiceCE(torch.autograd.Function):
         gs = gloss.reshape(1).float().contiguous()
         check(lib.dgtta_dice_ce_bwd(ptr(logits), c, ptr(labels), ptr(ws), 1.0, ptr(gs), ptr(g), c, b, c, v,
                                     stream_of(logits.device)), "dgtta_dice_ce_bwd")
-        return g, None, None, None
+        return g, None, None, None, None
 
 
-def dice_ce_loss(logits, labels, smooth=1e-5, do_bg=False):
+def dice_ce_loss(logits, labels, smooth=1e-5, do_bg=False, batch_dice=False):
     """nnU-Net's pre-training loss DC_and_CE_loss [3P] (soft Dice per sample without background + cross-entropy) of logits
     [B,C,D,H,W] (fp32) against an integer label map [B,1,D,H,W] / [B,D,H,W] (labels outside [0, C) are ignored).
+    batch_dice: the plans' switch of that name - the Dice sums are pooled over the batch before the ratio (csrc/dice_ce.hip, from
+    memory of nnU-Net's MemoryEfficientSoftDiceLoss, unpinned); every row of the returned dice then holds the class's one value.
     Returns (loss, dice [B,C], (ce, -mean dice)); differentiable w.r.t. the logits."""
     require_cuda(logits, labels)
     if labels.dtype != torch.int64:
         labels = labels.long()
-    return _DiceCE.apply(logits.float(), labels, smooth, do_bg)
+    return _DiceCE.apply(logits.float(), labels, smooth, do_bg, bool(batch_dice))
 
 
 class _DiceCEStrided(torch.autograd.Function):
     """DC+CE of low-resolution logits against a strided view of the full-resolution label map (csrc/dice_ce.hip, _ds)."""
 
     @staticmethod
-    def forward(ctx, logits, labels, strides, smooth, do_bg):
+    def forward(ctx, logits, labels, strides, smooth, do_bg, batch_dice=False):
         lib = _lib.load()
         b, c, d, h, w = logits.shape
         logits = logits.contiguous(memory_format=torch.channels_last_3d)
@@ -425,8 +431,13 @@ class _DiceCEStrided(torch.autograd.Function):
         dice = torch.empty((b, c), dtype=torch.float32, device=logits.device)
         nbytes = lib.dgtta_dice_ce_ds_ws_bytes(b, c, d, h, w)
         ws = _ws(nbytes, logits.device)
-        check(lib.dgtta_dice_ce_ds_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, d, h, w, *strides,
-                                       float(smooth), int(do_bg), stream_of(logits.device)), "dgtta_dice_ce_ds_fwd")
+        if batch_dice:
+            check(lib.dgtta_dice_ce_ds_batch_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, d, h, w,
+                                                 *strides, float(smooth), int(do_bg), 1, stream_of(logits.device)),
+                  "dgtta_dice_ce_ds_batch_fwd")
+        else:
+            check(lib.dgtta_dice_ce_ds_fwd(ptr(logits), c, ptr(labels), ptr(loss3), ptr(dice), ptr(ws), nbytes, b, c, d, h, w, *strides,
+                                           float(smooth), int(do_bg), stream_of(logits.device)), "dgtta_dice_ce_ds_fwd")
         ctx.save_for_backward(logits, labels, ws)
         ctx.meta = (b, c, d, h, w, strides)
         ctx.mark_non_differentiable(dice)
@@ -441,7 +452,7 @@ class _DiceCEStrided(torch.autograd.Function):
         gs = gloss.reshape(1).float().contiguous()      # (carries the scale's weight of the multi-scale sum)
         check(lib.dgtta_dice_ce_ds_bwd(ptr(logits), c, ptr(labels), ptr(ws), 1.0, ptr(gs), ptr(g), c, b, c, d, h, w, *strides,
                                        stream_of(logits.device)), "dgtta_dice_ce_ds_bwd")
-        return g, None, None, None, None
+        return g, None, None, None, None, None
 
 
 def deep_supervision_weights(n):
@@ -463,14 +474,15 @@ def _label_strides(out_shape, label_shape):
     return tuple(strides)
 
 
-def deep_supervision_loss(outputs, labels, smooth=1e-5, do_bg=False, weights=None):
+def deep_supervision_loss(outputs, labels, smooth=1e-5, do_bg=False, weights=None, batch_dice=False):
     """nnU-Net's multi-scale loss (DeepSupervisionWrapper [3P] around DC_and_CE_loss): sum_i w_i * dice_ce(outputs[i], labels at
     the resolution of outputs[i]).  outputs: logits [B,C,d_i,h_i,w_i], highest resolution first (what HipPlainConvUNet returns
     with deep_supervision on); labels: the FULL-resolution integer map [B,1,D,H,W] / [B,D,H,W] - every output is compared
     with the strided view labels[i sd + sd/2, j sh + sh/2, k sw + sw/2] of it (csrc/dice_ce.hip; a restatement from memory of
     nnU-Net's DownsampleSegForDSTransform2, unpinned), no downsampled label map is built.  The strides follow from the shapes
     and must divide exactly (ValueError).  weights: default deep_supervision_weights(len(outputs)); a zero-weight scale is
-    skipped in both directions.  Returns (loss, [per-scale loss or None where skipped]); differentiable w.r.t. every output."""
+    skipped in both directions.  batch_dice: every scale's Dice term pools its sums over the batch (dice_ce_loss).
+    Returns (loss, [per-scale loss or None where skipped]); differentiable w.r.t. every output."""
     outputs = list(outputs)
     if labels.dim() == 5:
         labels = labels[:, 0]
@@ -490,7 +502,7 @@ def deep_supervision_loss(outputs, labels, smooth=1e-5, do_bg=False, weights=Non
         if wgt == 0:
             per_scale.append(None)
             continue
-        li, _, _ = _DiceCEStrided.apply(o.float(), labels, st, smooth, do_bg)
+        li, _, _ = _DiceCEStrided.apply(o.float(), labels, st, smooth, do_bg, bool(batch_dice))
         per_scale.append(li.detach())
         total = li * wgt if total is None else total + li * wgt
     if total is None:

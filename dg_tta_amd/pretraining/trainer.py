@@ -5,8 +5,27 @@ this step into `nnUNetv2_train` (dg_tta/run.py pretrain); nnunetv2 is not needed
 the network is restated from memory of nnunetv2 2.2 (UNPINNED): SGD with Nesterov momentum 0.99, weight decay 3e-5,
 gradient-norm clipping at 12 (optim.HipSGD, csrc/sgd.hip), polynomial learning rate from 1e-2 stepped per epoch
 (optim.PolyLRScheduler), 250 training + 50 validation iterations per epoch, 33 % of a batch centred on foreground,
-DC+CE loss with deep supervision (ops.deep_supervision_loss as it stands: the Dice term per sample, whatever the plans'
-`batch_dice` says), online pseudo-Dice from the validation batches.
+DC+CE loss with deep supervision (ops.deep_supervision_loss), online pseudo-Dice from the validation batches.
+
+THE DICE TERM: `dice="sample"` (the default, `--dice sample`) takes it per sample, whatever the plans' `batch_dice` says - when
+they say true, BATCH_DICE_NOTE is printed at the start.  `dice="plans"` (`--dice plans`) obeys the resolved configuration's
+`batch_dice` (plans_batch_dice: `inherits_from` is followed, a missing key is false): true pools the Dice sums over the batch
+before the ratio (csrc/dice_ce.hip; nnU-Net's MemoryEfficientSoftDiceLoss(batch_dice=True) from memory, UNPINNED), in the training
+and in the validation loss of every epoch alike.
+
+THE BEST CHECKPOINT: after every epoch the moving average of the pseudo-Dice (ema_step: the first finite value, then
+0.9 ema + 0.1 value; a NaN epoch leaves it alone) is logged under `ema_fg_dice`, and when it exceeds every earlier one
+checkpoint_best.pth is written beside checkpoint_latest.pth / checkpoint_final.pth (nnU-Net's rule from memory, UNPINNED).
+A checkpoint written before the key existed continues: the series is rebuilt from `mean_fg_dice` (rebuild_ema).
+
+THE FINAL VALIDATION (`final_validation=True`, `--validate`; `validate_fold`, `--val` for a fold trained earlier): every validation
+case of the fold (fold "all": its training cases, as nnU-Net does) is predicted from its preprocessed `data` with the network
+load_network builds from checkpoint_final.pth - the trainer's hooks registered, the internal augmentation off - through the
+sliding-window path of tta/inference.py with the checkpoint's mirror axes, argmax over all classes, one case at a time.
+fold_<k>/validation/ receives <case>.npy (the label map in the PREPROCESSED geometry, smallest unsigned integer type that holds
+the labels) and summary.json in the layout of tta/evaluation.py, against the `seg` of the case's .npz with -1 read as background.
+nnU-Net evaluates in the case's original geometry against gt_segmentations/; training here writes no per-case geometry
+properties, so the comparison stays in the preprocessed geometry.
 
 REDUCED AUGMENTATION: the DG trainers' own augmentation runs (GIN / MIND forward pre-hooks; for the *_MultiRes trainers
 SimulateDiscreteLowResolutionTransform with the reference's arguments, nnUNetTrainer_GIN_MIND_MultiRes.py:61-67), mirroring
@@ -32,6 +51,7 @@ import os
 import re
 import time
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -73,6 +93,12 @@ FULL_AUGMENTATION_NOTE = (
     "and mirroring (off as the DG trainers set it).")
 AUGMENTATIONS = ("reduced", "spatial", "full")
 MAX_AUG_ITEMS = 16           # items per ops.sample_patches_aug launch
+DICE_MODES = ("sample", "plans")
+BATCH_DICE_NOTE = (
+    "pretrain: PER-SAMPLE DICE - the plans of this configuration say batch_dice: true, which is NOT honoured: the Dice term of the "
+    "loss is taken per sample (nnU-Net would pool its sums over the batch).  `--dice plans` (train_fold(dice=\"plans\")) obeys the "
+    "plans.")
+EMA_DECAY = 0.9
 
 
 # ------------------------------------------------------------------------------------------------ host logic (no GPU)
@@ -126,6 +152,44 @@ def draw_center(locations, rng):
         return None
     loc = locations[classes[int(rng.randint(len(classes)))]]
     return tuple(int(x) for x in loc[int(rng.randint(len(loc)))])
+
+
+def plans_batch_dice(plans, configuration):
+    """The resolved configuration's `batch_dice` (`inherits_from` followed), false when the key is absent."""
+    return bool(_configuration(plans, configuration).get("batch_dice", False))
+
+
+def ema_step(ema, value, decay=EMA_DECAY):
+    """nnU-Net's moving average of the pseudo-Dice (from memory, unpinned).  ema: the average so far, None (or NaN) before the first
+    finite value; value: this epoch's mean_fg_dice.  The first finite value starts the average, a NaN value leaves it unchanged."""
+    if ema is not None and not np.isfinite(ema):
+        ema = None
+    if not np.isfinite(value):
+        return ema
+    return float(value) if ema is None else decay * ema + (1.0 - decay) * float(value)
+
+
+def is_new_best(ema, best):
+    """checkpoint_best.pth is written when the average strictly exceeds the best so far (None: there is none yet)."""
+    return ema is not None and np.isfinite(ema) and (best is None or ema > best)
+
+
+def rebuild_ema(mean_fg_dice):
+    """(series, best) from a log's mean_fg_dice - what a run logs under `ema_fg_dice` (NaN before the first finite value) and the
+    best average it saw (None if none): how a checkpoint without the key is continued."""
+    series, ema, best = [], None, None
+    for v in mean_fg_dice:
+        ema = ema_step(ema, v)
+        series.append(float("nan") if ema is None else ema)
+        if is_new_best(ema, best):
+            best = ema
+    return series, best
+
+
+def best_of(series):
+    """The best average of a logged `ema_fg_dice` series: its largest finite entry, None without one."""
+    finite = [v for v in series if np.isfinite(v)]
+    return max(finite) if finite else None
 
 
 def _configuration(plans, configuration):
@@ -296,12 +360,16 @@ def _mirror(imgs, target, axes):
 
 # ------------------------------------------------------------------------------------------------ the loop
 def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iterations_per_epoch=250, val_iterations=50,
-               device="cuda", act_dtype=torch.float32, continue_training=False, seed=None, augmentation="reduced"):
+               device="cuda", act_dtype=torch.float32, continue_training=False, seed=None, augmentation="reduced", dice="sample",
+               final_validation=False):
     """Trains one fold and writes the model folder (module docstring).  dataset: numeric id or folder name; fold: 0..4 or
     "all".  augmentation: "reduced" (module docstring), "spatial" (adds nnU-Net's rotation / scaling to the training
     batches, pretraining/spatial.py; validation batches are never augmented), "full" (the rotation / scaling plus nnU-Net's
     intensity chain, pretraining/intensity.py), or the objects to draw from: a SpatialAugmentation, an IntensityAugmentation
-    or a (SpatialAugmentation, IntensityAugmentation) pair.  Returns the path of checkpoint_final.pth."""
+    or a (SpatialAugmentation, IntensityAugmentation) pair.  dice: "sample" or "plans" (module docstring, THE DICE TERM).
+    final_validation: validate_fold runs once checkpoint_final.pth is written.  Returns the path of checkpoint_final.pth."""
+    if dice not in DICE_MODES:
+        raise ValueError(f"dice {dice!r}: one of {', '.join(DICE_MODES)} expected")
     spatial = intensity = None
     if isinstance(augmentation, SpatialAugmentation):
         spatial = augmentation
@@ -323,6 +391,61 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("dg_tta_amd trains on the MI355X only (no CPU fallback)")
+    f = _resolve_fold(dataset, configuration, fold, trainer_name)
+    plans, dataset_json, out_dir, fold_dir = f.plans, f.dataset_json, f.out_dir, f.fold_dir
+    batch_dice = dice == "plans" and plans_batch_dice(plans, configuration)
+    if dice == "sample" and plans_batch_dice(plans, configuration):
+        print(BATCH_DICE_NOTE)
+    fold_dir.mkdir(parents=True, exist_ok=True)
+    with open(out_dir / "plans.json", "w") as fh:
+        json.dump(plans, fh, indent=4)
+    with open(out_dir / "dataset.json", "w") as fh:
+        json.dump(dataset_json, fh, indent=4)
+    final = _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val_iterations, device, act_dtype,
+                   continue_training, seed, spatial, intensity, mirror_axes, batch_dice)
+    if final_validation:
+        validate_fold(dataset, configuration, f.fold, trainer_name, device=device, act_dtype=act_dtype)
+    return final
+
+
+def validate_fold(dataset, configuration, fold, trainer_name, device="cuda", act_dtype=torch.float32):
+    """The final validation of a trained fold (module docstring, THE FINAL VALIDATION): predicts every validation case with
+    fold_<k>/checkpoint_final.pth and writes fold_<k>/validation/<case>.npy and summary.json.  Returns the summary dict."""
+    from ..tta.evaluation import case_metrics, summarize_cases
+    from ..tta.inference import run_inference
+    from ..tta.nnunet_utils import load_network
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("dg_tta_amd validates on the MI355X only (no CPU fallback)")
+    f = _resolve_fold(dataset, configuration, fold, trainer_name)
+    final = f.fold_dir / "checkpoint_final.pth"
+    if not final.is_file():
+        raise FileNotFoundError(f"{final} not found: the final validation needs a fold that was trained to the end")
+    predictor, patch, network, parameters = load_network(final, device, act_dtype=act_dtype)
+    network = network.to(device)
+    disable_internal_augmentation()                         # load_network switched it on, as tta_main finds it
+    num_classes = network.cfg["num_classes"]
+    labels = list(range(num_classes))
+    dtype = next(t for t in (np.uint8, np.uint16, np.uint32) if num_classes - 1 <= np.iinfo(t).max)
+    out = f.fold_dir / "validation"
+    out.mkdir(parents=True, exist_ok=True)
+    per_case = []
+    for name in f.val_names:                                # one at a time: a case's volume and accumulator are gone before the next
+        npz = f.entries[name][0]                            # (written by the training, which loads every validation case)
+        with np.load(npz) as z:
+            data, seg = z["data"], z["seg"][0]
+        pred = run_inference(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)), network, parameters, patch,
+                             mirror_axes=predictor.allowed_mirroring_axes).numpy().astype(dtype)
+        np.save(out / f"{name}.npy", pred)
+        per_case.append({"metrics": case_metrics(pred, np.where(seg < 0, 0, seg), labels, device),
+                         "prediction_file": str(out / f"{name}.npy"), "reference_file": str(npz)})
+        print(f"pretrain: validated {name}")
+    return summarize_cases(per_case, labels, out / "summary.json")
+
+
+def _resolve_fold(dataset, configuration, fold, trainer_name):
+    """What a fold is made of: plans, dataset.json, the resolved configuration, the cases on disk, the split (written when the
+    dataset has none) and the folders of the model."""
     fold = "all" if str(fold) == "all" else int(fold)
     dataset_name = maybe_convert_to_dataset_name(dataset)
     plans, dataset_json, pre, raw = load_dataset_files(dataset_name)
@@ -353,13 +476,15 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
         raise FileNotFoundError(f"{splits_file} names cases that are not in the dataset: {missing[:6]}")
 
     out_dir = Path(nnunet_path("nnUNet_results")) / dataset_name / f"{trainer_name}__nnUNetPlans__{configuration}"
-    fold_dir = out_dir / fold_folder_name(fold)
-    fold_dir.mkdir(parents=True, exist_ok=True)
-    with open(out_dir / "plans.json", "w") as f:
-        json.dump(plans, f, indent=4)
-    with open(out_dir / "dataset.json", "w") as f:
-        json.dump(dataset_json, f, indent=4)
+    return SimpleNamespace(fold=fold, plans=plans, dataset_json=dataset_json, conf=conf, entries=entries, train_names=train_names,
+                           val_names=val_names, out_dir=out_dir, fold_dir=out_dir / fold_folder_name(fold))
 
+
+def _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val_iterations, device, act_dtype, continue_training,
+           seed, spatial, intensity, mirror_axes, batch_dice):
+    """The training loop of train_fold on a resolved fold."""
+    fold, plans, dataset_json, conf, entries = f.fold, f.plans, f.dataset_json, f.conf, f.entries
+    train_names, val_names, fold_dir = f.train_names, f.val_names, f.fold_dir
     if seed is not None:
         torch.manual_seed(seed)
         torch.cuda.manual_seed(seed)
@@ -372,8 +497,8 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
     for p in net.parameters():
         p.requires_grad_(True)
     opt = HipSGD(net.parameters(), lr=INITIAL_LR, grad_scale=net.loss_scale)
-    log = dict(train_losses=[], val_losses=[], mean_fg_dice=[], lrs=[])
-    start_epoch = 0
+    log = dict(train_losses=[], val_losses=[], mean_fg_dice=[], lrs=[], ema_fg_dice=[])
+    start_epoch, best = 0, None
     if continue_training:
         src = next((p for p in (fold_dir / "checkpoint_latest.pth", fold_dir / "checkpoint_final.pth") if p.is_file()), None)
         if src is None:
@@ -382,7 +507,11 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
         net.load_state_dict(ck["network_weights"])
         opt.load_state_dict(ck["optimizer_state"])
         opt.grad_scale = float((ck.get("grad_scaler_state") or {}).get("scale", opt.grad_scale))
-        start_epoch, log = int(ck["current_epoch"]), {k: list(ck["logging"][k]) for k in log}
+        start_epoch, log = int(ck["current_epoch"]), {k: list(ck["logging"][k]) for k in log if k in ck["logging"]}
+        if "ema_fg_dice" in log:
+            best = best_of(log["ema_fg_dice"])
+        else:                                               # a checkpoint from before the best-checkpoint rule
+            log["ema_fg_dice"], best = rebuild_ema(log["mean_fg_dice"])
         print(f"pretrain: continuing from {src} at epoch {start_epoch} (random streams are not restored)")
     sched = PolyLRScheduler(opt, INITIAL_LR, num_epochs)
     multires = None
@@ -422,7 +551,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                         print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
                     imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial, intensity=intensity)
                     imgs, target = _mirror(imgs, target, mirror_axes)
-                    loss, _ = ops.deep_supervision_loss(net(imgs), target)
+                    loss, _ = ops.deep_supervision_loss(net(imgs), target, batch_dice=batch_dice)
                     torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
                                                                           device=device))
                     opt.step()
@@ -435,7 +564,7 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                     for _ in range(val_iterations):
                         imgs, target, picks = _sample(val_cases, batch_size, patch, device, None)
                         outs = net(imgs)
-                        loss, _ = ops.deep_supervision_loss(outs, target)
+                        loss, _ = ops.deep_supervision_loss(outs, target, batch_dice=batch_dice)
                         va_losses.append(loss)
                         counts += ops.argmax_dice(outs[0], target)[1]
                         recent.update((c.name, epoch) for c in picks)
@@ -451,6 +580,9 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                 log["val_losses"].append(float(host[1]))
                 log["mean_fg_dice"].append(mean_dice)
                 log["lrs"].append(lr)
+                prev = log["ema_fg_dice"][-1] if log["ema_fg_dice"] else None
+                ema = ema_step(prev, mean_dice)
+                log["ema_fg_dice"].append(float("nan") if ema is None else ema)
                 logf.write(f"epoch {epoch} lr {lr:.6g} train_loss {float(host[0]):.4f} val_loss {float(host[1]):.4f} "
                            f"pseudo_dice {mean_dice:.4f} loss_scale {opt.grad_scale:g} skipped_steps {opt.skipped_steps} "
                            f"time {time.time() - t0:.1f}s\n")
@@ -462,6 +594,9 @@ def train_fold(dataset, configuration, fold, trainer_name, num_epochs=1000, iter
                         del recent[n]
                 if (epoch + 1) % SAVE_EVERY == 0 and epoch + 1 < num_epochs:
                     save("checkpoint_latest.pth", epoch + 1)
+                if is_new_best(ema, best):
+                    best = ema
+                    save("checkpoint_best.pth", epoch + 1)
         opt.resolve_overflow()
         save("checkpoint_latest.pth", max(num_epochs, start_epoch))
         save("checkpoint_final.pth", max(num_epochs, start_epoch))

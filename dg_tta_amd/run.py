@@ -108,6 +108,14 @@ class DGTTAProgram:
         parser.add_argument("--augmentation", choices=["reduced", "spatial", "full"], default="reduced",
                             help="spatial: nnU-Net's rotation / scaling on the training batches; full: that plus its noise / blur / "
                                  "brightness / contrast / low-resolution / gamma chain")
+        parser.add_argument("--dice", choices=["sample", "plans"], default="sample",
+                            help="sample: the Dice term of the loss per sample, whatever the plans say; plans: pooled over the batch "
+                                 "when the configuration's batch_dice is true, as nnU-Net trains it")
+        parser.add_argument("--validate", action="store_true",
+                            help="after training, predict every validation case of the fold with checkpoint_final.pth and write "
+                                 "fold_<k>/validation/ (label maps and summary.json, in the preprocessed geometry)")
+        parser.add_argument("--val", dest="validation_only", action="store_true",
+                            help="do not train: run that validation on the fold's existing checkpoint_final.pth")
         return parser
 
     def pretrain(self):
@@ -116,6 +124,14 @@ class DGTTAProgram:
         if args.fold != "all" and not args.fold.isnumeric():
             raise SystemExit(f"pretrain: fold {args.fold!r} is neither a number nor 'all'")
         from .pretraining.trainer import FULL_AUGMENTATION_NOTE, REDUCED_AUGMENTATION_NOTE, SPATIAL_AUGMENTATION_NOTE, train_fold
+        act_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+        if args.validation_only:
+            from .pretraining.trainer import validate_fold
+            summary = validate_fold(args.dataset_id, args.configuration, args.fold, args.trainer, device=torch.device(args.device),
+                                    act_dtype=act_dtype)
+            print(f"pretrain: validated {len(summary['metric_per_case'])} cases, foreground mean Dice "
+                  f"{summary['foreground_mean']['Dice']:.4f}")
+            return
         print({"spatial": SPATIAL_AUGMENTATION_NOTE, "full": FULL_AUGMENTATION_NOTE}.get(args.augmentation, REDUCED_AUGMENTATION_NOTE))
         from .pretraining.hooks import trainer_mirror_axes
         axes = trainer_mirror_axes(args.trainer)
@@ -126,7 +142,7 @@ class DGTTAProgram:
         final = train_fold(args.dataset_id, args.configuration, args.fold, args.trainer, num_epochs=args.num_epochs,
                            iterations_per_epoch=args.iterations_per_epoch, val_iterations=args.val_iterations,
                            device=torch.device(args.device), continue_training=args.continue_training, seed=args.seed, augmentation=args.augmentation,
-                           act_dtype={"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype])
+                           act_dtype=act_dtype, dice=args.dice, final_validation=args.validate)
         print(f"pretrain: wrote {final}")
 
     def prepare_tta(self):

@@ -149,6 +149,12 @@ def compute_metrics_on_folder_simple(folder_ref, folder_pred, labels, output_fil
         else:
             m = case_metrics(load_label_map(f), load_label_map(ref), labels, device)
         per_case.append({"metrics": m, "prediction_file": str(f), "reference_file": str(ref)})
+    return summarize_cases(per_case, labels, output_file, surface_metrics)
+
+
+def summarize_cases(per_case, labels, output_file=None, surface_metrics=False):
+    """The summary dict of compute_metrics_on_folder_simple from its per-case entries
+    [{"metrics": case_metrics(...), "prediction_file", "reference_file"}]; written as JSON to output_file when given."""
     keys = ["Dice", "IoU", "FP", "TP", "FN", "TN", "n_pred", "n_ref"] + (SURFACE_KEYS if surface_metrics else [])
     means = {}
     for lab in labels:

@@ -219,6 +219,19 @@ int dgtta_dice_ce_ds_fwd(const float *logits, int ldc, const int64_t *labels_ful
 int dgtta_dice_ce_ds_bwd(const float *logits, int ldc, const int64_t *labels_full, const void *ws, float grad_scale,
                          const float *grad_scale_dev, float *grad_logits, int ldg, int B, int C, int d, int h, int w, int sd,
                          int sh, int sw, void *stream);
+/* The forward functions above with the plans' `batch_dice` switch.  batch_dice = 0: dgtta_dice_ce_fwd / dgtta_dice_ce_ds_fwd bit
+ * for bit.  batch_dice = 1 - nnU-Net's MemoryEfficientSoftDiceLoss(batch_dice=True) inside DC_and_CE_loss [3P nnunetv2==2.2.1, not
+ * available here], restated from memory, UNPINNED - pools the three sums over the batch before the ratio:
+ *   dice_c = (2 sum_b sum_v p y + smooth) / max(sum_b sum_v p + sum_b sum_v y + smooth, 1e-8);  loss3[2] = -mean_{c >= first} dice_c
+ * loss3[1] (cross-entropy) is unchanged; every row of dice[B][C] holds dice_c.  The per-sample sums are formed in the order of the
+ * per-sample mode and added over b in ascending order in double, without atomics: bit-reproducible.  Same workspace (size and
+ * layout) as above; the matching backward is dgtta_dice_ce_bwd / dgtta_dice_ce_ds_bwd, unchanged.  Any other batch_dice:
+ * DGTTA_ERR_BADARG. */
+int dgtta_dice_ce_batch_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
+                            size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, int batch_dice, void *stream);
+int dgtta_dice_ce_ds_batch_fwd(const float *logits, int ldc, const int64_t *labels_full, float *loss3, float *dice, void *ws,
+                               size_t ws_bytes, int B, int C, int d, int h, int w, int sd, int sh, int sw, float smooth,
+                               int do_bg, int batch_dice, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * AdamW (decoupled weight decay, bias-corrected, no amsgrad) over a list of tensors.  Replaces
