@@ -91,6 +91,8 @@ SIGNATURES = {
     "dgtta_seghead_warp_fwd": (I, [P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),
     "dgtta_seghead_warp_bwd": (I, [P, P, P, P, P, P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
     "dgtta_seghead_warp_bwd_g16": (I, [P, P, P, P, P, P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
+    "dgtta_seghead_warp_bwd_g16_d16": (I, [P, P, P, P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, P]),
+    "dgtta_instnorm_lrelu_bwd_head": (I, [P, P, P, I, P, I, P, P, P, P, I, P, P, P, SZ, I, I, I64, F, I, I, P]),
     "dgtta_ncdhw_to_ndhwc": (I, [P, P, I, I, I64, I, I, P]),
     "dgtta_ndhwc_to_ncdhw": (I, [P, P, I, I, I64, I, I, P]),
     "dgtta_argmax_dice": (I, [P, I, I, P, P, P, I, I64, P]),

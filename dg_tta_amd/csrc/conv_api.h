@@ -145,7 +145,8 @@ int convTa_wgrad_mfma(const ConvProblem &P, Src x, Src dout, float *dw_t, Region
 // ---------------------------------------------------------------------------------------------------- head_wgrad.hip
 size_t head_wgrad_mfma_ws_bytes(int Cin, int nsel, int64_t rows);
 int head_wgrad_mfma(const void *x, int ldx, const float *dout, int lddo, float *dw_sel, void *ws, size_t ws_bytes, int Cin,
-                    int nsel, int64_t rows, int accumulate, int dtype, hipStream_t st, bool have_d16);
+                    int nsel, int64_t rows, int accumulate, int dtype, hipStream_t st, bool have_d16,
+                    const unsigned short *d16_ext = nullptr);
 
 // ---------------------------------------------------------------------------------------------------- seghead_mfma.hip
 // 1x1x1 heads with Cin a multiple of 32 (32..320), nsel <= 128, 16-bit storage; DGTTA_ERR_UNSUPPORTED for anything else

@@ -441,6 +441,140 @@ __global__ void bias_finalize_kernel(const double *__restrict__ partial, int nbl
   if (threadIdx.x == 0) db[c] = accumulate ? db[c] + (float)s : (float)s;
 }
 
+// ============================================================================ backward of the block in front of the head
+// gz of that block is W^T d16: a linear function of the gathered logit gradient the fused head + warp backward leaves (rows of 16
+// values in the storage type, half the bytes of a gz row).  Both passes of the backward rebuild it instead of loading it:
+// gz[c] = sum_k W[sel[k]][c] * float(d16[k]) on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 products and sums), used
+// unrounded where the passes above use the loaded gz.  32 channels, 16 classes, 16-bit storage.
+// A wave takes 16 rows at a time: lane l has row l & 15 and channels 8 g .. 8 g + 7 (g = l >> 4) - the 16-byte reads of y of the
+// passes above, dealt to the lanes row-minor.  B operand: the lane's 8 bytes of its d16 row, classes 4 g + s in step s.  A
+// operand: 8 weight registers, W[sel[4 g + s]][ch(l & 15)], where matrix row m stands for channel 8 (m >> 2) + (m & 3) in the
+// first accumulator and 4 more in the second - so that D leaves exactly the lane's 8 channels on it.  Sum order per channel:
+// steps s = 0..3, the four classes {s, 4 + s, 8 + s, 12 + s} inside one instruction.
+// APPLY 0: partial[b][blk][c][2] = (sum da, sum da * xhat) as chan_reduce_vec_kernel<T, 1>; APPLY 1: dy as in_apply_vec_kernel<T, 1>.
+constexpr int INH_C = 32, INH_NS = 16;
+
+__device__ __forceinline__ uint2 ld8_nt(const void *p) {
+  typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
+  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(p));
+  return make_uint2(v[0], v[1]);
+}
+
+template <typename T, int APPLY>
+__global__ __launch_bounds__(256) void in_bwd_head_kernel(const T *__restrict__ y, int ldy, const unsigned short *__restrict__ d16,
+                                                          const float *__restrict__ w, const int *__restrict__ sel,
+                                                          const float *__restrict__ mean_rstd, const float *__restrict__ gamma,
+                                                          const float *__restrict__ beta, const float *__restrict__ c12,
+                                                          float slope, double *__restrict__ partial, T *__restrict__ dy,
+                                                          int lddy, int64_t V, int nt) {
+  __shared__ float sred[APPLY ? 1 : 64 * INH_C * 2];      // [wave * 16 + row lane][c][2]
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, g = lane >> 4;
+  float wa0[4], wa1[4];
+  {
+    const int ch = 8 * (n >> 2) + (n & 3);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int k = 4 * g + s;
+      const float *wr = w + (int64_t)(sel ? sel[k] : k) * INH_C + ch;
+      wa0[s] = wr[0];
+      wa1[s] = wr[4];
+    }
+  }
+  float mu[8], rs[8], ga[8], be[8], k1[8], k2[8], s0[8], s1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c = 8 * g + e;
+    mu[e] = mean_rstd[((int64_t)b * INH_C + c) * 2];
+    rs[e] = mean_rstd[((int64_t)b * INH_C + c) * 2 + 1];
+    ga[e] = gamma[c];
+    be[e] = beta[c];
+    k1[e] = APPLY ? c12[((int64_t)b * INH_C + c) * 2] : 0.f;
+    k2[e] = APPLY ? c12[((int64_t)b * INH_C + c) * 2 + 1] : 0.f;
+    s0[e] = s1[e] = 0.f;
+  }
+  const T *yb = y + (int64_t)b * V * ldy + 8 * g;
+  const unsigned short *db = d16 + (int64_t)b * V * INH_NS + 4 * g;
+  T *ob = APPLY ? dy + (int64_t)b * V * lddy + 8 * g : nullptr;
+  // W^T d of the lane's row and channels from its 8 bytes of d16 (every lane of the wave takes part: zeros for a row past V)
+  auto gz_of = [&](const uint2 &dv, float *gz) {
+    float d[4];
+    unpack2_16<T>(dv.x, d[0], d[1]);
+    unpack2_16<T>(dv.y, d[2], d[3]);
+    f32x4_t a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0[s], d[s], a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1[s], d[s], a1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gz[e] = a0[e], gz[4 + e] = a1[e];
+  };
+  auto one = [&](const uint4 &yv, const uint2 &dv, int64_t row) {
+    float f[8], gz[8], o[8];
+    unpack16<T>(yv, f);
+    gz_of(dv, gz);
+    if (row >= V) return;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xh = (f[e] - mu[e]) * rs[e];
+      const float a = xh * ga[e] + be[e];
+      const float gg = a > 0.f ? gz[e] : gz[e] * slope;
+      if (APPLY) {
+        o[e] = (ga[e] * rs[e]) * ((gg - k1[e]) - xh * k2[e]);
+      } else {
+        s0[e] += gg;
+        s1[e] += gg * xh;
+      }
+    }
+    if (APPLY) {
+      const uint4 pk = pack16<T>(o);
+      if (nt) st16_nt(ob + row * lddy, pk);
+      else *reinterpret_cast<uint4 *>(ob + row * lddy) = pk;
+    }
+  };
+  // units of 16 rows are dealt to the waves of the grid in turn (the interleaved order of the passes above), two in flight
+  // (four in flight: 132-140 registers, 3 waves per SIMD instead of 4, and 4 % slower - profiles/in_bwd_level0_ab.txt)
+  const int64_t ustep = (int64_t)gridDim.x * 4;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + wave; u * 16 < V; u += 2 * ustep) {      // (wave-uniform)
+    const int64_t r0 = u * 16 + n, r1 = (u + ustep) * 16 + n;
+    const bool two = (u + ustep) * 16 < V;                                            // (wave-uniform)
+    const uint4 zero4 = make_uint4(0, 0, 0, 0);
+    const uint2 zero2 = make_uint2(0, 0);
+    uint4 y0 = zero4, y1 = zero4;
+    uint2 d0 = zero2, d1 = zero2;
+    if (r0 < V) {
+      y0 = ld16_nt(yb + r0 * ldy);
+      d0 = ld8_nt(db + r0 * INH_NS);
+    }
+    if (two && r1 < V) {
+      y1 = ld16_nt(yb + r1 * ldy);
+      d1 = ld8_nt(db + r1 * INH_NS);
+    }
+    one(y0, d0, r0);
+    if (two) one(y1, d1, r1);
+  }
+  if (APPLY) return;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sred[((wave * 16 + n) * INH_C + 8 * g + e) * 2 + 0] = s0[e];
+    sred[((wave * 16 + n) * INH_C + 8 * g + e) * 2 + 1] = s1[e];
+  }
+  __syncthreads();
+  if (threadIdx.x < INH_C) {
+    const int c = threadIdx.x;
+    double t0 = 0.0, t1 = 0.0;
+    for (int k = 0; k < 64; ++k) {
+      t0 += (double)sred[(k * INH_C + c) * 2];
+      t1 += (double)sred[(k * INH_C + c) * 2 + 1];
+    }
+    double *p = partial + ((((int64_t)b * gridDim.x + blockIdx.x) * INH_C) + c) * 2;
+    p[0] = t0;
+    p[1] = t1;
+  }
+}
+
 }  // namespace
 
 __global__ void set_header_kernel(long long *hdr, long long v) { hdr[0] = v; }
@@ -573,4 +707,46 @@ extern "C" int dgtta_instnorm_lrelu_bwd_gstats(const void *gz, int ldgz, const v
   DG_REQUIRE(gstats, DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_gstats: null statistics");
   return instnorm_bwd_impl(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, gstats, ws, ws_bytes, B, C, V,
                            slope, accumulate, dtype, stream, "instnorm_lrelu_bwd_gstats");
+}
+
+// dgtta_instnorm_lrelu_bwd of the block in front of the head, its gz given as (d16, head weight rows, sel): gz = W^T d16 is
+// rebuilt in both passes and never stored (in_bwd_head_kernel).  32 channels, 16 selected classes, 16-bit storage.
+extern "C" int dgtta_instnorm_lrelu_bwd_head(const void *d16, const float *w, const int *sel, int nsel, const void *y, int ldy,
+                                             const float *gamma, const float *beta, const float *mean_rstd, void *dy, int lddy,
+                                             float *dgamma, float *dbeta, void *ws, size_t ws_bytes, int B, int C, int64_t V,
+                                             float slope, int accumulate, int dtype, void *stream) {
+  DG_REQUIRE(d16 && w && y && gamma && beta && mean_rstd && dy && dgamma && dbeta && ws, DGTTA_ERR_BADARG,
+             "instnorm_lrelu_bwd_head: null pointer");
+  DG_REQUIRE(B > 0 && V > 0 && ldy >= C && lddy >= C, DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_head: bad dims");
+  DG_REQUIRE(C == INH_C && nsel == INH_NS && (dtype == DGTTA_BF16 || dtype == DGTTA_F16), DGTTA_ERR_UNSUPPORTED,
+             "instnorm_lrelu_bwd_head: built for 32 channels, 16 selected classes and 16-bit storage (C %d, nsel %d, dtype %d)", C,
+             nsel, dtype);
+  DG_REQUIRE(ldy % 8 == 0 && lddy % 8 == 0 && !((uintptr_t)y & 15) && !((uintptr_t)dy & 15) && !((uintptr_t)d16 & 15),
+             DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_head: unaligned operand");
+  DG_REQUIRE(ws_bytes >= dgtta_instnorm_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "instnorm_lrelu_bwd_head: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = reduce_blocks(V, B);
+  double *partial = (double *)ws;
+  float *c12 = (float *)((char *)ws + align_up((size_t)B * nblk * C * 2 * sizeof(double), 256));
+  const int64_t units = cdiv64(V, 16);
+  const int blocks = (int)(cdiv64(units, 4 * 4) < 4096 ? cdiv64(units, 4 * 4) : 4096);
+  const int nt = dgtta_switches().in_nt - '0';
+#define INH_LAUNCH(T)                                                                                                         \
+  do {                                                                                                                        \
+    hipLaunchKernelGGL((in_bwd_head_kernel<T, 0>), dim3(nblk, B), dim3(256), 0, st, (const T *)y, ldy,                        \
+                       (const unsigned short *)d16, w, sel, mean_rstd, gamma, beta, (const float *)nullptr, slope, partial,  \
+                       (T *)nullptr, 0, V, nt);                                                                               \
+    DG_CHECK_LAUNCH("in_bwd_head_kernel<0>");                                                                                 \
+    hipLaunchKernelGGL(in_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, B, C, V, c12, dgamma, dbeta,         \
+                       accumulate);                                                                                           \
+    DG_CHECK_LAUNCH("in_bwd_finalize_kernel");                                                                                \
+    hipLaunchKernelGGL((in_bwd_head_kernel<T, 1>), dim3(blocks, B), dim3(256), 0, st, (const T *)y, ldy,                      \
+                       (const unsigned short *)d16, w, sel, mean_rstd, gamma, beta, (const float *)c12, slope,               \
+                       (double *)nullptr, (T *)dy, lddy, V, nt);                                                              \
+    DG_CHECK_LAUNCH("in_bwd_head_kernel<1>");                                                                                 \
+  } while (0)
+  if (dtype == DGTTA_BF16) INH_LAUNCH(bf16_t);
+  else INH_LAUNCH(f16_t);
+#undef INH_LAUNCH
+  return DGTTA_OK;
 }

@@ -621,7 +621,9 @@ __global__ __launch_bounds__(256) void head_warp_fwd_mfma_kernel(const T *__rest
 // Measured beside it and NOT kept (profiles/r06_ab.txt): W^T on the fp32 matrix cores through a class-major LDS slab (same
 // bits, but 82 instead of 80 registers = 5 instead of 6 waves per SIMD: 1.96 ms) and a chunked gather with 2 or 3 lines'
 // candidate rows in flight (2.14 / 2.17 ms: the candidate search is the cost, not the round trips - more slots, more search).
-template <typename T, bool G16 = false>
+// GZ = false: the kernel stops at d16 (a caller-owned buffer) - no W^T, no gz; the InstanceNorm backward of the block in front of
+// the head rebuilds gz from d16 on the fly (instnorm.hip, dgtta_instnorm_lrelu_bwd_head).
+template <typename T, bool G16 = false, bool GZ = true>
 __global__ __launch_bounds__(256, 6) void head_warp_bwd_kernel(const void *__restrict__ gdst_, const float *__restrict__ theta,
                                                             const float *__restrict__ w, const int *__restrict__ sel,
                                                             int nsel, T *__restrict__ gz, unsigned short *__restrict__ d16,
@@ -632,9 +634,11 @@ __global__ __launch_bounds__(256, 6) void head_warp_bwd_kernel(const void *__res
   __shared__ float sred[4][HW_NS];
   const float *gdst = (const float *)gdst_;
   const unsigned short *gdst16 = (const unsigned short *)gdst_;
-  for (int i = threadIdx.x; i < HW_NS * HW_CIN; i += 256) {
-    const int k = i / HW_CIN;
-    sw[i] = k < nsel ? w[(int64_t)(sel ? sel[k] : k) * HW_CIN + i % HW_CIN] : 0.f;
+  if (GZ) {
+    for (int i = threadIdx.x; i < HW_NS * HW_CIN; i += 256) {
+      const int k = i / HW_CIN;
+      sw[i] = k < nsel ? w[(int64_t)(sel ? sel[k] : k) * HW_CIN + i % HW_CIN] : 0.f;
+    }
   }
   const int64_t V = (int64_t)D * H * W;
   const int tilesZ = (D + 3) >> 2;
@@ -748,7 +752,7 @@ __global__ __launch_bounds__(256, 6) void head_warp_bwd_kernel(const void *__res
     // gz = W^T acc, a quarter (8 channels) at a time to keep the register footprint of the gather phase
     T *gp = gz + u * HW_CIN;
 #pragma unroll
-    for (int qt = 0; qt < 4; ++qt) {
+    for (int qt = 0; GZ && qt < 4; ++qt) {
       float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < HW_NS; ++k) {
@@ -999,8 +1003,10 @@ extern "C" int dgtta_seghead_warp_fwd(const void *z, const float *w, const float
 static int seghead_warp_bwd_impl(const void *z, const void *gout, int gout16, const float *theta, const float *h_theta,
                                  const float *w, const int *sel, int nsel, void *gz, float *dw_sel, float *db_sel, void *ws,
                                  size_t ws_bytes, int B, int Cin, int D, int H, int W, int tta_grid_algebra, int accumulate,
-                                 int dtype, void *stream) {
-  DG_REQUIRE(z && gout && theta && h_theta && w && gz && ws, DGTTA_ERR_BADARG, "seghead_warp_bwd: null pointer");
+                                 int dtype, void *stream, void *d16_out = nullptr) {
+  // d16_out: the mode without W^T - the gathered gradient alone, in the caller's buffer (w, sel and gz are not used)
+  DG_REQUIRE(z && gout && theta && h_theta && ws && (d16_out || (w && gz)), DGTTA_ERR_BADARG, "seghead_warp_bwd: null pointer");
+  if (d16_out) gz = d16_out;      // (for the alignment check below)
   DG_REQUIRE(B > 0 && B <= 16 && D > 0 && H > 0 && W > 0, DGTTA_ERR_BADARG, "seghead_warp_bwd: bad dims");
   DG_REQUIRE(head_warp_shape_ok(Cin, nsel, dtype), DGTTA_ERR_UNSUPPORTED, "seghead_warp_bwd: unsupported shape / dtype");
   DG_REQUIRE(!dw_sel || head_warp_wgrad_ok(nsel), DGTTA_ERR_UNSUPPORTED,
@@ -1017,24 +1023,29 @@ static int seghead_warp_bwd_impl(const void *z, const void *gout, int gout16, co
   double *bias_partial = (double *)ws;
   void *ws_main = (char *)ws + head_warp_bias_region(B, D, H, W);
   const size_t main_bytes = ws_bytes - head_warp_bias_region(B, D, H, W);
-  unsigned short *d16 = (unsigned short *)ws_main;           // first region of head_wgrad_mfma's workspace
+  // the 16-bit copy of the gathered gradient: the first region of head_wgrad_mfma's workspace, or the caller's buffer
+  unsigned short *d16 = d16_out ? (unsigned short *)d16_out : (unsigned short *)ws_main;
   const int gx = cdiv(W, 16), gy = cdiv(H, 4);
   const int64_t nblk = (int64_t)gx * gy * cdiv(D, 4) * B;
   DG_REQUIRE(nblk < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "seghead_warp_bwd: too many tiles");
-#define HWB_LAUNCH(T, G)                                                                                            \
-  hipLaunchKernelGGL((head_warp_bwd_kernel<T, G>), dim3((unsigned)nblk), dim3(256), 0, st, gout, theta, w, sel, nsel, \
+#define HWB_LAUNCH(T, G, GZ)                                                                                            \
+  hipLaunchKernelGGL((head_warp_bwd_kernel<T, G, GZ>), dim3((unsigned)nblk), dim3(256), 0, st, gout, theta, w, sel, nsel, \
                      (T *)gz, d16, db_sel ? bias_partial : nullptr, D, H, W, tta_grid_algebra, gx, gy)
-  if (dtype == DGTTA_BF16) {
-    if (gout16) HWB_LAUNCH(bf16_t, true);
-    else HWB_LAUNCH(bf16_t, false);
+  if (d16_out) {      // (offered with the 16-bit logit gradient only)
+    if (dtype == DGTTA_BF16) HWB_LAUNCH(bf16_t, true, false);
+    else HWB_LAUNCH(f16_t, true, false);
+  } else if (dtype == DGTTA_BF16) {
+    if (gout16) HWB_LAUNCH(bf16_t, true, true);
+    else HWB_LAUNCH(bf16_t, false, true);
   } else {
-    if (gout16) HWB_LAUNCH(f16_t, true);
-    else HWB_LAUNCH(f16_t, false);
+    if (gout16) HWB_LAUNCH(f16_t, true, true);
+    else HWB_LAUNCH(f16_t, false, true);
   }
 #undef HWB_LAUNCH
   DG_CHECK_LAUNCH("head_warp_bwd_kernel");
   if (dw_sel) {
-    const int rc = head_wgrad_mfma(z, Cin, nullptr, nsel, dw_sel, ws_main, main_bytes, Cin, nsel, rows, accumulate, dtype, st, true);
+    const int rc = head_wgrad_mfma(z, Cin, nullptr, nsel, dw_sel, ws_main, main_bytes, Cin, nsel, rows, accumulate, dtype, st, true,
+                                   d16_out ? d16 : nullptr);
     DG_REQUIRE(rc == DGTTA_OK, rc, "seghead_warp_bwd: head weight gradient failed (%d)", rc);
   }
   if (db_sel) {
@@ -1061,4 +1072,16 @@ extern "C" int dgtta_seghead_warp_bwd_g16(const void *z, const void *gout16, con
                                           int accumulate, int dtype, void *stream) {
   return seghead_warp_bwd_impl(z, gout16, 1, theta, h_theta, w, sel, nsel, gz, dw_sel, db_sel, ws, ws_bytes, B, Cin, D, H, W,
                                tta_grid_algebra, accumulate, dtype, stream);
+}
+
+// dgtta_seghead_warp_bwd_g16 without the data gradient: the gathered logit gradient d16 (rows of nsel values in the storage type,
+// each rounded once) goes to the caller's buffer, the weight / bias gradient is computed from it as before.  gz = W^T d16 is left
+// to dgtta_instnorm_lrelu_bwd_head, which never stores it.
+extern "C" int dgtta_seghead_warp_bwd_g16_d16(const void *z, const void *gout16, const float *theta, const float *h_theta,
+                                              int nsel, void *d16_out, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes,
+                                              int B, int Cin, int D, int H, int W, int tta_grid_algebra, int accumulate, int dtype,
+                                              void *stream) {
+  DG_REQUIRE(d16_out, DGTTA_ERR_BADARG, "seghead_warp_bwd_g16_d16: null pointer");
+  return seghead_warp_bwd_impl(z, gout16, 1, theta, h_theta, nullptr, nullptr, nsel, nullptr, dw_sel, db_sel, ws, ws_bytes, B, Cin,
+                               D, H, W, tta_grid_algebra, accumulate, dtype, stream, d16_out);
 }

@@ -562,8 +562,15 @@ def _aux_head_backward(p, head, z, sel, nsel, gout, gz, dims):
         _scatter_head_grads(p, head, sel, dws, dbs)
 
 
+# The gradient rows of the head's input as their two factors (DGTTA_HEAD_GZ_FOLD): d16, the gathered logit gradient (rows of
+# nsel values in the storage type), and the head whose selected weight rows multiply it.  gz = W^T d16 is never stored: the
+# InstanceNorm backward of the block in front of the head rebuilds it in both of its passes (dgtta_instnorm_lrelu_bwd_head).
+_HeadGrad = collections.namedtuple("_HeadGrad", "d16 head sel nsel")
+
+
 def _head_backward(p, head, z, sel, nsel, fw, g16, gout, dims):
-    """Backward of `_head_forward` from gout (or g16, what the loss left in the Grad16Sink): the gradient rows of z."""
+    """Backward of `_head_forward` from gout (or g16, what the loss left in the Grad16Sink): the gradient rows of z - or, on
+    the fused head + warp path with 16 classes of a 16-bit network, a _HeadGrad in their place."""
     lib, B, dt, st = p.lib, p.B, p.dt, p.st
     D, H, W = dims
     if g16 is not None and any(gout.stride()):
@@ -572,10 +579,21 @@ def _head_backward(p, head, z, sel, nsel, fw, g16, gout, dims):
         g16 = None
     g = None if g16 is not None else gout.contiguous(memory_format=torch.channels_last_3d).float()      # [B,nsel,D,H,W] stored NDHWC
     cin = head.in_channels
-    gz = p.empty(B, D, H, W, cin)
     need_hw = head.weight.requires_grad or head.bias.requires_grad
     dws = p.empty(nsel, cin, dtype=torch.float32) if need_hw else None
     dbs = p.empty(nsel, dtype=torch.float32) if need_hw else None
+    if (fw is not None and g16 is not None and nsel == 16 and cin == 32 and z.ld == 32 and p.esz == 2 and p.impl != 1
+            and os.environ.get("DGTTA_HEAD_GZ_FOLD", "1") != "0"):
+        nb = lib.dgtta_seghead_warp_bwd_ws_bytes(B, cin, nsel, D, H, W)
+        ws = p.ws.get(nb)
+        assert tuple(g16.shape) == (B, D, H, W, nsel) and g16.dtype == p.adt and g16.is_contiguous()
+        d16 = p.empty(B, D, H, W, nsel)
+        check(lib.dgtta_seghead_warp_bwd_g16_d16(z.ptr, ptr(g16), ptr(fw[0]), ptr(fw[1]), nsel, ptr(d16), ptr(dws), ptr(dbs), ptr(ws),
+                                                 nb, B, cin, D, H, W, 1, 0, dt, st), "dgtta_seghead_warp_bwd_g16_d16")
+        if need_hw:
+            _scatter_head_grads(p, head, sel, dws, dbs)
+        return _HeadGrad(d16, head, sel, nsel)
+    gz = p.empty(B, D, H, W, cin)
     if fw is not None:      # g is the gradient of the WARPED logits: fused gather + W^T (+ weight / bias gradient)
         nb = lib.dgtta_seghead_warp_bwd_ws_bytes(B, cin, nsel, D, H, W)
         ws = p.ws.get(nb)
@@ -595,7 +613,7 @@ def _head_backward(p, head, z, sel, nsel, fw, g16, gout, dims):
 
 def _norm_backward(p, blk, gz, gstats):
     """InstanceNorm + LeakyReLU backward of `blk` from gradient rows gz: dy (dense, fresh).  gstats: the reduction's sums,
-    where the data gradient that produced gz left them."""
+    where the data gradient that produced gz left them.  gz may be a _HeadGrad (the block in front of the head)."""
     lib, B, cout, v = p.lib, p.B, blk.cout, blk.vout
     norm = blk.mod.norm
     dy = p.empty(B, *blk.dout, cout)
@@ -603,7 +621,12 @@ def _norm_backward(p, blk, gz, gstats):
     ws = p.ws.get(nb)
     dgam = p.gbuf(norm.weight) if norm.weight.requires_grad else torch.empty_like(norm.weight)
     dbet = p.gbuf(norm.bias) if norm.bias.requires_grad else torch.empty_like(norm.bias)
-    if gstats is not None:
+    if isinstance(gz, _HeadGrad):
+        assert cout == 32 and gstats is None
+        check(lib.dgtta_instnorm_lrelu_bwd_head(ptr(gz.d16), ptr(gz.head.weight), ptr(gz.sel), gz.nsel, ptr(blk.y), cout,
+                                                ptr(norm.weight), ptr(norm.bias), ptr(blk.mr), ptr(dy), cout, ptr(dgam), ptr(dbet),
+                                                ptr(ws), nb, B, cout, v, SLOPE, p.acc, p.dt, p.st), "dgtta_instnorm_lrelu_bwd_head")
+    elif gstats is not None:
         check(lib.dgtta_instnorm_lrelu_bwd_gstats(gz.ptr, gz.ld, ptr(blk.y), cout, ptr(norm.weight), ptr(norm.bias), ptr(blk.mr),
                                                   ptr(dy), cout, ptr(dgam), ptr(dbet), ptr(gstats), ptr(ws), nb, B, cout, v,
                                                   SLOPE, p.acc, p.dt, p.st), "dgtta_instnorm_lrelu_bwd_gstats")

@@ -355,6 +355,14 @@ int dgtta_instnorm_lrelu_bwd_gstats(const void *gz, int ldgz, const void *y, int
                                     const float *mean_rstd, void *dy, int lddy, float *dgamma, float *dbeta,
                                     const void *gstats, void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope,
                                     int accumulate, int dtype, void *stream);
+/* dgtta_instnorm_lrelu_bwd of the block in front of the segmentation head, with gz given as its factors: d16 [B][V][nsel] (dtype),
+ * what dgtta_seghead_warp_bwd_g16_d16 left, and the head's fp32 weight w [classes][C] with the selected rows sel (NULL: rows
+ * 0..nsel-1).  gz[c] = sum_k w[sel[k]][c] * float(d16[k]) is rebuilt in fp32 in both passes and used unrounded; it is never stored.
+ * C = 32, nsel = 16, bf16 / fp16 only (else DGTTA_ERR_UNSUPPORTED and nothing is launched); ws as dgtta_instnorm_lrelu_bwd. */
+int dgtta_instnorm_lrelu_bwd_head(const void *d16, const float *w, const int *sel, int nsel, const void *y, int ldy,
+                                  const float *gamma, const float *beta, const float *mean_rstd, void *dy, int lddy,
+                                  float *dgamma, float *dbeta, void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope,
+                                  int accumulate, int dtype, void *stream);
 
 /* ConvTranspose3d(Cin, Cout, kernel 2, stride 2, bias): w_t torch layout [Cin][Cout][2][2][2] fp32.
  * out[b][2v+o][co] = bias[co] + sum_ci x[b][v][ci] * w[ci][co][o]. */
@@ -458,6 +466,12 @@ int dgtta_seghead_warp_bwd(const void *z, const float *gout, const float *theta,
 int dgtta_seghead_warp_bwd_g16(const void *z, const void *gout16, const float *theta, const float *h_theta, const float *w,
                                const int *sel, int nsel, void *gz, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes, int B,
                                int Cin, int D, int H, int W, int tta_grid_algebra, int accumulate, int dtype, void *stream);
+/* dgtta_seghead_warp_bwd_g16 without the data gradient: d16_out [B][D][H][W][nsel] (dtype, 16-byte aligned, caller-owned) receives
+ * the gathered logit gradient, each value rounded once - the operand the weight gradient reads; dw_sel / db_sel are bit for bit
+ * those of dgtta_seghead_warp_bwd_g16.  gz = W^T d16 is left to dgtta_instnorm_lrelu_bwd_head, which never stores it. */
+int dgtta_seghead_warp_bwd_g16_d16(const void *z, const void *gout16, const float *theta, const float *h_theta, int nsel,
+                                   void *d16_out, float *dw_sel, float *db_sel, void *ws, size_t ws_bytes, int B, int Cin, int D,
+                                   int H, int W, int tta_grid_algebra, int accumulate, int dtype, void *stream);
 
 /* Layout / dtype converters between the reference's NCDHW fp32 and internal NDHWC. */
 int dgtta_ncdhw_to_ndhwc(const float *src, void *dst, int B, int C, int64_t V, int ldc, int dtype, void *stream);

@@ -46,3 +46,36 @@ e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 20
 gb = B * V * C * 2 * 3 / 1e9
 print(f"instnorm fwd {B}x{n}^3x{C}: {ms*1e3:.1f} us, {gb/ms:.2f} TB/s over 3 tensor passes ({gb:.2f} GB)")
+
+# the block in front of the head (C = 32): gz as its factors (d16, head rows) - dgtta_instnorm_lrelu_bwd_head, gz never stored -
+# against the same layer through dgtta_instnorm_lrelu_bwd on a stored gz; and the fused head + warp backward with / without W^T
+if C == 32:
+    from dg_tta_amd.tta.augmentation_utils import get_rand_affine
+    NS = 16
+    d16 = torch.randn((B, V, NS), device=dev).to(torch.bfloat16)
+    w = torch.randn(105, C, device=dev) * 0.1
+    sel = (torch.arange(NS) * 3).to(torch.int32).to(dev)
+    def runh():
+        check(lib.dgtta_instnorm_lrelu_bwd_head(ptr(d16), ptr(w), ptr(sel), NS, ptr(y), C, ptr(gamma), ptr(beta), ptr(mr), ptr(dy), C, ptr(dg),
+                                                ptr(db), ptr(ws), nb, B, C, V, 0.01, 1, ops.BF16, stream_of(dev)), "in_bwd_head")
+    _, rinv = get_rand_affine(B)
+    rinv = rinv.float().contiguous()
+    th = rinv.to(dev)
+    g16 = torch.randn((B, n, n, n, NS), device=dev).to(torch.bfloat16)
+    dws, dbs = torch.empty(NS, C, device=dev), torch.empty(NS, device=dev)
+    nbh = lib.dgtta_seghead_warp_bwd_ws_bytes(B, C, NS, n, n, n)
+    wsh = torch.empty(nbh, dtype=torch.uint8, device=dev)
+    def runw():
+        check(lib.dgtta_seghead_warp_bwd_g16(ptr(y), ptr(g16), ptr(th), ptr(rinv), ptr(w), ptr(sel), NS, ptr(gz), ptr(dws), ptr(dbs), ptr(wsh),
+                                             nbh, B, C, n, n, n, 1, 0, ops.BF16, stream_of(dev)), "hw_bwd")
+    def runwd():
+        check(lib.dgtta_seghead_warp_bwd_g16_d16(ptr(y), ptr(g16), ptr(th), ptr(rinv), NS, ptr(d16), ptr(dws), ptr(dbs), ptr(wsh), nbh, B, C,
+                                                 n, n, n, 1, 0, ops.BF16, stream_of(dev)), "hw_bwd_d16")
+    for name, fn in (("instnorm bwd, stored gz", run), ("instnorm bwd from d16", runh), ("head+warp bwd with gz (incl. wgrad, bias)", runw),
+                     ("head+warp bwd, d16 only (incl. wgrad, bias)", runwd)):
+        for _ in range(20): fn()      # (sustained clocks)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(20): fn()
+        e1.record(); torch.cuda.synchronize()
+        print(f"{name:46s} {B}x{n}^3: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us")
