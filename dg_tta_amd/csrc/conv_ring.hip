@@ -31,6 +31,7 @@
 // Zero padding and ragged edges: the DMA and the stores are raw BUFFER operations; a lane outside the volume gets an
 // offset beyond the descriptor's range, which reads as zero and drops the store.
 #include "conv_common.h"
+#include "instnorm_math.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -183,9 +184,9 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
       if (tid < 32) {
         const int c = n0 + tid;
         const float mu = gst.mr[((long long)b * Cout + c) * 2], rs = gst.mr[((long long)b * Cout + c) * 2 + 1];
-        const float a = gst.gamma[c] * rs;
+        const float a = in_alpha(rs, gst.gamma[c]);
         gcst[tid * 2] = a;
-        gcst[tid * 2 + 1] = gst.beta[c] - mu * a;
+        gcst[tid * 2 + 1] = in_beta(gst.beta[c], mu, a);
       }
     }
     // the compiler's wait for these loads belongs HERE: left to the first use inside the step loop it becomes a
@@ -301,9 +302,7 @@ __global__ __launch_bounds__(RingCfgT<KH>::NT) void conv3_ring_kernel(const bf16
             unpack2_16<T16>(val[t], g0, g1);
             unpack2_16<T16>(yq[t], yy0, yy1);
             const f32x2_t g2 = {g0, g1}, y2 = {yy0, yy1};
-            const f32x2_t a2 = __builtin_elementwise_fma(gA, y2, gB);
-            const f32x2_t gsl = g2 * gst.slope;
-            const f32x2_t q2 = {a2[0] > 0.f ? g2[0] : gsl[0], a2[1] > 0.f ? g2[1] : gsl[1]};
+            const f32x2_t q2 = in_da2(g2, y2, gA, gB, gst.slope);
             gs1[t] += q2;
             gs2[t] = __builtin_elementwise_fma(q2, y2, gs2[t]);
           }

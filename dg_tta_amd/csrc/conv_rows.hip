@@ -1,5 +1,6 @@
 // Row-reuse 3x3x3 convolution kernel (bf16, stride 1) -- see the block comment below.
 #include "conv_common.h"
+#include "instnorm_math.h"
 #include <stdlib.h>
 
 namespace {
@@ -252,9 +253,9 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
         if (tid < 32) {
           const int c = cur.n0 + tid;
           const float mu = gst.mr[((long long)cur.b * Cout + c) * 2], rs = gst.mr[((long long)cur.b * Cout + c) * 2 + 1];
-          const float a = gst.gamma[c] * rs;
+          const float a = in_alpha(rs, gst.gamma[c]);
           gcst[tid * 2] = a;
-          gcst[tid * 2 + 1] = gst.beta[c] - mu * a;
+          gcst[tid * 2 + 1] = in_beta(gst.beta[c], mu, a);
         }
         for (int i = tid; i < NW * 32 * 2; i += Cfg::NT) red[i] = 0.f;
         gst_newrun = false;         // (published by the barriers between here and the epilogue)
@@ -403,9 +404,7 @@ __global__ __launch_bounds__(WD *WH * 64) void conv3_rows_kernel(const bf16_t *_
                 unpack2_16<T16>(gw[t], g0, g1);
                 unpack2_16<T16>(yw[t], y0, y1);
                 const f32x2_t g2 = {g0, g1}, y2 = {y0, y1};
-                const f32x2_t a2 = __builtin_elementwise_fma(gA[t], y2, gB[t]);
-                const f32x2_t gsl = g2 * gst.slope;
-                const f32x2_t q2 = {a2[0] > 0.f ? g2[0] : gsl[0], a2[1] > 0.f ? g2[1] : gsl[1]};
+                const f32x2_t q2 = in_da2(g2, y2, gA[t], gB[t], gst.slope);
                 gs1[t] += q2;
                 gs2[t] = __builtin_elementwise_fma(q2, y2, gs2[t]);
               }

@@ -92,12 +92,17 @@ __device__ __forceinline__ bf16x8_t tr_operand(const unsigned char *p) {
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
-// ---------------------------------------------------------------- 16-byte non-temporal accesses (data streamed once)
+// ---------------------------------------------------------------- 16- and 8-byte non-temporal accesses (data streamed once)
 // (st16_nt takes its value by value: through a reference the kernels of conv_s2.hip and instnorm.hip come out scheduled
 // differently)
 __device__ __forceinline__ uint4 ld16_nt(const void *p) {
   const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
   return make_uint4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ uint2 ld8_nt(const void *p) {
+  typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
+  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(p));
+  return make_uint2(v[0], v[1]);
 }
 __device__ __forceinline__ void st16_nt(void *p, uint4 val) {
   const u32x4_t nv = {val.x, val.y, val.z, val.w};

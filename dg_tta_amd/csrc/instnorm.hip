@@ -3,6 +3,7 @@
 // Semantics follow torch.nn.{InstanceNorm3d, LeakyReLU} as used by nnUNet's PlainConvUNet.
 #include "conv_api.h"
 #include "gfx950.h"
+#include "instnorm_math.h"
 
 namespace {
 
@@ -44,12 +45,10 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const T *__restrict__ 
         } else if (MODE == 2) {
           s0 += v;
         } else {
-          const float xh = (v - mu) * rs;
-          const float a = xh * ga + be;
-          float g = ld_f<T>(gz + ((int64_t)b * V + r) * ldgz + c);
-          g = a > 0.f ? g : g * slope;
-          s0 += g;
-          s1 += g * xh;
+          const float xh = in_xhat(v, mu, rs);
+          const float da = in_da(in_act(xh, ga, be), ld_f<T>(gz + ((int64_t)b * V + r) * ldgz + c), slope);
+          s0 += da;
+          s1 += da * xh;
         }
       }
     }
@@ -134,11 +133,10 @@ __global__ __launch_bounds__(256) void chan_reduce_vec_kernel(const T *__restric
           } else if (MODE == 2) {
             s0[e] += f[e];
           } else {
-            const float xh = (f[e] - mu[e]) * rs[e];
-            const float a = xh * ga[e] + be[e];
-            const float gg = a > 0.f ? g[e] : g[e] * slope;
-            s0[e] += gg;
-            s1[e] += gg * xh;
+            const float xh = in_xhat(f[e], mu[e], rs[e]);
+            const float da = in_da(in_act(xh, ga[e], be[e]), g[e], slope);
+            s0[e] += da;
+            s1[e] += da * xh;
           }
         }
       }
@@ -187,6 +185,14 @@ static void launch_chan_reduce(const void *y, int ldy, const void *gz, int ldgz,
 // 16-byte vectorised InstanceNorm+LeakyReLU apply kernels (forward MODE 0, backward MODE 1): grid (blocks, B); the
 // per-channel constants of sample b are staged in LDS once per workgroup; each thread streams 16-byte channel groups.
 // Same arithmetic as in_lrelu_apply_kernel / in_lrelu_bwd_apply_kernel.
+// one element from its channel's staged constants k: forward (alpha, beta'), backward (mu, rs, ga, be, c1, c2)
+template <int MODE>
+__device__ __forceinline__ float in_apply_elem(float y, float gz, const float *k, float slope) {
+  if (MODE == 0) return in_fwd(y, k[0], k[1], slope);
+  const float xh = in_xhat(y, k[0], k[1]);
+  return in_dy(in_da(in_act(xh, k[2], k[3]), gz, slope), xh, k[2], k[1], k[4], k[5]);
+}
+
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__ y, int ldy, const T *__restrict__ gz,
                                                            int ldgz, const float *__restrict__ mean_rstd,
@@ -201,9 +207,9 @@ __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__
   for (int c = threadIdx.x; c < C; c += 256) {
     const float mu = mean_rstd[((int64_t)b * C + c) * 2], rs = mean_rstd[((int64_t)b * C + c) * 2 + 1];
     if (MODE == 0) {
-      const float al = rs * gamma[c];
+      const float al = in_alpha(rs, gamma[c]);
       sc[c * NK] = al;
-      sc[c * NK + 1] = beta[c] - mu * al;
+      sc[c * NK + 1] = in_beta(beta[c], mu, al);
     } else {
       sc[c * NK] = mu;
       sc[c * NK + 1] = rs;
@@ -236,16 +242,7 @@ __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__
       unpack16<T>(yv, f);
       if (MODE == 1) unpack16<T>(gv, g);
 #pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        if constexpr (MODE == 0) {
-          o[e] = lrelu(f[e] * kc[e][0] + kc[e][1], slope);
-        } else {
-          const float xh = (f[e] - kc[e][0]) * kc[e][1];
-          const float a = xh * kc[e][2] + kc[e][3];
-          const float gg = a > 0.f ? g[e] : g[e] * slope;
-          o[e] = (kc[e][2] * kc[e][1]) * ((gg - kc[e][4]) - xh * kc[e][5]);
-        }
-      }
+      for (int e = 0; e < EPV; ++e) o[e] = in_apply_elem<MODE>(f[e], MODE == 1 ? g[e] : 0.f, kc[e], slope);
       const uint4 pk = pack16<T>(o);
       if (nt) st16_nt(ob + row * ldo + c0, pk);
       else *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pk;
@@ -276,17 +273,7 @@ __global__ __launch_bounds__(256) void in_apply_vec_kernel(const T *__restrict__
     unpack16<T>(*reinterpret_cast<const uint4 *>(yb + row * ldy + c0), f);
     if (MODE == 1) unpack16<T>(*reinterpret_cast<const uint4 *>(gb + row * ldgz + c0), g);
 #pragma unroll
-    for (int e = 0; e < EPV; ++e) {
-      const float *k = sc + (c0 + e) * NK;
-      if (MODE == 0) {
-        o[e] = lrelu(f[e] * k[0] + k[1], slope);
-      } else {
-        const float xh = (f[e] - k[0]) * k[1];
-        const float a = xh * k[2] + k[3];
-        const float gg = a > 0.f ? g[e] : g[e] * slope;
-        o[e] = (k[2] * k[1]) * ((gg - k[4]) - xh * k[5]);
-      }
-    }
+    for (int e = 0; e < EPV; ++e) o[e] = in_apply_elem<MODE>(f[e], MODE == 1 ? g[e] : 0.f, sc + (c0 + e) * NK, slope);
     *reinterpret_cast<uint4 *>(ob + row * ldo + c0) = pack16<T>(o);
   }
 }
@@ -343,19 +330,22 @@ __global__ void in_lrelu_apply_kernel(const T *__restrict__ y, int ldy, const fl
     const int64_t row = i / C;  // b*V + v
     const int b = (int)(row / V);
     const float mu = mean_rstd[((int64_t)b * C + c) * 2], rs = mean_rstd[((int64_t)b * C + c) * 2 + 1];
-    const float al = rs * gamma[c];
-    const float bt = beta[c] - mu * al;
-    const float a = ld_f<T>(y + row * ldy + c) * al + bt;
-    st_f<T>(z + row * ldz + c, lrelu(a, slope));
+    const float al = in_alpha(rs, gamma[c]);
+    const float bt = in_beta(beta[c], mu, al);
+    const float v = ld_f<T>(y + row * ldy + c);
+    st_f<T>(z + row * ldz + c, in_fwd(v, al, bt, slope));
   }
 }
 
 // backward finalize: c1 = mean(da), c2 = mean(da*xhat); dgamma (+)= sum_b sum(da*xhat); dbeta (+)= sum_b sum(da).
-// one 256-thread workgroup per channel
-__global__ void in_bwd_finalize_kernel(const double *__restrict__ partial, int nblk, int B, int C, int64_t V,
-                                       float *__restrict__ c12, float *__restrict__ dgamma, float *__restrict__ dbeta,
-                                       int accumulate) {
+// one 256-thread workgroup per channel; the number of partial blocks is read from the device-side header when hdr != NULL.
+// mean_rstd != NULL: the partials are the (sum g', sum g' y) the data-gradient kernel left (conv_rows.hip / conv_ring.hip, GST) per
+// (sample, tile), in the layout of the forward statistics (header = tiles per sample); sum g' xhat = rstd (sum g' y - mean sum g').
+__global__ void in_bwd_finalize_kernel(const double *__restrict__ partial, const long long *__restrict__ hdr, int nblk_h, int B,
+                                       int C, int64_t V, const float *__restrict__ mean_rstd, float *__restrict__ c12,
+                                       float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate) {
   const int c = blockIdx.x;
+  const int nblk = hdr ? (int)hdr[0] : nblk_h;
   __shared__ double red[8];
   double g_acc = 0.0, b_acc = 0.0;
   for (int b = 0; b < B; ++b) {
@@ -366,45 +356,16 @@ __global__ void in_bwd_finalize_kernel(const double *__restrict__ partial, int n
       s1 += v.y;
     }
     block_sum2_d(s0, s1, red);
+    if (mean_rstd) {
+      const double mu = (double)mean_rstd[((int64_t)b * C + c) * 2], rs = (double)mean_rstd[((int64_t)b * C + c) * 2 + 1];
+      s1 = rs * (s1 - mu * s0);
+    }
     if (threadIdx.x == 0) {
       c12[((int64_t)b * C + c) * 2] = (float)(s0 / (double)V);
       c12[((int64_t)b * C + c) * 2 + 1] = (float)(s1 / (double)V);
     }
     b_acc += s0;
     g_acc += s1;
-  }
-  if (threadIdx.x == 0) {
-    dgamma[c] = accumulate ? dgamma[c] + (float)g_acc : (float)g_acc;
-    dbeta[c] = accumulate ? dbeta[c] + (float)b_acc : (float)b_acc;
-  }
-}
-
-// The same from the partial sums the data-gradient kernel left (conv_rows.hip, GST): per (sample, tile) sums of g' and
-// g' * y in the layout of the forward statistics (header = tiles per sample); sum g' xhat = rstd (sum g' y - mean sum g').
-__global__ void in_bwd_finalize_gstats_kernel(const double *__restrict__ stats, int B, int C, int64_t V,
-                                              const float *__restrict__ mean_rstd, float *__restrict__ c12,
-                                              float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate) {
-  const int c = blockIdx.x;
-  __shared__ double red[8];
-  const int nblk = (int)reinterpret_cast<const long long *>(stats)[0];
-  const double *partial = stats + 32;
-  double g_acc = 0.0, b_acc = 0.0;
-  for (int b = 0; b < B; ++b) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int k = threadIdx.x; k < nblk; k += 256) {
-      const double2 v = *reinterpret_cast<const double2 *>(partial + ((((int64_t)b * nblk + k) * C) + c) * 2);
-      s0 += v.x;
-      s1 += v.y;
-    }
-    block_sum2_d(s0, s1, red);
-    const double mu = (double)mean_rstd[((int64_t)b * C + c) * 2], rs = (double)mean_rstd[((int64_t)b * C + c) * 2 + 1];
-    const double s1x = rs * (s1 - mu * s0);
-    if (threadIdx.x == 0) {
-      c12[((int64_t)b * C + c) * 2] = (float)(s0 / (double)V);
-      c12[((int64_t)b * C + c) * 2 + 1] = (float)(s1x / (double)V);
-    }
-    b_acc += s0;
-    g_acc += s1x;
   }
   if (threadIdx.x == 0) {
     dgamma[c] = accumulate ? dgamma[c] + (float)g_acc : (float)g_acc;
@@ -424,11 +385,9 @@ __global__ void in_lrelu_bwd_apply_kernel(const T *__restrict__ gz, int ldgz, co
     const int b = (int)(row / V);
     const int64_t bc = (int64_t)b * C + c;
     const float mu = mean_rstd[bc * 2], rs = mean_rstd[bc * 2 + 1], ga = gamma[c];
-    const float xh = (ld_f<T>(y + row * ldy + c) - mu) * rs;
-    const float a = xh * ga + beta[c];
-    float g = ld_f<T>(gz + row * ldgz + c);
-    g = a > 0.f ? g : g * slope;
-    st_f<T>(dy + row * lddy + c, (ga * rs) * ((g - c12[bc * 2]) - xh * c12[bc * 2 + 1]));
+    const float xh = in_xhat(ld_f<T>(y + row * ldy + c), mu, rs);
+    const float da = in_da(in_act(xh, ga, beta[c]), ld_f<T>(gz + row * ldgz + c), slope);
+    st_f<T>(dy + row * lddy + c, in_dy(da, xh, ga, rs, c12[bc * 2], c12[bc * 2 + 1]));
   }
 }
 
@@ -453,12 +412,6 @@ __global__ void bias_finalize_kernel(const double *__restrict__ partial, int nbl
 // steps s = 0..3, the four classes {s, 4 + s, 8 + s, 12 + s} inside one instruction.
 // APPLY 0: partial[b][blk][c][2] = (sum da, sum da * xhat) as chan_reduce_vec_kernel<T, 1>; APPLY 1: dy as in_apply_vec_kernel<T, 1>.
 constexpr int INH_C = 32, INH_NS = 16;
-
-__device__ __forceinline__ uint2 ld8_nt(const void *p) {
-  typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(p));
-  return make_uint2(v[0], v[1]);
-}
 
 template <typename T, int APPLY>
 __global__ __launch_bounds__(256) void in_bwd_head_kernel(const T *__restrict__ y, int ldy, const unsigned short *__restrict__ d16,
@@ -518,11 +471,10 @@ __global__ __launch_bounds__(256) void in_bwd_head_kernel(const T *__restrict__ 
     if (row >= V) return;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float xh = (f[e] - mu[e]) * rs[e];
-      const float a = xh * ga[e] + be[e];
-      const float gg = a > 0.f ? gz[e] : gz[e] * slope;
+      const float xh = in_xhat(f[e], mu[e], rs[e]);
+      const float gg = in_da(in_act(xh, ga[e], be[e]), gz[e], slope);
       if (APPLY) {
-        o[e] = (ga[e] * rs[e]) * ((gg - k1[e]) - xh * k2[e]);
+        o[e] = in_dy(gg, xh, ga[e], rs[e], k1[e], k2[e]);
       } else {
         s0[e] += gg;
         s1[e] += gg * xh;
@@ -606,10 +558,61 @@ int conv_bias_grad(const void *dy, int lddy, float *db, void *ws, int B, int C, 
   return DGTTA_OK;
 }
 
+// ============================================================================ InstanceNorm + LeakyReLU launchers
+// Their workspace, [partial | c12]: the partial sums of the reduction pass (double) and the backward's (c1, c2) per (sample,
+// channel), each region a multiple of 256 bytes.  The size query returns total(), the launchers carve their pointers with the
+// accessors: one layout serves both.
+struct InWsLayout {
+  size_t partial, c12;
+  size_t total() const { return partial + c12; }
+  double *partial_of(void *ws) const { return (double *)ws; }
+  float *c12_of(void *ws) const { return (float *)((char *)ws + partial); }
+};
+static InWsLayout in_ws_layout(int B, int C, int64_t V) {
+  return {align_up((size_t)B * reduce_blocks(V, B) * C * 2 * sizeof(double), 256), align_up((size_t)B * C * 2 * sizeof(float), 256)};
+}
+
 extern "C" size_t dgtta_instnorm_ws_bytes(int B, int C, int64_t V) {
   if (B <= 0 || C <= 0 || V <= 0) return 0;      // a size query of an empty problem (the launchers reject it with DGTTA_ERR_BADARG)
-  return align_up((size_t)B * reduce_blocks(V, B) * C * 2 * sizeof(double), 256) +
-         align_up((size_t)B * C * 2 * sizeof(float), 256);
+  return in_ws_layout(B, C, V).total();
+}
+
+// in_apply_vec_kernel takes whole 16-byte channel groups of 16-byte aligned rows, of every operand of the pass (the forward has
+// no gz: NULL, 0); its grid is one workgroup per 1024 groups of a sample, at most 4096
+static bool apply_vec_ok(int epv, int C, const void *y, int ldy, const void *gz, int ldgz, const void *out, int ldo) {
+  auto ok = [&](const void *p, int ld) { return ld % epv == 0 && !((uintptr_t)p & 15); };
+  return C % epv == 0 && ok(y, ldy) && ok(gz, ldgz) && ok(out, ldo) && C <= 2048;
+}
+static int apply_vec_blocks(int epv, int C, int64_t V) {
+  const int64_t n = cdiv64(V * (C / epv), 256 * 4);
+  return (int)(n < 4096 ? (n > 0 ? n : 1) : 4096);
+}
+
+// the apply pass of the forward (MODE 0: out = z; gz = c12 = NULL) or of the backward (MODE 1: out = dy): the 16-byte kernel
+// where the operands allow it, else the scalar one
+template <int MODE>
+static int launch_in_apply(const void *y, int ldy, const void *gz, int ldgz, const float *mean_rstd, const float *gamma,
+                           const float *beta, const float *c12, void *out, int ldo, int B, int C, int64_t V, float slope,
+                           int dtype, hipStream_t st) {
+  const int epv = 16 / (int)esize(dtype);
+  if (apply_vec_ok(epv, C, y, ldy, gz, ldgz, out, ldo)) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_vec_kernel<T, MODE>), dim3(apply_vec_blocks(epv, C, V), B), dim3(256),
+                                         (size_t)C * (MODE == 0 ? 2 : 6) * 4, st, (const T *)y, ldy, (const T *)gz, ldgz,
+                                         mean_rstd, gamma, beta, c12, (T *)out, ldo, C, V, slope,
+                                         dgtta_switches().in_nt - '0'));
+    DG_CHECK_LAUNCH(MODE == 0 ? "in_apply_vec_kernel<0>" : "in_apply_vec_kernel<1>");
+    return DGTTA_OK;
+  }
+  const int64_t total = (int64_t)B * V * C;
+  if (MODE == 0)
+    DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st, (const T *)y,
+                                         ldy, mean_rstd, gamma, beta, (T *)out, ldo, C, V, slope, total));
+  else
+    DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_bwd_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st,
+                                         (const T *)gz, ldgz, (const T *)y, ldy, mean_rstd, gamma, beta, c12, (T *)out, ldo,
+                                         C, V, slope, total));
+  DG_CHECK_LAUNCH(MODE == 0 ? "in_lrelu_apply_kernel" : "in_lrelu_bwd_apply_kernel");
+  return DGTTA_OK;
 }
 
 extern "C" int dgtta_instnorm_lrelu_fwd(const void *y, int ldy, const void *stats, const float *gamma, const float *beta,
@@ -625,7 +628,7 @@ extern "C" int dgtta_instnorm_lrelu_fwd(const void *y, int ldy, const void *stat
     hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(B * C), dim3(256), 0, st, (const double *)stats + 32,
                        (const long long *)stats, 0, B, C, V, eps, mean_rstd);
   } else {
-    double *partial = (double *)ws;
+    double *partial = in_ws_layout(B, C, V).partial_of(ws);
     DISPATCH_T(dtype, (launch_chan_reduce<T, 0>(y, ldy, nullptr, 0, nullptr, nullptr, nullptr, 0.f, partial, nblk, B, C, V, st)));
     DG_CHECK_LAUNCH("chan_reduce_kernel<0>");
     hipLaunchKernelGGL(in_stats_finalize_kernel, dim3(B * C), dim3(256), 0, st, (const double *)partial,
@@ -633,70 +636,79 @@ extern "C" int dgtta_instnorm_lrelu_fwd(const void *y, int ldy, const void *stat
   }
   DG_CHECK_LAUNCH("in_stats_finalize_kernel");
   if (!z) return DGTTA_OK;
-  const int64_t total = (int64_t)B * V * C;
-  const int esz = (int)esize(dtype), epv = 16 / esz;
-  if (C % epv == 0 && ldy % epv == 0 && ldz % epv == 0 && !((uintptr_t)y & 15) && !((uintptr_t)z & 15) && C <= 2048) {
-    const int64_t items = V * (C / epv);
-    const int blocks = (int)(cdiv64(items, 256 * 4) < 4096 ? (cdiv64(items, 256 * 4) > 0 ? cdiv64(items, 256 * 4) : 1) : 4096);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_vec_kernel<T, 0>), dim3(blocks, B), dim3(256), (size_t)C * 2 * 4, st,
-                                         (const T *)y, ldy, (const T *)nullptr, 0, mean_rstd, gamma, beta, nullptr, (T *)z,
-                                         ldz, C, V, slope, dgtta_switches().in_nt - '0'));
-    DG_CHECK_LAUNCH("in_apply_vec_kernel<0>");
-    return DGTTA_OK;
+  return launch_in_apply<0>(y, ldy, nullptr, 0, mean_rstd, gamma, beta, nullptr, z, ldz, B, C, V, slope, dtype, st);
+}
+
+// gz of the block in front of the head, given as what it is a linear function of: gz = W^T d16 (in_bwd_head_kernel)
+struct InBwdHead {
+  const void *d16;
+  const float *w;
+  const int *sel;
+};
+// pass APPLY of in_bwd_head_kernel on `grid` workgroups per sample (16-bit storage: the entry point admits nothing else)
+template <int APPLY>
+static void launch_in_bwd_head(const InBwdHead &h, const void *y, int ldy, const float *mean_rstd, const float *gamma,
+                               const float *beta, const float *c12, float slope, double *partial, void *dy, int lddy, int grid,
+                               int B, int64_t V, int dtype, hipStream_t st) {
+  auto go = [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((in_bwd_head_kernel<T, APPLY>), dim3(grid, B), dim3(256), 0, st, (const T *)y, ldy,
+                       (const unsigned short *)h.d16, h.w, h.sel, mean_rstd, gamma, beta, c12, slope, partial, (T *)dy, lddy, V,
+                       dgtta_switches().in_nt - '0');
+  };
+  if (dtype == DGTTA_BF16) go(bf16_t{});
+  else go(f16_t{});
+}
+
+// One InstanceNorm + LeakyReLU backward, arguments checked by the entry points: sums -> finalize -> apply.  The sums (sum da,
+// sum da * xhat) per (sample, channel) come from a reduction pass over (y, gz); or, gstats != NULL, from the partials that the
+// data-gradient kernel which produced gz left: no pass over y and gz; or, head != NULL, from a pass that rebuilds gz from the
+// head's d16, as the apply then does too: gz is never stored.
+static int instnorm_bwd_run(const void *gz, int ldgz, const InBwdHead *head, const void *gstats, const void *y, int ldy,
+                            const float *gamma, const float *beta, const float *mean_rstd, void *dy, int lddy, float *dgamma,
+                            float *dbeta, void *ws, int B, int C, int64_t V, float slope, int accumulate, int dtype,
+                            hipStream_t st) {
+  const InWsLayout lay = in_ws_layout(B, C, V);
+  const int nblk = reduce_blocks(V, B);
+  double *partial = lay.partial_of(ws);
+  float *c12 = lay.c12_of(ws);
+  if (head) {
+    launch_in_bwd_head<0>(*head, y, ldy, mean_rstd, gamma, beta, nullptr, slope, partial, nullptr, 0, nblk, B, V, dtype, st);
+    DG_CHECK_LAUNCH("in_bwd_head_kernel<0>");
+  } else if (!gstats) {
+    DISPATCH_T(dtype, (launch_chan_reduce<T, 1>(y, ldy, gz, ldgz, mean_rstd, gamma, beta, slope, partial, nblk, B, C, V, st)));
+    DG_CHECK_LAUNCH("chan_reduce_kernel<1>");
   }
-  DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st,
-                                       (const T *)y, ldy, mean_rstd, gamma, beta, (T *)z, ldz, C, V, slope, total));
-  DG_CHECK_LAUNCH("in_lrelu_apply_kernel");
+  // gstats: header + partials in the layout of the forward statistics, sums of g' y that the finalize converts with mean_rstd
+  hipLaunchKernelGGL(in_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, gstats ? (const double *)gstats + 32 : partial,
+                     (const long long *)gstats, nblk, B, C, V, gstats ? mean_rstd : nullptr, c12, dgamma, dbeta, accumulate);
+  DG_CHECK_LAUNCH("in_bwd_finalize_kernel");
+  if (!head) return launch_in_apply<1>(y, ldy, gz, ldgz, mean_rstd, gamma, beta, c12, dy, lddy, B, C, V, slope, dtype, st);
+  const int64_t units = cdiv64(V, 16);
+  const int blocks = (int)(cdiv64(units, 4 * 4) < 4096 ? cdiv64(units, 4 * 4) : 4096);
+  launch_in_bwd_head<1>(*head, y, ldy, mean_rstd, gamma, beta, c12, slope, nullptr, dy, lddy, blocks, B, V, dtype, st);
+  DG_CHECK_LAUNCH("in_bwd_head_kernel<1>");
   return DGTTA_OK;
 }
 
-static int instnorm_bwd_impl(const void *gz, int ldgz, const void *y, int ldy, const float *gamma, const float *beta,
-                             const float *mean_rstd, void *dy, int lddy, float *dgamma, float *dbeta, const void *gstats,
-                             void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope, int accumulate, int dtype,
-                             void *stream, const char *name) {
+// the checks the two entry points that take a stored gz share
+static int instnorm_bwd_stored(const void *gz, int ldgz, const void *y, int ldy, const float *gamma, const float *beta,
+                               const float *mean_rstd, void *dy, int lddy, float *dgamma, float *dbeta, const void *gstats,
+                               void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope, int accumulate, int dtype,
+                               void *stream, const char *name) {
   DG_REQUIRE(gz && y && gamma && beta && mean_rstd && dy && dgamma && dbeta && ws, DGTTA_ERR_BADARG, "%s: null pointer", name);
   DG_REQUIRE(B > 0 && C > 0 && V > 0 && ldy >= C && ldgz >= C && lddy >= C, DGTTA_ERR_BADARG, "%s: bad dims", name);
   DG_REQUIRE(ws_bytes >= dgtta_instnorm_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "%s: workspace too small", name);
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = reduce_blocks(V, B);
-  double *partial = (double *)ws;
-  float *c12 = (float *)((char *)ws + align_up((size_t)B * nblk * C * 2 * sizeof(double), 256));
-  if (gstats) {     // the sums came out of the data-gradient kernel that produced gz: no pass over y and gz
-    hipLaunchKernelGGL(in_bwd_finalize_gstats_kernel, dim3(C), dim3(256), 0, st, (const double *)gstats, B, C, V, mean_rstd, c12,
-                       dgamma, dbeta, accumulate);
-    DG_CHECK_LAUNCH("in_bwd_finalize_gstats_kernel");
-  } else {
-    DISPATCH_T(dtype, (launch_chan_reduce<T, 1>(y, ldy, gz, ldgz, mean_rstd, gamma, beta, slope, partial, nblk, B, C, V, st)));
-    DG_CHECK_LAUNCH("chan_reduce_kernel<1>");
-    hipLaunchKernelGGL(in_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, B, C, V, c12, dgamma, dbeta,
-                       accumulate);
-    DG_CHECK_LAUNCH("in_bwd_finalize_kernel");
-  }
-  const int64_t total = (int64_t)B * V * C;
-  const int esz = (int)esize(dtype), epv = 16 / esz;
-  if (C % epv == 0 && ldy % epv == 0 && ldgz % epv == 0 && lddy % epv == 0 && !((uintptr_t)y & 15) && !((uintptr_t)gz & 15) &&
-      !((uintptr_t)dy & 15) && C <= 2048) {
-    const int64_t items = V * (C / epv);
-    const int blocks = (int)(cdiv64(items, 256 * 4) < 4096 ? (cdiv64(items, 256 * 4) > 0 ? cdiv64(items, 256 * 4) : 1) : 4096);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_vec_kernel<T, 1>), dim3(blocks, B), dim3(256), (size_t)C * 6 * 4, st,
-                                         (const T *)y, ldy, (const T *)gz, ldgz, mean_rstd, gamma, beta, c12, (T *)dy, lddy,
-                                         C, V, slope, dgtta_switches().in_nt - '0'));
-    DG_CHECK_LAUNCH("in_apply_vec_kernel<1>");
-    return DGTTA_OK;
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL((in_lrelu_bwd_apply_kernel<T>), dim3(gs_blocks(total)), dim3(256), 0, st,
-                                       (const T *)gz, ldgz, (const T *)y, ldy, mean_rstd, gamma, beta, c12, (T *)dy, lddy,
-                                       C, V, slope, total));
-  DG_CHECK_LAUNCH("in_lrelu_bwd_apply_kernel");
-  return DGTTA_OK;
+  return instnorm_bwd_run(gz, ldgz, nullptr, gstats, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, ws, B, C, V, slope,
+                          accumulate, dtype, (hipStream_t)stream);
 }
 
 extern "C" int dgtta_instnorm_lrelu_bwd(const void *gz, int ldgz, const void *y, int ldy, const float *gamma,
                                         const float *beta, const float *mean_rstd, void *dy, int lddy, float *dgamma,
                                         float *dbeta, void *ws, size_t ws_bytes, int B, int C, int64_t V, float slope,
                                         int accumulate, int dtype, void *stream) {
-  return instnorm_bwd_impl(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, nullptr, ws, ws_bytes, B, C, V,
-                           slope, accumulate, dtype, stream, "instnorm_lrelu_bwd");
+  return instnorm_bwd_stored(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, nullptr, ws, ws_bytes, B, C, V,
+                             slope, accumulate, dtype, stream, "instnorm_lrelu_bwd");
 }
 
 extern "C" int dgtta_instnorm_lrelu_bwd_gstats(const void *gz, int ldgz, const void *y, int ldy, const float *gamma,
@@ -705,8 +717,8 @@ extern "C" int dgtta_instnorm_lrelu_bwd_gstats(const void *gz, int ldgz, const v
                                                int B, int C, int64_t V, float slope, int accumulate, int dtype,
                                                void *stream) {
   DG_REQUIRE(gstats, DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_gstats: null statistics");
-  return instnorm_bwd_impl(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, gstats, ws, ws_bytes, B, C, V,
-                           slope, accumulate, dtype, stream, "instnorm_lrelu_bwd_gstats");
+  return instnorm_bwd_stored(gz, ldgz, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, gstats, ws, ws_bytes, B, C, V,
+                             slope, accumulate, dtype, stream, "instnorm_lrelu_bwd_gstats");
 }
 
 // dgtta_instnorm_lrelu_bwd of the block in front of the head, its gz given as (d16, head weight rows, sel): gz = W^T d16 is
@@ -724,29 +736,7 @@ extern "C" int dgtta_instnorm_lrelu_bwd_head(const void *d16, const float *w, co
   DG_REQUIRE(ldy % 8 == 0 && lddy % 8 == 0 && !((uintptr_t)y & 15) && !((uintptr_t)dy & 15) && !((uintptr_t)d16 & 15),
              DGTTA_ERR_BADARG, "instnorm_lrelu_bwd_head: unaligned operand");
   DG_REQUIRE(ws_bytes >= dgtta_instnorm_ws_bytes(B, C, V), DGTTA_ERR_WORKSPACE, "instnorm_lrelu_bwd_head: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = reduce_blocks(V, B);
-  double *partial = (double *)ws;
-  float *c12 = (float *)((char *)ws + align_up((size_t)B * nblk * C * 2 * sizeof(double), 256));
-  const int64_t units = cdiv64(V, 16);
-  const int blocks = (int)(cdiv64(units, 4 * 4) < 4096 ? cdiv64(units, 4 * 4) : 4096);
-  const int nt = dgtta_switches().in_nt - '0';
-#define INH_LAUNCH(T)                                                                                                         \
-  do {                                                                                                                        \
-    hipLaunchKernelGGL((in_bwd_head_kernel<T, 0>), dim3(nblk, B), dim3(256), 0, st, (const T *)y, ldy,                        \
-                       (const unsigned short *)d16, w, sel, mean_rstd, gamma, beta, (const float *)nullptr, slope, partial,  \
-                       (T *)nullptr, 0, V, nt);                                                                               \
-    DG_CHECK_LAUNCH("in_bwd_head_kernel<0>");                                                                                 \
-    hipLaunchKernelGGL(in_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, B, C, V, c12, dgamma, dbeta,         \
-                       accumulate);                                                                                           \
-    DG_CHECK_LAUNCH("in_bwd_finalize_kernel");                                                                                \
-    hipLaunchKernelGGL((in_bwd_head_kernel<T, 1>), dim3(blocks, B), dim3(256), 0, st, (const T *)y, ldy,                      \
-                       (const unsigned short *)d16, w, sel, mean_rstd, gamma, beta, (const float *)c12, slope,               \
-                       (double *)nullptr, (T *)dy, lddy, V, nt);                                                              \
-    DG_CHECK_LAUNCH("in_bwd_head_kernel<1>");                                                                                 \
-  } while (0)
-  if (dtype == DGTTA_BF16) INH_LAUNCH(bf16_t);
-  else INH_LAUNCH(f16_t);
-#undef INH_LAUNCH
-  return DGTTA_OK;
+  const InBwdHead head = {d16, w, sel};
+  return instnorm_bwd_run(nullptr, 0, &head, nullptr, y, ldy, gamma, beta, mean_rstd, dy, lddy, dgamma, dbeta, ws, B, C, V, slope,
+                          accumulate, dtype, (hipStream_t)stream);
 }

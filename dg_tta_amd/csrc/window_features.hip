@@ -26,6 +26,7 @@
 // the window's place in the volume, its checks and the index arithmetic are window_api.h's, shared with window_logits.hip.  Then the
 // head kernels that read the accumulator (argmax, softmax, export chunk).
 #include "gfx950.h"
+#include "instnorm_math.h"
 #include "window_api.h"
 
 namespace {
@@ -95,9 +96,9 @@ __global__ __launch_bounds__(256) void feature_accumulate_kernel(WfSources ws, c
   if (NORM) {
     if (threadIdx.x < NS * WF_CIN) {
       const int k = threadIdx.x / WF_CIN, c = threadIdx.x % WF_CIN;
-      const float al = ws.mean_rstd[k][c * 2 + 1] * gamma[c];
+      const float al = in_alpha(ws.mean_rstd[k][c * 2 + 1], gamma[c]);
       sal[k][c] = al;
-      sbe[k][c] = beta[c] - ws.mean_rstd[k][c * 2] * al;
+      sbe[k][c] = in_beta(beta[c], ws.mean_rstd[k][c * 2], al);
     }
     __syncthreads();
   }
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void feature_accumulate_kernel(WfSources ws, c
   for (int k = 0; k < NS; ++k) {
     float zv[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) zv[e] = NORM ? wf_round<T>(lrelu(f[k][e] * sal[k][q * 4 + e] + sbe[k][q * 4 + e], slope)) : f[k][e];
+    for (int e = 0; e < 4; ++e) zv[e] = NORM ? wf_round<T>(in_fwd(f[k][e], sal[k][q * 4 + e], sbe[k][q * 4 + e], slope)) : f[k][e];
     a.x += g[k] * zv[0], a.y += g[k] * zv[1], a.z += g[k] * zv[2], a.w += g[k] * zv[3];
     n += g[k];
   }

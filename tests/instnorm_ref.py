@@ -8,7 +8,7 @@ per-(sample, channel) quantities are [B, C].
     dy = gamma rstd ((da - S0 / V) - xhat S1 / V)      dgamma = sum_b S1      dbeta = sum_b S0
 
 partials() lays per-tile sums out as the conv epilogues and the data-gradient kernel do (dgtta_conv3d_stats_bytes,
-in_bwd_finalize_gstats_kernel): a 256-byte header whose first int64 is the number of tiles per sample, then
+in_bwd_finalize_kernel given mean_rstd): a 256-byte header whose first int64 is the number of tiles per sample, then
 [B][nblk][C][2] doubles - (sum y, sum y^2) for the forward, (sum da, sum da y) for the backward.
 """
 import torch

@@ -437,7 +437,7 @@ def test_constant_channel():
 @pytest.mark.parametrize("case", [(2, 32, 3000, 1, 0, "normal"), (1, 320, 300, 2, 0, "normal"), (2, 5, 1000, 0, 3, "normal"),
                                   (2, 5, 1000, 0, 3, "offset")], ids=lambda c: "B{}-C{}-V{}-dt{}-ld+{}-{}".format(*c))
 def test_backward_from_gstats_partials(case):
-    """in_bwd_finalize_gstats_kernel: per-tile (sum g', sum g' y) in float64 (what the data-gradient kernel leaves) turned
+    """in_bwd_finalize_kernel given mean_rstd: per-tile (sum g', sum g' y) in float64 (what the data-gradient kernel leaves) turned
     into c1, c2, dgamma, dbeta as rs (s1 - mu s0) in double - also where the mean is 100 x the standard deviation - and
     the apply pass on them, against the reference with the bounds of double sums and against dgtta_instnorm_lrelu_bwd
     on the same inputs within the sum of both paths' bounds."""
