@@ -139,7 +139,12 @@ SIGNATURES = {
     "dgtta_feature_window_accumulate_norm_mirror": (I, [P, P, P, P, F, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_seghead_window_accumulate_mirror_t": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_window_accumulate_mirror_t": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_fingerprint_ws_bytes": (SZ, [I64, I]),
+    "dgtta_fingerprint_sweep": (I, [P, P, I, I64, I, C.c_double, I64, I, I, C.POINTER(C.c_uint32), I, P, P, P, SZ, P]),
 }
+
+FP_BINS, FP_MAX_PREFIXES = 2048, 6
+SEG_U8, SEG_I16, SEG_I32 = 0, 1, 2
 
 
 class PatchItem(C.Structure):

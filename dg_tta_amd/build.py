@@ -11,7 +11,7 @@ SOURCES = ["lib.hip", "mind3d.hip", "gin.hip", "warp.hip", "softdice.hip", "dice
            "window_logits.hip", "conv_dispatch.hip", "conv_ref.hip", "instnorm.hip", "seghead.hip", "seghead_mfma.hip", "layout_argmax.hip", "conv_mfma.hip",
            "conv_rows.hip", "conv_ring.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_wgrad_flat.hip", "conv_wgrad_s2.hip", "conv_wgrad_reduce.hip",
            "conv_wgrad_ring.hip", "convt_wgrad.hip", "head_wgrad.hip", "convt_gemm.hip", "conv_s2.hip", "conv_aniso.hip", "deform.hip", "surface.hip",
-           "components.hip", "sgd.hip", "spatial_aug.hip", "intensity_aug.hip", "mirror.hip"]
+           "components.hip", "sgd.hip", "spatial_aug.hip", "intensity_aug.hip", "mirror.hip", "fingerprint.hip"]
 # conv_ring.hip: the 64-input-channel step body (432 MFMAs, 192 fragment reads, fully unrolled) is above hipcc's default
 # pragma-unroll threshold; partially unrolled its register arrays are indexed dynamically and land in scratch
 EXTRA_FLAGS = {"conv_ring.hip": ["-mllvm", "-pragma-unroll-threshold=262144"]}

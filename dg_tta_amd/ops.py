@@ -1279,6 +1279,78 @@ def gauss_blur3(x, items, sigmas, out=None, scratch=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ dataset fingerprint
+FP_BINS, FP_MAX_PREFIXES = _lib.FP_BINS, _lib.FP_MAX_PREFIXES
+_FP_SEG = {torch.uint8: _lib.SEG_U8, torch.int16: _lib.SEG_I16, torch.int32: _lib.SEG_I32}
+
+
+def fingerprint_state(device):
+    """The initial running state of the moment sweeps: an int64 tensor [7] holding DgttaFingerprintState of include/dgtta.h
+    (count, nonfinite, first_nonfinite_case as integers; min, max, sum, sumsq_centred as the bits of doubles)."""
+    s = torch.zeros(7, dtype=torch.float64)
+    s[3], s[4] = float("inf"), float("-inf")
+    s = s.view(torch.int64)
+    s[2] = -1
+    return s.to(device)
+
+
+def fingerprint_read_state(state):
+    """The state as a dict of Python numbers (one copy from the device)."""
+    i = state.cpu()
+    f = i.view(torch.float64)
+    return {"count": int(i[0]), "nonfinite": int(i[1]), "first_nonfinite_case": int(i[2]), "min": float(f[3]), "max": float(f[4]),
+            "sum": float(f[5]), "sumsq_centred": float(f[6])}
+
+
+def fingerprint_counters(device, n_prefixes=1):
+    """Zeroed running histogram of a sweep: int64 [n_prefixes, FP_BINS] (the kernels count in unsigned 64 bits)."""
+    return torch.zeros((int(n_prefixes), FP_BINS), dtype=torch.int64, device=device)
+
+
+def fingerprint_ws_bytes(voxels, n_prefixes):
+    return int(_lib.load().dgtta_fingerprint_ws_bytes(int(voxels), int(n_prefixes)))
+
+
+def fingerprint_sweep(x, seg, counters, prefix_bits=0, digit_bits=11, prefixes=None, moment=0, state=None, mean=0.0, case_index=0,
+                      ws=None):
+    """One case of one fingerprint sweep (csrc/fingerprint.hip).  x: float32 CUDA tensor, seg: uint8 / int16 / int32 labels of the
+    same number of voxels; foreground is seg > 0.  counters [len(prefixes), FP_BINS] (int64, the caller's running histogram)
+    grows by the digit histogram - the `digit_bits` key bits after the leading `prefix_bits` - of the finite foreground values
+    whose key starts with one of `prefixes` (prefix_bits = 0: of all of them).  moment 1 / 2 adds the case to `state`
+    (fingerprint_state): count, min, max, sum and non-finite count / the sum of (x - mean)^2.  Nothing is read back."""
+    name = "fingerprint_sweep"
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"{name}: `x` must be a non-empty contiguous float32 CUDA tensor (there is no CPU fallback)")
+    if not isinstance(seg, torch.Tensor) or seg.device != x.device or seg.dtype not in _FP_SEG or not seg.is_contiguous() or \
+            seg.numel() != x.numel():
+        raise ValueError(f"{name}: `seg` must be a contiguous uint8 / int16 / int32 tensor of x's size on x's device")
+    prefix_bits, digit_bits, moment = int(prefix_bits), int(digit_bits), int(moment)
+    if prefix_bits != 0 and prefixes is None:
+        raise ValueError(f"{name}: a prefix of {prefix_bits} bits needs `prefixes`")
+    prefixes = [0] if prefix_bits == 0 else [int(p) for p in prefixes]
+    n = len(prefixes)
+    if not 1 <= n <= FP_MAX_PREFIXES or len(set(prefixes)) != n or any(not 0 <= p < 2 ** 32 for p in prefixes):
+        raise ValueError(f"{name}: 1..{FP_MAX_PREFIXES} distinct 32-bit prefixes expected (got {prefixes})")
+    if not isinstance(counters, torch.Tensor) or counters.device != x.device or counters.dtype != torch.int64 or \
+            not counters.is_contiguous() or tuple(counters.shape) != (n, FP_BINS):
+        raise ValueError(f"{name}: `counters` must be a contiguous int64 tensor [{n}, {FP_BINS}] on x's device")
+    if moment not in (0, 1, 2):
+        raise ValueError(f"{name}: moment {moment} not in (0, 1, 2)")
+    if moment and (not isinstance(state, torch.Tensor) or state.device != x.device or state.dtype != torch.int64 or
+                   not state.is_contiguous() or state.numel() != 7):
+        raise ValueError(f"{name}: `state` must be the int64 tensor [7] of fingerprint_state on x's device")
+    need = fingerprint_ws_bytes(x.numel(), n)
+    if ws is None:
+        ws = _ws(need, x.device)
+    elif not ws.is_cuda or ws.device != x.device or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"{name}: `ws` is a contiguous uint8 CUDA tensor of at least {need} bytes")
+    h_pre = (C.c_uint32 * n)(*prefixes)
+    check(_lib.load().dgtta_fingerprint_sweep(ptr(x), ptr(seg), _FP_SEG[seg.dtype], x.numel(), moment, float(mean), int(case_index),
+                                              prefix_bits, digit_bits, h_pre, n, ptr(counters), ptr(state) if moment else None, ptr(ws),
+                                              ws.numel(), stream_of(x.device)), "dgtta_fingerprint_sweep")
+    return counters
+
+
 # ------------------------------------------------------------------------------------------------ resampling
 def resize_volume(x, new_shape, order, axes=None):
     """skimage.transform.resize(x[c], new_shape, order, mode='edge', anti_aliasing=False, clip=False) for every leading

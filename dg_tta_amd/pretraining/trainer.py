@@ -210,7 +210,7 @@ def load_dataset_files(dataset_name):
         raise FileNotFoundError(
             f"{plans_file} not found: `dgtta pretrain` trains from existing plans and does no experiment planning.  Put the "
             f"nnUNetPlans.json of this dataset there (nnUNetv2_plan_and_preprocess writes it; the plans.json of a model trained "
-            f"on comparable data, with its patch size and spacing, works too).")
+            f"on comparable data, with its patch size and spacing, works too), or run `dgtta plan` on the raw dataset.")
     with open(plans_file) as f:
         plans = json.load(f)
     for folder in (pre, raw):

@@ -1,7 +1,8 @@
 """`dgtta` command line — same sub-commands, positional arguments and option names as the reference's dg_tta/run.py
 (prepare_tta :71-118, run_tta :120-209).  `pretrain` takes the arguments of `nnUNetv2_train`, which the reference dispatches
 into, and trains on this engine (pretraining/trainer.py); `inject_trainers` patches an installed nnunetv2 and has nothing
-to do here.  Extra, optional: `run_tta --gpus N` fans out one process per GPU
+to do here.  `plan` stands for the planning half of `nnUNetv2_plan_and_preprocess`: the dataset fingerprint (on the GPU) and nnU-Net
+2.2.1's ExperimentPlanner (planning/), so that `pretrain` can start from a raw dataset.  Extra, optional: `run_tta --gpus N` fans out one process per GPU
 (sample-sharded, no collectives), `--dtype {fp32,bf16,fp16}` (default fp32 = the reference's precision).
 """
 import argparse
@@ -68,6 +69,7 @@ class DGTTAProgram:
         parser = argparse.ArgumentParser(description="DG-TTA for nnUNetv2 (MI355X engine)", usage="""dgtta <command> [<args>]
 
         Commands are:
+        plan            Fingerprint the source dataset and plan the experiment (writes nnUNetPlans.json)
         pretrain        Pre-train on the source dataset (GIN / MIND trainers)
         prepare_tta     Prepare test-time adaptation
         run_tta         Run test-time adaptation
@@ -83,6 +85,52 @@ class DGTTAProgram:
     def inject_trainers(self):
         raise SystemExit("inject_trainers patches an installed nnunetv2 so that nnUNetv2_train finds the DG trainers; "
                          "nothing is injected here: `dgtta pretrain` trains on this engine and no longer needs it.")
+
+    def plan(self):
+        parser = argparse.ArgumentParser(description="Fingerprint the raw source dataset on the GPU and plan the experiment as "
+                                         "nnU-Net 2.2.1's ExperimentPlanner does (nnUNetv2_plan_and_preprocess without the eager "
+                                         "preprocessing)", usage="dgtta plan [-h]")
+        parser.add_argument("dataset_id", help="Dataset name or numeric id of the source dataset in nnUNet_raw")
+        parser.add_argument("--device", help="Device of the fingerprint sweeps; 'cpu' runs them in numpy", default="cuda")
+        parser.add_argument("--cache_gib", type=float, default=64.0,
+                            help="device memory (GiB) the cropped cases may occupy between the sweeps; the rest is read from disk "
+                                 "again.  The result does not depend on it")
+        parser.add_argument("--overwrite", action="store_true", help="replace an existing nnUNetPlans.json")
+        args = parser.parse_args(self.argv[2:])
+        from .planning.fingerprint import extract_fingerprint
+        from .planning.planner import channel_schemes, plan_experiment
+        from .tta.config_log_utils import maybe_convert_to_dataset_name, nnunet_path
+        dataset_name = maybe_convert_to_dataset_name(args.dataset_id)
+        raw = Path(nnunet_path("nnUNet_raw")) / dataset_name
+        pre = Path(nnunet_path("nnUNet_preprocessed")) / dataset_name
+        if not (raw / "dataset.json").is_file():
+            raise SystemExit(f"plan: {raw / 'dataset.json'} not found")
+        plans_file = pre / "nnUNetPlans.json"
+        if plans_file.is_file() and not args.overwrite:
+            raise SystemExit(f"plan: {plans_file} exists; pass --overwrite to replace it")
+        with open(raw / "dataset.json") as f:
+            dataset_json = json.load(f)
+        try:
+            channel_schemes(dataset_json)               # a dataset.json the planner refuses costs no sweep and leaves no file
+        except ValueError as e:
+            raise SystemExit(f"plan: {raw / 'dataset.json'}: {e}") from e
+        fingerprint = extract_fingerprint(raw, dataset_json, device=torch.device(args.device), cache_bytes=int(args.cache_gib * 2 ** 30),
+                                          output_file=pre / "dataset_fingerprint.json")
+        plans = plan_experiment(fingerprint, dataset_json, dataset_name=dataset_name)
+        for name, content in (("nnUNetPlans.json", plans), ("dataset.json", dataset_json)):
+            with open(pre / name, "w") as f:
+                json.dump(content, f, indent=4)
+        for name, conf in plans["configurations"].items():
+            if "inherits_from" in conf:
+                print(f"plan: {name}: inherits from {conf['inherits_from']}, previous stage {conf['previous_stage']}")
+            else:
+                print(f"plan: {name}: spacing {conf['spacing']}, median shape {conf['median_image_size_in_voxels']}, patch "
+                      f"{conf['patch_size']}, batch {conf['batch_size']}, {len(conf['pool_op_kernel_sizes'])} stages, "
+                      f"{conf['normalization_schemes']}")
+        print(f"plan: wrote {plans_file}.  Not planned: `2d` (no 2-D kernels here), ResEnc planners, the `architecture` schema of "
+              f"nnU-Net >= 2.4.  `3d_lowres` and the cascade are written when nnU-Net would plan them; training the cascade is not "
+              f"built.  Nothing is preprocessed now: `dgtta pretrain` preprocesses each case on first use.  The intensity "
+              f"statistics are exact over all foreground voxels (nnU-Net samples 10 000 per case).")
 
     @staticmethod
     def _pretrain_parser(trainers=None):

@@ -56,6 +56,17 @@ def crop_to_nonzero(data, seg, nonzero_label=-1):
     return data, seg, bbox
 
 
+def nonzero_box_gpu(data):
+    """(hole-filled non-zero mask uint8 [X,Y,Z] on the device, bbox [[lo, hi), ...]) of a float32 device tensor [C,X,Y,Z]: the
+    device half of crop_to_nonzero_gpu, for callers that keep the volume on the device (planning/fingerprint.py)."""
+    raw = ops.nonzero_mask(data)
+    filled, _, box = ops.fill_holes(raw, 6, return_box=True)
+    box = box.cpu().tolist()
+    if box[0] > box[3]:
+        raise ValueError("crop_to_nonzero_gpu: every voxel of the case is zero, there is no box to crop to")
+    return filled, [[box[k], box[3 + k] + 1] for k in range(3)]
+
+
 def crop_to_nonzero_gpu(data, seg, device, nonzero_label=-1):
     """crop_to_nonzero with the mask, its hole filling and its bounding box on the GPU (csrc/components.hip: ops.nonzero_mask,
     ops.fill_holes); equal to the host function in every element and dtype, by test.  data: float32 numpy [C,X,Y,Z]; only the
@@ -63,12 +74,7 @@ def crop_to_nonzero_gpu(data, seg, device, nonzero_label=-1):
     if not isinstance(data, np.ndarray) or data.dtype != np.float32 or data.ndim != 4:
         raise ValueError(f"crop_to_nonzero_gpu: float32 numpy data [C,X,Y,Z] expected, got {getattr(data, 'shape', None)} "
                          f"{getattr(data, 'dtype', type(data))}")
-    raw = ops.nonzero_mask(torch.from_numpy(np.ascontiguousarray(data)).to(device))
-    filled, _, box = ops.fill_holes(raw, 6, return_box=True)
-    box = box.cpu().tolist()
-    if box[0] > box[3]:
-        raise ValueError("crop_to_nonzero_gpu: every voxel of the case is zero, there is no box to crop to")
-    bbox = [[box[k], box[3 + k] + 1] for k in range(3)]
+    filled, bbox = nonzero_box_gpu(torch.from_numpy(np.ascontiguousarray(data)).to(device))
     sl = tuple(slice(a, b) for a, b in bbox)
     data = data[(slice(None),) + sl]
     mask = filled[sl].contiguous().cpu().numpy().astype(bool)[None]

@@ -828,6 +828,48 @@ int dgtta_seghead_window_accumulate_mirror_t(const void *z, const float *w, cons
 int dgtta_window_accumulate_mirror_t(const float *patch, const float *gauss, void *acc, float *nsum, int C, int PD, int PH, int PW,
                                      int X, int Y, int Z, int x0, int y0, int z0, int acc_dtype, int mirror, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dataset fingerprint (csrc/fingerprint.hip, dg_tta_amd/planning/fingerprint.py): exact pooled statistics of the foreground
+ * voxels (seg > 0) of one image channel over all training cases.  One call per case and sweep; the kernels hold no state: the
+ * running histogram `counters` and the running `state` are the caller's device buffers, zeroed / initialised by the caller and
+ * carried from case to case.  x: fp32 [V]; seg: [V] labels of type seg_dtype (DGTTA_SEG_*).  Three launches at most, all on
+ * `stream`; nothing is allocated and the stream is not waited for.
+ *
+ * Histogram.  key(v) = bits(v) ^ 0x80000000 for a value with a clear sign bit, ~bits(v) otherwise: unsigned order of the keys =
+ * order of the values (-0.0 sorts before +0.0).  With the key's leading prefix_bits bits as its prefix and the next digit_bits
+ * (1 .. 11) bits as its digit, counters[t][d] (uint64 [n_prefixes][DGTTA_FP_BINS]) grows by the number of finite foreground
+ * values whose prefix is h_prefixes[t] and whose digit is d.  prefix_bits = 0: one histogram of all finite foreground values,
+ * h_prefixes is not read, n_prefixes = 1.  The prefixes (HOST array, copied into the kernel arguments) are distinct.  Every
+ * workgroup counts in LDS and stores its histogram to a slab of `ws`; a second launch adds the slabs in ascending order.
+ * Exact: integer counts only.
+ *
+ * Moments.  moment = 0: none.  moment = 1: state->count, min, max, sum (double) and nonfinite grow by the case's finite /
+ * non-finite foreground values; first_nonfinite_case becomes case_index if the case has a non-finite foreground value and the
+ * field is still negative.  moment = 2: sumsq_centred grows by the case's sum of ((double)x - mean)^2.  Non-finite foreground
+ * values are counted and left out of everything else (histogram included).  Double sums per thread in index order, a fixed tree
+ * across the workgroup, the workgroups' partials added in ascending order, the case's sum added to the state: the same bits on
+ * every run for a given order of the cases.  No floating-point atomics.
+ * Initial state: count = nonfinite = 0, first_nonfinite_case = -1, min = +inf, max = -inf, sum = sumsq_centred = 0.
+ * ws: dgtta_fingerprint_ws_bytes(V, n_prefixes) bytes (0 for arguments out of range), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define DGTTA_FP_BINS 2048
+#define DGTTA_FP_MAX_PREFIXES 6
+#define DGTTA_SEG_U8 0
+#define DGTTA_SEG_I16 1
+#define DGTTA_SEG_I32 2
+typedef struct DgttaFingerprintState {
+  uint64_t count;               /* finite foreground values */
+  uint64_t nonfinite;           /* NaN / inf foreground values */
+  int64_t first_nonfinite_case; /* case_index of the first case that had one, else negative */
+  double min, max;              /* exact fp32 values */
+  double sum;                   /* of the finite foreground values */
+  double sumsq_centred;         /* of (x - mean)^2 */
+} DgttaFingerprintState;
+size_t dgtta_fingerprint_ws_bytes(int64_t V, int n_prefixes);
+int dgtta_fingerprint_sweep(const float *x, const void *seg, int seg_dtype, int64_t V, int moment, double mean, int64_t case_index,
+                            int prefix_bits, int digit_bits, const uint32_t *h_prefixes, int n_prefixes, uint64_t *counters,
+                            DgttaFingerprintState *state, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
