@@ -45,6 +45,17 @@ SIGNATURES = {
     "dgtta_dice_ce_ds_bwd": (I, [P, I, P, P, F, P, P, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_dice_ce_batch_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I64, F, I, I, P]),
     "dgtta_dice_ce_ds_batch_fwd": (I, [P, I, P, P, P, P, SZ, I, I, I, I, I, I, I, I, F, I, I, P]),
+    "dgtta_region_loss_ws_bytes": (SZ, [I, I, I64]),
+    "dgtta_region_loss_fwd": (I, [P, I, P, P, I, P, P, P, SZ, I, I, I64, F, P]),
+    "dgtta_region_loss_batch_fwd": (I, [P, I, P, P, I, P, P, P, SZ, I, I, I64, F, I, P]),
+    "dgtta_region_loss_bwd": (I, [P, I, P, P, I, P, F, P, P, I, I, I, I64, P]),
+    "dgtta_region_loss_ds_ws_bytes": (SZ, [I, I, I, I, I]),
+    "dgtta_region_loss_ds_fwd": (I, [P, I, P, P, I, P, P, P, SZ, I, I, I, I, I, I, I, I, F, P]),
+    "dgtta_region_loss_ds_batch_fwd": (I, [P, I, P, P, I, P, P, P, SZ, I, I, I, I, I, I, I, I, F, I, P]),
+    "dgtta_region_loss_ds_bwd": (I, [P, I, P, P, I, P, F, P, P, I, I, I, I, I, I, I, I, I, P]),
+    "dgtta_region_counts": (I, [P, I, I, P, P, I, P, I64, P]),
+    "dgtta_logits_regions": (I, [P, I, I, I64, C.POINTER(I), P, P]),
+    "dgtta_feature_head_regions": (I, [P, I64, P, P, P, I, I, I, I64, C.POINTER(I), P, P]),
     "dgtta_adamw_step": (I, [C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(I64), I, F, F, F, F, F,
                              I, F, P, P]),
     "dgtta_grads_nonfinite": (I, [C.POINTER(P), C.POINTER(I64), I, P, P]),

@@ -7,7 +7,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = Path(__file__).resolve().parent / "libdgtta_hip.so"
-SOURCES = ["lib.hip", "mind3d.hip", "gin.hip", "warp.hip", "softdice.hip", "dice_ce.hip", "adamw.hip", "resample.hip", "window_features.hip",
+SOURCES = ["lib.hip", "mind3d.hip", "gin.hip", "warp.hip", "softdice.hip", "dice_ce.hip", "region_loss.hip", "region_map.hip", "adamw.hip", "resample.hip", "window_features.hip",
            "window_logits.hip", "conv_dispatch.hip", "conv_ref.hip", "instnorm.hip", "seghead.hip", "seghead_mfma.hip", "layout_argmax.hip", "conv_mfma.hip",
            "conv_rows.hip", "conv_ring.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_wgrad_flat.hip", "conv_wgrad_s2.hip", "conv_wgrad_reduce.hip",
            "conv_wgrad_ring.hip", "convt_wgrad.hip", "head_wgrad.hip", "convt_gemm.hip", "conv_s2.hip", "conv_aniso.hip", "deform.hip", "surface.hip",

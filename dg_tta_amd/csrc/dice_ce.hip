@@ -27,6 +27,7 @@
 // is a restatement FROM MEMORY of that transform's nearest-neighbour choice and is UNPINNED.  The kernels read the label
 // through the index map below: no downsampled label tensor exists.  Strides (1, 1, 1) are the plain loss, bit for bit.
 #include "common.h"
+#include "label_map.h"
 
 namespace {
 
@@ -34,18 +35,6 @@ constexpr int DC_MAXC = 128;
 constexpr int DC_TILE = 128;               // voxels per tile: rows are staged through LDS as ONE contiguous run (a lane that walks
                                            // its own 420-byte row straight from memory runs at 0.3 TB/s, DESIGN.md "20x trap")
 constexpr int DC_THREADS = 256;
-
-// where the label of voxel v of sample b lives: dense [B][V], or a strided view of a full-resolution map (h == 0: dense)
-struct DcLabels {
-  int h, w, sd, sh, sw;
-  int64_t H, W, Vfull;
-  __device__ __forceinline__ int64_t at(int b, int64_t v, int64_t V) const {
-    if (h == 0) return (int64_t)b * V + v;
-    const int64_t i = v / ((int64_t)h * w), rem = v - i * ((int64_t)h * w);
-    const int64_t j = rem / w, k = rem - j * w;
-    return (int64_t)b * Vfull + ((i * sd + sd / 2) * H + (j * sh + sh / 2)) * W + (k * sw + sw / 2);
-  }
-};
 
 __host__ __device__ inline int dc_pitch(int C) { return C | 1; }
 inline int dc_blocks(int64_t V) {
@@ -356,8 +345,6 @@ static int dice_ce_bwd(const float *logits, int ldc, const int64_t *labels, cons
   return DGTTA_OK;
 }
 
-static const DcLabels DC_DENSE = {0, 0, 1, 1, 1, 0, 0, 0};
-
 extern "C" int dgtta_dice_ce_fwd(const float *logits, int ldc, const int64_t *labels, float *loss3, float *dice, void *ws,
                                  size_t ws_bytes, int B, int C, int64_t V, float smooth, int do_bg, void *stream) {
   return dice_ce_fwd(logits, ldc, labels, loss3, dice, ws, ws_bytes, B, C, V, smooth, do_bg, 0, stream, DC_DENSE);
@@ -376,15 +363,6 @@ extern "C" int dgtta_dice_ce_bwd(const float *logits, int ldc, const int64_t *la
 }
 
 // ---- the same loss on logits [B][d][h][w][ld] against the full-resolution label map [B][d sd][h sh][w sw]
-static bool dc_ds_dims_ok(int d, int h, int w, int sd, int sh, int sw) {
-  return d > 0 && h > 0 && w > 0 && sd > 0 && sh > 0 && sw > 0 && (int64_t)d * sd < (1ll << 31) && (int64_t)h * sh < (1ll << 31) &&
-         (int64_t)w * sw < (1ll << 31);
-}
-static DcLabels dc_ds_labels(int d, int h, int w, int sd, int sh, int sw) {
-  DcLabels lm = {h, w, sd, sh, sw, (int64_t)h * sh, (int64_t)w * sw, (int64_t)d * sd * h * sh * w * sw};
-  return lm;
-}
-
 extern "C" size_t dgtta_dice_ce_ds_ws_bytes(int B, int C, int d, int h, int w) {
   if (d <= 0 || h <= 0 || w <= 0) return 0;
   return dgtta_dice_ce_ws_bytes(B, C, (int64_t)d * h * w);

@@ -24,7 +24,7 @@
 // Layout: ONE accumulate kernel template (feature_accumulate_kernel<T, NS, NORM, MIR>: storage type, windows per launch, folded
 // InstanceNorm apply, mirrored source) behind one host launcher that the five dgtta_feature_window_accumulate* entries forward to;
 // the window's place in the volume, its checks and the index arithmetic are window_api.h's, shared with window_logits.hip.  Then the
-// head kernels that read the accumulator (argmax, softmax, export chunk).
+// head kernels that read the accumulator (argmax, softmax, region label map, export chunk).
 #include "gfx950.h"
 #include "instnorm_math.h"
 #include "window_api.h"
@@ -374,6 +374,42 @@ __global__ __launch_bounds__(256) void feature_head_softmax_mfma_kernel(const fl
   });
 }
 
+// Label map of a REGION-based head (region_loss.hip's header: R <= 32 sigmoid outputs, one class block) on the same tile loop:
+// seg = 0; for i = 0 .. R-1 in order: seg = order[i] where the ensemble-mean logit l_i > 0 - nnU-Net's
+// convert_probabilities_to_segmentation for regions, from memory, UNPINNED.  The mean is a positive multiple of the unscaled
+// accumulator, so its sign decides (a sum of exactly 0 is not in the region).  A lane's classes ascend with q, so the last q with
+// acc > 0 is the half's last positive region; the voxel's is the larger of the two halves'.  The same accumulation order as the
+// argmax and softmax kernels.  order sits behind bsum in LDS.
+struct WfOrder {
+  int c[32];
+};
+
+__global__ __launch_bounds__(256) void feature_head_regions_mfma_kernel(const float *__restrict__ facc, int64_t member_stride,
+                                                                        const float *__restrict__ nsum, const float *__restrict__ w,
+                                                                        const float *__restrict__ bsum, int M, int R, int64_t V,
+                                                                        WfOrder order, int64_t *__restrict__ label) {
+  extern __shared__ __attribute__((aligned(16))) float sw[];      // [M][32][WF_WPITCH], bsum [32], order [32] (ints)
+  int *s_ord = reinterpret_cast<int *>(sw + (size_t)M * 32 * WF_WPITCH + 32);
+  const int tid = threadIdx.x;
+  {
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) mine = tid == k ? order.c[k] : mine;      // (no runtime index into the kernel argument)
+    if (tid < 32) s_ord[tid] = mine;
+  }      // (feature_head_tiles synchronises before the first tile)
+  feature_head_tiles<1>(facc, member_stride, nsum, w, bsum, M, R, V, sw, [&](const f32x16_t(&acc)[1], float, int64_t v, bool valid, int h) {
+    int li = -1;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int c = (q & 3) + 8 * (q >> 2) + 4 * h;
+      if (c < R && acc[0][q] > 0.f) li = c;
+    }
+    const int oi = __shfl_xor(li, 32, 64);
+    li = oi > li ? oi : li;
+    if (h == 0 && valid) label[v] = li >= 0 ? s_ord[li] : 0;
+  });
+}
+
 // Export path (original geometry): classes c0 .. c0 + cg - 1 of the normalised ensemble logits as doubles,
 // dst[x][y][z][j] = sum_m (W_m[c0 + j] . F_m(sv)) / n(sv) + bsum[c0 + j] - the input of the dgtta_resample_axis passes, as
 // dgtta_logits_chunk_f64 is for the logits-space accumulator (products and sums in double).
@@ -582,6 +618,31 @@ extern "C" int dgtta_feature_head_softmax(const float *facc, int64_t member_stri
 #undef WF_SOFTMAX_N
 #undef WF_SOFTMAX
   DG_CHECK_LAUNCH("feature_head_softmax_mfma_kernel");
+  return DGTTA_OK;
+}
+
+extern "C" int dgtta_feature_head_regions(const float *facc, int64_t member_stride, const float *nsum, const float *w, const float *bsum,
+                                          int M, int Cin, int R, int64_t V, const int *h_order, int64_t *label_out, void *stream) {
+  DG_REQUIRE(facc && nsum && w && bsum && h_order && label_out, DGTTA_ERR_BADARG, "feature_head_regions: null pointer");
+  DG_REQUIRE(Cin == WF_CIN, DGTTA_ERR_UNSUPPORTED, "feature_head_regions: built for %d feature channels (got %d)", WF_CIN, Cin);
+  DG_REQUIRE(M >= 1 && R >= 1 && V >= 1 && (M == 1 || member_stride >= V * WF_CIN), DGTTA_ERR_BADARG, "feature_head_regions: bad sizes");
+  DG_REQUIRE(((uintptr_t)facc & 15) == 0 && (member_stride & 3) == 0, DGTTA_ERR_BADARG, "feature_head_regions: unaligned accumulator");
+  const size_t lds = ((size_t)M * 32 * WF_WPITCH + 32) * sizeof(float) + 32 * sizeof(int);
+  DG_REQUIRE(R <= 32 && lds <= 160 * 1024, DGTTA_ERR_UNSUPPORTED,
+             "feature_head_regions: %d regions x %d members: at most 32 regions and a weight image that fits the LDS", R, M);
+  WfOrder order{};
+  for (int i = 0; i < R; ++i) {
+    DG_REQUIRE(h_order[i] > 0, DGTTA_ERR_BADARG, "feature_head_regions: regions_class_order[%d] = %d is not a positive label", i, h_order[i]);
+    order.c[i] = h_order[i];
+  }
+  static DynLdsOnce once;
+  DG_REQUIRE(ensure_dyn_lds(once, (const void *)feature_head_regions_mfma_kernel, 160 * 1024) == hipSuccess, DGTTA_ERR_LAUNCH,
+             "feature_head_regions: cannot raise the dynamic LDS limit");
+  const int64_t ntile = cdiv64(V, 32);
+  const unsigned grid = (unsigned)(cdiv64(ntile, 4) < 2048 ? cdiv64(ntile, 4) : 2048);
+  hipLaunchKernelGGL(feature_head_regions_mfma_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, facc, member_stride, nsum, w, bsum,
+                     M, R, V, order, label_out);
+  DG_CHECK_LAUNCH("feature_head_regions_mfma_kernel");
   return DGTTA_OK;
 }
 

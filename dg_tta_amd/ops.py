@@ -510,6 +510,197 @@ def deep_supervision_loss(outputs, labels, smooth=1e-5, do_bg=False, weights=Non
     return total, per_scale
 
 
+# ------------------------------------------------------------------------------------------------ region-based datasets
+MAX_REGIONS, MAX_REGION_TABLE = 32, 1024
+
+
+def region_table(table, device):
+    """The membership table of dg_tta_amd.labels (uint32 [L]: bit r of entry y = label y belongs to region r) as an int32 device
+    tensor holding the same bits (what the region kernels read)."""
+    if isinstance(table, torch.Tensor):
+        if table.dtype != torch.int32 or table.dim() != 1:
+            raise ValueError("region table: a uint32 numpy array or a 1-D int32 tensor (the same bits) expected")
+        t = table.to(device).contiguous()
+    else:
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(table))
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < 0 or a.max() > 0xffffffff)):
+            raise ValueError("region table: a 1-D array of 32-bit masks expected")
+        t = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(device)
+    if not 1 <= t.numel() <= MAX_REGION_TABLE:
+        raise ValueError(f"region table: 1..{MAX_REGION_TABLE} label values expected, got {t.numel()}")
+    return t
+
+
+class _RegionLoss(torch.autograd.Function):
+    """DC+BCE of region logits against an integer label map and the membership table (csrc/region_loss.hip); strides None: dense
+    labels [B, V], else the full-resolution map read through the deep-supervision index map."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, table, strides, smooth, batch_dice):
+        lib = _lib.load()
+        b, r, d, h, w = logits.shape
+        logits = logits.contiguous(memory_format=torch.channels_last_3d)
+        labels = labels.contiguous()
+        dev, L = logits.device, table.numel()
+        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
+        dice = torch.empty((b, r), dtype=torch.float32, device=dev)
+        if strides is None:
+            v = d * h * w
+            nbytes = lib.dgtta_region_loss_ws_bytes(b, r, v)
+            ws = _ws(nbytes, dev)
+            check(lib.dgtta_region_loss_batch_fwd(ptr(logits), r, ptr(labels), ptr(table), L, ptr(loss3), ptr(dice), ptr(ws), nbytes, b, r, v,
+                                                  float(smooth), int(batch_dice), stream_of(dev)), "dgtta_region_loss_batch_fwd")
+        else:
+            nbytes = lib.dgtta_region_loss_ds_ws_bytes(b, r, d, h, w)
+            ws = _ws(nbytes, dev)
+            check(lib.dgtta_region_loss_ds_batch_fwd(ptr(logits), r, ptr(labels), ptr(table), L, ptr(loss3), ptr(dice), ptr(ws), nbytes, b, r,
+                                                     d, h, w, *strides, float(smooth), int(batch_dice), stream_of(dev)),
+                  "dgtta_region_loss_ds_batch_fwd")
+        ctx.save_for_backward(logits, labels, table, ws)
+        ctx.meta = (b, r, d, h, w, strides)
+        ctx.mark_non_differentiable(dice)
+        return loss3[0], dice, loss3[1:].detach()
+
+    @staticmethod
+    def backward(ctx, gloss, _gdice, _gparts):
+        logits, labels, table, ws = ctx.saved_tensors
+        b, r, d, h, w, strides = ctx.meta
+        lib = _lib.load()
+        g = torch.empty_like(logits, memory_format=torch.preserve_format)
+        gs = gloss.reshape(1).float().contiguous()      # (carries the scale's weight of the multi-scale sum)
+        st = stream_of(logits.device)
+        if strides is None:
+            check(lib.dgtta_region_loss_bwd(ptr(logits), r, ptr(labels), ptr(table), table.numel(), ptr(ws), 1.0, ptr(gs), ptr(g), r, b, r,
+                                            d * h * w, st), "dgtta_region_loss_bwd")
+        else:
+            check(lib.dgtta_region_loss_ds_bwd(ptr(logits), r, ptr(labels), ptr(table), table.numel(), ptr(ws), 1.0, ptr(gs), ptr(g), r, b, r,
+                                               d, h, w, *strides, st), "dgtta_region_loss_ds_bwd")
+        return g, None, None, None, None, None
+
+
+def _region_logits(logits, name):
+    if logits.dim() != 5 or not 1 <= logits.shape[1] <= MAX_REGIONS:
+        raise ValueError(f"{name}: logits [B,R,D,H,W] with 1 <= R <= {MAX_REGIONS} expected, got {tuple(logits.shape)}")
+
+
+def region_loss(logits, labels, table, smooth=1e-5, batch_dice=False):
+    """nnU-Net's loss of region-based training, DC_and_BCE_loss [3P] (soft Dice per sample over all R regions + binary
+    cross-entropy, csrc/region_loss.hip; from memory, unpinned): logits [B,R,D,H,W] (fp32, one sigmoid output per region) against
+    an integer label map [B,1,D,H,W] / [B,D,H,W] and the membership `table` (dg_tta_amd.labels: uint32 [L], bit r of entry y = label
+    y belongs to region r).  Labels outside [0, L) are ignored.  No region target tensor is built.  batch_dice: the Dice sums are
+    pooled over the batch before the ratio.  Returns (loss, dice [B,R], (bce, -mean dice)); differentiable w.r.t. the logits."""
+    require_cuda(logits, labels)
+    _region_logits(logits, "region_loss")
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    labels = labels.reshape(logits.shape[0], -1)
+    if labels.shape[1] != logits[0, 0].numel():
+        raise ValueError("region_loss: the label map does not have the logits' voxels")
+    return _RegionLoss.apply(logits.float(), labels, region_table(table, logits.device), None, smooth, bool(batch_dice))
+
+
+def deep_supervision_region_loss(outputs, labels, table, weights=None, batch_dice=False, smooth=1e-5):
+    """deep_supervision_loss for a region head: sum_i w_i * region_loss(outputs[i], labels at the resolution of outputs[i]), every
+    output compared with the strided view of the FULL-resolution label map (no downsampled map, no region target tensor).
+    Returns (loss, [per-scale loss or None where skipped]); differentiable w.r.t. every output."""
+    outputs = list(outputs)
+    if labels.dim() == 5:
+        labels = labels[:, 0]
+    if weights is None:
+        weights = deep_supervision_weights(len(outputs))
+    if len(weights) != len(outputs):
+        raise ValueError(f"deep_supervision_region_loss: {len(weights)} weights for {len(outputs)} outputs")
+    strides = [_label_strides(o.shape[2:], labels.shape[1:]) for o in outputs]
+    for o in outputs:
+        _region_logits(o, "deep_supervision_region_loss")
+        if o.shape[0] != labels.shape[0]:
+            raise ValueError("deep_supervision_region_loss: batch sizes of outputs and labels differ")
+    require_cuda(labels, *outputs)
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    table = region_table(table, labels.device)
+    total, per_scale = None, []
+    for o, st, wgt in zip(outputs, strides, weights):
+        if wgt == 0:
+            per_scale.append(None)
+            continue
+        li, _, _ = _RegionLoss.apply(o.float(), labels, table, st, smooth, bool(batch_dice))
+        per_scale.append(li.detach())
+        total = li * wgt if total is None else total + li * wgt
+    if total is None:
+        raise ValueError("deep_supervision_region_loss: every weight is zero")
+    return total, per_scale
+
+
+def region_counts(logits, labels, table):
+    """Per-region counts of the hard prediction logits > 0 (sigmoid > 0.5; exactly 0 is "not predicted") against the regions of
+    an integer label map, over the voxels whose label lies inside the table: int64 [3, R] = TP, FP, FN - the online pseudo-Dice
+    2 TP / (2 TP + FP + FN) of a region trainer (csrc/region_map.hip), what argmax_dice's counts are for the softmax case."""
+    require_cuda(logits, labels)
+    _region_logits(logits, "region_counts")
+    lib = _lib.load()
+    b, r = logits.shape[:2]
+    lg = logits.float().contiguous(memory_format=torch.channels_last_3d)
+    lb = labels.reshape(-1).to(torch.int64).contiguous()
+    if lb.numel() != b * lg[0, 0].numel():
+        raise ValueError("region_counts: the label map does not have the logits' voxels")
+    table = region_table(table, lg.device)
+    counts = torch.empty((3, r), dtype=torch.int64, device=lg.device)
+    check(lib.dgtta_region_counts(ptr(lg), r, r, ptr(lb), ptr(table), table.numel(), ptr(counts), lb.numel(), stream_of(lg.device)),
+          "dgtta_region_counts")
+    return counts
+
+
+def check_regions_class_order(order, num_regions):
+    """`regions_class_order` as plain ints: one positive label per region.  ValueError otherwise (before anything touches the GPU)."""
+    order = [int(x) for x in order]
+    if len(order) != num_regions or not 1 <= num_regions <= MAX_REGIONS or min(order) <= 0:
+        raise ValueError(f"regions_class_order: {num_regions} positive labels expected (1..{MAX_REGIONS} regions), got {order}")
+    return order
+
+
+def logits_regions(acc, order):
+    """Label map of a voxel-major accumulator of region logits [..., R] (fp32 or fp16, contiguous): 0, then order[i] wherever
+    output i is > 0, for i = 0 .. R-1 in order - the last positive region wins (csrc/region_map.hip; nnU-Net's
+    convert_probabilities_to_segmentation for regions, from memory, unpinned).  int64."""
+    require_cuda(acc)
+    if acc.dtype not in (torch.float32, torch.float16) or not acc.is_contiguous():
+        raise ValueError("logits_regions: contiguous fp32 / fp16 rows expected")
+    order = check_regions_class_order(order, acc.shape[-1])
+    lib = _lib.load()
+    out = torch.empty(acc.shape[:-1], dtype=torch.int64, device=acc.device)
+    check(lib.dgtta_logits_regions(ptr(acc), F32 if acc.dtype == torch.float32 else F16, len(order), out.numel(), (C_int * len(order))(*order),
+                                   ptr(out), stream_of(acc.device)), "dgtta_logits_regions")
+    return out
+
+
+def feature_head_regions_supported(M, R):
+    """dgtta_feature_head_regions takes R <= 32 regions and a weight image of M members that fits the LDS."""
+    return 1 <= R <= MAX_REGIONS and (M * 32 * 36 + 32) * 4 + 128 <= 160 * 1024
+
+
+def feature_head_regions(facc, nsum, w, bsum, order):
+    """Region label map of feature-space window accumulators (csrc/window_features.hip): the inputs of feature_head_argmax with a
+    head of R region outputs, plus `order` = regions_class_order -> int64 [X,Y,Z]: 0, then order[i] wherever
+    sum_m w[m,i] . facc[m,v] + nsum[v] bsum[i] > 0, i = 0 .. R-1 in order (the sign of the accumulated sum is the sign of the
+    ensemble-mean logit)."""
+    if facc.dim() == 4:
+        facc, w = facc[None], (w[None] if w.dim() == 2 else w)
+    if not (facc.is_cuda and facc.dtype == torch.float32 and facc[0].is_contiguous() and facc.shape[-1] == 32):
+        raise ValueError("feature_head_regions: fp32 GPU accumulators [M,X,Y,Z,32] expected")
+    M, R = facc.shape[0], w.shape[1]
+    if tuple(w.shape) != (M, R, 32) or tuple(bsum.shape) != (R,) or tuple(nsum.shape) != tuple(facc.shape[1:4]):
+        raise ValueError("feature_head_regions: w [M,R,32], bsum [R], nsum [X,Y,Z] expected")
+    order = check_regions_class_order(order, R)
+    lib = _lib.load()
+    w, bsum, nsum = w.float().contiguous(), bsum.float().contiguous(), nsum.float().contiguous()
+    out = torch.empty(facc.shape[1:4], dtype=torch.int64, device=facc.device)
+    check(lib.dgtta_feature_head_regions(ptr(facc), facc.stride(0) if M > 1 else 0, ptr(nsum), ptr(w), ptr(bsum), M, 32, R, out.numel(),
+                                         (C_int * R)(*order), ptr(out), stream_of(facc.device)), "dgtta_feature_head_regions")
+    return out
+
+
 class _SoftDice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

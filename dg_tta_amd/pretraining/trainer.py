@@ -45,7 +45,17 @@ item and every axis of trainer_mirror_axes(trainer_name) = (0, 1, 2), independen
 Its checkpoint carries inference_allowed_mirroring_axes = [0, 1, 2], which sliding-window inference obeys (tta/inference.py); a DG
 trainer's carries None, draws nothing for mirroring and runs the code it ran before.  Multi-channel data stays out.  Experiment planning is out of
 scope: nnUNetPlans.json must exist.  Random streams are not part of a checkpoint: a continued run draws differently from
-an uninterrupted one."""
+an uninterrupted one.
+
+REGION-BASED DATASETS (dg_tta_amd/labels.py: a dataset.json whose label values are lists, plus `regions_class_order`; nnU-Net's
+second label model, from memory of nnunetv2 2.2.1, UNPINNED): the head has one sigmoid output per region and no background
+channel, the loss is DC+BCE with deep supervision (ops.deep_supervision_region_loss, csrc/region_loss.hip: the kernels read the
+integer label map and the membership table, no region target tensor is built), the pseudo-Dice is 2 TP / (2 TP + FP + FN) per
+region of the prediction logit > 0 (ops.region_counts) and `mean_fg_dice` / `ema_fg_dice` are its mean over the regions, every
+region is a class of the foreground oversampling, the checkpoint records `regions_class_order`, and the final validation writes
+the region label map (0, then regions_class_order[i] where output i is positive, in order) and a summary keyed by region.  The
+stock trainer and the six DG trainers alike: the hooks do not care what the head means.  `--dice plans` pools the Dice sums of
+a region over the batch.  Left out: the ignore label, more than 32 regions, test-time adaptation (prepare_tta / run_tta refuse)."""
 import json
 import os
 import re
@@ -57,6 +67,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..labels import label_model
 from ..optim import HipSGD, PolyLRScheduler
 from ..synthetic import he_init_
 from ..tta.config_log_utils import maybe_convert_to_dataset_name, nnunet_path
@@ -125,9 +136,23 @@ def fold_folder_name(fold):
     return f"fold_{fold}"
 
 
-def class_locations(seg, max_per_class=MAX_LOCATIONS_PER_CLASS, seed=1234):
+def class_locations(seg, max_per_class=MAX_LOCATIONS_PER_CLASS, seed=1234, regions=None):
     """{class id > 0: int array [n, 3] of (D, H, W) voxels}, at most max_per_class per class, drawn once per case with a
-    seeded generator (nnU-Net samples them at preprocessing time in the same way)."""
+    seeded generator (nnU-Net samples them at preprocessing time in the same way).
+    regions (tuples of label values, a region-based dataset): every region present in the case is a class, keyed by its tuple -
+    its voxels are those of isin(seg, region), drawn region by region in the given order from the one generator."""
+    if regions is not None:
+        arr = np.asarray(seg)
+        rs = np.random.RandomState(seed)
+        out = {}
+        for region in regions:
+            idx = np.flatnonzero(np.isin(arr.reshape(-1), list(region)))
+            if idx.size == 0:
+                continue
+            if idx.size > max_per_class:
+                idx = idx[rs.choice(idx.size, max_per_class, replace=False)]
+            out[tuple(int(x) for x in region)] = np.stack(np.unravel_index(idx, arr.shape), axis=1)
+        return out
     flat = np.asarray(seg).reshape(-1)
     order = np.argsort(flat, kind="stable")
     vals, starts = np.unique(flat[order], return_index=True)
@@ -236,15 +261,15 @@ def find_cases(data_dir, raw, file_ending):
 
 # ------------------------------------------------------------------------------------------------ cases
 class _Case:
-    def __init__(self, name, data, seg):
+    def __init__(self, name, data, seg, regions=None):
         seg = np.where(seg < 0, 0, seg)                 # nnU-Net's "outside the non-zero mask" label (-1) trains as background
         self.name = name
         self.tensor = as_label_map_case(torch.from_numpy(np.ascontiguousarray(data[0], dtype=np.float32)),
                                         torch.from_numpy(np.ascontiguousarray(seg[0], dtype=np.float32)))
-        self.locations = class_locations(seg[0])
+        self.locations = class_locations(seg[0], regions=regions)
 
 
-def load_case(name, entry, plans, configuration, device):
+def load_case(name, entry, plans, configuration, device, regions=None):
     """Reads <case>.npz (keys `data` [C, D, H, W], `seg` [1, D, H, W]); a missing file is made from the raw image + label
     with tta/preprocessing.run_case and written first, so there is one code path.  (nnU-Net's per-case .pkl of geometry
     properties is not written: training does not read it.)"""
@@ -261,7 +286,7 @@ def load_case(name, entry, plans, configuration, device):
     if data.shape[0] != 1:
         raise NotImplementedError(f"case {name}: {data.shape[0]} image channels; the DG trainers' hooks and the stock "
                                   f"nnUNetTrainer as built here take one")
-    return _Case(name, data, seg)
+    return _Case(name, data, seg, regions)
 
 
 def build_network(plans, dataset_json, configuration, trainer_name, act_dtype=torch.float32, seed=7):
@@ -424,9 +449,15 @@ def validate_fold(dataset, configuration, fold, trainer_name, device="cuda", act
     predictor, patch, network, parameters = load_network(final, device, act_dtype=act_dtype)
     network = network.to(device)
     disable_internal_augmentation()                         # load_network switched it on, as tta_main finds it
-    num_classes = network.cfg["num_classes"]
-    labels = list(range(num_classes))
-    dtype = next(t for t in (np.uint8, np.uint16, np.uint32) if num_classes - 1 <= np.iinfo(t).max)
+    lm = label_model(predictor.dataset_json)
+    order = lm.regions_class_order                          # None: a label-based model, argmax over its classes
+    if order is not None:
+        from ..tta.evaluation import region_key
+        labels, top = [region_key(r) for r in lm.foreground_regions], max(order)
+    else:
+        labels = list(range(network.cfg["num_classes"]))
+        top = network.cfg["num_classes"] - 1
+    dtype = next(t for t in (np.uint8, np.uint16, np.uint32) if top <= np.iinfo(t).max)
     out = f.fold_dir / "validation"
     out.mkdir(parents=True, exist_ok=True)
     per_case = []
@@ -435,9 +466,10 @@ def validate_fold(dataset, configuration, fold, trainer_name, device="cuda", act
         with np.load(npz) as z:
             data, seg = z["data"], z["seg"][0]
         pred = run_inference(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)), network, parameters, patch,
-                             mirror_axes=predictor.allowed_mirroring_axes).numpy().astype(dtype)
+                             mirror_axes=predictor.allowed_mirroring_axes, regions_class_order=order).numpy().astype(dtype)
         np.save(out / f"{name}.npy", pred)
-        per_case.append({"metrics": case_metrics(pred, np.where(seg < 0, 0, seg), labels, device),
+        per_case.append({"metrics": case_metrics(pred, np.where(seg < 0, 0, seg), labels, device,
+                                                 regions=lm.foreground_regions if order is not None else None),
                          "prediction_file": str(out / f"{name}.npy"), "reference_file": str(npz)})
         print(f"pretrain: validated {name}")
     return summarize_cases(per_case, labels, out / "summary.json")
@@ -492,7 +524,14 @@ def _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val
     net, patch = build_network(plans, dataset_json, configuration, trainer_name, act_dtype,
                                seed=seed if seed is not None else int(np.random.randint(2 ** 31 - 1)))
     batch_size = int(conf["batch_size"])
-    num_classes = net.cfg["num_classes"]
+    num_classes = net.cfg["num_classes"]                    # (a region-based dataset: its R regions, no background channel)
+    lm = label_model(dataset_json)
+    table = ops.region_table(lm.table, device) if lm.has_regions else None
+
+    def loss_of(outs, target):
+        if table is not None:
+            return ops.deep_supervision_region_loss(outs, target, table, batch_dice=batch_dice)
+        return ops.deep_supervision_loss(outs, target, batch_dice=batch_dice)
     net = net.to(device)
     for p in net.parameters():
         p.requires_grad_(True)
@@ -525,13 +564,14 @@ def _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val
     def cases_of(names):
         for n in names:
             if n not in loaded:
-                loaded[n] = load_case(n, entries[n], plans, configuration, device)
+                loaded[n] = load_case(n, entries[n], plans, configuration, device, lm.foreground_regions)
         return [loaded[n] for n in names]
 
     train_cases, val_cases = cases_of(train_names), cases_of(val_names)
 
     def save(name, epoch):
-        torch.save({"network_weights": {k: v.detach().cpu() for k, v in net.state_dict().items()},
+        extra = {} if lm.regions_class_order is None else {"regions_class_order": list(lm.regions_class_order)}
+        torch.save({**extra, "network_weights": {k: v.detach().cpu() for k, v in net.state_dict().items()},
                     "optimizer_state": opt.state_dict(), "current_epoch": epoch, "trainer_name": trainer_name,
                     "init_args": dict(plans=plans, configuration=configuration, fold=fold, dataset_json=dataset_json),
                     "inference_allowed_mirroring_axes": None if mirror_axes is None else list(mirror_axes), "logging": log,
@@ -551,7 +591,7 @@ def _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val
                         print(f"pretrain: gradient overflow, step skipped, loss scale -> {opt.grad_scale:g}")
                     imgs, target, picks = _sample(train_cases, batch_size, patch, device, multires, spatial, intensity=intensity)
                     imgs, target = _mirror(imgs, target, mirror_axes)
-                    loss, _ = ops.deep_supervision_loss(net(imgs), target, batch_dice=batch_dice)
+                    loss, _ = loss_of(net(imgs), target)
                     torch.autograd.backward(loss, grad_tensors=torch.full((), float(opt.grad_scale), dtype=torch.float32,
                                                                           device=device))
                     opt.step()
@@ -564,14 +604,17 @@ def _train(f, trainer_name, configuration, num_epochs, iterations_per_epoch, val
                     for _ in range(val_iterations):
                         imgs, target, picks = _sample(val_cases, batch_size, patch, device, None)
                         outs = net(imgs)
-                        loss, _ = ops.deep_supervision_loss(outs, target, batch_dice=batch_dice)
+                        loss, _ = loss_of(outs, target)
                         va_losses.append(loss)
-                        counts += ops.argmax_dice(outs[0], target)[1]
+                        counts += ops.region_counts(outs[0], target, table) if table is not None else ops.argmax_dice(outs[0], target)[1]
                         recent.update((c.name, epoch) for c in picks)
                 # the one read-back of the epoch: mean losses and the per-class pseudo-Dice 2 TP / (2 TP + FP + FN) summed over
                 # the validation batches (counts rows: predicted, reference, both)
                 nan = torch.full((1,), float("nan"), dtype=torch.float64, device=device)
-                dice = 2.0 * counts[2, 1:].double() / (counts[0, 1:] + counts[1, 1:]).double()
+                if table is not None:                       # rows TP, FP, FN per region; every region is foreground
+                    dice = 2.0 * counts[0].double() / (2 * counts[0] + counts[1] + counts[2]).double()
+                else:
+                    dice = 2.0 * counts[2, 1:].double() / (counts[0, 1:] + counts[1, 1:]).double()
                 host = torch.cat([torch.stack(tr_losses).double().mean()[None] if tr_losses else nan,
                                   torch.stack(va_losses).double().mean()[None] if va_losses else nan, dice]).cpu()
                 fg = host[2:][~torch.isnan(host[2:])]

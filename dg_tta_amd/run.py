@@ -225,6 +225,12 @@ class DGTTAProgram:
                                                                args.pretrainer_config, args.pretrainer_fold)
         tta_data_dir, plan_dir, results_dir, pre_name, tta_name = get_tta_folders(ds, int(args.tta_dataset_id), trainer,
                                                                                   cfg, fold)
+        if (Path(plan_dir) / "tta_plan.json").is_file():      # a region-based model is refused before any directory is made
+            from .labels import refuse_region_tta_of_weights
+            with open(Path(plan_dir) / "tta_plan.json", "r") as f:
+                weights = json.load(f).get("pretrained_weights_filepath")
+            if weights:
+                refuse_region_tta_of_weights(weights, f"run_tta: {weights}")
         run_name = args.run_name
         if run_name is None and int(os.environ.get("WORLD_SIZE", 1)) > 1:
             # every rank would invent its own timestamp + random name and then wait for the others in a directory of its own

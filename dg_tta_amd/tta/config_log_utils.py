@@ -167,6 +167,15 @@ def prepare_tta(pretrained_dataset_id, tta_dataset_id, pretrainer, pretrainer_co
     assert root_dir.is_dir()
     _, plan_dir, results_dir, pretrained_dataset_name, tta_dataset_name = get_tta_folders(
         pretrained_dataset_id, tta_dataset_id, pretrainer, pretrainer_config, pretrainer_fold)
+    if not isinstance(pretrained_dataset_id, str):      # a region-based source model is refused before anything is written
+        from ..labels import refuse_region_tta, refuse_region_tta_of_weights
+        refuse_region_tta_of_weights(Path(nnunet_path("nnUNet_results"), pretrained_dataset_name,
+                                          f"{pretrainer}__nnUNetPlans__{pretrainer_config}", "fold_x", "checkpoint_final.pth"),
+                                     f"prepare_tta: {pretrained_dataset_name}")      # (the model folder's dataset.json)
+        source_json = Path(nnunet_path("nnUNet_raw"), pretrained_dataset_name) / "dataset.json"
+        if source_json.is_file():
+            with open(source_json, "r") as f:
+                refuse_region_tta(json.load(f), f"prepare_tta: {pretrained_dataset_name}")
     shutil.rmtree(plan_dir, ignore_errors=True)
     plan_dir.mkdir(exist_ok=True, parents=True)
     results_dir.mkdir(exist_ok=True, parents=True)

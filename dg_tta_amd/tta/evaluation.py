@@ -99,9 +99,52 @@ def surface_metrics(pred, ref, labels, spacing=(1.0, 1.0, 1.0), nsd_tolerance_mm
     return out
 
 
-def case_metrics(pred, ref, labels, device="cuda", spacing=None, surface=False, nsd_tolerance_mm=1.0):
+def region_key(region):
+    """The key of a region in a metrics dict, as nnU-Net writes it: the label itself for a one-label region, else the tuple of its
+    labels (JSON: "3", "(2, 3)")."""
+    region = (region,) if isinstance(region, (int, np.integer)) else tuple(int(x) for x in region)
+    return int(region[0]) if len(region) == 1 else region
+
+
+def _key(lab):
+    return lab if isinstance(lab, tuple) else int(lab)
+
+
+def region_case_metrics(pred, ref, regions, device="cuda"):
+    """case_metrics per REGION instead of per label (region-based datasets, dg_tta_amd/labels.py): metrics[region_key(r)] = {Dice,
+    IoU, FP, TP, FN, TN, n_pred, n_ref} of the masks isin(pred, r) and isin(ref, r).  regions: tuples of label values.  The masks
+    come from a table lookup, the counts from the label-count kernel on the two binary maps."""
+    if tuple(pred.shape) != tuple(ref.shape):
+        raise ValueError(f"shape mismatch: prediction {tuple(pred.shape)} vs reference {tuple(ref.shape)}")
+    regions = [tuple(int(x) for x in r) for r in regions]
+    p = torch.as_tensor(np.ascontiguousarray(pred).astype(np.int64)).to(device).reshape(-1)
+    r = torch.as_tensor(np.ascontiguousarray(ref).astype(np.int64)).to(device).reshape(-1)
+    top = max([x for reg in regions for x in reg] + [int(p.max()), int(r.max()), 0]) + 1
+    if int(p.min()) < 0 or int(r.min()) < 0:
+        raise ValueError("region_case_metrics: negative label values")
+    total = int(p.numel())
+    out = {}
+    for reg in regions:
+        member = torch.zeros(top, dtype=torch.int64, device=p.device)
+        member[list(reg)] = 1
+        _, counts = ops.argmax_dice_from_labels(member[p], member[r], 2)        # rows: n_pred, n_ref, TP
+        c = counts[:, 1].cpu().tolist()
+        n_pred, n_ref, tp = int(c[0]), int(c[1]), int(c[2])
+        fp, fn = n_pred - tp, n_ref - tp
+        dice, iou = (float("nan"), float("nan")) if tp + fp + fn == 0 else (2 * tp / (2 * tp + fp + fn), tp / (tp + fp + fn))
+        out[region_key(reg)] = {"Dice": dice, "IoU": iou, "FP": fp, "TP": tp, "FN": fn, "TN": total - tp - fp - fn, "n_pred": n_pred,
+                                "n_ref": n_ref}
+    return out
+
+
+def case_metrics(pred, ref, labels, device="cuda", spacing=None, surface=False, nsd_tolerance_mm=1.0, regions=None):
     """metrics[label] = {Dice, IoU, FP, TP, FN, TN, n_pred, n_ref} for two integer label maps of equal shape; with `surface`
-    also {HD95, HD, ASSD, NSD} at `spacing` (millimetres along the array axes; None = unit spacing)."""
+    also {HD95, HD, ASSD, NSD} at `spacing` (millimetres along the array axes; None = unit spacing).
+    regions (tuples of label values; `labels` is then not read): the region form, region_case_metrics - overlap metrics only."""
+    if regions is not None:
+        if surface:
+            raise NotImplementedError("case_metrics: surface metrics per region are not built")
+        return region_case_metrics(pred, ref, regions, device)
     if tuple(pred.shape) != tuple(ref.shape):
         raise ValueError(f"shape mismatch: prediction {tuple(pred.shape)} vs reference {tuple(ref.shape)}")
     nlab = int(max(labels)) + 1
@@ -154,16 +197,17 @@ def compute_metrics_on_folder_simple(folder_ref, folder_pred, labels, output_fil
 
 def summarize_cases(per_case, labels, output_file=None, surface_metrics=False):
     """The summary dict of compute_metrics_on_folder_simple from its per-case entries
-    [{"metrics": case_metrics(...), "prediction_file", "reference_file"}]; written as JSON to output_file when given."""
+    [{"metrics": case_metrics(...), "prediction_file", "reference_file"}]; written as JSON to output_file when given.
+    The region form: `labels` holds the keys of region_case_metrics (region_key: ints and tuples); every region is foreground."""
     keys = ["Dice", "IoU", "FP", "TP", "FN", "TN", "n_pred", "n_ref"] + (SURFACE_KEYS if surface_metrics else [])
     means = {}
     for lab in labels:
-        means[int(lab)] = {}
+        means[_key(lab)] = {}
         for k in keys:
-            vals = np.array([c["metrics"][int(lab)][k] for c in per_case], dtype=np.float64)
-            means[int(lab)][k] = float(np.nanmean(vals)) if vals.size and not np.all(np.isnan(vals)) else float("nan")
+            vals = np.array([c["metrics"][_key(lab)][k] for c in per_case], dtype=np.float64)
+            means[_key(lab)][k] = float(np.nanmean(vals)) if vals.size and not np.all(np.isnan(vals)) else float("nan")
     fg = [l for l in labels if l != 0]
-    foreground_mean = {k: float(np.mean([means[int(l)][k] for l in fg])) if fg else float("nan") for k in keys}
+    foreground_mean = {k: float(np.mean([means[_key(l)][k] for l in fg])) if fg else float("nan") for k in keys}
     summary = {"metric_per_case": per_case, "mean": means, "foreground_mean": foreground_mean}
     if output_file is not None:
         Path(output_file).parent.mkdir(parents=True, exist_ok=True)

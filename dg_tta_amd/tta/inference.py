@@ -143,16 +143,20 @@ FEATURE_HEAD_MAX_CLASSES_MFMA = 128      # dgtta_feature_head_argmax: classes x 
 FEATURE_HEAD_MAX_CLASSES_VALU = 160      # its vector-ALU kernel with M > 1 members parks C * 256 * 4 B of partial sums in LDS
 
 
-def _can_accumulate_features(model, members=1):
+def _can_accumulate_features(model, members=1, regions=False):
     """Feature-space accumulation needs the network's offer (head = 1x1x1 conv on 32 channels, nothing selected), nothing
     between the head and the accumulation (every forward hook is the plan's untouched model-output modifier = identity), and a
     head the final head + argmax kernel takes (C <= 128, or one member, or C <= 160) - checked UP FRONT, so that a
-    wider ensemble goes to the logits-space accumulator instead of failing after every member's sliding-window pass."""
+    wider ensemble goes to the logits-space accumulator instead of failing after every member's sliding-window pass.
+    regions: the label map will be the region one (WindowFeatures.regions): the head must then be one dgtta_feature_head_regions
+    takes (R <= 32 outputs, an ensemble whose weight image fits the LDS; R = 1 included)."""
     m = _inner(model)
     if not (hasattr(m, "can_fuse_window_feature_accumulate") and m.can_fuse_window_feature_accumulate() and
             _only_identity_output_hooks(m)):
         return False
     ncls = _num_classes(m)
+    if regions:
+        return ops.feature_head_regions_supported(members, ncls)
     return ncls <= FEATURE_HEAD_MAX_CLASSES_MFMA or members == 1 or ncls <= FEATURE_HEAD_MAX_CLASSES_VALU
 
 
@@ -173,6 +177,11 @@ class WindowFeatures:
     def argmax(self):
         """Label map [X,Y,Z] (int64, padded geometry): argmax over all classes of the ensemble logits, first maximum wins."""
         return ops.feature_head_argmax(self.facc, self.nsum, self.w, self.bsum)
+
+    def regions(self, order):
+        """Label map [X,Y,Z] (int64, padded geometry) of a REGION head: 0, then order[i] = regions_class_order[i] wherever the
+        ensemble logit of output i is > 0, in order - the last positive region wins (ops.feature_head_regions; unpinned)."""
+        return ops.feature_head_regions(self.facc, self.nsum, self.w, self.bsum, order)
 
     def softmax(self, classes, prob_dtype=torch.float32):
         """(label int64, confidence fp32, entropy fp32 [X,Y,Z], probs prob_dtype [K,X,Y,Z]) in the padded geometry: softmax over all
@@ -397,11 +406,12 @@ def predict_ensemble_features(data, model, parameter_sets, patch_size, mirror_ax
 
 
 @torch.no_grad()
-def predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes=None):
+def predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes=None, regions=False):
     """What run_inference / dgtta run_tta predict with: (acc, nsum, crop) for export_segmentation - acc a WindowFeatures when
     DGTTA_WINDOW_ACC=features (default) and the network offers it, else the logits-space accumulator of predict_ensemble_logits.
-    mirror_axes: the checkpoint's inference_allowed_mirroring_axes (None for the DG trainers)."""
-    if window_acc_mode() == "features" and _can_accumulate_features(model, len(parameter_sets)):
+    mirror_axes: the checkpoint's inference_allowed_mirroring_axes (None for the DG trainers).  regions: the head is a region head
+    (the feature-space form is then offered for the heads the region label-map kernel takes)."""
+    if window_acc_mode() == "features" and _can_accumulate_features(model, len(parameter_sets), regions=regions):
         feats = predict_ensemble_features(data, model, parameter_sets, patch_size, mirror_axes)
         return feats, feats.nsum, feats.crop
     return predict_ensemble_logits(data, model, parameter_sets, patch_size, mirror_axes)
@@ -424,12 +434,20 @@ def predict_ensemble_logits(data, model, parameter_sets, patch_size, mirror_axes
 
 
 @torch.no_grad()
-def run_inference(data, model, parameter_sets, patch_size, label_mapping=None, optimized_labels=None, mirror_axes=None):
+def run_inference(data, model, parameter_sets, patch_size, label_mapping=None, optimized_labels=None, mirror_axes=None,
+                  regions_class_order=None):
     """Ensemble prediction of one preprocessed case in the PREPROCESSED geometry.  Returns the label map [X,Y,Z] (int64,
-    CPU), mapped to the target ids when label_mapping/optimized_labels are given (tta.py:407-411)."""
+    CPU), mapped to the target ids when label_mapping/optimized_labels are given (tta.py:407-411).
+    regions_class_order: the model is a region model (dg_tta_amd/labels.py) - its R outputs are sigmoid logits of overlapping
+    regions and the label map is the region one (0, then regions_class_order[i] wherever the ensemble-mean logit of output i is
+    > 0, in order) instead of the argmax, for both accumulators, mirroring included.  No label mapping then."""
     from .torch_utils import get_map_idxs
-    acc, nsum, crop = predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes)
-    seg = torch.as_tensor(export_segmentation(acc, nsum, crop, None, None, None).astype(np.int64))
+    if regions_class_order is not None:
+        if label_mapping is not None:
+            raise ValueError("run_inference: a region label map holds regions_class_order's labels; there is no label mapping for it")
+        regions_class_order = ops.check_regions_class_order(regions_class_order, _num_classes(model))
+    acc, nsum, crop = predict_ensemble(data, model, parameter_sets, patch_size, mirror_axes, regions=regions_class_order is not None)
+    seg = torch.as_tensor(export_segmentation(acc, nsum, crop, None, None, None, regions_class_order).astype(np.int64))
     if label_mapping is not None:
         seg = map_label(seg[None], get_map_idxs(label_mapping, optimized_labels, "pretrain_labels"), "argmaxed")[0]
     return seg
@@ -448,8 +466,11 @@ def _resolved_configuration(plans, configuration):
 
 
 @torch.no_grad()
-def export_segmentation(acc, nsum, crop, properties, plans, configuration):
+def export_segmentation(acc, nsum, crop, properties, plans, configuration, regions_class_order=None):
     """Label map (pretrain class ids, numpy) of accumulated ensemble logits.
+    regions_class_order (a region head, preprocessed geometry only): the region label map replaces the argmax - the sign of the
+    accumulated logit is the sign of the ensemble mean, so there is no division pass either; the export of region predictions
+    to the original geometry is not built (NotImplementedError).
 
     properties None: argmax in the preprocessed geometry (sum over members of acc_m / nsum has the argmax of sum_m acc_m,
     nsum > 0 being shared: no division pass).  Otherwise nnU-Net's
@@ -460,7 +481,9 @@ def export_segmentation(acc, nsum, crop, properties, plans, configuration):
     'bbox_used_for_cropping' and transposed back with the plans' transpose_backward.  The resampling runs on the GPU class
     group by class group with a running argmax, so the full-resolution 105-class volume never exists."""
     C = acc.shape[3]
-    label_map = _label_map_fn(acc)
+    if regions_class_order is not None and properties is not None:
+        raise NotImplementedError("export_segmentation: region predictions are exported in the preprocessed geometry only")
+    label_map = _label_map_fn(acc, regions_class_order)
     cs, cur_shape = _crop_extents(acc, crop)
     if properties is None:
         return label_map()[tuple(crop)].cpu().numpy()
@@ -476,7 +499,10 @@ def export_segmentation(acc, nsum, crop, properties, plans, configuration):
     return _paste_label_map(seg, C, properties, plans)
 
 
-def _label_map_fn(acc):
+def _label_map_fn(acc, regions_class_order=None):
+    if regions_class_order is not None:
+        return (lambda: acc.regions(regions_class_order)) if isinstance(acc, WindowFeatures) else \
+            (lambda: ops.logits_regions(acc, regions_class_order))
     return (lambda: acc.argmax()) if isinstance(acc, WindowFeatures) else (lambda: ops.argmax_rows(acc))
 
 

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ..gin import gin_hook
+from ..labels import num_network_outputs
 from ..mind import mind_hook
 from ..unet import HipPlainConvUNet
 from ..utils import enable_internal_augmentation
@@ -36,7 +37,7 @@ def unet_cfg_from_plans(plans, dataset_json, configuration, in_channels):
     base, cap = conf["UNet_base_num_features"], conf["unet_max_num_features"]
     feats = tuple(min(base * 2 ** i, cap) for i in range(len(pools)))
     cfg = dict(features=feats, n_conv_enc=tuple(conf["n_conv_per_stage_encoder"]),
-               n_conv_dec=tuple(conf["n_conv_per_stage_decoder"]), in_channels=in_channels, num_classes=len(dataset_json["labels"]))
+               n_conv_dec=tuple(conf["n_conv_per_stage_decoder"]), in_channels=in_channels, num_classes=num_network_outputs(dataset_json))      # (R region outputs for a region-based dataset)
     if (all(len(p) == 3 and len(set(p)) == 1 and p[0] in (1, 2) for p in pools) and len(kernels) == len(pools)
             and all(list(k) == [3, 3, 3] for k in kernels)):
         cfg["strides"] = tuple(p[0] for p in pools)      # isotropic plan (TS104): int strides, no kernel_sizes

@@ -464,6 +464,11 @@ def tta_main(run_name, config, tta_data_dir, save_base_path, label_mapping, modi
     sequence of the reference's order (all TTA first, then inference) - an externally seeded run without config['seed']
     follows the reference's stream."""
     from .nnunet_utils import load_network, load_tta_data
+    from ..labels import refuse_region_tta, refuse_region_tta_of_weights
+    if network_bundle is not None:      # a region-based model is refused before any file is written or any volume is read
+        refuse_region_tta(getattr(network_bundle[0], "dataset_json", None), "run_tta")
+    elif config.get("pretrained_weights_filepath"):
+        refuse_region_tta_of_weights(config["pretrained_weights_filepath"], f"run_tta: {config['pretrained_weights_filepath']}")
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("dg_tta_amd runs on the MI355X only (device must be 'cuda' / 'cuda:N'); there is no CPU path")

@@ -233,6 +233,60 @@ int dgtta_dice_ce_ds_batch_fwd(const float *logits, int ldc, const int64_t *labe
                                size_t ws_bytes, int B, int C, int d, int h, int w, int sd, int sh, int sw, float smooth,
                                int do_bg, int batch_dice, void *stream);
 
+/* REGION-BASED datasets - nnU-Net's second label model: a dataset.json whose label values are lists describes R overlapping
+ * regions of the label map, the network has R sigmoid outputs and no background channel.  Everything below is restated from
+ * memory of nnunetv2 2.2.1 [3P, not available here]: UNPINNED.
+ *   table      uint32 [L], L = largest label value + 1 <= 1024: bit r of table[y] is set when label y belongs to region r
+ *              (R <= 32); t[b][v][r] = bit r of table[labels[b][v]].  A voxel is VALID when 0 <= label < L; any other voxel is
+ *              left out of every sum and receives a zero gradient.  No region target tensor is ever built.
+ * Loss: DC_and_BCE_loss with MemoryEfficientSoftDiceLoss(do_bg=True, smooth), weights 1 / 1.  s = sigmoid(logits):
+ *   loss3[1] = (1 / (N R)) sum_{valid v, r} [max(z, 0) - t z + log1p(exp(-|z|))]      N = valid voxels of the batch (no valid
+ *              voxel: 0, and a zero gradient)
+ *   dice[b][r] = (2 sum_v s t + smooth) / max(sum_v s + sum_v t + smooth, 1e-8);  loss3[2] = -mean_{b, r} dice
+ *   loss3[0] = loss3[1] + loss3[2]
+ * logits / grad_logits voxel-major fp32 [B][V][ld], labels int64 [B][V]; the _ds_ forms take logits [B][d][h][w][ld] and the
+ * FULL-resolution label map [B][d sd][h sh][w sw], read at (i sd + sd / 2, j sh + sh / 2, k sw + sw / 2) as dgtta_dice_ce_ds_*
+ * do (strides (1, 1, 1): the dense entries bit for bit).  The _batch_ forms take the plans' batch_dice (0: the plain entries bit
+ * for bit; 1: the three Dice sums are pooled over b before the ratio, loss3[1] unchanged, every row of dice holds the region's
+ * one value; anything else DGTTA_ERR_BADARG).  bwd: grad_logits = grad_scale * (*grad_scale_dev if given) * d loss3[0] /
+ * d logits.  ws: dgtta_region_loss_ws_bytes(B, R, V), kept between fwd and bwd.  1 <= B <= 8, 1 <= R <= 32.  Double partial sums
+ * in fixed slots, one finalize workgroup, no floating-point atomics: bit-reproducible. */
+size_t dgtta_region_loss_ws_bytes(int B, int R, int64_t V);
+int dgtta_region_loss_fwd(const float *logits, int ldc, const int64_t *labels, const uint32_t *table, int L, float *loss3,
+                          float *dice, void *ws, size_t ws_bytes, int B, int R, int64_t V, float smooth, void *stream);
+int dgtta_region_loss_batch_fwd(const float *logits, int ldc, const int64_t *labels, const uint32_t *table, int L, float *loss3,
+                                float *dice, void *ws, size_t ws_bytes, int B, int R, int64_t V, float smooth, int batch_dice,
+                                void *stream);
+int dgtta_region_loss_bwd(const float *logits, int ldc, const int64_t *labels, const uint32_t *table, int L, const void *ws,
+                          float grad_scale, const float *grad_scale_dev, float *grad_logits, int ldg, int B, int R, int64_t V,
+                          void *stream);
+size_t dgtta_region_loss_ds_ws_bytes(int B, int R, int d, int h, int w);
+int dgtta_region_loss_ds_fwd(const float *logits, int ldc, const int64_t *labels_full, const uint32_t *table, int L, float *loss3,
+                             float *dice, void *ws, size_t ws_bytes, int B, int R, int d, int h, int w, int sd, int sh, int sw,
+                             float smooth, void *stream);
+int dgtta_region_loss_ds_batch_fwd(const float *logits, int ldc, const int64_t *labels_full, const uint32_t *table, int L,
+                                   float *loss3, float *dice, void *ws, size_t ws_bytes, int B, int R, int d, int h, int w, int sd,
+                                   int sh, int sw, float smooth, int batch_dice, void *stream);
+int dgtta_region_loss_ds_bwd(const float *logits, int ldc, const int64_t *labels_full, const uint32_t *table, int L,
+                             const void *ws, float grad_scale, const float *grad_scale_dev, float *grad_logits, int ldg, int B,
+                             int R, int d, int h, int w, int sd, int sh, int sw, void *stream);
+/* Online pseudo-Dice of a region head: counts int64 [3][R] = TP, FP, FN per region of the prediction logits > 0 (sigmoid > 0.5;
+ * a logit of exactly 0 is "not predicted") over the valid voxels of logits fp32 [rows][ldc] / labels int64 [rows].  counts is
+ * cleared by the call.  Integer sums only. */
+int dgtta_region_counts(const float *logits, int ldc, int R, const int64_t *labels, const uint32_t *table, int L,
+                        int64_t *counts, int64_t rows, void *stream);
+/* Label map of region logits - convert_probabilities_to_segmentation: label = 0; for i = 0 .. R-1 in order: label = order[i]
+ * where the ensemble-mean logit of output i is > 0 (the last positive region in the order wins; exactly 0 is not in the region).
+ * The mean is a positive multiple of the accumulated sum, so the accumulator's sign decides.  h_order: HOST array of R positive
+ * labels (regions_class_order; anything else DGTTA_ERR_BADARG), label_out int64.
+ * dgtta_logits_regions: the logits-space window accumulator acc [rows][R], fp32 or fp16 (acc_dtype).
+ * dgtta_feature_head_regions: the feature-space accumulators, arguments as dgtta_feature_head_argmax; accumulator i is
+ *   sum_m w[m][i] . facc[m][v] + nsum[v] bsum[i], formed in that function's order on the matrix cores.  R <= 32 and a weight
+ *   image of M members that fits the LDS (M <= 35), else DGTTA_ERR_UNSUPPORTED. */
+int dgtta_logits_regions(const void *acc, int acc_dtype, int R, int64_t rows, const int *h_order, int64_t *label_out, void *stream);
+int dgtta_feature_head_regions(const float *facc, int64_t member_stride, const float *nsum, const float *w, const float *bsum, int M,
+                               int Cin, int R, int64_t V, const int *h_order, int64_t *label_out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * AdamW (decoupled weight decay, bias-corrected, no amsgrad) over a list of tensors.  Replaces
  * torch.optim.AdamW(model.parameters(), lr).step() at dg_tta/tta/tta.py:185,278 (betas 0.9/0.999,
