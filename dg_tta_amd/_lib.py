@@ -122,6 +122,7 @@ SIGNATURES = {
     "dgtta_feature_logits_chunk_f64": (I, [P, I64, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_logits_chunk_f64_t": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dgtta_argmax_merge_f64": (I, [P, I64, I, I, P, P, I, P]),
+    "dgtta_regions_merge_f64": (I, [P, I64, I, I, C.c_double, C.POINTER(I), I, P, P, I, I, P]),
     "dgtta_feature_head_softmax": (I, [P, I64, P, P, P, I, I, I, I64, C.POINTER(I), I, I, P, P, P, P, P]),
     "dgtta_softmax_merge_f64": (I, [P, I64, I, I, C.c_double, P, P, P, C.POINTER(I), I, P, I, P]),
     "dgtta_softmax_finalize_f64": (I, [P, P, P, P, I64, I, I, P, P, P, P]),

@@ -180,7 +180,81 @@ __global__ void softmax_finalize_kernel(const double *__restrict__ run_max, cons
   for (int k = 0; k < K; ++k) st_f<PT>(probs + (int64_t)k * V + v, (float)(exp(stash[(int64_t)k * V + v] - m) / S));
 }
 
+// Region end of the same loop (region_map.hip's header: R sigmoid outputs of overlapping regions, no background channel): the label
+// starts from 0 and takes order[c0 + j] wherever vals[v][j] > 0, j ascending over groups merged in ascending c0 - the last positive
+// region wins; 0, -0 and NaN are not positive.  The probability plane c0 + j receives sigmoid(scale * vals[v][j]), evaluated in
+// double by the branch that never overflows.  A lane owns a voxel and reads its contiguous row of cg doubles; the label and every
+// plane are stored lane-contiguously.  The group's slice of the order rides in the kernel argument (no device allocation, no copy).
+constexpr int RG_MAXR = 32;
+
+struct RegionOrder {
+  int c[RG_MAXR];      // c[j] = regions_class_order[c0 + j], j < cg
+};
+
+struct NoProbs {};      // PT of the label-only instantiation
+
+template <typename PT>
+__global__ __launch_bounds__(256) void regions_merge_kernel(const double *__restrict__ vals, int64_t V, int cg, double scale,
+                                                            RegionOrder order, int *__restrict__ label, PT *__restrict__ planes,
+                                                            int first) {
+  __shared__ int s_ord[RG_MAXR];
+  if (threadIdx.x < RG_MAXR) {
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < RG_MAXR; ++k) mine = (int)threadIdx.x == k ? order.c[k] : mine;      // (no runtime index into the kernel argument)
+    s_ord[threadIdx.x] = mine;
+  }
+  __syncthreads();
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  const double *row = vals + v * cg;
+  int lab = first ? 0 : label[v];
+  for (int j = 0; j < cg; ++j) {
+    const double s = row[j];
+    if (s > 0.0) lab = s_ord[j];
+    if constexpr (!std::is_same<PT, NoProbs>::value) {
+      const double x = scale * s;
+      double p;
+      if (x >= 0.0) {
+        p = 1.0 / (1.0 + exp(-x));
+      } else {
+        const double e = exp(x);
+        p = e / (1.0 + e);      // (NaN fails x >= 0 and comes out of this branch as NaN)
+      }
+      st_f<PT>(planes + (int64_t)j * V + v, (float)p);
+    }
+  }
+  label[v] = lab;
+}
+
 }  // namespace
+
+extern "C" int dgtta_regions_merge_f64(const double *vals, int64_t V, int cg, int c0, double scale, const int *h_order, int R,
+                                       int *label, void *probs_out, int prob_dtype, int first, void *stream) {
+  DG_REQUIRE(vals && h_order && label, DGTTA_ERR_BADARG, "regions_merge: null pointer");
+  DG_REQUIRE(R >= 1 && R <= RG_MAXR && V > 0 && cg > 0 && c0 >= 0 && c0 <= R - cg, DGTTA_ERR_BADARG,
+             "regions_merge: need 1<=R<=%d, V>0 and outputs c0..c0+cg-1 inside [0,R) (R=%d c0=%d cg=%d)", RG_MAXR, R, c0, cg);
+  DG_REQUIRE(scale > 0.0, DGTTA_ERR_BADARG, "regions_merge: scale = 1 / members must be positive");
+  for (int i = 0; i < R; ++i)
+    DG_REQUIRE(h_order[i] > 0, DGTTA_ERR_BADARG, "regions_merge: regions_class_order[%d] = %d is not a positive label", i, h_order[i]);
+  DG_REQUIRE(!probs_out || prob_dtype == DGTTA_F32 || prob_dtype == DGTTA_F16, DGTTA_ERR_BADARG,
+             "regions_merge: probabilities are fp32 or fp16");
+  DG_REQUIRE(cdiv64(V, 256) < (1ll << 31), DGTTA_ERR_UNSUPPORTED, "regions_merge: too many voxels");
+  RegionOrder order{};
+  for (int j = 0; j < cg; ++j) order.c[j] = h_order[c0 + j];
+  const dim3 grid((unsigned)cdiv64(V, 256));
+  if (!probs_out)
+    hipLaunchKernelGGL(regions_merge_kernel<NoProbs>, grid, dim3(256), 0, (hipStream_t)stream, vals, V, cg, scale, order, label,
+                       (NoProbs *)nullptr, first);
+  else if (prob_dtype == DGTTA_F32)
+    hipLaunchKernelGGL(regions_merge_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vals, V, cg, scale, order, label,
+                       (float *)probs_out + (int64_t)c0 * V, first);
+  else
+    hipLaunchKernelGGL(regions_merge_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, vals, V, cg, scale, order, label,
+                       (f16_t *)probs_out + (int64_t)c0 * V, first);
+  DG_CHECK_LAUNCH("regions_merge_kernel");
+  return DGTTA_OK;
+}
 
 extern "C" int dgtta_softmax_merge_f64(const double *vals, int64_t V, int cg, int c0, double scale, double *run_max, double *run_sum,
                                        double *run_dot, const int *h_sel, int K, double *stash, int first, void *stream) {

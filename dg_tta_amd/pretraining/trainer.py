@@ -55,7 +55,8 @@ region of the prediction logit > 0 (ops.region_counts) and `mean_fg_dice` / `ema
 region is a class of the foreground oversampling, the checkpoint records `regions_class_order`, and the final validation writes
 the region label map (0, then regions_class_order[i] where output i is positive, in order) and a summary keyed by region.  The
 stock trainer and the six DG trainers alike: the hooks do not care what the head means.  `--dice plans` pools the Dice sums of
-a region over the batch.  Left out: the ignore label, more than 32 regions, test-time adaptation (prepare_tta / run_tta refuse)."""
+a region over the batch.  A new image is labelled in its original geometry by `dgtta predict` (dg_tta_amd/predict.py).  Left out:
+the ignore label, more than 32 regions, test-time adaptation (prepare_tta / run_tta refuse)."""
 import json
 import os
 import re

@@ -2,7 +2,8 @@
 (prepare_tta :71-118, run_tta :120-209).  `pretrain` takes the arguments of `nnUNetv2_train`, which the reference dispatches
 into, and trains on this engine (pretraining/trainer.py); `inject_trainers` patches an installed nnunetv2 and has nothing
 to do here.  `plan` stands for the planning half of `nnUNetv2_plan_and_preprocess`: the dataset fingerprint (on the GPU) and nnU-Net
-2.2.1's ExperimentPlanner (planning/), so that `pretrain` can start from a raw dataset.  Extra, optional: `run_tta --gpus N` fans out one process per GPU
+2.2.1's ExperimentPlanner (planning/), so that `pretrain` can start from a raw dataset.  `predict` takes the arguments of
+`nnUNetv2_predict` and applies a trained model folder to a folder of images without adaptation (predict.py).  Extra, optional: `run_tta --gpus N` fans out one process per GPU
 (sample-sharded, no collectives), `--dtype {fp32,bf16,fp16}` (default fp32 = the reference's precision).
 """
 import argparse
@@ -73,6 +74,7 @@ class DGTTAProgram:
         pretrain        Pre-train on the source dataset (GIN / MIND trainers)
         prepare_tta     Prepare test-time adaptation
         run_tta         Run test-time adaptation
+        predict         Predict a folder of images with a trained model (fold ensemble, no adaptation)
         """)
         parser.add_argument("command", help="Subcommand to run")
         args = parser.parse_args(self.argv[1:2])
@@ -192,6 +194,52 @@ class DGTTAProgram:
                            device=torch.device(args.device), continue_training=args.continue_training, seed=args.seed, augmentation=args.augmentation,
                            act_dtype=act_dtype, dice=args.dice, final_validation=args.validate)
         print(f"pretrain: wrote {final}")
+
+    @staticmethod
+    def _predict_parser():
+        """nnUNetv2_predict's arguments and defaults (nnunetv2 2.2.1, from memory: unpinned).  Not accepted: -npp, -nps,
+        -prev_stage_predictions, -num_parts / -part_id (one process, one GPU) and the postprocessing_* plan keys."""
+        parser = argparse.ArgumentParser(description="Predict a folder of images with the ensemble of a trained model's folds "
+                                         "(arguments as in nnUNetv2_predict; no test-time adaptation, no post-processing)",
+                                         usage="dgtta predict [-h]")
+        parser.add_argument("-i", dest="input_folder", required=True,
+                            help="folder of images: <case>_0000.<ext> (NIfTI / NRRD / MetaImage), or preprocessed .npy / .npz arrays")
+        parser.add_argument("-o", dest="output_folder", required=True, help="folder the label maps are written to")
+        parser.add_argument("-d", dest="dataset_id", required=True, help="Dataset name or numeric id the model was trained on")
+        parser.add_argument("-c", dest="configuration", required=True, help="Configuration of the plans, e.g. 3d_fullres")
+        parser.add_argument("-tr", dest="trainer", default="nnUNetTrainer", help="trainer of the model folder")
+        parser.add_argument("-p", dest="plans", default="nnUNetPlans", help="plans identifier of the model folder")
+        parser.add_argument("-f", dest="folds", nargs="+", default=["0", "1", "2", "3", "4"],
+                            help="folds whose checkpoints form the ensemble: numbers, or 'all'")
+        parser.add_argument("-chk", dest="checkpoint_name", default="checkpoint_final.pth")
+        parser.add_argument("--disable_mirroring", "--disable_tta", dest="disable_mirroring", action="store_true",
+                            help="no mirrored passes, whatever the checkpoint allows.  --disable_tta is nnU-Net's name for the same "
+                                 "switch: it means mirroring and has nothing to do with DG-TTA")
+        parser.add_argument("--save_probabilities", action="store_true",
+                            help="also write <case>.npz: softmax probabilities of every class (label models, at most 32 classes) or "
+                                 "sigmoid probabilities of every region (region models), float16")
+        parser.add_argument("--continue_prediction", action="store_true", help="skip the cases whose output files exist")
+        parser.add_argument("--device", help="Device to be used", default="cuda")
+        parser.add_argument("--dtype", choices=["fp32", "fp16", "bf16"], default=DEFAULT_DTYPE, help="activation storage")
+        return parser
+
+    def predict(self):
+        args = self._predict_parser().parse_args(self.argv[2:])
+        for k in args.folds:
+            if k != "all" and not k.isnumeric():
+                raise SystemExit(f"predict: fold {k!r} is neither a number nor 'all'")
+        from .predict import model_folder_of, predict_from_model_folder
+        folder = model_folder_of(args.dataset_id, args.configuration, args.trainer, args.plans)
+        try:
+            written = predict_from_model_folder(
+                folder, args.input_folder, args.output_folder, folds=[k if k == "all" else int(k) for k in args.folds],
+                checkpoint_name=args.checkpoint_name, device=torch.device(args.device),
+                act_dtype={"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype],
+                use_mirroring=not args.disable_mirroring, save_probabilities=args.save_probabilities,
+                continue_prediction=args.continue_prediction)
+        except FileNotFoundError as e:
+            raise SystemExit(f"predict: {e}") from e
+        print(f"predict: wrote {len(written)} label maps to {args.output_folder}")
 
     def prepare_tta(self):
         parser = argparse.ArgumentParser(description="Prepare DG-TTA", usage="dgtta prepare_tta [-h]")

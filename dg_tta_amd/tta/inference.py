@@ -468,9 +468,9 @@ def _resolved_configuration(plans, configuration):
 @torch.no_grad()
 def export_segmentation(acc, nsum, crop, properties, plans, configuration, regions_class_order=None):
     """Label map (pretrain class ids, numpy) of accumulated ensemble logits.
-    regions_class_order (a region head, preprocessed geometry only): the region label map replaces the argmax - the sign of the
-    accumulated logit is the sign of the ensemble mean, so there is no division pass either; the export of region predictions
-    to the original geometry is not built (NotImplementedError).
+    regions_class_order (a region head): the region label map replaces the argmax - the sign of the accumulated logit is the sign
+    of the ensemble mean, so there is no division pass either.  With `properties` the logits are resampled as below and merged by
+    dgtta_regions_merge_f64 (_RunningRegions) instead of the running argmax; the map then holds regions_class_order's labels.
 
     properties None: argmax in the preprocessed geometry (sum over members of acc_m / nsum has the argmax of sum_m acc_m,
     nsum > 0 being shared: no division pass).  Otherwise nnU-Net's
@@ -481,8 +481,8 @@ def export_segmentation(acc, nsum, crop, properties, plans, configuration, regio
     'bbox_used_for_cropping' and transposed back with the plans' transpose_backward.  The resampling runs on the GPU class
     group by class group with a running argmax, so the full-resolution 105-class volume never exists."""
     C = acc.shape[3]
-    if regions_class_order is not None and properties is not None:
-        raise NotImplementedError("export_segmentation: region predictions are exported in the preprocessed geometry only")
+    if regions_class_order is not None:
+        regions_class_order = ops.check_regions_class_order(regions_class_order, C)
     label_map = _label_map_fn(acc, regions_class_order)
     cs, cur_shape = _crop_extents(acc, crop)
     if properties is None:
@@ -492,11 +492,12 @@ def export_segmentation(acc, nsum, crop, properties, plans, configuration, regio
         seg = label_map()[tuple(crop)].cpu().numpy()
     else:
         orders = _probability_resampling_orders(properties, plans, configuration)
-        merge = _RunningArgmax(tgt_shape, nsum.device)
+        merge = _RunningArgmax(tgt_shape, nsum.device) if regions_class_order is None else \
+            _RunningRegions(tgt_shape, nsum.device, regions_class_order, 1.0)      # (labels only: the scale is not read)
         for c0, cg, cur in _resampled_class_groups(acc, nsum, cs, tgt_shape, orders):
             merge.add(cur, c0, cg)
         seg = merge.labels()
-    return _paste_label_map(seg, C, properties, plans)
+    return _paste_label_map(seg, C, properties, plans, max_label=_max_label(C, regions_class_order))
 
 
 def _label_map_fn(acc, regions_class_order=None):
@@ -609,9 +610,45 @@ class _RunningSoftmax:
         return conf.reshape(self.shape), ent.reshape(self.shape), probs.reshape(self.K, *self.shape)
 
 
-def _paste_label_map(seg, C, properties, plans):
+class _RunningRegions:
+    """dgtta_regions_merge_f64 over the class groups: the region label map of the resampled logits (0, then order[i] wherever the
+    summed logit of output i is > 0, in order: the last positive region wins) and, with prob_dtype, the sigmoid of the
+    ensemble-mean logit scale * vals of every output in planes [R, V] - written group by group, no stash."""
+
+    def __init__(self, shape, dev, order, scale, prob_dtype=None):
+        import ctypes
+        self.shape, self.dev, self.R, self.scale, self.prob_dtype = list(shape), dev, len(order), float(scale), prob_dtype
+        self.order = (ctypes.c_int * len(order))(*[int(v) for v in order])
+        self.vout = int(np.prod(shape, dtype=np.int64))
+        self.label = torch.empty(self.vout, dtype=torch.int32, device=dev)
+        self.probs = None if prob_dtype is None else torch.empty((self.R, self.vout), dtype=prob_dtype, device=dev)
+        self.code = 0 if prob_dtype is None else ops.prob_dtype_code(prob_dtype)
+
+    def add(self, vals, c0, cg):
+        check(_lib.load().dgtta_regions_merge_f64(ptr(vals), self.vout, cg, c0, self.scale, self.order, self.R, ptr(self.label),
+                                                  ptr(self.probs), self.code, int(c0 == 0), stream_of(self.dev)),
+              "dgtta_regions_merge_f64")
+
+    def labels(self):
+        return self.label.reshape(self.shape).cpu().numpy()
+
+    def probabilities(self):
+        """probs prob_dtype [R, *shape] on the GPU."""
+        if self.probs is None:
+            raise ValueError("_RunningRegions was built without a probability type")
+        return self.probs.reshape(self.R, *self.shape)
+
+
+def _max_label(C, regions_class_order=None):
+    """The largest value a label map can hold: the last class id, or the largest label of regions_class_order."""
+    return C - 1 if regions_class_order is None else max(int(v) for v in regions_class_order)
+
+
+def _paste_label_map(seg, C, properties, plans, max_label=None):
+    """max_label: the largest value the map can hold (C - 1 when None: class ids); it picks the integer type."""
+    max_label = C - 1 if max_label is None else int(max_label)
     full = np.zeros(tuple(int(v) for v in properties["shape_before_cropping"]),
-                    dtype=np.uint8 if C - 1 < 255 else np.uint16)
+                    dtype=np.uint8 if max_label < 255 else np.uint16 if max_label <= 65535 else np.uint32)
     sl = tuple(slice(int(a), int(b)) for a, b in properties["bbox_used_for_cropping"])
     full[sl] = seg
     return np.ascontiguousarray(full.transpose(plans["transpose_backward"]))
@@ -685,3 +722,45 @@ def export_probabilities(acc, nsum, crop, properties, plans, configuration, memb
     return {"segmentation": _paste_label_map(seg, C, properties, plans),
             "probabilities": np.ascontiguousarray(full_p.transpose([0] + [a + 1 for a in tb])),
             "confidence": np.ascontiguousarray(full_c.transpose(tb)), "entropy": np.ascontiguousarray(full_e.transpose(tb))}
+
+
+@torch.no_grad()
+def export_region_probabilities(acc, nsum, crop, properties, plans, configuration, members, regions_class_order,
+                                prob_dtype=np.float16):
+    """Sigmoid end of the accumulated ensemble logits of a REGION head, in the geometry export_segmentation returns (properties
+    None: the preprocessed geometry; otherwise resampled, pasted into `shape_before_cropping` and transposed back).  Returns
+
+      segmentation   the label map export_segmentation(..., regions_class_order=...) returns for the same accumulators
+      probabilities  [R, ...] `prob_dtype` (float16 or float32): p_i = sigmoid(l_i), l_i the ensemble-MEAN window-normalised logit
+                     acc / nsum / members of output i.  The regions overlap: the planes do not sum to 1
+
+    Resampled exports resample the logits first and squash afterwards - nnU-Net 2.2.1's order from memory, UNPINNED, the one
+    export_probabilities states.  Outside the crop box: label 0 and probability 0.  Always the class-group loop (orders [0, 0, 0]
+    when nothing is resampled); the label of an unresampled export is _label_map_fn's own - dividing a non-zero fp32 sum by a
+    positive weight in double cannot change its sign, so both routes agree."""
+    C = acc.shape[3]
+    order = ops.check_regions_class_order(regions_class_order, C)
+    tdtype = {np.dtype(np.float16): torch.float16, np.dtype(np.float32): torch.float32}.get(np.dtype(prob_dtype))
+    if tdtype is None:
+        raise ValueError(f"probabilities are stored as float16 or float32, not {prob_dtype}")
+    members = int(members)
+    if members < 1 or (isinstance(acc, WindowFeatures) and acc.facc.shape[0] != members):
+        raise ValueError(f"members = {members} does not match the accumulator")
+    cs, cur_shape = _crop_extents(acc, crop)
+    tgt_shape = cur_shape if properties is None else [int(v) for v in properties["shape_after_cropping_and_before_resampling"]]
+    resample = tgt_shape != cur_shape
+    orders = _probability_resampling_orders(properties, plans, configuration) if resample else [0, 0, 0]
+    merge = _RunningRegions(tgt_shape, nsum.device, order, 1.0 / members, tdtype)
+    for c0, cg, cur in _resampled_class_groups(acc, nsum, cs, tgt_shape, orders):
+        merge.add(cur, c0, cg)
+    seg = merge.labels() if resample else _label_map_fn(acc, order)()[tuple(crop)].cpu().numpy()
+    probs = merge.probabilities().cpu().numpy()
+    if properties is None:
+        return {"segmentation": seg, "probabilities": np.ascontiguousarray(probs)}
+    full_shape = tuple(int(v) for v in properties["shape_before_cropping"])
+    sl = tuple(slice(int(a), int(b)) for a, b in properties["bbox_used_for_cropping"])
+    full_p = np.zeros((C, *full_shape), dtype=probs.dtype)
+    full_p[(slice(None), *sl)] = probs
+    tb = [int(a) for a in plans["transpose_backward"]]
+    return {"segmentation": _paste_label_map(seg, C, properties, plans, max_label=_max_label(C, order)),
+            "probabilities": np.ascontiguousarray(full_p.transpose([0] + [a + 1 for a in tb]))}

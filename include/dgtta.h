@@ -581,13 +581,25 @@ int dgtta_resample_axis(const double *src, double *dst, void *ws, size_t ws_byte
  * dgtta_logits_chunk_f64: dst[x][y][z][j] = acc[x0+x][y0+y][z0+z][c0+j] / nsum[..] as double (classes c0..c0+cg-1 of the
  * window accumulator, cropped back from the padding to the patch size), the input of the dgtta_resample_axis passes.
  * dgtta_argmax_merge_f64: running argmax over class groups: vals double [V][cg] holds classes c0..; best_val / best_idx
- * are initialised when first != 0.  Ties keep the lower class id (argmax semantics). */
+ * are initialised when first != 0.  Ties keep the lower class id (argmax semantics).
+ * dgtta_regions_merge_f64: the region end of the same loop (a region head: R sigmoid outputs of overlapping regions, see
+ * dgtta_logits_regions).  vals double [V][cg] holds outputs c0..c0+cg-1 of the SUM over members of the window-normalised logits
+ * (what the *_chunk_f64 functions return after the dgtta_resample_axis passes).  label int32 [V] starts from 0 when first != 0,
+ * otherwise from what it holds; for j = 0..cg-1 in order, label = h_order[c0 + j] where vals[v][j] > 0 (exactly 0, -0.0 and NaN are
+ * not in the region; the sign of the sum is the sign of the mean).  Merged in ascending c0 the calls are nnU-Net's
+ * convert_probabilities_to_segmentation for regions: the last positive region of regions_class_order wins.  probs_out: NULL, or
+ * [R][V] plane-major of prob_dtype (DGTTA_F32 / DGTTA_F16): plane c0 + j receives sigmoid(scale * vals[v][j]), scale = 1 / members,
+ * evaluated in double by the branch that never overflows.  h_order is a HOST array of R positive labels, 1 <= R <= 32, c0 >= 0,
+ * c0 + cg <= R, V > 0, scale > 0, prob_dtype one of the two when probs_out is set: anything else DGTTA_ERR_BADARG.  Restated from
+ * memory of nnunetv2 2.2.1, UNPINNED. */
 int dgtta_logits_chunk_f64(const float *acc, const float *nsum, double *dst, int C, int X, int Y, int Z, int x0, int y0,
                            int z0, int xs, int ys, int zs, int c0, int cg, void *stream);
 int dgtta_argmax_merge_f64(const double *vals, int64_t V, int cg, int c0, double *best_val, int *best_idx, int first,
                            void *stream);
 int dgtta_logits_chunk_f64_t(const void *acc, const float *nsum, double *dst, int C, int X, int Y, int Z, int x0, int y0,
                              int z0, int xs, int ys, int zs, int c0, int cg, int acc_dtype, void *stream);
+int dgtta_regions_merge_f64(const double *vals, int64_t V, int cg, int c0, double scale, const int *h_order, int R, int *label,
+                            void *probs_out, int prob_dtype, int first, void *stream);
 
 /* Sliding-window accumulation in FEATURE space (round 5).  The segmentation head is a 1x1x1 convolution and the last layer of the
  * network, so sum_w g_w (W z_w + b) = W (sum_w g_w z_w) + b sum_w g_w: the volume accumulator holds the 32 Gaussian-weighted feature
